@@ -4,6 +4,7 @@ depth-4 / 32-base-filter U-Net (BASELINE.json configs[1]; reference fetal_net/mo
 per GPU, synthetic data resident in HBM, random-init (glorot) weights.
 
   python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR      (also writes what the last timed step computed: dump_outputs)
 
 N > 1: one rank per GPU over RCCL.  Under a launcher (torch.distributed.run sets RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*) this
 process IS one rank; started bare (`python bench.py --gpus 8`) it becomes a parent that starts the N ranks as child processes - before
@@ -566,6 +567,32 @@ def per_layer_table(eng, detail_ms, steps):
                     "MFMA ceiling (23.9 %%, SURVEY 0/8d)" % steps}
 
 
+def dump_outputs(d, eng, sums, batch, spatial, max_logits=1 << 23, max_params=1 << 22):
+    """`--dump-outputs DIR`: what the caller of the timed step receives from its last call - the one main() starts from the seeded
+    parameters, zero Adam moments and the first pool batch - as .npy files (at most 48 MiB in all):
+      sums    float64 [8]   the 8 metric sums of the Dice step (Dice / VOD / accuracy terms: the slots of train_step's sums that
+                            metrics_from_sums reads; the slots behind them collect terms of other loss kinds - the unclipped focal term
+                            is +inf once a sigmoid saturates to 1.0f, as in the reference - and are no result of this step)
+      logits  float32       the step's forward output [batch, D, H, W, labels] (up to 2^23 values; beyond that a fixed seeded sample, flat)
+      params  float32       the flat fp32 parameter vector after the step's Adam update (up to 2^22 values, else a fixed seeded sample)
+    Samples draw sorted indices from np.random.RandomState(0): two builds with the same plan compare element for element."""
+    os.makedirs(d, exist_ok=True)
+
+    def sample(t, cap):
+        v = t.detach().float().cpu().numpy().reshape(-1)
+        if v.size <= cap:
+            return v
+        return v[np.sort(np.random.RandomState(0).choice(v.size, cap, replace=False))]
+
+    logits = sample(eng.logits, max_logits)
+    if logits.size == eng.logits.numel():
+        logits = logits.reshape((batch,) + tuple(spatial) + (-1,))
+    arrays = {"sums": sums.detach()[:8].cpu().numpy().astype(np.float64), "logits": logits, "params": sample(eng.P, max_params)}
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+    return {name: list(v.shape) for name, v in arrays.items()}
+
+
 def launch_ranks(n, argv, port_tries=3):
     """Parent of a bare `bench.py --gpus N`: N children, one per GPU, each a rank of a 127.0.0.1 rendezvous.  The parent never touches
     the GPU (a process that has initialised HIP must not fork/exec workers on this pool).  Returns the exit code."""
@@ -697,9 +724,15 @@ def main():
                     help="also write the per-layer table (every 3x3x3 conv x fwd/dgrad/wgrad: exclusive ms, TFLOP/s / 2.5 PF, algorithmic "
                          "GB/s / 8 TB/s; SURVEY 8d) to this file")
     ap.add_argument("--selftest-cpu", action="store_true", help="exercise the N-rank launcher on the CPU (gloo); measures nothing")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs).  That last step then starts "
+                         "from the seeded initial weights, zero Adam moments and the first pool batch (restored outside the clock), so that the "
+                         "same arguments give the same inputs on every run")
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     if a.launch_timing_every is None:
         a.launch_timing_every = 5 if a.steps <= 20 else 10
     if a.config != "cfg1":
@@ -749,6 +782,8 @@ def main():
     eng = UNetEngine(plan, a.batch, dtype=torch.bfloat16, dist_ctx=dctx, seed=42)
     if dctx is not None:
         dctx.broadcast_params(eng)
+    # --dump-outputs: the seeded parameters the last timed step starts from (see the timed loop)
+    P0 = eng.P.clone() if a.dump_outputs else None
     if a.serialize_streams:
         eng._wg_stream = None
     # Input data (round 4): a pool of batches of the LEARNABLE task (tools/learnable_task.py), resident in HBM, walked round-robin, trained on
@@ -875,9 +910,25 @@ def main():
     # of 64 one-wave workgroups each - outside the K steps' kernels, inside the synchronised bracket (2 x ~5 us of 0.7 s)
     stamp0, stamp1 = torch.zeros(16, dtype=torch.int64, device="cuda"), torch.zeros(16, dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
+    paused = 0.0
     t0 = time.perf_counter()
     ops.clock_stamp(stamp0)
     for i in range(a.steps):
+        if P0 is not None and i == a.steps - 1:
+            # --dump-outputs: the last step starts from the seeded weights, zero Adam moments and the first pool batch.  The steps before it
+            # sum weight-gradient partials with fp32 atomics, and over many Adam steps their rounding grows into differences far above
+            # rounding; from this fixed state the dumped step differs from run to run (and from build to build) by its own rounding
+            # only.  The restore is kept out of the clock.
+            torch.cuda.synchronize()
+            t_p = time.perf_counter()
+            eng.P.copy_(P0)
+            eng.M.zero_()
+            eng.V.zero_()
+            eng.t = 0
+            eng.refresh_weight_copies()
+            nxt[0] = 0
+            torch.cuda.synchronize()
+            paused += time.perf_counter() - t_p
         timer.on = (not a.no_launch_timing) and (i % every == 0)
         sampled += 1 if timer.on else 0
         sums = step()
@@ -885,13 +936,14 @@ def main():
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - paused
     timer.on = False
     if world > 1:
         import torch.distributed as dist
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    dumped = dump_outputs(a.dump_outputs, eng, sums, a.batch, spatial) if (a.dump_outputs and rank == 0) else None
     tot_timed = timer.totals_ms()
     detail = timer.detail_ms()          # exclusive only when everything ran on one stream (replaced by the second pass below otherwise)
     tot_excl = None
@@ -937,6 +989,8 @@ def main():
         "hbm_roofline_frac_conv_algorithmic": (value / world) * ALGO_BYTES_PER_PATCH / 1e9 / PEAK_HBM_GBS,
     }
     ghz, per_xcd = ops.clock_ghz(stamp0, stamp1)
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     out["clock_ghz"] = None if ghz is None else round(ghz, 3)
     out["clock_ghz_note"] = ("average shader clock over the timed region of rank 0: d(s_memtime) / d(s_memrealtime) x 0.1 GHz between two stamps on the "
                              "main stream, median over the XCDs (per XCD: %s); the chip is power-limited under this workload, 2.4 GHz is the "
