@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <initializer_list>
 #include "../../include/fmri_hip.h"
 
 typedef unsigned short bf16_t;  // raw bf16 bits in memory
@@ -58,6 +60,17 @@ __device__ __forceinline__ void fmri_grad_add(const FmriDetCfg& c, float* p, flo
     } while (0)
 
 static inline hipStream_t as_stream(fmri_stream_t s) { return (hipStream_t)s; }
+
+// Run-time switch `name` (an FMRI_* environment variable): its integer value if that is one of `allowed`, else `def` - unset, or a value
+// outside the switch's documented set, selects the default.  Callers read a switch once and keep it in a function-local static.
+static inline int env_int(const char* name, int def, std::initializer_list<int> allowed) {
+    const char* e = getenv(name);
+    if (!e) return def;
+    const int v = atoi(e);
+    for (int a : allowed)
+        if (v == a) return v;
+    return def;
+}
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

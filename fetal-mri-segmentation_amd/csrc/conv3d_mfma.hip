@@ -52,7 +52,6 @@ struct FwdTail {
     int n_per;
     int n_grp;              // G
     const float* nss;
-    int prio;               // != 0: the MFMA waves raise their issue priority (s_setprio 3) over the producer wave on their SIMD (FMRI_FWD_PRIO, A/B)
 };
 
 // MODE selects what the 3x3x3 machinery computes:
@@ -733,11 +732,6 @@ k_conv_fwd_mfma(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__
 // producers' registers apart: the 16 prefetched mask lines (64 registers) and the 9 logit weights are only allocated where they are used -
 // with everything in one kernel the producers' path spilled 18 registers and the pooled-copy launch (enc0b forward, bound by its producers)
 // ran 5 % slower for registers only the other cases need.
-// S16 (round 5): the MFMA waves issue v_mfma_f32_16x16x32_bf16 instead of 32x32x16 - the SAME output tile per wave (one d-plane of the tile:
-// 128 voxels x BN channels, 128 accumulator registers) cut into 8 h-rows of 16 voxels x BN / 16 channel fragments, the whole 32-channel chunk
-// as ONE k-step.  LDS bytes per MAC are the same ((M + N) * K); what changes is the energy per MAC: on live data the chip is power-limited
-//  and holds a higher clock on this shape (MI355X guide, 'DVFS give-back' item 7).  A 16-lane group of a fragment read is one
-// h-row of the halo at one 16-byte slot - the access pattern the column-keyed swizzle was derived for - and no row rotation is needed.
 // F32 (round 6, the parity mode on the benchmarked kernel structure): fp32 tensors and filters on v_mfma_f32_32x32x2_f32 (exact fp32: the
 // guide's chip table - an fmaf chain per output).  A 64-byte halo / filter row is then 16 fp32 channels instead of 32 bf16 ones and everything
 // that moves or addresses BYTES is unchanged: the launcher passes every channel count that is a memory stride in units of 2 bytes (s.C0, s.C1 =
@@ -746,19 +740,19 @@ k_conv_fwd_mfma(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__
 // differs: a 16-byte fragment is 4 k-values per lane instead of 8 - four MFMAs of k = 2 in place of one of k = 16 - the staged tile holds fp32
 // (NT = 1: 32 channels x 4 B = the 128-byte voxel line of the 64-wide bf16 block), and the element-wise tails (ReLU mask, residual, pool)
 // work on floats.
-template <int NT, bool PL, int MODE, bool RES, bool ASYNC = false, int EPI = -1, bool FH = false, bool S16 = false, bool F32 = false>   // FH: fast halo addressing (producers, below)
+template <int NT, int MODE, bool RES, bool ASYNC = false, int EPI = -1, bool FH = false, bool F32 = false>   // FH: fast halo addressing (producers, below)
 __global__ void __launch_bounds__(fw::NTHREADS)
 k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ bias, const bf16_t* __restrict__ mask,
               const bf16_t* residual, bf16_t* y, int N, int D, int H, int W, int Cout, int act, float alpha, FwdTail tail) {
     constexpr int TD = fw::TD, TH = fw::TH, TW = fw::TW;
     static_assert(!(RES && MODE != 0), "unsupported combination");
-    static_assert(!F32 || (NT == 1 && !PL && !RES && !S16 && EPI < 4 && EPI != 2), "fp32 form: 32-wide blocks, 3-D, asynchronous residual, no logits / normalisation tails");
+    static_assert(!F32 || (NT == 1 && !RES && EPI < 4 && EPI != 2), "fp32 form: 32-wide blocks, asynchronous residual, no logits / normalisation tails");
     constexpr bool PAR = MODE != 0;
     // TIGHT (round 3; the 3-D parity modes): a parity class reads, per axis, only the low-res voxels {g-1, g} or {g, g+1} - a
     // (TD+1) x (TH+1) x (TW+1) box whose origin depends on the parity, not the 6 x 10 x 18 box of the 3-tap conv: 765 instead of 1080 rows,
     // 48 instead of 68 LDS-DMA instructions per chunk.  These launches are bound by their producers' DMA issue (7.7 instructions per wave
     // and 32-MFMA phase): the matrix pipe was 0.38-0.48 busy on them (profiles/r03_pmc_mfma.json).
-    constexpr bool TIGHT = PAR && !PL;
+    constexpr bool TIGHT = PAR;
     constexpr int HD = TIGHT ? TD + 1 : TD + 2, HH = TIGHT ? TH + 1 : TH + 2, HW = TIGHT ? TW + 1 : TW + 2, HVOX = HD * HH * HW;
     constexpr int H_INSTR = (HVOX * 4 + 63) / 64, HALO_BYTES = H_INSTR * 1024;
     // the two halo slots: back to back, or - TIGHT, where a slot (48 KiB) is smaller than the staged tile (64 KiB) - with a 16 KiB gap between
@@ -773,20 +767,16 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
     // per wave and barrier, 2 phases per chunk - with 16 KiB filter slots (BN = 64)
     constexpr int RPP = TIGHT ? 2 : 1;                   // (kd, kh) filter rows per phase
     constexpr int FILT_BYTES = (RPP * NKW > 3 ? RPP * NKW : 3) * BN * 64;
-    constexpr int F_INSTR = RPP * NKW * BN * 64 / 1024;  // 12 / 6 (8 / 4 in the planar up modes, 16 / 8 in the 3-D ones)
+    constexpr int F_INSTR = RPP * NKW * BN * 64 / 1024;  // 12 / 6 (16 / 8 in the parity modes)
     constexpr int DW = 4;                                // DMA (producer) waves = MFMA (consumer) waves
     constexpr int JT = 4;                                // column tiles per consumer wave
-    constexpr int F_PER_WAVE = (F_INSTR + DW - 1) / DW;  // 3 / 2 (2 / 1)
-    // halo DMA instructions per producer wave and chunk.  Planar (2-D slices): halo planes 0 and 5 are never read, only the instructions
-    // 11..56 that touch planes 1-4 are issued (46 -> 12 per wave, the last two are zero copies so that every wave issues the same number)
-    constexpr int H_I0 = PL ? 11 : 0, H_I1 = PL ? 57 : H_INSTR;
-    constexpr int NPIECE = (H_I1 - H_I0 + DW - 1) / DW;  // 17 (12)
-    constexpr int NPAR = PL ? 4 : 8;
-    constexpr int NROW = PAR ? (PL ? 2 : 4) : (PL ? 3 : 9);       // (kd, kh) filter rows per chunk
-    constexpr int NPH = NROW / RPP;                                // phases per chunk
+    constexpr int F_PER_WAVE = (F_INSTR + DW - 1) / DW;  // 3 / 2 (4 / 2)
+    constexpr int NPIECE = (H_INSTR + DW - 1) / DW;      // halo DMA instructions per producer wave and chunk: 17 (12)
+    constexpr int NPAR = 8;
+    constexpr int NROW = PAR ? 4 : 9;                    // (kd, kh) filter rows per chunk
+    constexpr int NPH = NROW / RPP;                      // phases per chunk
     static_assert(NPH * RPP == NROW, "rows per phase");
-    constexpr int PH0 = PL ? 3 : 0;
-    constexpr bool ASY = ASYNC && !RES && !PL && MODE == 0;
+    constexpr bool ASY = ASYNC && !RES && MODE == 0;
     constexpr bool HAS_MASK = EPI < 0 || EPI == 1, HAS_LOGITS = !F32 && (EPI < 0 || EPI == 2), HAS_POOL = EPI <= 0;
     // EPI 3 (ASYNC only): y = act(staged + residual) - the skip launch of the parity form.  The MFMA waves stage bf16(acc + bias) WITHOUT the
     // activation; the producers add the residual lines (prefetched like the mask lines) in fp32, activate, round and store.  One bf16 rounding
@@ -890,10 +880,7 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
         const int rt = v >> 5, rr = v & 31;
         int64_t org;
         unsigned off;
-        if constexpr (MODE == 1 && PL) {
-            org = ((((int64_t)it.n * D + it.d0) * 2 * H + 2 * it.h0 + ((it.par >> 1) & 1)) * 2 * W + 2 * it.w0 + (it.par & 1)) * CoutB + (F32 ? 2 : 1) * it.co0;
-            off = ((tile_d(rt) * 2 * H + 2 * tile_h(rt, rr)) * 2 * W + 2 * lane_w(rr)) * CoutB + q * 8;
-        } else if constexpr (MODE == 1) {
+        if constexpr (MODE == 1) {
             org = ((((int64_t)it.n * 2 * D + 2 * it.d0 + (it.par >> 2)) * 2 * H + 2 * it.h0 + ((it.par >> 1) & 1)) * 2 * W + 2 * it.w0 + (it.par & 1)) * CoutB + (F32 ? 2 : 1) * it.co0;
             off = ((2 * tile_d(rt) * 2 * H + 2 * tile_h(rt, rr)) * 2 * W + 2 * lane_w(rr)) * CoutB + q * 8;
         } else {
@@ -1169,7 +1156,7 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
         // halo piece ph: hd | hh<<4 | hw<<8 | ls<<13 | valid<<15 | edge<<16, edge = which faces of the halo box the row lies on
         // (bit 0 hd == 0, 1 hd == HD-1, 2 hh == 0, 3 hh == HH-1, 4 hw == 0, 5 hw == HW-1): the only rows a border tile can have outside the volume
         auto make_pack = [&](int ph, int ln) {
-            const int i = (H_I0 + ph * DW + dwv) * 64 + ln;
+            const int i = (ph * DW + dwv) * 64 + ln;
             const int hv = i >> 2, ps = i & 3;
             const int hvc = hv < HVOX ? hv : 0;
             const int hw_ = hvc % HW, hq = hvc / HW;
@@ -1198,7 +1185,7 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
         auto issue_filter = [&](const FwdItem& it, int pl, int fb) {
             int64_t slab;
             int koff;
-            if constexpr (MODE == 0) { slab = PH0 + pl; koff = it.ch << 5; }
+            if constexpr (MODE == 0) { slab = pl; koff = it.ch << 5; }
             else if constexpr (MODE == 1) { slab = it.par * NROW + pl * RPP; koff = it.ch << 5; }
             else { slab = (it.ch / kpc) * NROW + pl * RPP; koff = (it.ch % kpc) << 5; }
             const bf16_t* const base = wt + ((slab * NKW * Cout + it.co0) * Krow + koff);
@@ -1210,9 +1197,9 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
         // source address of every halo piece, kept across the chunks of a tile (+ 32 channels per chunk) - except in the instantiations
         // whose drain needs the registers (EPI 5 / 6: prefetched lines + partial sums): those rebuild a piece's address when they issue it
         constexpr bool KEEP_HP = EPI < 5;
-        const bf16_t* hp[(KEEP_HP && !(FH && !PL && EPI < 5)) ? NPIECE : 1];
-        unsigned hoff[(FH && !PL && EPI < 5) ? NPIECE : 1];      // FH: the per-lane byte offset of each piece inside the halo box (constant for the whole kernel)
-        unsigned heff[(FH && !PL && EPI < 5) ? NPIECE : 1];      // ... as issued for the current tile: out of range (DMA_OOB) where the row leaves the volume
+        const bf16_t* hp[(KEEP_HP && !(FH && EPI < 5)) ? NPIECE : 1];
+        unsigned hoff[(FH && EPI < 5) ? NPIECE : 1];      // FH: the per-lane byte offset of each piece inside the halo box (constant for the whole kernel)
+        unsigned heff[(FH && EPI < 5) ? NPIECE : 1];      // ... as issued for the current tile: out of range (DMA_OOB) where the row leaves the volume
         auto halo_src = [&](const FwdItem& it, int pk) -> const bf16_t* {
             int od = 0, oh = 0, ow = 0;                            // TIGHT: the box starts at g - 1 + (parity of the taps) per axis
             if constexpr (TIGHT) {
@@ -1224,9 +1211,9 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
             const bool ok = ((pk >> 15) & 1) && (unsigned)gd < (unsigned)D && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W;
             if constexpr (MODE == 2) {
                 const int p = it.ch / kpc, coff = (it.ch % kpc) << 5;
-                const int sd = PL ? min(max(gd, 0), D - 1) : 2 * min(max(gd, 0), D - 1) + (p >> 2);
+                const int sd = 2 * min(max(gd, 0), D - 1) + (p >> 2);
                 const int sh = 2 * min(max(gh, 0), H - 1) + ((p >> 1) & 1), sw = 2 * min(max(gw, 0), W - 1) + (p & 1);
-                const int64_t off = ((((int64_t)it.n * (PL ? D : 2 * D) + sd) * 2 * H + sh) * 2 * W + sw) * s.C0 + coff + ls * 8;
+                const int64_t off = ((((int64_t)it.n * 2 * D + sd) * 2 * H + sh) * 2 * W + sw) * s.C0 + coff + ls * 8;
                 return ok ? s.p0 + off : (const bf16_t*)zpage;
             } else {
                 const int cc = it.ch << 5;
@@ -1243,12 +1230,12 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
                 return ok ? real : (const bf16_t*)zpage;
             }
         };
-        static_assert(NPIECE * DW >= H_I1 - H_I0 && NPIECE * DW - (H_I1 - H_I0) < DW, "piece map");
+        static_assert(NPIECE * DW >= H_INSTR && NPIECE * DW - H_INSTR < DW, "piece map");
         auto issue_halo = [&](int ph, int slot, const bf16_t* src) {
-            const int instr = H_I0 + ph * DW + dwv;
+            const int instr = ph * DW + dwv;
             // every wave issues exactly NPIECE instructions per chunk (the counted s_waitcnt below relies on it): the few past the last live
             // instruction copy zeros into the dead rows behind it
-            const bool dead = instr >= H_I1;
+            const bool dead = instr >= H_INSTR;
             dma16(dead ? (const void*)zpage : (const void*)src, __builtin_amdgcn_readfirstlane(lds0 + slot * HALO_STRIDE + instr * 1024));
         };
         // FAST halo addressing (round 4; plain single-source 3-D launches = every MODE 0 launch of the benchmarked step).  The producers'
@@ -1263,13 +1250,13 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
         // `global_load_lds` with a scalar base + 32-bit lane offset and NO vector address arithmetic, border tiles select the zero page per lane.
         // The parity modes (TIGHT box; MODE 2 gathers voxel 2g + p of dy) have the same structure: the parity moves the box's origin (od, oh, ow) -
         // and with it which faces can leave the volume - and, MODE 2, the scalar base; the lane constant uses doubled strides there.
-        constexpr bool FASTH_CT = FH && !PL && KEEP_HP && KEEP_PACK;
+        constexpr bool FASTH_CT = FH && KEEP_HP && KEEP_PACK;
         // ... for launches whose pieces are mostly FRESH: with many chunks per tile (or, MODE 2, per parity class) the old scheme's "advance
         // every lane's pointer by 64 B" (two vector instructions per piece) beats one base computation per item + a per-lane border select per
         // piece (measured: dec2a / dec1a parity launches 3-7 % slower with the fast form, enc0b 10-15 % and dec0a's input gradient 7 % faster).
-        // Its OWN instantiation (template parameter FH, chosen by the launcher for single-source launches with at most two chunks per fresh
-        // address): compiled into one kernel behind a run-time switch, the second path cost the launches that do not take it 5-8 %
-        // (profiles/r04_fast_halo_ab.log).
+        // (Round 5's buffer-descriptor form below reversed that: the launcher now takes FH for every single-source launch.)  Its OWN
+        // instantiation (template parameter FH): compiled into one kernel behind a run-time switch, the second path cost the launches that do
+        // not take it 5-8 % (profiles/r04_fast_halo_ab.log).
         constexpr bool fasth = FASTH_CT;
         auto fast_off = [&](int pk) -> unsigned {
             const int hd_ = pk & 15, hh_ = (pk >> 4) & 15, hw_ = (pk >> 8) & 31, ls = (pk >> 13) & 3;
@@ -1308,10 +1295,10 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
         // selected the zero page per lane for every piece of every chunk of a border tile, and the launches with many chunks per tile, whose
         // deep levels consist of border tiles, stayed on the pointer-advance scheme for it.)
         auto issue_halo_fast = [&](int ph, int slot, i32x4 rs, unsigned tmask, bool fresh_item) {
-            const int instr = H_I0 + ph * DW + dwv;
+            const int instr = ph * DW + dwv;
             const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + slot * HALO_STRIDE + instr * 1024);
             if (fresh_item) {
-                const bool bad = instr >= H_I1 || (((unsigned)h_pack[ph] >> 16) & (tmask | 64u)) != 0;
+                const bool bad = instr >= H_INSTR || (((unsigned)h_pack[ph] >> 16) & (tmask | 64u)) != 0;
                 heff[ph] = bad ? DMA_OOB : hoff[ph];
             }
             dma16_buf(rs, heff[ph], dst);
@@ -1536,69 +1523,31 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
 
     // ---------------------------------------------------------------------------------------------------------------- consumer
     const int cw = wv;
-    if (tail.prio) __builtin_amdgcn_s_setprio(3);
-    static_assert(!(S16 && PL), "the 16x16x32 form covers the 3-D launches");
-    // S16: fragment index j = h-row of the wave's d-plane (16 voxels along w: lane & 15), c = 16-channel block; a lane's four accumulator
-    // registers are channels 16 c + 4 kq .. + 3 of its voxel (kq = lane >> 4, also the 8-channel k-group the lane reads of both operands)
-    constexpr int JN = S16 ? 8 : JT, CN = S16 ? 2 * NT : NT;
-    typedef std::conditional_t<S16, f32x4, f32x16> acc_t;
-    const int w16 = lane & 15, kq = lane >> 4;
-    acc_t acc[JN][CN];
-    // (S16 keeps only the first NT floats4 of bv: [c >> 2][c & 3] = the lane's 4 channels of 16-channel block c)
+    f32x16 acc[JT][NT];
     auto load_bias = [&](int co0, float4 (&bv)[NT][4]) {
-        if constexpr (S16) {
 #pragma unroll
-            for (int c = 0; c < CN; ++c)
-                bv[c >> 2][c & 3] = bias ? *reinterpret_cast<const float4*>(bias + co0 + c * 16 + 4 * kq) : make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
+        for (int c = 0; c < NT; ++c)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq)
+                bv[c][gq] = bias ? *reinterpret_cast<const float4*>(bias + co0 + c * 32 + 8 * gq + 4 * hk) : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    auto init_acc = [&](const float4 (&bv)[NT][4]) {
+#pragma unroll
+        for (int j = 0; j < JT; ++j)
 #pragma unroll
             for (int c = 0; c < NT; ++c)
 #pragma unroll
-                for (int gq = 0; gq < 4; ++gq)
-                    bv[c][gq] = bias ? *reinterpret_cast<const float4*>(bias + co0 + c * 32 + 8 * gq + 4 * hk) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto init_acc = [&](const float4 (&bv)[NT][4]) {
-        if constexpr (S16) {
-#pragma unroll
-            for (int j = 0; j < JN; ++j)
-#pragma unroll
-                for (int c = 0; c < CN; ++c) {
-                    acc[j][c] = __builtin_bit_cast(f32x4, bv[c >> 2][c & 3]);
+                for (int gq = 0; gq < 4; ++gq) {
+                    acc[j][c][4 * gq] = bv[c][gq].x;
+                    acc[j][c][4 * gq + 1] = bv[c][gq].y;
+                    acc[j][c][4 * gq + 2] = bv[c][gq].z;
+                    acc[j][c][4 * gq + 3] = bv[c][gq].w;
                 }
-        } else {
-#pragma unroll
-            for (int j = 0; j < JT; ++j)
-#pragma unroll
-                for (int c = 0; c < NT; ++c)
-#pragma unroll
-                    for (int gq = 0; gq < 4; ++gq) {
-                        acc[j][c][4 * gq] = bv[c][gq].x;
-                        acc[j][c][4 * gq + 1] = bv[c][gq].y;
-                        acc[j][c][4 * gq + 2] = bv[c][gq].z;
-                        acc[j][c][4 * gq + 3] = bv[c][gq].w;
-                    }
-        }
     };
     // RES with per-border-class bias (tail.bias27): accumulators of the tile `it` start from the bias of each lane's own output voxel.
     // Interior tiles (most) take the interior class 13 for every lane; tiles on a face of the volume look the class up per voxel.
     auto init_acc_b27 = [&](const FwdItem& it) {
         const bool border = it.d0 == 0 || it.d0 + TD == D || it.h0 == 0 || it.h0 + TH == H || it.w0 == 0 || it.w0 + TW == W;
-        if constexpr (S16) {
-#pragma unroll
-            for (int j = 0; j < JN; ++j) {
-                int cls = 13;
-                if (border) {
-                    const int d = it.d0 + cw, h = it.h0 + j, w = it.w0 + w16;
-                    cls = ((d == 0 ? 0 : (d == D - 1 ? 2 : 1)) * 3 + (h == 0 ? 0 : (h == H - 1 ? 2 : 1))) * 3 + (w == 0 ? 0 : (w == W - 1 ? 2 : 1));
-                }
-                const float* const bp = tail.bias27 + (int64_t)cls * Cout + it.co0 + 4 * kq;
-#pragma unroll
-                for (int c = 0; c < CN; ++c) {
-                    acc[j][c] = *reinterpret_cast<const f32x4*>(bp + c * 16);
-                }
-            }
-        } else {
 #pragma unroll
         for (int j = 0; j < JT; ++j) {
             int cls = 13;
@@ -1619,21 +1568,19 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
                     acc[j][c][4 * gq + 3] = b4.w;
                 }
         }
-        }
     };
     // lane r of a column tile: h-row r>>4, w rotated by HW mod 16 on the second row (conflict-free ds_read_b128 groups, see k_conv_fwd_mfma)
     // B-fragment (halo) addresses of this lane: [k-step][kw (+ the parity's first kw)] for column tile 0 of this wave, filter row (0, 0), in
     // the halo slot the NEXT request goes to (the slot's base is added / subtracted once per item); everything else is an immediate
     static_assert(JT == 4, "tile_d(JT * cw + j) = cw, tile_h = 2 j + (r >> 4)");
-    // (S16: pre[0][kw] only - voxel w16 of h-row 0 of the wave's d-plane, slot kq: the chunk's 32 channels are one k-step)
     int pre[2][3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int hwc = (S16 ? w16 : lane_w(r)) + k;
-        pre[0][k] = S16 ? (cw * HH * HW + hwc) * 64 + ((kq ^ halo_key(hwc)) << 4) : ((cw * HH + (r >> 4)) * HW + hwc) * 64 + ((hk ^ halo_key(hwc)) << 4);
+        const int hwc = lane_w(r) + k;
+        pre[0][k] = ((cw * HH + (r >> 4)) * HW + hwc) * 64 + ((hk ^ halo_key(hwc)) << 4);
         pre[1][k] = pre[0][k] ^ 32;
     }
-    const int fa[2] = {S16 ? swz64(w16, kq) : swz64(r, hk), swz64(r, hk) ^ 32};
+    const int fa[2] = {swz64(r, hk), swz64(r, hk) ^ 32};
     if ((RES || HAS_RESID) && tail.bias27) init_acc_b27(cur);
     else {
         float4 bv0[NT][4];
@@ -1644,12 +1591,8 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
     unsigned long long cprof[12] = {};
     PROF_T(ck0);
 #endif
-    // double-buffered filter / halo fragments (live across the phases of a tile).  S16: a halo fragment serves CN consecutive MFMAs and is
-    // dead after them - the next step's is requested into the same registers (fb_[0] only)
-    // (S16, NBR = 4: the halo fragments run FOUR 4-MFMA blocks - 256 cycles of matrix pipe, the look-ahead of the 32x32x16 form - ahead
-    // of their use in a ring of four: a whole step's eight fragments held 16 registers more than the 64-wide instantiations have)
-    constexpr int NBR = 4;
-    bf16x8_t fa_[2][CN], fb_[2][S16 ? NBR : JN];
+    // double-buffered filter / halo fragments (live across the phases of a tile)
+    bf16x8_t fa_[2][NT], fb_[2][JT];
     // RES: the residual's 16-byte lines this lane adds in the epilogue, [column tile][store instruction] (see the RES epilogue)
     constexpr int RKK = RES ? 32 / (64 / (BN / 8)) : 1;
     // column tiles whose lines are requested a phase early: none - 16 registers per tile at BN = 64 held across the last phase's MFMAs made
@@ -1663,9 +1606,7 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
         return *reinterpret_cast<const uint4*>(residual + org + ((tile_d(rt) * H + tile_h(rt, rr)) * W + lane_w(rr)) * Cout + q8 * 8);
     };
     // The consumers' stream: item_next() works out the item after `cur`, run_item() is the phases of `cur`, tile_epilogue() what follows a
-    // tile's last chunk.  The 32x32x16 form drives them as ONE flat loop over items (rounds 1-4).  S16 drives them as a loop over tiles
-    // around a loop over the tile's chunks: in the flat form hipcc (ROCm 7.2) failed to coalesce the accumulator phis of the conditional
-    // epilogue for the 32 four-register accumulators - three copies of all of them alive at the merge, 545 spills at BN = 64.
+    // tile's last chunk, driven as ONE flat loop over items.
     bool has_next = true;
     FwdItem nxt = cur;
     int npair = pair;
@@ -1683,49 +1624,38 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
     auto run_item = [&]() {
 #pragma unroll
         for (int k = 0; k < 3; ++k) asm volatile("" : "+v"(pre[0][k]), "+v"(pre[1][k]));
-        // (halo slot, halo row offset of the (kd,kh) row, first kw) of phase `pl` of item `it` whose halo sits in slot `slot`
-        auto phase_hoff = [&](const FwdItem& it, int pl, int& kw0) {
-            kw0 = 0;
-            if constexpr (!PAR) return (((PH0 + pl) / 3) * HH + ((PH0 + pl) % 3)) * HW;
-            else {
-                if constexpr (TIGHT) return pl * HH * HW;        // phase pl = filter rows (kd' = pl, kh' = 0, 1); the parity is in the box's origin
-                const int p = MODE == 1 ? it.par : (NPAR - 1) - it.ch / kpc;
-                kw0 = p & 1;
-                if constexpr (PL) return (HH + pl + ((p >> 1) & 1)) * HW;
-                else return (((pl >> 1) + (p >> 2)) * HH + ((pl & 1) + ((p >> 1) & 1))) * HW;
-            }
+        // halo row offset of the (kd,kh) row of phase `pl`
+        auto phase_hoff = [](int pl) {
+            if constexpr (!PAR) return ((pl / 3) * HH + (pl % 3)) * HW;
+            else return pl * HH * HW;                        // TIGHT: phase pl = filter rows (kd' = pl, kh' = 0, 1); the parity is in the box's origin
         };
-        constexpr int NST = RPP * NKW * (S16 ? 1 : 2);         // steps of a phase: (filter row, kw, k-step); S16: (filter row, kw)
+        constexpr int NST = RPP * NKW * 2;                   // steps of a phase: (filter row, kw, k-step)
         // One wave per SIMD feeds the MFMA pipe alone: the fragments of step st+1 (a (kw, k-step) pair) are requested before the MFMAs of
         // step st are issued, into the other half of a double register set, threaded between those MFMAs (left to the compiler the reads
         // sat right in front of their MFMAs).  The pipeline runs ACROSS the phase barrier inside a tile: once the fragments of a phase's
         // last step are in registers this wave is done reading the rings, so it passes the next phase's barrier BEFORE issuing that step's
         // MFMAs and requests the next phase's first fragments under them - only the first phase of a tile starts with an exposed LDS latency.
         auto load_a = [&](const unsigned char* lfp, int st, int buf) {
-            const int t = S16 ? st : st >> 1, ks = S16 ? 0 : st & 1;          // t = filter row of the phase * NKW + kw: the slab holds them in this order
+            const int t = st >> 1, ks = st & 1;          // t = filter row of the phase * NKW + kw: the slab holds them in this order
 #pragma unroll
-            for (int c = 0; c < CN; ++c) fa_[buf][c] = *reinterpret_cast<const bf16x8_t*>(lfp + fa[ks] + (t * BN + c * (S16 ? 16 : 32)) * 64);
+            for (int c = 0; c < NT; ++c) fa_[buf][c] = *reinterpret_cast<const bf16x8_t*>(lfp + fa[ks] + (t * BN + c * 32) * 64);
         };
-        auto load_b = [&](int hoffp, int kw0p, int st, int buf, int j) {
-            const int t = S16 ? st : st >> 1, ks = S16 ? 0 : st & 1;
+        auto load_b = [&](int hoffp, int st, int buf, int j) {
+            const int t = st >> 1, ks = st & 1;
             const int kw = t % NKW, row = t / NKW;       // (row > 0 only with RPP = 2: the phase's second filter row = the next h-row of the halo)
-            int base;
-            if constexpr (PAR && !TIGHT) base = kw0p ? pre[ks][kw + 1] : pre[ks][kw];
-            else base = pre[ks][kw];
-            // a 32-voxel column tile is two h-rows (the lane's row is in `pre`), an S16 fragment is one
-            fb_[S16 ? 0 : buf][S16 ? j % NBR : j] = *reinterpret_cast<const bf16x8_t*>(lds + base + (hoffp + (row + (S16 ? j : 2 * j)) * HW) * 64);
+            // a 32-voxel column tile is two h-rows (the lane's row is in `pre`)
+            fb_[buf][j] = *reinterpret_cast<const bf16x8_t*>(lds + pre[ks][kw] + (hoffp + (row + 2 * j) * HW) * 64);
         };
 #pragma unroll
         for (int pl = 0; pl < NPH; ++pl, ++g) {
             PROF_T(c0);
             const unsigned char* const lf = lds + HALO_SPAN + (g & 1) * FILT_BYTES;
-            int kw0;
-            const int hoff = phase_hoff(cur, pl, kw0);
+            const int hoff = phase_hoff(pl);
             if (pl == 0 && cur.ch == 0) {          // first phase of a tile: nothing was primed across the epilogue
                 __builtin_amdgcn_s_barrier();
                 load_a(lf, 0, 0);
 #pragma unroll
-                for (int j = 0; j < (S16 ? NBR : JN); ++j) load_b(hoff, kw0, 0, 0, j);
+                for (int j = 0; j < JT; ++j) load_b(hoff, 0, 0, j);
             }
             PROF_T(c1);
             if constexpr (RES) {
@@ -1743,45 +1673,35 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
                 // a next phase of the SAME tile follows (same chunk, or the next chunk of this tile in the other halo slot)
                 const bool chain = last && (pl + 1 < NPH || cur.ch + 1 < nch);
                 const unsigned char* lfn = lf;
-                int hoffn = hoff, kw0n = kw0, stn = st + 1;
+                int hoffn = hoff, stn = st + 1;
                 if (last) {
                     stn = 0;
                     lfn = lds + HALO_SPAN + ((g + 1) & 1) * FILT_BYTES;
-                    if (pl + 1 < NPH) hoffn = phase_hoff(cur, pl + 1, kw0n);
+                    if (pl + 1 < NPH) hoffn = phase_hoff(pl + 1);
                     else {
                         // every later request is for the next item, whose halo sits in the other slot: move the six addresses there
-                        hoffn = phase_hoff(nxt, 0, kw0n);
-                        if constexpr (!S16) {
-                            const int dlt = hb ? -HALO_STRIDE : HALO_STRIDE;
+                        hoffn = phase_hoff(0);
+                        const int dlt = hb ? -HALO_STRIDE : HALO_STRIDE;
 #pragma unroll
-                            for (int k = 0; k < 3; ++k) { pre[0][k] += dlt; pre[1][k] += dlt; }
-                        }
+                        for (int k = 0; k < 3; ++k) { pre[0][k] += dlt; pre[1][k] += dlt; }
                     }
                 }
                 // the hand-over to the next phase: this phase's last fragments are in registers = this wave is done with the rings, so it
                 // passes the next phase's barrier here, in front of the MFMAs that still use them
-                auto hand_over = [&]() {
-                    if (chain) {
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();                          // = the next phase's barrier
-                    }
-                };
-                if constexpr (!S16) hand_over();
+                if (chain) {
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();                          // = the next phase's barrier
+                }
                 // The two filter-fragment buffers alternate per step through the whole chunk (step pl * NST + st; a chunk's first step uses
-                // buffer 0).  The plain S16 form has 27 steps per chunk: its last step sits in buffer 0 as well, so the next chunk's first
-                // filter fragments are requested AFTER that step's MFMAs have been issued (one exposed LDS latency per chunk, ~1 %; a third
-                // buffer costs 16 registers the 64-wide instantiations do not have: 41 spills, some inside this loop).
+                // buffer 0)
                 const int ab = (pl * NST + st) & 1;
-                const bool late = (NPH * NST) % 2 == 1 && pl == NPH - 1 && last;
                 const int abn = (last && pl == NPH - 1) ? 0 : ab ^ 1;
-                // (S16, last step: the next phase's filter fragments are requested behind the hand-over, inside the block loop)
-                if ((!last || (chain && !S16)) && !late) load_a(lfn, stn, abn);
+                if (!last || chain) load_a(lfn, stn, abn);
 #pragma unroll
-                for (int j = 0; j < JN; ++j) {
+                for (int j = 0; j < JT; ++j) {
 #pragma unroll
-                    for (int c = 0; c < CN; ++c) {
-                        if constexpr (S16) acc[j][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_[ab][c], fb_[0][j % NBR], acc[j][c], 0, 0, 0);
-                        else if constexpr (F32) {
+                    for (int c = 0; c < NT; ++c) {
+                        if constexpr (F32) {
                             // the 16 bytes of a fragment are four fp32 k-values: lanes 0-31 hold channels 8 ks + i, lanes 32-63 channels
                             // 8 ks + 4 + i of the same row - the two k of MFMA i, in both operands alike
                             const f32x4 af = __builtin_bit_cast(f32x4, fa_[ab][c]), bf = __builtin_bit_cast(f32x4, fb_[ab][j]);
@@ -1789,28 +1709,9 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
                             for (int i = 0; i < 4; ++i) acc[j][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[i], acc[j][c], 0, 0, 0);
                         } else acc[j][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa_[ab][c], fb_[ab][j], acc[j][c], 0, 0, 0);
                     }
-                    if constexpr (S16) {
-                        // the fragment NBR blocks on takes this one's place: of this step while it has them, else of the next one
-                        if (j + NBR < JN) load_b(hoff, kw0, st, 0, j + NBR);
-                        else {
-                            if (last && j + NBR == JN) {
-                                // a phase's last step: its last request into the rings went out a block ago.  (The chunk's last phase: the next
-                                // item's halo sits in the other slot - the three addresses move there now, not before: the requests of
-                                // blocks 0 .. JN - NBR - 1 still went to this chunk's slot, which the barrier below hands to the producers.)
-                                hand_over();
-                                if (pl + 1 == NPH) {
-                                    const int dlt = hb ? -HALO_STRIDE : HALO_STRIDE;
-#pragma unroll
-                                    for (int k = 0; k < 3; ++k) pre[0][k] += dlt;
-                                }
-                                if (chain && !late) load_a(lfn, stn, abn);
-                            }
-                            if (!last || chain) load_b(hoffn, kw0n, stn, 0, j + NBR - JN);
-                        }
-                    } else if (!last || chain) load_b(hoffn, kw0n, stn, abn, j);
+                    if (!last || chain) load_b(hoffn, stn, abn, j);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if (late && chain) load_a(lfn, stn, abn);
             }
             PROF_T(c2);
 #ifdef FMRI_PROF
@@ -1837,19 +1738,6 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
             unsigned char* const stage = lds + hb * HALO_BYTES + cw * (32 * BN * 4);
 #pragma unroll
             for (int j = 0; j < JT; ++j) {
-                if constexpr (S16) {
-                    // column tile j = h-rows 2 j and 2 j + 1 of the plane; the lane's voxel sits at index rr of the tile (second row rotated, lane_w)
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        const int rr = jj ? 16 + ((w16 + (HW & 15)) & 15) : w16;
-#pragma unroll
-                        for (int c = 0; c < CN; ++c) {
-                            const int q = c * 4 + kq;
-                            *reinterpret_cast<float4*>(stage + rr * (BN * 4) + (((q ^ rr) & (PPV - 1)) << 4)) =
-                                make_float4(acc[2 * j + jj][c][0], acc[2 * j + jj][c][1], acc[2 * j + jj][c][2], acc[2 * j + jj][c][3]);
-                        }
-                    }
-                } else {
 #pragma unroll
                 for (int c = 0; c < NT; ++c)
 #pragma unroll
@@ -1858,7 +1746,6 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
                         *reinterpret_cast<float4*>(stage + r * (BN * 4) + (((q ^ r) & (PPV - 1)) << 4)) =
                             make_float4(acc[j][c][4 * gq], acc[j][c][4 * gq + 1], acc[j][c][4 * gq + 2], acc[j][c][4 * gq + 3]);
                     }
-                }
                 const int rt = JT * cw + j;
 #pragma unroll
                 for (int kk = 0; kk < 32 / VPI; ++kk) {
@@ -1903,44 +1790,7 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
                 constexpr int ACT = decltype(act_tag)::value;
                 unsigned zero2_ = 0u;
                 asm volatile("" : "+v"(zero2_));
-                if constexpr (S16) {
-                    // a lane holds 4 channels (two dwords of bf16) of its voxel per 16-channel block; v_permlane16_swap of blocks 2 p and 2 p + 1
-                    // (rows 1 <-> 0 and 3 <-> 2 of the two operands) leaves every lane with one 16-byte piece: lane row kq gets piece
-                    // 4 p + 2 (kq & 1) + (kq >> 1) of the voxel's BN / 8
-#pragma unroll
-                    for (int j = 0; j < JN; ++j) {
-                        const int v = (j >> 1) * 32 + ((j & 1) ? 16 + ((w16 + (HW & 15)) & 15) : w16);      // place in the staged tile (lane_w's rotation on odd rows)
-                        const int vs = NT == 2 ? (v & 7) : ((v >> 2) & 3);
-#pragma unroll
-                        for (int p = 0; p < NT; ++p) {
-                            unsigned pk[2][2];
-#pragma unroll
-                            for (int u = 0; u < 2; ++u) {
-                                float o[4];
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) {
-                                    const float vv = acc[j][2 * p + u][i];
-                                    if constexpr (ACT == FMRI_ACT_LEAKY) o[i] = vmax(vv, __builtin_fmaf(vv, act_s, 0.f));
-                                    else o[i] = vv;
-                                }
-                                pk[u][0] = pack2bf(o[0], o[1]);
-                                pk[u][1] = pack2bf(o[2], o[3]);
-                                if constexpr (ACT == FMRI_ACT_RELU) {
-                                    pk[u][0] = relu2(pk[u][0], zero2_);
-                                    pk[u][1] = relu2(pk[u][1], zero2_);
-                                }
-                            }
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) {
-                                auto sw = __builtin_amdgcn_permlane16_swap(pk[0][q], pk[1][q], false, false);
-                                pk[0][q] = sw[0];
-                                pk[1][q] = sw[1];
-                            }
-                            const int q = p * 4 + ((kq & 1) << 1) + (kq >> 1);
-                            *reinterpret_cast<uint4*>(stage + v * (BN * 2) + (((q ^ vs) & SWM) << 4)) = make_uint4(pk[0][0], pk[0][1], pk[1][0], pk[1][1]);
-                        }
-                    }
-                } else if constexpr (F32) {
+                if constexpr (F32) {
                     // a lane's registers 4 gq .. 4 gq + 3 are channels 8 gq + 4 hk .. + 3 of its voxel: one 16-byte piece (number 2 gq + hk of the
                     // voxel's eight) as they are - no packing, no half-wave exchange
 #pragma unroll
@@ -2026,31 +1876,14 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
         { PROF_T(ce1); cprof[4] += ce1 - ce0; }
 #endif
     };
-    if constexpr (S16) {
-        while (true) {
-            while (true) {
-                item_next();
-                run_item();
-                if (cur.ch == nch - 1) break;
-                cur = nxt;
-                hb ^= 1;
-            }
-            tile_epilogue();
-            if (!has_next) break;
-            cur = nxt;
-            pair = npair;
-            hb ^= 1;
-        }
-    } else {
-        while (true) {
-            item_next();
-            run_item();
-            if (cur.ch == nch - 1) tile_epilogue();
-            if (!has_next) break;
-            cur = nxt;
-            pair = npair;
-            hb ^= 1;
-        }
+    while (true) {
+        item_next();
+        run_item();
+        if (cur.ch == nch - 1) tile_epilogue();
+        if (!has_next) break;
+        cur = nxt;
+        pair = npair;
+        hb ^= 1;
     }
 #ifdef FMRI_PROF
     PROF_T(ck1);
@@ -2063,18 +1896,14 @@ k_conv_fwd_ws(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__ b
 }  // namespace
 
 // --------------------------------------------------------------------------------------------------------- host dispatch
-static int fwd_f32_mfma() {             // FMRI_F32_MFMA=0: fp32 tensors stay on the VALU kernels of conv3d_generic.hip (rounds 1-5)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("FMRI_F32_MFMA");
-        v = e ? atoi(e) : 1;
-    }
+int fmri_f32_mfma() {                   // FMRI_F32_MFMA=0: fp32 tensors stay on the VALU kernels of conv3d_generic.hip (rounds 1-5)
+    static const int v = env_int("FMRI_F32_MFMA", 1, {0, 1});
     return v;
 }
 bool conv3d_fwd_mfma_ok(int C0, int C1, int Cout, int D, int H, int W, int dtype) {
     if (dtype == FMRI_F32) {
         // fp32 on v_mfma_f32_32x32x2_f32 (k_conv_fwd_ws<..., F32>): 16-channel chunks (64-byte rows), 32-wide Cout blocks, the 4x8x16 tiling
-        if (!fwd_f32_mfma() || (C0 % 16) || (C1 % 16) || C0 + C1 < 16 || (Cout % 32)) return false;
+        if (!fmri_f32_mfma() || (C0 % 16) || (C1 % 16) || C0 + C1 < 16 || (Cout % 32)) return false;
         if ((D % fw::TD) || (H % fw::TH) || (W % fw::TW)) return false;
         C0 *= 2;                                         // everything below counts 2-byte units
         C1 *= 2;
@@ -2095,42 +1924,24 @@ bool conv3d_fwd_needs_cube(int D, int H, int W) { return (D % fw::TD) || (H % fw
 
 // mode 0: plain conv (residual != nullptr selects the RES epilogue); 1: up-forward (src0 = LOW-res tensor, D/H/W = low-res dims,
 // y = [2D][2H][2W] partial sums); 2: up-backward (src0 = dy [2D][2H][2W][C0], y = gradient of the low-res tensor)
-static int fwd_use_ws() {               // FMRI_FWD_WS=0: the symmetric kernel (every wave issues DMA and MFMAs) instead of the warp-specialised one
-    static int use_ws = -1;
-    if (use_ws < 0) {
-        const char* e = getenv("FMRI_FWD_WS");
-        use_ws = e ? atoi(e) : 1;
-    }
-    return use_ws;
-}
-static int fwd_fast_halo() {            // FMRI_FAST_HALO=0: every halo piece's address worked out per lane as in rounds 1-3 (A/B)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("FMRI_FAST_HALO");
-        v = e ? atoi(e) : 1;
-    }
-    return v;
-}
-static int fwd_async() {                // FMRI_FWD_ASYNC=0: the tile's stores by all eight waves behind a barrier (the round-2 epilogue)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("FMRI_FWD_ASYNC");
-        v = e ? atoi(e) : 1;
-    }
-    return v;
-}
-static int fwd_mfma16() {               // FMRI_MFMA16=0: v_mfma_f32_32x32x16_bf16 in the warp-specialised forward kernel (rounds 1-4), 1: 16x16x32 (S16)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("FMRI_MFMA16");
-        v = e ? atoi(e) : 0;
-    }
+static bool fwd_use_ws() {              // FMRI_FWD_WS=0: the symmetric kernel (every wave issues DMA and MFMAs) instead of the warp-specialised one
+    static const bool v = env_int("FMRI_FWD_WS", 1, {0, 1});
     return v;
 }
 static bool fwd_wide(int mode, int planar, int ntile, int Cout) {
     // 64-wide Cout blocks halve the halo traffic per MFMA, but a launch with fewer (tile, block) pairs than CUs (the 8x16x16 bottleneck
     // level) leaves CUs idle: 32-wide blocks double the pairs there
     return Cout % 64 == 0 && (int64_t)ntile * (Cout / 64) * (mode == 1 ? (planar ? 4 : 8) : 1) >= fwd_cu_count();
+}
+
+// launches the kernel instantiation given as the macro's argument with the launcher's arguments and `grid` workgroups
+#define FMRI_FWD(...)                                                                                                      \
+    __VA_ARGS__<<<grid, fw::NTHREADS, 0, st>>>(s, (const bf16_t*)w, bias, (const bf16_t*)mask, (const bf16_t*)residual, (bf16_t*)y, N, D, H, W, \
+                                               Cout, act, alpha, tail)
+// body(std::true_type / std::false_type): a run-time choice between two instantiations
+template <class F> static void fwd_choose(bool b, F&& body) {
+    if (b) body(std::true_type{});
+    else body(std::false_type{});
 }
 
 // fp32 launches: 32-wide Cout blocks, asynchronous epilogue throughout (plain store / pooled copy, ReLU mask, residual), parity modes on the
@@ -2145,27 +1956,22 @@ static int conv3d_fwd_mfma_launch_f32(int mode, const void* src0, int C0, int up
     const int ncu = fwd_cu_count();
     const int np = ntile * (Cout / 32) * (mode == 1 ? 8 : 1);
     const int grid = np < ncu ? np : ncu;
-    const bool fh = fwd_fast_halo() && C1 == 0 && !up0;
-    tail.prio = 0;
-#define FMRI_F32K(MODE_, A_, EPI_, FH_)                                                                                   \
-    k_conv_fwd_ws<1, false, MODE_, false, A_, EPI_, FH_, false, true><<<grid, fw::NTHREADS, 0, st>>>(                     \
-        s, (const bf16_t*)w, bias, (const bf16_t*)mask, (const bf16_t*)residual, (bf16_t*)y, N, D, H, W, Cout, act, alpha, tail)
+    const bool fh = C1 == 0 && !up0;                     // fast halo addressing: single plain source
     if (mode == 1) {
         if (mask || residual || tail.pool) return FMRI_E_SHAPE;
-        FMRI_F32K(1, false, -1, true);
+        FMRI_FWD(k_conv_fwd_ws<1, 1, false, false, -1, true, true>);
     } else if (mode == 2) {
         if (residual || tail.pool) return FMRI_E_SHAPE;
-        FMRI_F32K(2, false, -1, true);
-    } else if (residual) {
-        if (mask || tail.pool) return FMRI_E_SHAPE;
-        if (fh) FMRI_F32K(0, true, 3, true); else FMRI_F32K(0, true, 3, false);
-    } else if (mask) {
-        if (tail.pool) return FMRI_E_SHAPE;
-        if (fh) FMRI_F32K(0, true, 1, true); else FMRI_F32K(0, true, 1, false);
+        FMRI_FWD(k_conv_fwd_ws<1, 2, false, false, -1, true, true>);
     } else {
-        if (fh) FMRI_F32K(0, true, 0, true); else FMRI_F32K(0, true, 0, false);
+        if ((residual && (mask || tail.pool)) || (mask && tail.pool)) return FMRI_E_SHAPE;
+        fwd_choose(fh, [&](auto fh_) {
+            constexpr bool FH = decltype(fh_)::value;
+            if (residual) FMRI_FWD(k_conv_fwd_ws<1, 0, false, true, 3, FH, true>);
+            else if (mask) FMRI_FWD(k_conv_fwd_ws<1, 0, false, true, 1, FH, true>);
+            else FMRI_FWD(k_conv_fwd_ws<1, 0, false, true, 0, FH, true>);
+        });
     }
-#undef FMRI_F32K
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
@@ -2182,132 +1988,88 @@ static int conv3d_fwd_mfma_launch(int mode, const void* src0, int C0, int up0, i
     const bool cube = (D % fw::TD) || (H % fw::TH) || (W % fw::TW);       // only the 8x8x8 tiling fits (conv3d_fwd_mfma_ok)
     const int ntile = cube ? N * (D / 8) * (H / 8) * (W / 8) : N * (D / fw::TD) * (H / fw::TH) * (W / fw::TW);
     const int ncu = fwd_cu_count();
-    const int use_ws = fwd_use_ws();
-    // fast halo addressing (k_conv_fwd_ws<..., FH = true>): single plain source, at most two 32-channel chunks per freshly addressed halo
-    // (round 5: the warp-specialised kernel's form goes through a buffer descriptor and fixes a tile's out-of-volume offsets up once per
-    // tile: it serves every single-source 3-D launch (same-box A/B, profiles/r05_buffer_halo_ab.log: forward family -1.9 %, step +0.9 %;
-    // FMRI_FH_MAXCH = the most chunks per fresh address for which it is taken, 2 = the round-4 rule)
-    static int fh_maxch = -1;
-    if (fh_maxch < 0) {
-        const char* e = getenv("FMRI_FH_MAXCH");
-        fh_maxch = e ? atoi(e) : 1 << 20;
-    }
-    const int nchunk_fresh = mode == 2 ? C0 / 32 : (C0 + C1) / 32;
-    const bool fh_any = fwd_fast_halo() && !cube && C1 == 0 && !up0 && nchunk_fresh <= fh_maxch;
-    const bool fh = fh_any && !planar;                 // (the warp-specialised kernel's form covers the 3-D launches)
-    const bool s16 = fwd_mfma16() && !planar;
-    {
-        static int prio = -1;
-        if (prio < 0) {
-            const char* e = getenv("FMRI_FWD_PRIO");
-            prio = e ? atoi(e) : 0;
-        }
-        tail.prio = prio;
-    }
-#define FMRI_WS2(NT_, PL_, MODE_, RES_, A_, EPI_, FH_, GRID_)                                                              \
-    do {                                                                                                                  \
-        if (s16 && !(PL_))                                                                                                \
-            k_conv_fwd_ws<NT_, PL_, MODE_, RES_, A_, EPI_, FH_, !(PL_)><<<GRID_, fw::NTHREADS, 0, st>>>(                  \
-                s, (const bf16_t*)w, bias, (const bf16_t*)mask, (const bf16_t*)residual, (bf16_t*)y, N, D, H, W, Cout, act, alpha, tail); \
-        else                                                                                                              \
-            k_conv_fwd_ws<NT_, PL_, MODE_, RES_, A_, EPI_, FH_, false><<<GRID_, fw::NTHREADS, 0, st>>>(                   \
-                s, (const bf16_t*)w, bias, (const bf16_t*)mask, (const bf16_t*)residual, (bf16_t*)y, N, D, H, W, Cout, act, alpha, tail); \
-    } while (0)
-#define FMRI_WS(NT_, PL_, MODE_, RES_, A_, EPI_, GRID_)                                                                    \
-    do {                                                                                                                  \
-        if (fh && !(PL_)) FMRI_WS2(NT_, PL_, MODE_, RES_, A_, EPI_, !(PL_), GRID_);                                       \
-        else FMRI_WS2(NT_, PL_, MODE_, RES_, A_, EPI_, false, GRID_);                                                     \
-    } while (0)
-#define FMRI_LAUNCH_FWD(NT_, PL_, MODE_, RES_)                                                                             \
-    do {                                                                                                                  \
-        const int np = ntile * (Cout / (32 * NT_)) * (MODE_ == 1 ? (PL_ ? 4 : 8) : 1);                                    \
-        constexpr bool A_ = !(PL_) && !(RES_) && (MODE_) == 0;   /* asynchronous epilogue: plain 3-D launches */         \
-        const int epi_ = mask ? ((tail.pool || tail.logits) ? -1 : 1) : (tail.logits ? (tail.pool ? -1 : 2) : 0);                  \
-        if (use_ws && A_ && fwd_async() && np > ncu && epi_ >= 0) {   /* a single pair per workgroup has nothing to hide the stores under */ \
-            if (epi_ == 0) FMRI_WS(NT_, PL_, MODE_, RES_, A_, (A_ ? 0 : -1), (np < ncu ? np : ncu));                              \
-            else if (epi_ == 1) FMRI_WS(NT_, PL_, MODE_, RES_, A_, (A_ ? 1 : -1), (np < ncu ? np : ncu));                         \
-            else FMRI_WS(NT_, PL_, MODE_, RES_, A_, (A_ ? 2 : -1), (np < ncu ? np : ncu));                                        \
-        } else if (use_ws && (!(PL_) || use_ws > 1))   /* planar: the producers are the bottleneck - symmetric kernel */ \
-            FMRI_WS(NT_, PL_, MODE_, RES_, false, -1, (np < ncu ? np : ncu));                                             \
-        else if (fh_any && (MODE_) == 0)                                                                                  \
-            k_conv_fwd_mfma<NT_, PL_, MODE_, RES_, false, (MODE_) == 0><<<np < ncu ? np : ncu, fw::NTHREADS, 0, st>>>(    \
-                s, (const bf16_t*)w, bias, (const bf16_t*)mask, (const bf16_t*)residual, (bf16_t*)y, N, D, H, W, Cout, act, alpha, tail); \
-        else                                                                                                              \
-            k_conv_fwd_mfma<NT_, PL_, MODE_, RES_><<<np < ncu ? np : ncu, fw::NTHREADS, 0, st>>>(                         \
-                s, (const bf16_t*)w, bias, (const bf16_t*)mask, (const bf16_t*)residual, (bf16_t*)y, N, D, H, W, Cout, act, alpha, tail); \
-    } while (0)
+    const bool use_ws = fwd_use_ws();
+    // fast halo addressing (FH instantiations): every single-source launch on the 4x8x16 tiling (round 5: the warp-specialised kernel's form
+    // goes through a buffer descriptor and fixes a tile's out-of-volume offsets up once per tile; same-box A/B, profiles/r05_buffer_halo_ab.log:
+    // forward family -1.9 %, step +0.9 %)
+    const bool fh = !cube && C1 == 0 && !up0;
     const bool wide = fwd_wide(mode, planar, ntile, Cout);
+    const int np = ntile * (Cout / (wide ? 64 : 32)) * (mode == 1 ? (planar ? 4 : 8) : 1);      // (tile, Cout block) pairs
+    const int grid = np < ncu ? np : ncu;
+    // body(std::integral_constant<int, NT>): NT = 32-wide Cout tiles per workgroup
+    auto by_width = [&](auto body) {
+        if (wide) body(std::integral_constant<int, 2>{});
+        else body(std::integral_constant<int, 1>{});
+    };
     if (tail.nws) {
         // normalisation tails (EPI 4: statistics of the output, 6: the same behind the residual, 5: the backward reductions): asynchronous
         // epilogue only - conv3d_fwd_ntail_ok() tells the caller beforehand
-        const int np_ = ntile * (Cout / (wide ? 64 : 32));
-        if (cube || mode != 0 || planar || !use_ws || !fwd_async() || np_ <= ncu || tail.pool || tail.logits || tail.bias27) return FMRI_E_SHAPE;
+        if (cube || mode != 0 || planar || !use_ws || np <= ncu || tail.pool || tail.logits || tail.bias27) return FMRI_E_SHAPE;
         if (tail.nss ? (!mask || residual) : (mask != nullptr)) return FMRI_E_SHAPE;
-#define FMRI_LAUNCH_NT(NT_, EPI_) FMRI_WS2(NT_, false, 0, false, true, EPI_, false, ncu)
-        if (tail.nss) { if (wide) FMRI_LAUNCH_NT(2, 5); else FMRI_LAUNCH_NT(1, 5); }
-        else if (residual) { if (wide) FMRI_LAUNCH_NT(2, 6); else FMRI_LAUNCH_NT(1, 6); }
-        else { if (wide) FMRI_LAUNCH_NT(2, 4); else FMRI_LAUNCH_NT(1, 4); }
-#undef FMRI_LAUNCH_NT
-        FMRI_LAUNCH_CHECK();
-        return FMRI_OK;
-    }
-    if (planar && (tail.pool || tail.logits)) {
+        by_width([&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if (tail.nss) FMRI_FWD(k_conv_fwd_ws<NT, 0, false, true, 5>);
+            else if (residual) FMRI_FWD(k_conv_fwd_ws<NT, 0, false, true, 6>);
+            else FMRI_FWD(k_conv_fwd_ws<NT, 0, false, true, 4>);
+        });
+    } else if (planar && (tail.pool || tail.logits)) {
         // 2-D slices: the pooled copy / the final conv's logits come out of the symmetric kernel's epilogue (TAIL instantiations)
         if (cube || mode != 0 || residual || mask || C1 != 0 || up0 || (tail.logits && Cout != (wide ? 64 : 32))) return FMRI_E_SHAPE;
-        const int np = ntile * (Cout / (wide ? 64 : 32));
-#define FMRI_PT(NT_, FH_)                                                                                                  \
-    k_conv_fwd_mfma<NT_, true, 0, false, false, FH_, true><<<np < ncu ? np : ncu, fw::NTHREADS, 0, st>>>(                  \
-        s, (const bf16_t*)w, bias, nullptr, nullptr, (bf16_t*)y, N, D, H, W, Cout, act, alpha, tail)
-        if (wide) { if (fh_any) FMRI_PT(2, true); else FMRI_PT(2, false); }
-        else { if (fh_any) FMRI_PT(1, true); else FMRI_PT(1, false); }
-#undef FMRI_PT
-        FMRI_LAUNCH_CHECK();
-        return FMRI_OK;
-    }
-    if (cube) {
+        by_width([&](auto nt) { FMRI_FWD(k_conv_fwd_mfma<decltype(nt)::value, true, 0, false, false, true, true>); });
+    } else if (cube) {
         if (mode != 0 || residual || planar) return FMRI_E_SHAPE;
-        const int nt = wide ? 2 : 1;
-        const int np = ntile * (Cout / (32 * nt));
-        if (wide)
-            k_conv_fwd_mfma<2, false, 0, false, true><<<np < ncu ? np : ncu, fw::NTHREADS, 0, st>>>(
-                s, (const bf16_t*)w, bias, (const bf16_t*)mask, nullptr, (bf16_t*)y, N, D, H, W, Cout, act, alpha, tail);
-        else
-            k_conv_fwd_mfma<1, false, 0, false, true><<<np < ncu ? np : ncu, fw::NTHREADS, 0, st>>>(
-                s, (const bf16_t*)w, bias, (const bf16_t*)mask, nullptr, (bf16_t*)y, N, D, H, W, Cout, act, alpha, tail);
-    } else if (mode == 1 && planar) {
-        if (wide) FMRI_LAUNCH_FWD(2, true, 1, false); else FMRI_LAUNCH_FWD(1, true, 1, false);
-    } else if (mode == 1) {
-        if (wide) FMRI_LAUNCH_FWD(2, false, 1, false); else FMRI_LAUNCH_FWD(1, false, 1, false);
-    } else if (mode == 2 && planar) {
-        if (wide) FMRI_LAUNCH_FWD(2, true, 2, false); else FMRI_LAUNCH_FWD(1, true, 2, false);
-    } else if (mode == 2) {
-        if (wide) FMRI_LAUNCH_FWD(2, false, 2, false); else FMRI_LAUNCH_FWD(1, false, 2, false);
-    } else if (residual && planar) {
-        if (wide) FMRI_LAUNCH_FWD(2, true, 0, true); else FMRI_LAUNCH_FWD(1, true, 0, true);
+        by_width([&](auto nt) { FMRI_FWD(k_conv_fwd_mfma<decltype(nt)::value, false, 0, false, true>); });
+    } else if (mode != 0) {
+        // parity modes (single plain source: fast halo addressing); planar: the producers are the bottleneck - symmetric kernel
+        by_width([&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if (mode == 1) {
+                if (planar) FMRI_FWD(k_conv_fwd_mfma<NT, true, 1, false>);
+                else if (use_ws) FMRI_FWD(k_conv_fwd_ws<NT, 1, false, false, -1, true>);
+                else FMRI_FWD(k_conv_fwd_mfma<NT, false, 1, false>);
+            } else {
+                if (planar) FMRI_FWD(k_conv_fwd_mfma<NT, true, 2, false>);
+                else if (use_ws) FMRI_FWD(k_conv_fwd_ws<NT, 2, false, false, -1, true>);
+                else FMRI_FWD(k_conv_fwd_mfma<NT, false, 2, false>);
+            }
+        });
     } else if (residual) {
         // the residual added by the producers in the asynchronous drain (EPI 3) - FMRI_RES_ASYNC=0 keeps the RES epilogue on the MFMA waves.
         // Both add bf16(partial sum) + residual in fp32: the same bits from either, so a result does not depend on the grid size
-        static int res_async = -1;
-        if (res_async < 0) {
-            const char* e = getenv("FMRI_RES_ASYNC");
-            res_async = e ? atoi(e) : 1;
-        }
-        const int np_ = ntile * (Cout / (wide ? 64 : 32));
-        if (res_async && use_ws && fwd_async() && np_ > ncu && !mask && !tail.pool && !tail.logits) {
-            if (wide) FMRI_WS(2, false, 0, false, true, 3, ncu);
-            else FMRI_WS(1, false, 0, false, true, 3, ncu);
-        } else if (wide) FMRI_LAUNCH_FWD(2, false, 0, true); else FMRI_LAUNCH_FWD(1, false, 0, true);
-    } else if (wide) {
-        if (planar) FMRI_LAUNCH_FWD(2, true, 0, false); else FMRI_LAUNCH_FWD(2, false, 0, false);
+        static const int res_async = env_int("FMRI_RES_ASYNC", 1, {0, 1});
+        const bool drain = res_async && !planar && use_ws && np > ncu && !mask && !tail.pool && !tail.logits;
+        by_width([&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            fwd_choose(fh, [&](auto fh_) {
+                constexpr bool FH = decltype(fh_)::value;
+                if (planar) FMRI_FWD(k_conv_fwd_mfma<NT, true, 0, true, false, FH>);
+                else if (drain) FMRI_FWD(k_conv_fwd_ws<NT, 0, false, true, 3, FH>);
+                else if (use_ws) FMRI_FWD(k_conv_fwd_ws<NT, 0, true, false, -1, FH>);
+                else FMRI_FWD(k_conv_fwd_mfma<NT, false, 0, true, false, FH>);
+            });
+        });
     } else {
-        if (planar) FMRI_LAUNCH_FWD(1, true, 0, false); else FMRI_LAUNCH_FWD(1, false, 0, false);
+        // plain launches: 3-D ones with more pairs than workgroups take the asynchronous epilogue (a single pair per workgroup has nothing to
+        // hide the stores under), one instantiation per epilogue (EPI 0: store / pooled copy, 1: ReLU mask, 2: logits); planar: symmetric kernel
+        const int epi = mask ? ((tail.pool || tail.logits) ? -1 : 1) : (tail.logits ? (tail.pool ? -1 : 2) : 0);
+        const bool drain = !planar && use_ws && np > ncu && epi >= 0;
+        by_width([&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            fwd_choose(fh, [&](auto fh_) {
+                constexpr bool FH = decltype(fh_)::value;
+                if (drain && epi == 0) FMRI_FWD(k_conv_fwd_ws<NT, 0, false, true, 0, FH>);
+                else if (drain && epi == 1) FMRI_FWD(k_conv_fwd_ws<NT, 0, false, true, 1, FH>);
+                else if (drain) FMRI_FWD(k_conv_fwd_ws<NT, 0, false, true, 2, FH>);
+                else if (use_ws && !planar) FMRI_FWD(k_conv_fwd_ws<NT, 0, false, false, -1, FH>);
+                else if (planar) FMRI_FWD(k_conv_fwd_mfma<NT, true, 0, false, false, FH>);
+                else FMRI_FWD(k_conv_fwd_mfma<NT, false, 0, false, false, FH>);
+            });
+        });
     }
-#undef FMRI_LAUNCH_FWD
-#undef FMRI_WS
-#undef FMRI_WS2
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
+#undef FMRI_FWD
 int conv3d_fwd_mfma_ex(int mode, const void* src0, int C0, int up0, int planar, const void* src1, int C1, const void* w, const float* bias,
                        const void* mask, const void* residual, void* y, int N, int D, int H, int W, int Cout, int act, float alpha, int dtype,
                        hipStream_t st) {
@@ -2324,7 +2086,7 @@ int conv3d_fwd_tail_ok(int C0, int Cout, int N, int D, int H, int W, int dtype, 
         if (dtype != FMRI_BF16) return 0;
         return 1 | (Cout == (fwd_wide(0, 1, ntile, Cout) ? 64 : 32) ? 2 : 0);
     }
-    if (fwd_use_ws() == 0) return 0;
+    if (!fwd_use_ws()) return 0;
     if (dtype == FMRI_F32) return 1;                     // the pooled copy rides the fp32 drain; the logits need a 64-wide block
     const int bn = fwd_wide(0, 0, ntile, Cout) ? 64 : 32;
     return 1 | (Cout == bn ? 2 : 0);
@@ -2338,7 +2100,7 @@ int conv3d_fwd_mfma_tail(const void* src0, int C0, const void* w, const float* b
 }
 // can this plain 3-D launch carry a normalisation tail (statistics of its output / the backward reductions in its asynchronous epilogue)?
 int conv3d_fwd_ntail_ok(int C0, int C1, int Cout, int N, int D, int H, int W, int dtype) {
-    if (dtype != FMRI_BF16 || !conv3d_fwd_mfma_ok(C0, C1, Cout, D, H, W, dtype) || conv3d_fwd_needs_cube(D, H, W) || !fwd_use_ws() || !fwd_async()) return 0;
+    if (dtype != FMRI_BF16 || !conv3d_fwd_mfma_ok(C0, C1, Cout, D, H, W, dtype) || conv3d_fwd_needs_cube(D, H, W) || !fwd_use_ws()) return 0;
     const int ntile = N * (D / fw::TD) * (H / fw::TH) * (W / fw::TW);
     return ntile * (Cout / (fwd_wide(0, 0, ntile, Cout) ? 64 : 32)) > fwd_cu_count();
 }

@@ -58,11 +58,8 @@ __device__ __forceinline__ bf16x8_t tr_frag(const unsigned char* base, int row0,
 // dims), the Cout blocks enumerate (parity, 64-channel block), only kd in {pd, pd+1} gets workgroups and only the 4 (kh,kw) taps
 // {ph,ph+1} x {pw,pw+1} are accumulated; the dy tile is gathered from the parity-p voxels of the [2D][2H][2W] gradient.
 // Result layout [8 p][2][2][2][Cout][C0] fp32 (atomics), expanded into the 27-tap gradient by k_expand_up_wgrad.
-// WS: warp-specialised variant - eight waves, ONE workgroup per CU: waves 0-3 (one per SIMD) read fragments and issue MFMAs exactly as the
-// four waves of the plain kernel do, waves 4-7 issue all LDS-DMA (tools/prof_wgrad.py: a wave of the plain kernel spends 35-50 % of its time
-// issuing its ten DMA instructions per unit, wherever they are placed).
-template <int CI_T, bool UPW, bool WS = false>  // CI_T = 32-wide input-channel tiles per workgroup (1 or 2); output-channel block is always 64
-__global__ void __launch_bounds__(WS ? 512 : wg::NTHREADS, WS ? 1 : 2)
+template <int CI_T, bool UPW>  // CI_T = 32-wide input-channel tiles per workgroup (1 or 2); output-channel block is always 64
+__global__ void __launch_bounds__(wg::NTHREADS, 2)
 k_conv_wgrad_mfma(SrcB s, const bf16_t* __restrict__ dy, float* __restrict__ dw, float* __restrict__ db, int N, int D, int H,
                   int W, int Cout, int nslab, float* __restrict__ slab_ws, int dw_ld) {
     using namespace wg;
@@ -73,11 +70,10 @@ k_conv_wgrad_mfma(SrcB s, const bf16_t* __restrict__ dy, float* __restrict__ dw,
     constexpr int Y_INSTR = YROWS * 8 / 64;              // 16
     constexpr int XPW = (X_INSTR + 3) / 4;               // x instructions per wave (6 or 3; short waves re-issue their first)
     constexpr int YPW = Y_INSTR / 4;                     // 4
-    constexpr int PER_WAVE = XPW + YPW;                  // 10 or 7 DMA instructions per wave per unit
     constexpr int X_BYTES = X_INSTR * 1024;
     constexpr int Y_BYTES = Y_INSTR * 1024;
     constexpr int STAGE_BYTES = X_BYTES + Y_BYTES;
-    constexpr int NSTAGE = WS ? 3 : 2;                   // WS: the producers run TWO units ahead (one workgroup per CU leaves the LDS for it)
+    constexpr int NSTAGE = 2;
     __shared__ __attribute__((aligned(16))) unsigned char lds[NSTAGE * STAGE_BYTES];
     const unsigned char* const zpage = zero_page_addr();
 
@@ -106,9 +102,7 @@ k_conv_wgrad_mfma(SrcB s, const bf16_t* __restrict__ dy, float* __restrict__ dw,
     const int sD = D >> shd, sH = H >> sh, sW = W >> sh;
 
     const int t = threadIdx.x, lane = t & 63;
-    const int wv_all = __builtin_amdgcn_readfirstlane(t >> 6);
-    const bool producer = WS && wv_all >= 4;
-    const int wv = wv_all & 3;                             // index among the four waves of this wave's role
+    const int wv = __builtin_amdgcn_readfirstlane(t >> 6) & 3;      // (& 3: the compiler learns the wave index is below 4)
     const int r = lane & 31, hk = lane >> 5;
     const int ct = wv & 1;
     const int it = (CI_T == 2) ? (wv >> 1) : 0;
@@ -239,74 +233,22 @@ k_conv_wgrad_mfma(SrcB s, const bf16_t* __restrict__ dy, float* __restrict__ dw,
     unsigned long long wprof[12] = {};
     PROF_T(wk0);
 #endif
-    if (u < u_end && (!WS || producer)) {
+    if (u < u_end) {
         cursor_set(u);
         issue(0);
     }
-    if (WS && producer && u + 1 < u_end) issue(1);
     for (; u < u_end; ++u, buf = (buf + 1 == NSTAGE ? 0 : buf + 1)) {
         const bool more = (u + 1) < u_end;
         PROF_T(w0);
         // ONE barrier per unit: "my DMA for this unit has landed" + "everybody is done reading the ring slot of the previous unit" (a wave
-        // gets here only after its MFMAs on it) - then that slot is refilled: with the unit after this one (plain kernel, 2 slots) or the
-        // one after that (WS, 3 slots: the wait below leaves the youngest unit's DMA in flight)
-        if (WS) {
-            if (producer) {
-                if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_WAVE) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        // gets here only after its MFMAs on it) - then that slot is refilled with the unit after this one
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         PROF_T(w1);
         __builtin_amdgcn_s_barrier();
         PROF_T(w2);
-        if (WS) {
-            if (producer && u + 2 < u_end) issue(buf == 0 ? 2 : buf - 1);                 // = (buf + 2) % 3: the slot of the previous unit
-        } else if (more) issue(buf ^ 1);
+        if (more) issue(buf ^ 1);
         PROF_T(w3);
-        if (producer) continue;
         const unsigned char* const sb = lds + buf * STAGE_BYTES;
-        if constexpr (WS && CI_T == 2) {
-            // One consumer wave per SIMD: nobody else hides the latency of the transposing reads, so the fragments run two MFMAs ahead of
-            // their use (3-deep x-fragment ring, double dy fragment), threaded between the MFMAs.
-            typedef __attribute__((ext_vector_type(8))) short s16x8;
-            constexpr int NS = 8 * NACC;
-            auto row_of = [&](int st) {
-                const int ks8 = st / NACC, tap = st % NACC;
-                return UPW ? (ks8 + (tap >> 1) + PH_) * XW + (tap & 1) + PW_ : (ks8 + tap / 3) * XW + (tap % 3);
-            };
-            auto load_bf = [&](int st) {
-                const int c = row_of(st);
-                const unsigned char* pb = sb + pre_x[c & 3] + (c >> 2) * 4 * XROWB;
-                s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)pb);
-                s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(pb + 4 * XROWB));
-                return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-            };
-            auto load_af = [&](int ks8) {
-                const unsigned char* pa = sb + pre_y + ks8 * TW * 128;
-                s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)pa);
-                s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(pa + 4 * 128));
-                return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-            };
-            s16x8 af2[2], bf3[3];
-            af2[0] = load_af(0);
-            bf3[0] = load_bf(0);
-            bf3[1] = load_bf(1);
-#pragma unroll
-            for (int st = 0; st < NS; ++st) {
-                const int ks8 = st / NACC, tap = st % NACC;
-                if (st + 2 < NS) bf3[(st + 2) % 3] = load_bf(st + 2);
-                if (tap == NACC - 3 && ks8 + 1 < 8) af2[(ks8 + 1) & 1] = load_af(ks8 + 1);
-                if (do_bias && tap == 0) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) bsum += bf2f((unsigned short)af2[ks8 & 1][j]);
-                }
-                acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, af2[ks8 & 1]), __builtin_bit_cast(bf16x8_t, bf3[st % 3]),
-                                                                  acc[tap], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else
 #pragma unroll
         for (int ks8 = 0; ks8 < 8; ++ks8) {
             if (CI_T == 1 && (ks8 & 1) != ksl) continue;              // Cin-block 32: the two wave pairs split the k-steps
@@ -353,7 +295,6 @@ k_conv_wgrad_mfma(SrcB s, const bf16_t* __restrict__ dy, float* __restrict__ dw,
     } else {
         run(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
     }
-    if (producer) return;
     const FmriDetCfg dc = g_det_cfg;                    // deterministic mode: fixed-point shadow of the gradient buffer (common.h)
     // ---- flush: D rows = co, cols = ci (128-B contiguous per half-wave).  With a workspace: plain stores of this workgroup's partial
     // slab [9][64][CIB] (summed per element by k_wgrad_reduce: deterministic, ~5x the atomic rate); without: fp32 atomics into dw.
@@ -402,42 +343,35 @@ k_conv_wgrad_mfma(SrcB s, const bf16_t* __restrict__ dy, float* __restrict__ dw,
 // (~20 MB of DMA requests in flight chip-wide): the weight gradient is bound by its LDS-DMA stream.  Here a workgroup owns a (Cout, Cin)
 // block for ALL 27 taps and walks up a column of d-plane tiles with a 4-slot ring of x planes (d-1, d, d+1 in use, d+2 in flight) and a
 // 2-slot ring of dy planes: one new x plane + one dy plane per step feed all three kd.  wave = tap group of 7 | 7 | 7 | 6 taps.
-//   BLK = 32: (32 Cout, 32 Cin) block, 4 waves, TWO workgroups per CU (64 KiB of LDS each) - two independent barrier domains, as in the
-//             kernel above; 112 accumulator registers per wave leave room for a 4-deep fragment ring.  19.5 KB of DMA per 216 MFMAs =
-//             90 B per MFMA (-33 %).
-//   BLK = 64 (round 6, "one wave per SIMD"): (64 Cout, 32 Cin) block, 4 waves, ONE workgroup per CU.  A wave holds 7 taps x 2 Cout halves x
-//             32 x 32 = 224 accumulator registers and has its SIMD's whole 512-entry register file: an x fragment serves two MFMAs (0.64 KB of
-//             LDS reads per MFMA instead of 1.14), 27.5 KB of DMA per 432 MFMAs = 64 B per MFMA, the fragment ring runs PF reads ahead in
-//             registers (nobody else hides the read latency), and the unit's DMA pieces are issued one at a time BETWEEN MFMAs (SPREAD) instead
-//             of as a burst behind the barrier.  (Rounds 2-5 had a (64, 64) block on 8 waves here - two waves per SIMD at 224 accumulators
-//             each, i.e. inside 256 registers: spills, one barrier domain for eight waves, 8-25 % slower.  Removed.)
+// (32 Cout, 32 Cin) block, 4 waves, TWO workgroups per CU (64 KiB of LDS each) - two independent barrier domains, as in the kernel above;
+// 112 accumulator registers per wave leave room for a 4-deep fragment ring.  19.5 KB of DMA per 216 MFMAs = 90 B per MFMA (-33 %).
+// (Rounds 2-5 had a (64, 64) block on 8 waves here - two waves per SIMD at 224 accumulators each, i.e. inside 256 registers: spills, one
+// barrier domain for eight waves, 8-25 % slower.  Round 6 measured a (64 Cout, 32 Cin) block with one wave per SIMD level with this form:
+// DESIGN.md 3.4.)
 // Flush: fp32 atomics (128 contiguous bytes per half-wave).  Bit-identical sums on exactly representable data (tests).
 // F32 (round 6, the fp32 parity mode on this kernel's structure): fp32 planes, a (32 Cout, 32 Cin) block on v_mfma_f32_32x32x2_f32 - rows of
 // 128 bytes for both operands, the plane ring / DMA pieces / cursor / flush of the bf16 kernel; a fragment is ONE voxel per half-wave
 // (lane = channel), so it is a plain ds_read_b32 per operand and MFMA, no transposing read.  One workgroup per CU (124 KiB of LDS).
-template <int BLK, bool F32 = false>
+template <bool F32 = false>
 struct WkCfg {
     static constexpr int NW = 4;                                  // waves per workgroup = tap groups (all of them issue DMA)
-    static constexpr int NH = F32 ? 1 : BLK / 32;                 // Cout halves (32 channels each) per wave
-    static constexpr int XROWB = F32 ? 128 : 64, YROWB = F32 ? 128 : BLK * 2;      // bytes per x row (32 input channels) / per dy row in LDS
+    static constexpr int NH = 1;                                  // Cout halves (32 channels each) per wave
+    static constexpr int XROWB = F32 ? 128 : 64, YROWB = F32 ? 128 : 64;       // bytes per x row (32 input channels) / per dy row in LDS
     static constexpr int XRS = XROWB / 16, YRS = YROWB / 16;      // 16-byte slots per row
     static constexpr int X_INSTR = (wg::XROWS * XRS + 63) / 64;   // DMA wave-instructions per x plane: 12
     static constexpr int Y_INSTR = wg::YROWS * YRS / 64;          // ... per dy plane: 8 / 16
     static constexpr int XS_BYTES = X_INSTR * 1024, YS_BYTES = Y_INSTR * 1024;
     static constexpr int NXS = 4, NYS = 2;
     static constexpr int LDS_BYTES = NXS * XS_BYTES + NYS * YS_BYTES;      // 65,536 / 81,920
-    static constexpr int PF = BLK == 64 ? 4 : 3;                  // x fragments in flight ahead of their MFMAs
+    static constexpr int PF = 3;                                  // x fragments in flight ahead of their MFMAs
     static constexpr int XPW = (X_INSTR + NW - 1) / NW, YPW = (Y_INSTR + NW - 1) / NW;      // 3, 2 / 4
-    // DMA pieces of the next unit issued between the MFMAs of this one (one wave per SIMD: nobody else issues under this wave's matrix work).
-    // The 32-block kernel keeps its burst behind the barrier: the spread form is level there (profiles/r06_kd32_spread_ab.log)
-    static constexpr bool SPREAD = BLK == 64 && !F32;
-    static constexpr int SP0 = 1, SPD = 3;                        // ... piece p behind step SP0 + SPD * p (a step = NH MFMAs)
+    // (the next unit's DMA pieces go out as a burst behind the barrier: spread between the MFMAs they were level, profiles/r06_kd32_spread_ab.log)
 };
 
-template <int BLK, int G, class Hook>   // tap group: taps 7G .. 7G + NTAP - 1 of the 27; hook(step) runs behind every step's MFMAs
+template <int G>   // tap group: taps 7G .. 7G + NTAP - 1 of the 27
 __device__ __forceinline__ void wk_compute(const unsigned char* lds, const int (&xb)[3], int yb, const int (&pre_x)[4], int pre_y,
-                                           f32x16 (&acc)[G == 3 ? 6 : 7][WkCfg<BLK>::NH], float (&bsum)[2], bool do_bias, Hook&& hook) {
-    typedef WkCfg<BLK> K;
+                                           f32x16 (&acc)[G == 3 ? 6 : 7][WkCfg<>::NH], float (&bsum)[2], bool do_bias) {
+    typedef WkCfg<> K;
     constexpr int NTAP = G == 3 ? 6 : 7, T0 = 7 * G, NH = K::NH, XROWB = K::XROWB, YROWB = K::YROWB;
     typedef __attribute__((ext_vector_type(8))) short s16x8;
     auto load_a = [&](int ks8, s16x8 (&av)[NH]) {
@@ -460,104 +394,32 @@ __device__ __forceinline__ void wk_compute(const unsigned char* lds, const int (
         s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(pb + 4 * XROWB));
         return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
     };
-    // Fixed register budget: the dy fragments of a k-step are single-buffered, the x fragments run PF steps ahead of their MFMAs in a
-    // register ring; sched_barrier keeps the compiler from hoisting more reads (left alone it spills thousands of registers at BLK = 64).
+    // Fixed register budget: the dy fragments of a k-step are single-buffered (the other workgroup's wave on the SIMD covers their
+    // latency), the x fragments run PF steps ahead of their MFMAs in a register ring; sched_barrier keeps the compiler from hoisting more reads
     constexpr int NS = 8 * NTAP, PF = K::PF, RING = PF + 1;
-    // DBA (one wave per SIMD): the dy fragments of the next k-step are requested three steps before it starts (double-buffered) - with
-    // two waves per SIMD the partner covers that latency and the registers are better spent elsewhere
-    constexpr bool DBA = BLK == 64;
-    s16x8 av[DBA ? 2 : 1][NH], b[RING];
+    s16x8 av[NH], b[RING];
 #pragma unroll
     for (int q = 0; q < PF; ++q) b[q] = load_b(q);
-    if constexpr (DBA) load_a(0, av[0]);
 #pragma unroll
     for (int ks8 = 0; ks8 < 8; ++ks8) {
-        const int ab = DBA ? (ks8 & 1) : 0;
-        if constexpr (!DBA) load_a(ks8, av[0]);
+        load_a(ks8, av);
         if constexpr (G == 3) {
             if (do_bias) {
                 // bias gradient = sum of the dy fragments (the 6-tap group has registers to spare)
 #pragma unroll
                 for (int h = 0; h < NH; ++h)
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) bsum[h] += bf2f((unsigned short)av[ab][h][q]);
+                    for (int q = 0; q < 8; ++q) bsum[h] += bf2f((unsigned short)av[h][q]);
             }
         }
 #pragma unroll
         for (int j = 0; j < NTAP; ++j) {
             const int st = ks8 * NTAP + j;
             if (st + PF < NS) b[(st + PF) % RING] = load_b(st + PF);
-            if constexpr (DBA) {
-                if (j == NTAP - 3 && ks8 + 1 < 8) load_a(ks8 + 1, av[ab ^ 1]);
-            }
             const bf16x8_t bb = __builtin_bit_cast(bf16x8_t, b[st % RING]);
 #pragma unroll
             for (int h = 0; h < NH; ++h)
-                acc[j][h] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, av[ab][h]), bb, acc[j][h], 0, 0, 0);
-            hook(ks8 * NTAP + j);            // (the loops are fully unrolled: the step is a constant in every copy)
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
-
-// S16 (round 5; BLK = 32): the same (32 Cout, 32 Cin) x 7-tap block per wave on v_mfma_f32_16x16x32_bf16 - four 16 x 16 accumulators per tap,
-// k = 32 voxels = two h-rows of the 8 x 16 plane tile per step.  The order of the voxels inside the k dimension is free as long as both
-// operands use the same one: k-group g (= lane >> 4, 8 voxels) of a step is h-row 2 m + (g >> 1), w = 4 (g & 1) + {0..3} and + 8, so one
-// transposing read (4 voxel rows x 32 bytes per 16-lane group) touches rows R .. R + 3 in group 0 and R + 4 .. R + 7 in group 1; with the
-// 32-byte halves of a 64-byte LDS row flipped on bit 2 of the row index (applied on the DMA source, WkCfg rows) the two groups of a
-// half-wave fall into different bank halves - the job the Cin / Cout half-selection does in the 32x32x16 form.
-template <int G>
-__device__ __forceinline__ void wk_compute16(const unsigned char* lds, const int (&xb)[3], int yb, const int (&pre_x)[8], int pre_y,
-                                             f32x4 (&acc)[G == 3 ? 6 : 7][2][2], float (&bsum)[2], bool do_bias) {
-    constexpr int NTAP = G == 3 ? 6 : 7, T0 = 7 * G, ROWB = 64;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    // dy fragment of k-step m, Cout half h: rows m * 32 + (lane part), 16-channel half h = +32 bytes (flipped with the row's swizzle bit,
-    // which the lane part already carries: m * 32 rows never change it)
-    auto load_a = [&](int m, s16x8 (&av)[2]) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const unsigned char* p0 = lds + yb + (h ? (pre_y ^ 32) : pre_y) + m * 32 * ROWB;
-            s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-            s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 8 * ROWB));
-            av[h] = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-    };
-    // x fragment of (k-step m, tap T0 + j), Cin half h: halo row (2 m + kh) * XW + kw + (lane part); the lane part's swizzle bit depends on
-    // the row constant mod 8 (pre_x[c & 7]), the rest of the constant is a multiple of 8 rows
-    auto load_b = [&](int st, int h) {
-        const int m = st / NTAP, t = T0 + st % NTAP, kd = t / 9, kh = (t / 3) % 3, kw = t % 3;
-        const int c = (2 * m + kh) * wg::XW + kw;
-        const unsigned char* pb = lds + xb[kd] + (h ? (pre_x[c & 7] ^ 32) : pre_x[c & 7]) + (c >> 3) * 8 * ROWB;
-        s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)pb);
-        // (the second read is 8 rows on: same swizzle bit)
-        s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(pb + 8 * ROWB));
-        return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-    constexpr int NS = 4 * NTAP, PF = 2, RING = PF + 1;      // x fragment pairs in flight ahead of their MFMAs
-    s16x8 av[2], b[RING][2];
-#pragma unroll
-    for (int q = 0; q < PF; ++q) { b[q][0] = load_b(q, 0); b[q][1] = load_b(q, 1); }
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        load_a(m, av);
-        if constexpr (G == 3) {
-            if (do_bias) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) bsum[h] += bf2f((unsigned short)av[h][q]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NTAP; ++j) {
-            const int st = m * NTAP + j;
-            if (st + PF < NS) { b[(st + PF) % RING][0] = load_b(st + PF, 0); b[(st + PF) % RING][1] = load_b(st + PF, 1); }
-#pragma unroll
-            for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                for (int ho = 0; ho < 2; ++ho)
-                    acc[j][ho][hi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, av[ho]), __builtin_bit_cast(bf16x8_t, b[st % RING][hi]),
-                                                                            acc[j][ho][hi], 0, 0, 0);
+                acc[j][h] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, av[h]), bb, acc[j][h], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -597,23 +459,21 @@ struct WkArgs {
 };
 
 // everything a wave does, instantiated per tap group so that the accumulators are one fixed register set for the kernel's lifetime
-template <int BLK, int G, bool S16 = false, bool F32 = false>
+template <int G, bool F32 = false>
 __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int wv, int lane) {
-    static_assert(!S16 || BLK == 32, "the 16x16x32 form is built for the 4-wave kernel");
-    static_assert(!F32 || (BLK == 32 && !S16), "the fp32 form: 32 x 32 blocks");
-    typedef WkCfg<BLK, F32> K;
+    typedef WkCfg<F32> K;
     constexpr int EU = F32 ? 2 : 1;                      // 2-byte units per element: channel counts that are memory strides come in these (s.C0, s.C1)
     constexpr int NTAP = G == 3 ? 6 : 7, NW = K::NW, NH = K::NH, XROWB = K::XROWB, YROWB = K::YROWB, XRS = K::XRS, YRS = K::YRS;
     const SrcB& s = a.s;
     const int N = a.N, D = a.D, H = a.H, W = a.W, Cout = a.Cout;
     const int Cin = s.C0 + s.C1;
-    const int ncib = Cin / (32 * EU), ncob = Cout / BLK;
+    const int ncib = Cin / (32 * EU), ncob = Cout / 32;
     const int CoutB = EU * Cout;                         // voxel stride of dy in 2-byte units
     const int ncombo = ncob * ncib;
     const int wg_id = xcd_logical_id(blockIdx.x, gridDim.x);      // the (Cout, Cin) blocks of one slab (same planes) on one XCD / L2
     const int combo = wg_id % ncombo, slab = wg_id / ncombo;
     const int cib = combo % ncib, cob = combo / ncib;
-    const int co0 = cob * BLK, ccr = cib * 32, cc = ccr * EU;          // ccr: first input channel of the block; cc: the same in 2-byte units
+    const int co0 = cob * 32, ccr = cib * 32, cc = ccr * EU;          // ccr: first input channel of the block; cc: the same in 2-byte units
 
     const bool from0 = cc < s.C0;
     const bf16_t* sp = from0 ? s.p0 : s.p1;
@@ -627,21 +487,13 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
     // bias gradient = sum over the dy fragments: in the 6-tap group (it has registers to spare) of Cin block 0
     const bool do_bias = G == 3 && (a.db != nullptr) && cib == 0;
 
-    f32x16 acc[S16 ? 1 : NTAP][NH];
-    f32x4 acc16[S16 ? NTAP : 1][2][2];
-    if constexpr (S16) {
+    f32x16 acc[NTAP][NH];
 #pragma unroll
-        for (int q = 0; q < NTAP; ++q)
+    for (int q = 0; q < NTAP; ++q)
 #pragma unroll
-            for (int h = 0; h < 4; ++h) acc16[q][h >> 1][h & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else {
+        for (int h = 0; h < NH; ++h)
 #pragma unroll
-        for (int q = 0; q < NTAP; ++q)
-#pragma unroll
-            for (int h = 0; h < NH; ++h)
-#pragma unroll
-                for (int k = 0; k < 16; ++k) acc[q][h][k] = 0.f;
-    }
+            for (int k = 0; k < 16; ++k) acc[q][h][k] = 0.f;
     float bsum[2] = {0.f, 0.f};
 
     const int twn = W / wg::TW, thn = H / wg::TH;
@@ -669,8 +521,8 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
             const int id = xid(k);
             const int i = id * 64 + lane;
             const int row = i / XRS, ps = i % XRS;
-            // 128-byte rows flip their 64-byte halves on row bit 1 (wg_slot_off); S16: 64-byte rows flip their 32-byte halves on row bit 2
-            const int ls = XRS == 8 ? (ps ^ (((row >> 1) & 1) << 2)) : (S16 ? (ps ^ (((row >> 2) & 1) << 1)) : ps);
+            // 128-byte rows flip their 64-byte halves on row bit 1 (wg_slot_off)
+            const int ls = XRS == 8 ? (ps ^ (((row >> 1) & 1) << 2)) : ps;
             const int xh = row / wg::XW, xw = row % wg::XW;
             const int gh = h0 - 1 + xh, gw = w0 - 1 + xw;
             const bool ok = id < K::X_INSTR && row < wg::XROWS && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W;
@@ -683,7 +535,7 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
             const int id = yid(k);
             const int i = id * 64 + lane;
             const int row = i / YRS, ps = i % YRS;
-            const int ls = YRS == 8 ? (ps ^ (((row >> 1) & 1) << 2)) : (S16 ? (ps ^ (((row >> 2) & 1) << 1)) : ps);
+            const int ls = YRS == 8 ? (ps ^ (((row >> 1) & 1) << 2)) : ps;
             y_off[k] = (((row >> 4) * W + (row & 15)) * CoutB + ls * 8) * 2;     // bytes
         }
     };
@@ -720,19 +572,13 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
     const int gq = lane >> 4, qd = (lane & 15) >> 2, pp = lane & 3;
     const int lrow = 8 * (gq >> 1) + qd;
     const int lslot_x = 2 * (gq & 1) + (pp >> 1), lslot_y = 2 * (gq & 1) + (pp >> 1);
-    int pre_x[S16 ? 8 : 4];
+    int pre_x[4];
     int pre_y;
     if constexpr (F32) {
         // row (m + hk) of a 128-byte-row image, channel r: one dword per lane (the x and the dy image share the layout)
 #pragma unroll
         for (int m = 0; m < 4; ++m) pre_x[m] = (m + hk) * 128 + ((r * 4) ^ ((((m + hk) >> 1) & 1) << 6));
         pre_y = 0;
-    } else if constexpr (S16) {
-        // lane (g = k-group, qd = voxel row of the read, pp = 8-byte piece of the 32-byte half): voxel (h-row g >> 1, w = 4 (g & 1) + qd) of the step
-        const int lx = (gq >> 1) * wg::XW + 4 * (gq & 1) + qd, ly = (gq >> 1) * wg::TW + 4 * (gq & 1) + qd;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) pre_x[m] = ((lx + m) * 64 + pp * 8) ^ ((((lx + m) >> 2) & 1) << 5);
-        pre_y = (ly * 64 + pp * 8) ^ (((ly >> 2) & 1) << 5);
     } else {
 #pragma unroll
         for (int m = 0; m < 4; ++m) pre_x[m] = wg_slot_off<XROWB>(lrow + m, lslot_x) + (pp & 1) * 8;
@@ -767,7 +613,6 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
             PROF_T(w2);
             const bool more = u + 1 < u_end;
             const bool fresh = more && d + 1 == D;       // the next unit starts a new column: it needs three new planes, one slot is free
-            i32x4 nx_rs = {0, 0, 0, 0}, ny_rs = {0, 0, 0, 0};
             if (more) {
                 if (fresh) {                             // advance the cursor to the next column of the run
                     int w0 = cw0 + wg::TW, h0 = ch0, n = cn;
@@ -775,35 +620,15 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
                     col_setup(n, h0, w0);
                     d = -1;
                 }
-                if constexpr (!K::SPREAD) {
-                    issue_x(fresh ? -1 : d + 2, (xs + 1) & 3);
-                    issue_y(d + 1, yb ^ 1);
-                }
+                issue_x(fresh ? -1 : d + 2, (xs + 1) & 3);
+                issue_y(d + 1, yb ^ 1);
             }
             PROF_T(w3);
             int xb[3] = {((xs + 2) & 3) * K::XS_BYTES, ((xs + 3) & 3) * K::XS_BYTES, xs * K::XS_BYTES};
 #pragma unroll
             for (int k = 0; k < 3; ++k) asm volatile("" : "+s"(xb[k]));       // slot bases stay scalar: base + lane offset is added per read
-            const int nslot = (xs + 1) & 3, nyb = yb ^ 1;
-            auto hook = [&](int st) {
-                if constexpr (K::SPREAD) {
-                    // behind step 0: the next unit's two descriptors - ~60 scalar instructions (64-bit multiplies) that sat between the barrier
-                    // and the unit's first MFMA; piece p of the next unit behind step SP0 + SPD p, the dy pieces first
-                    constexpr int SPD = K::SPD;
-                    if (st == 0 && more) {
-                        nx_rs = x_rsrc(fresh ? -1 : d + 2);
-                        ny_rs = y_rsrc(d + 1);
-                    }
-                    if (st >= K::SP0 && (st - K::SP0) % SPD == 0 && (st - K::SP0) / SPD < XPW_ + YPW_ && more) {
-                        const int pc = (st - K::SP0) / SPD;
-                        if (pc < YPW_) y_piece(ny_rs, nyb, pc);
-                        else x_piece(nx_rs, nslot, pc - YPW_);
-                    }
-                }
-            };
             if constexpr (F32) wk_compute_f32<G>(lds, xb, K::NXS * K::XS_BYTES + yb * K::YS_BYTES, pre_x, acc, bsum, do_bias);
-            else if constexpr (S16) wk_compute16<G>(lds, xb, K::NXS * K::XS_BYTES + yb * K::YS_BYTES, pre_x, pre_y, acc16, bsum, do_bias);
-            else wk_compute<BLK, G>(lds, xb, K::NXS * K::XS_BYTES + yb * K::YS_BYTES, pre_x, pre_y, acc, bsum, do_bias, hook);
+            else wk_compute<G>(lds, xb, K::NXS * K::XS_BYTES + yb * K::YS_BYTES, pre_x, pre_y, acc, bsum, do_bias);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             PROF_T(w4);
 #ifdef FMRI_PROF
@@ -830,34 +655,6 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
     }
     // ---- flush: D rows = co, cols = ci; fp32 atomics, 128 contiguous bytes per half-wave (deterministic mode: fixed-point shadow)
     const FmriDetCfg dc = g_det_cfg;
-    if constexpr (S16) {
-        // D rows = co (4 (lane >> 4) + reg inside the 16-channel half), cols = ci (lane & 15): 64 contiguous bytes per 16-lane group
-#pragma unroll
-        for (int j = 0; j < NTAP; ++j) {
-            const int tap = 7 * G + j;
-#pragma unroll
-            for (int ho = 0; ho < 2; ++ho)
-#pragma unroll
-                for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) {
-                        const int co = co0 + ho * 16 + 4 * (lane >> 4) + reg;
-                        const int ci = ccr + hi * 16 + (lane & 15);
-                        fmri_grad_add(dc, &a.dw[((int64_t)tap * Cout + co) * a.dw_ld + ci], acc16[j][ho][hi][reg]);
-                    }
-        }
-        if (do_bias) {
-            // a lane summed its 8 voxels of every step for Cout lane & 15 of half h: the four k-groups meet
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                float b = bsum[h];
-                b += __shfl_down(b, 32);
-                b += __shfl_down(b, 16);
-                if (lane < 16) fmri_grad_add(dc, &a.db[co0 + h * 16 + lane], b);
-            }
-        }
-        return;
-    }
 #pragma unroll
     for (int j = 0; j < NTAP; ++j) {
         const int tap = 7 * G + j;
@@ -880,16 +677,16 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
     }
 }
 
-template <int BLK, bool S16 = false, bool F32 = false>
-__global__ void __launch_bounds__(256, (BLK == 64 || F32) ? 1 : 2) k_conv_wgrad_kd(WkArgs a) {     // BLK = 64: no second workgroup -> 512 registers per wave
-    __shared__ __attribute__((aligned(16))) unsigned char lds[WkCfg<BLK, F32>::LDS_BYTES];
+template <bool F32 = false>
+__global__ void __launch_bounds__(256, F32 ? 1 : 2) k_conv_wgrad_kd(WkArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[WkCfg<F32>::LDS_BYTES];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     switch (wv & 3) {                                     // tap group
-        case 0: wk_run<BLK, 0, S16, F32>(a, lds, wv, lane); break;
-        case 1: wk_run<BLK, 1, S16, F32>(a, lds, wv, lane); break;
-        case 2: wk_run<BLK, 2, S16, F32>(a, lds, wv, lane); break;
-        default: wk_run<BLK, 3, S16, F32>(a, lds, wv, lane); break;
+        case 0: wk_run<0, F32>(a, lds, wv, lane); break;
+        case 1: wk_run<1, F32>(a, lds, wv, lane); break;
+        case 2: wk_run<2, F32>(a, lds, wv, lane); break;
+        default: wk_run<3, F32>(a, lds, wv, lane); break;
     }
 }
 
@@ -901,7 +698,7 @@ __global__ void __launch_bounds__(256, (BLK == 64 || F32) ? 1 : 2) k_conv_wgrad_
 // ONE new x plane and one gathered dy plane per unit feed 256 MFMAs - 152 B of LDS-DMA per MFMA.  Wave = (kd', kh') tap pair x both kw' x the
 // whole 64 x 64 block: 2 x 2 x 2 accumulators (128 registers); a dy fragment serves 4 MFMAs, an x fragment 2: 0.75 KB of LDS reads per MFMA.
 // One workgroup per CU (3 x 23 + 2 x 16 KiB of LDS), one wave per SIMD; the DMA pieces and descriptors of the next unit are issued between the
-// MFMAs as in k_conv_wgrad_kd<64>.  Same result layout as the UPW kernel: dWc[p][kd'][kh'][kw'][Cout][C0] fp32 (atomics).
+// MFMAs.  Same result layout as the UPW kernel: dWc[p][kd'][kh'][kw'][Cout][C0] fp32 (atomics).
 struct WuCfg {
     static constexpr int NW = 4;
     static constexpr int ROWB = 128, RS = 8;                               // 64 channels x 2 B per x row and per dy row
@@ -915,17 +712,13 @@ struct WuCfg {
     static constexpr int SP0 = 1, SPD = 2;                                 // DMA piece p of the next unit behind step SP0 + SPD p (32 steps per unit; SPD 1 level, 3 slower: profiles/r06_upw_kd_tune.log)
 };
 
-// W8: eight waves - waves 0-3 own Cin half 0 of the block, waves 4-7 Cin half 1 (64 accumulator registers each): two waves per SIMD, so that one
-// wave's DMA issue (10 pieces of ~100 cycles per 64-MFMA unit in the 4-wave form: 66 cycles per MFMA, profiles/r06_upw_kd_prof.log) runs under
-// its partner's MFMAs; a dy fragment then serves 2 MFMAs instead of 4 (1 KB of LDS reads per MFMA instead of 0.75).  Measured level with the
-// 4-wave form (62-66 cycles per MFMA slot, a 15 % barrier share: profiles/r06_upw_kd8_prof.log): kept as FMRI_UPW_KD=2, not the default.
-template <int G, bool W8>          // wave group G: taps kd' = G >> 1, kh' = G & 1, kw' = 0 | 1
+// (An 8-wave form - Cin halves split over two waves per SIMD - measured level with this one: profiles/r06_upw_kd8_prof.log)
+template <int G>          // wave group G: taps kd' = G >> 1, kh' = G & 1, kw' = 0 | 1
 __device__ __forceinline__ void wu_run(const WkArgs& a, unsigned char* lds, int wv, int lane) {
     typedef WuCfg K;
-    constexpr int KDP = G >> 1, KHP = G & 1, NW = W8 ? 8 : K::NW, ROWB = K::ROWB, RS = K::RS;
-    constexpr int NI = W8 ? 1 : 2;                                         // Cin halves per wave
-    constexpr int XPW = (K::X_INSTR + NW - 1) / NW, YPW = K::Y_INSTR / NW; // DMA pieces per wave and unit: 6 + 4 | 3 + 2
-    const int ih0 = W8 ? (wv >> 2) : 0;                                    // this wave's (first) Cin half
+    constexpr int KDP = G >> 1, KHP = G & 1, NW = K::NW, ROWB = K::ROWB, RS = K::RS;
+    constexpr int NI = 2;                                                  // Cin halves per wave
+    constexpr int XPW = K::XPW, YPW = K::YPW;                              // DMA pieces per wave and unit: 6 + 4
     typedef __attribute__((ext_vector_type(8))) short s16x8;
     const SrcB& s = a.s;
     const int N = a.N, D = a.D, H = a.H, W = a.W, Cout = a.Cout;          // D, H, W: the LOW-res grid (dy is [N][2D][2H][2W][Cout])
@@ -941,7 +734,7 @@ __device__ __forceinline__ void wu_run(const WkArgs& a, unsigned char* lds, int 
     const int pd = par >> 2, ph = (par >> 1) & 1, pw = par & 1;
     const int co0 = cob * 64, cc = cib * 64;
     const int r = lane & 31, hk = lane >> 5;
-    const bool do_bias = G == 0 && a.db != nullptr && cib == 0 && ih0 == 0;            // each parity class covers its own eighth of the voxels
+    const bool do_bias = G == 0 && a.db != nullptr && cib == 0;            // each parity class covers its own eighth of the voxels
 
     f32x16 acc[2][2][NI];                                                  // [kw'][Cout half][Cin half]
 #pragma unroll
@@ -1019,7 +812,7 @@ __device__ __forceinline__ void wu_run(const WkArgs& a, unsigned char* lds, int 
     const int shift = ph * wg::XW + pw;
     int pre_x[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) pre_x[m] = (wg_slot_off<ROWB>(lrow + shift + m, lslot) + (pp & 1) * 8) ^ (ih0 << 6);       // Cin half 1: ^ 64
+    for (int m = 0; m < 4; ++m) pre_x[m] = wg_slot_off<ROWB>(lrow + shift + m, lslot) + (pp & 1) * 8;       // Cin half 1: ^ 64
     const int pre_y = wg_slot_off<ROWB>(lrow, lslot) + (pp & 1) * 8;                                         // Cout half 1: ^ 64
 
     const int per = (nunits + a.nslab - 1) / a.nslab;
@@ -1089,7 +882,7 @@ __device__ __forceinline__ void wu_run(const WkArgs& a, unsigned char* lds, int 
             for (int st = 0; st < NS; ++st) {
                 const int ks8 = st / (2 * NI), j = (st / NI) & 1, i = st % NI, ab = ks8 & 1;
                 if (st + PF < NS) b[(st + PF) % RING] = load_b(st + PF);
-                if (st % (2 * NI) == (NI == 2 ? 1 : 0) && ks8 + 1 < 8) load_a(ks8 + 1, av[ab ^ 1]);
+                if (st % (2 * NI) == 1 && ks8 + 1 < 8) load_a(ks8 + 1, av[ab ^ 1]);
                 if (st % (2 * NI) == 0 && do_bias) {
 #pragma unroll
                     for (int h = 0; h < 2; ++h)
@@ -1148,7 +941,7 @@ __device__ __forceinline__ void wu_run(const WkArgs& a, unsigned char* lds, int 
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
                     const int co = co0 + h * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hk;
-                    const int ci = cc + (ih0 + i) * 32 + r;
+                    const int ci = cc + i * 32 + r;
                     atomicAdd(&a.dw[((int64_t)((par * 2 + KDP) * 4 + KHP * 2 + j) * Cout + co) * Cin + ci], acc[j][h][i][reg]);
                 }
     if (do_bias) {
@@ -1161,16 +954,15 @@ __device__ __forceinline__ void wu_run(const WkArgs& a, unsigned char* lds, int 
     }
 }
 
-template <bool W8>
-__global__ void __launch_bounds__(W8 ? 512 : 256, 1) k_conv_wgrad_up_kd(WkArgs a) {
+__global__ void __launch_bounds__(256, 1) k_conv_wgrad_up_kd(WkArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[WuCfg::LDS_BYTES];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     switch (wv & 3) {
-        case 0: wu_run<0, W8>(a, lds, wv, lane); break;
-        case 1: wu_run<1, W8>(a, lds, wv, lane); break;
-        case 2: wu_run<2, W8>(a, lds, wv, lane); break;
-        default: wu_run<3, W8>(a, lds, wv, lane); break;
+        case 0: wu_run<0>(a, lds, wv, lane); break;
+        case 1: wu_run<1>(a, lds, wv, lane); break;
+        case 2: wu_run<2>(a, lds, wv, lane); break;
+        default: wu_run<3>(a, lds, wv, lane); break;
     }
 }
 
@@ -1233,17 +1025,10 @@ k_wgrad_reduce(const float* __restrict__ ws, float* __restrict__ dw, int Cout, i
 
 }  // namespace
 
-static int wgrad_f32_mfma() {           // FMRI_F32_MFMA=0: fp32 tensors stay on the VALU kernels of conv3d_generic.hip (rounds 1-5)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("FMRI_F32_MFMA");
-        v = e ? atoi(e) : 1;
-    }
-    return v;
-}
+int fmri_f32_mfma();                    // FMRI_F32_MFMA (conv3d_mfma.hip)
 bool conv3d_wgrad_mfma_ok(int C0, int C1, int Cout, int D, int H, int W, int dtype) {
-    if (dtype == FMRI_F32)                // k_conv_wgrad_kd<32, false, F32>: (32 Cout, 32 Cin) blocks of fp32 planes
-        return wgrad_f32_mfma() && !(C0 % 32) && !(C1 % 32) && C0 + C1 >= 32 && !(Cout % 32) && !(H % wg::TH) && !(W % wg::TW) &&
+    if (dtype == FMRI_F32)                // k_conv_wgrad_kd<F32>: (32 Cout, 32 Cin) blocks of fp32 planes
+        return fmri_f32_mfma() && !(C0 % 32) && !(C1 % 32) && C0 + C1 >= 32 && !(Cout % 32) && !(H % wg::TH) && !(W % wg::TW) &&
                (long long)H * W * (C0 > C1 ? C0 : C1) * 4 < (1ll << 31) && (long long)H * W * Cout * 4 < (1ll << 31);
     if (dtype != FMRI_BF16) return false;
     if ((C0 % 32) || (C1 % 32) || C0 + C1 < 32 || (Cout % 64)) return false;
@@ -1253,28 +1038,19 @@ bool conv3d_wgrad_mfma_ok(int C0, int C1, int Cout, int D, int H, int W, int dty
     return true;
 }
 
-static void wgrad_plan(int C0, int C1, int Cout, int N, int D, int H, int W, int planar, bool with_ws, int& CIB, int& combos, int& nslab) {
+static void wgrad_plan(int C0, int C1, int Cout, int N, int D, int H, int W, int planar, int& CIB, int& combos, int& nslab) {
     const int Cin = C0 + C1;
     const bool wide = (C0 % 64 == 0) && (C1 % 64 == 0);
     CIB = wide ? 64 : 32;
     combos = (planar ? 1 : 3) * (Cout / 64) * (Cin / CIB);
     const int ntiles = N * D * (H / wg::TH) * (W / wg::TW);
     // Workgroups per launch.  Atomic flush: every workgroup adds 9 x 64 x 64 fp32 accumulators (147 KB) at ~1.3 TB/s, so small layers
-    // want few workgroups and large ones many (load balance / tail): measured per layer at BASELINE config 2 (tools/bench_conv.py,
-    // FMRI_WGRAD_WGS sweep) >= 0.9 TFLOP layers are fastest at ~2048, the rest at ~768, the smallest at ~512.  With a slab workspace the
-    // flush is a plain store + one reduction pass, and the sweep is repeated in FMRI_WGRAD_WGS_SLAB.
-    static int forced_wgs = -1, forced_slab = -1;
-    if (forced_wgs < 0) {
-        const char* e = getenv("FMRI_WGRAD_WGS");
-        forced_wgs = e ? atoi(e) : 0;
-        const char* f = getenv("FMRI_WGRAD_WGS_SLAB");
-        forced_slab = f ? atoi(f) : 0;
-    }
+    // want few workgroups and large ones many (load balance / tail): measured per layer at BASELINE config 2 (tools/bench_conv.py, sweep of
+    // the workgroup count) >= 0.9 TFLOP layers are fastest at ~2048, the rest at ~768, the smallest at ~512.  The launches with a slab
+    // workspace (plain store + one reduction pass instead of the atomic flush) use the same counts.
     const double flops = 2.0 * (planar ? 9 : 27) * (double)Cin * Cout * (double)N * D * H * W;
     int target_wgs = flops >= 0.9e12 ? 2048 : (flops >= 0.06e12 ? 768 : 512);
     if (planar) target_wgs = 512;       // 2-D slices (one kd plane per combo): two workgroups per CU throughout (configs[3] step: 13.7 -> 13.5 ms)
-    if (with_ws && forced_slab >= 64) target_wgs = forced_slab;
-    if (!with_ws && forced_wgs >= 64) target_wgs = forced_wgs;
     nslab = (target_wgs + combos - 1) / combos;
     if (nslab > ntiles) nslab = ntiles;
     if (nslab < 1) nslab = 1;
@@ -1282,44 +1058,34 @@ static void wgrad_plan(int C0, int C1, int Cout, int N, int D, int H, int W, int
 
 int64_t conv3d_wgrad_mfma_ws_bytes(int C0, int C1, int Cout, int N, int D, int H, int W, int planar) {
     int CIB, combos, nslab;
-    wgrad_plan(C0, C1, Cout, N, D, H, W, planar, true, CIB, combos, nslab);
+    wgrad_plan(C0, C1, Cout, N, D, H, W, planar, CIB, combos, nslab);
     return (int64_t)combos * nslab * (CIB == 32 ? 2 : 1) * 9 * 64 * CIB * (int64_t)sizeof(float);
 }
 
 // launches of at least this many FLOPs take the kd-sharing kernel with its atomic flush, smaller ones the per-kd kernel with the slab flush
-// (FMRI_WGRAD_KD_MIN_GFLOP overrides: A/B)
-static double wgrad_kd_min_flops() {
-    static double v = -1.0;
-    if (v < 0) {
-        const char* e = getenv("FMRI_WGRAD_KD_MIN_GFLOP");
-        v = e ? atof(e) * 1e9 : 0.3e12;
-    }
+// (round 2, per layer and inside the step; see conv3d_wgrad_mfma_ld.  Round 6 tried 20 GFLOP: per launch -5 ... -13 % on four small layers,
+// but the step 0.7 % slower - their atomic flushes land on the input-gradient stream's kernels)
+constexpr double WGRAD_KD_MIN_FLOPS = 0.3e12;
+// FMRI_WGRAD_KD: 0 = the per-kd kernel everywhere, 2 (default) = the kd-sharing kernel on the launches below, 3 = the same plus the
+// fused-upsample launches
+static int wgrad_kd_mode() {
+    static const int v = env_int("FMRI_WGRAD_KD", 2, {0, 2, 3});
     return v;
 }
 // does this launch take the kd-sharing kernel (k_conv_wgrad_kd)?  use_ws: the slab flush was chosen for it
-static bool wgrad_takes_kd(int C0, int C1, int Cout, int N, int D, int H, int W, int planar, int up0, bool use_ws, int* blk_out) {
-    static int kd_mode = -1, kd_blk = 32;
-    if (kd_mode < 0) {
-        const char* e = getenv("FMRI_WGRAD_KD");
-        kd_mode = e ? atoi(e) : 2;
-        const char* f = getenv("FMRI_WGRAD_KD_BLK");
-        kd_blk = (f && atoi(f) == 64) ? 64 : 32;
-    }
+static bool wgrad_takes_kd(int C0, int C1, int Cout, int N, int D, int H, int W, int planar, int up0, bool use_ws) {
+    const int kd_mode = wgrad_kd_mode();
     const double flops_ = 2.0 * (planar ? 9 : 27) * (double)(C0 + C1) * Cout * (double)N * D * H * W;
     const bool narrow = (C0 % 64) || (C1 % 64);
     const bool base = kd_mode && !planar && !use_ws && (!up0 || kd_mode == 3) && (C0 % 32 == 0) && (C1 % 32 == 0) && (Cout % 32 == 0);
-    // FMRI_WGRAD_KD_BLK=64: the one-wave-per-SIMD (64 Cout, 32 Cin) form on every launch of >= 0.3 TFLOP whose Cout it tiles; 32 elsewhere
-    const bool w1 = base && kd_blk == 64 && (Cout % 64 == 0) && (kd_mode == 3 || (kd_mode >= 2 && flops_ >= wgrad_kd_min_flops()));
-    if (blk_out) *blk_out = w1 ? 64 : 32;
-    return w1 || (base && ((kd_mode >= 2 && flops_ >= wgrad_kd_min_flops()) || (narrow && flops_ >= 0.1e12)));
+    return base && (flops_ >= WGRAD_KD_MIN_FLOPS || (narrow && flops_ >= 0.1e12));
 }
 // A 32-wide Cout (not a multiple of the per-kd kernel's 64-wide block) is fine where the kd-sharing kernel with its 32 x 32 blocks takes the
 // launch: no workspace (slab flush), see wgrad_takes_kd.  Lets the channel-padded layer-graph engine pass a 32-channel dy as it is (it
 // made a zero-extended 64-channel copy of it per layer and step: 1.4 ms of copies per Isensee step).
 bool conv3d_wgrad_cout32_ok(int C0, int C1, int Cout, int N, int D, int H, int W, int dtype, int planar, int up0) {
     if (dtype != FMRI_BF16 || (C0 % 32) || (C1 % 32) || C0 + C1 < 32 || (Cout % 32) || (H % wg::TH) || (W % wg::TW)) return false;
-    int blk = 32;
-    return wgrad_takes_kd(C0, C1, Cout, N, D, H, W, planar, up0, false, &blk) && blk == 32;
+    return wgrad_takes_kd(C0, C1, Cout, N, D, H, W, planar, up0, false);
 }
 // dw_ld: row length of the dw image the gradient is added into (>= C0 + C1; lets a launch over a subset of the input channels write
 // its columns of the full [27][Cout][Cin] gradient: pass dw already offset to the first column)
@@ -1329,14 +1095,10 @@ int conv3d_wgrad_mfma_ld(const void* src0, int C0, int up0, int planar, const vo
     const int Cin = C0 + C1;
     // The slab flush wins where the flush dominates (small layers: -25..35 %) and loses ~4 % on the >= 0.3 TFLOP layers, whose atomic
     // flush overlaps other workgroups' MFMA work while the reduction pass is a serial tail (tools/bench_conv.py, BENCH_WGRAD_WS=0|1).
-    static int force_slab = -1;
-    if (force_slab < 0) {
-        const char* e = getenv("FMRI_WGRAD_SLAB");      // 1: always use the workspace when given (bit-reproducible), 0: heuristic
-        force_slab = e ? atoi(e) : 0;
-    }
+    static const int force_slab = env_int("FMRI_WGRAD_SLAB", 0, {0, 1});      // 1: always use the workspace when given (bit-reproducible), 0: heuristic
     const double flops_ = 2.0 * (planar ? 9 : 27) * (double)(C0 + C1) * Cout * (double)N * D * H * W;
     const bool use_ws = workspace != nullptr && workspace_bytes >= conv3d_wgrad_mfma_ws_bytes(C0, C1, Cout, N, D, H, W, planar) &&
-                        (force_slab == 1 || flops_ < wgrad_kd_min_flops());
+                        (force_slab == 1 || flops_ < WGRAD_KD_MIN_FLOPS);
     // kd-sharing kernels (a workgroup owns a (Cout, Cin) block for all 27 taps and walks columns; see k_conv_wgrad_kd).  Measured per layer
     // (profiles/r02_wgrad_kd_sharing_ab.log): the 4-wave form wins where the per-kd kernel has to fall back to 32-wide Cin blocks (enc0b
     // 32 -> 64 at full resolution: -17 %), is level with it on the 64- and 128-channel layers (0 ... -5 %) and loses on the fused-upsample
@@ -1346,54 +1108,30 @@ int conv3d_wgrad_mfma_ld(const void* src0, int C0, int up0, int planar, const vo
     // family 4.64 -> 4.34 ms per step, step 13.96 -> 13.73 ms.  FMRI_WGRAD_KD: 0 = off, 1 = only the layers with a 32-wide Cin block and
     // >= 0.1 TFLOP (the default until then), 2 (default) = also every launch of >= 0.3 TFLOP without fused up-sampling (below that the
     // per-kd kernel is ahead, with the slab flush or - callers without a workspace, e.g. the layer-graph engine - with the atomic one:
-    // Isensee defaults 11.3 vs 11.65 ms per step), 3 = the fused-upsample launches too;
-    // FMRI_WGRAD_KD_BLK = 32 (two workgroups per CU, 32 x 32 blocks) | 64 (one workgroup per CU, one wave per SIMD, 64 x 32 blocks; round 6).
-    int kd_blk = 32;
-    if (wgrad_takes_kd(C0, C1, Cout, N, D, H, W, planar, up0, use_ws, &kd_blk)) {
-        const int combos_kd = (Cout / kd_blk) * (Cin / 32);
+    // Isensee defaults 11.3 vs 11.65 ms per step), 3 = the fused-upsample launches too.
+    if (wgrad_takes_kd(C0, C1, Cout, N, D, H, W, planar, up0, use_ws)) {
+        const int combos_kd = (Cout / 32) * (Cin / 32);
         const int nunits = N * D * (H / wg::TH) * (W / wg::TW);
-        static int kd_wgs = -1;
-        if (kd_wgs < 0) {
-            const char* e = getenv("FMRI_WGRAD_KD_WGS");
-            kd_wgs = e ? atoi(e) : 0;
-        }
         // workgroups per launch: two per CU, i.e. ONE resident round (round 3: four per CU until then - every workgroup ends in a flush of
         // 27 x 32 x 32 fp32 atomics onto the same filter block as the others of its column, so half the workgroups are half the flush
         // traffic: weight-gradient family 4.64-4.73 -> 4.44-4.57 ms per step, step +0.2 ... 2.1 % in four interleaved same-box pairs;
-        // one per CU leaves the second slot of the CUs empty: 5.1-5.2 ms).  FMRI_WGRAD_KD_WGS overrides.
-        const int target = kd_wgs > 0 ? kd_wgs : (kd_blk == 64 ? 1 : 2) * fwd_cu_count();      // BLK = 64: one (512-register) workgroup per CU
+        // one per CU leaves the second slot of the CUs empty: 5.1-5.2 ms)
+        const int target = 2 * fwd_cu_count();
         int nsl = (target + combos_kd - 1) / combos_kd;
         if (nsl > nunits) nsl = nunits;
         if (nsl < 1) nsl = 1;
         const WkArgs wa{s, (const bf16_t*)dy, dw, db, N, D, H, W, Cout, nsl, dw_ld};
-        static int wg16 = -1;                // FMRI_WGRAD_MFMA16=1: v_mfma_f32_16x16x32_bf16 in the kd-sharing kernel (wk_compute16)
-        if (wg16 < 0) {
-            const char* e = getenv("FMRI_WGRAD_MFMA16");
-            wg16 = e ? atoi(e) : 0;
-        }
-        if (kd_blk == 64) k_conv_wgrad_kd<64><<<combos_kd * nsl, 256, 0, st>>>(wa);
-        else if (wg16) k_conv_wgrad_kd<32, true><<<combos_kd * nsl, 256, 0, st>>>(wa);
-        else k_conv_wgrad_kd<32><<<combos_kd * nsl, 256, 0, st>>>(wa);
+        k_conv_wgrad_kd<><<<combos_kd * nsl, 256, 0, st>>>(wa);
         FMRI_LAUNCH_CHECK();
         return FMRI_OK;
     }
     if (Cout % 64) return FMRI_E_SHAPE;                      // the per-kd kernel tiles Cout by 64
     int CIB, combos, nslab;
-    wgrad_plan(C0, C1, Cout, N, D, H, W, planar, use_ws, CIB, combos, nslab);
+    wgrad_plan(C0, C1, Cout, N, D, H, W, planar, CIB, combos, nslab);
     float* ws = use_ws ? (float*)workspace : nullptr;
-    // Warp-specialised variant (8 waves, one workgroup per CU, 3-slot ring with the producers two units ahead): alone it is 2-5 % faster on
-    // the layers with >= 0.3 TFLOP and a few % slower on the small ones, but inside the two-stream training step the whole-CU workgroups
-    // interleave worse with the forward-type kernels of the other stream (-0.7 % per step) - kept as an option, off by default.
-    // FMRI_WGRAD_WS = 1 always / 2 by size.
-    static int wg_ws = -2;
-    if (wg_ws == -2) {
-        const char* e = getenv("FMRI_WGRAD_WS");
-        wg_ws = e ? atoi(e) : 0;
-    }
-    if (wg_ws == 1 || (wg_ws == 2 && flops_ >= 0.3e12)) {
-        if (CIB == 64) k_conv_wgrad_mfma<2, false, true><<<combos * nslab, 512, 0, st>>>(s, (const bf16_t*)dy, dw, db, N, D, H, W, Cout, nslab, ws, dw_ld);
-        else k_conv_wgrad_mfma<1, false, true><<<combos * nslab, 512, 0, st>>>(s, (const bf16_t*)dy, dw, db, N, D, H, W, Cout, nslab, ws, dw_ld);
-    } else if (CIB == 64) k_conv_wgrad_mfma<2, false><<<combos * nslab, wg::NTHREADS, 0, st>>>(s, (const bf16_t*)dy, dw, db, N, D, H, W, Cout, nslab, ws, dw_ld);
+    // (A warp-specialised form - 8 waves, one workgroup per CU, the producers two units ahead - was 2-5 % faster alone on the layers with
+    // >= 0.3 TFLOP, but inside the two-stream training step its whole-CU workgroups interleaved worse with the other stream: -0.7 % per step.)
+    if (CIB == 64) k_conv_wgrad_mfma<2, false><<<combos * nslab, wg::NTHREADS, 0, st>>>(s, (const bf16_t*)dy, dw, db, N, D, H, W, Cout, nslab, ws, dw_ld);
     else k_conv_wgrad_mfma<1, false><<<combos * nslab, wg::NTHREADS, 0, st>>>(s, (const bf16_t*)dy, dw, db, N, D, H, W, Cout, nslab, ws, dw_ld);
     if (use_ws) {
         const int ncob = Cout / 64, ncib = Cin / CIB;
@@ -1416,7 +1154,7 @@ int conv3d_wgrad_mfma_f32(const void* src0, int C0, int up0, const void* src1, i
     if (nsl > nunits) nsl = nunits;
     if (nsl < 1) nsl = 1;
     const WkArgs wa{s, (const bf16_t*)dy, dw, db, N, D, H, W, Cout, nsl, C0 + C1};
-    k_conv_wgrad_kd<32, false, true><<<combos * nsl, 256, 0, st>>>(wa);
+    k_conv_wgrad_kd<true><<<combos * nsl, 256, 0, st>>>(wa);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
@@ -1479,27 +1217,19 @@ int conv3d_upcat_wgrad_mfma_ex(const void* src0_low, int C0, const void* src1, i
         if (nslab > nunits) nslab = nunits;
         if (nslab < 1) nslab = 1;
         float* const dbu = C1 == 0 ? db : nullptr;         // with skip channels the plain launch below produces the bias gradient
-        const char* e = getenv("FMRI_WGRAD_WS");
-        const int ws_mode = e ? atoi(e) : 0;
         // kd'-sharing form (k_conv_wgrad_up_kd, round 6): 3-D, 64-wide blocks of both channel counts.  FMRI_UPW_KD=0: the per-kd' kernel (rounds 2-5),
-        // 1 (default): four waves, 2: eight waves.  Same-box A/B (profiles/r06_upw_kd8_ab.log): step 299.0 -> 300.8 / 301.0 patches/s, the three
-        // launches' weight gradients 2.30 -> 2.21 ms; both forms run at 62-66 cycles per MFMA slot (profiles/r06_upw_kd_prof.log, r06_upw_kd8_prof.log):
-        // at 152 B of LDS-DMA per MFMA the kernel asks the L2 for ~5.6 TB/s (2.5 GB per dec0a launch)
-        static int upw_kd = -1;
-        if (upw_kd < 0) {
-            const char* f = getenv("FMRI_UPW_KD");
-            upw_kd = f ? atoi(f) : 1;
-        }
+        // 1 (default): the kd'-sharing one.  Same-box A/B (profiles/r06_upw_kd8_ab.log): step 299.0 -> 300.8 patches/s, the three launches' weight
+        // gradients 2.30 -> 2.21 ms; 62-66 cycles per MFMA slot (profiles/r06_upw_kd_prof.log): at 152 B of LDS-DMA per MFMA the kernel asks the
+        // L2 for ~5.6 TB/s (2.5 GB per dec0a launch)
+        static const int upw_kd = env_int("FMRI_UPW_KD", 1, {0, 1});
         if (upw_kd && !planar && wide && Cout % 64 == 0) {
             const int combos_kd = 8 * (Cout / 64) * (C0 / 64);
             int nsl = (fwd_cu_count() + combos_kd - 1) / combos_kd;
             if (nsl > nunits) nsl = nunits;
             if (nsl < 1) nsl = 1;
             const WkArgs wa{s, (const bf16_t*)dy, dwc, dbu, N, Dl, Hl, Wl, Cout, nsl, C0};
-            if (upw_kd == 2) k_conv_wgrad_up_kd<true><<<combos_kd * nsl, 512, 0, st>>>(wa);        // FMRI_UPW_KD=2: the 8-wave form (two waves per SIMD): level
-            else k_conv_wgrad_up_kd<false><<<combos_kd * nsl, 256, 0, st>>>(wa);
-        } else if (wide && (ws_mode == 1 || (ws_mode == 2 && 2.0 * 8 * 8 * (double)C0 * Cout * N * Dl * Hl * Wl >= 0.3e12))) k_conv_wgrad_mfma<2, true, true><<<combos * nslab, 512, 0, st>>>(s, (const bf16_t*)dy, dwc, dbu, N, Dl, Hl, Wl, Cout, nslab, nullptr, C0);
-        else if (wide) k_conv_wgrad_mfma<2, true><<<combos * nslab, wg::NTHREADS, 0, st>>>(s, (const bf16_t*)dy, dwc, dbu, N, Dl, Hl, Wl, Cout, nslab, nullptr, C0);
+            k_conv_wgrad_up_kd<<<combos_kd * nsl, 256, 0, st>>>(wa);
+        } else if (wide) k_conv_wgrad_mfma<2, true><<<combos * nslab, wg::NTHREADS, 0, st>>>(s, (const bf16_t*)dy, dwc, dbu, N, Dl, Hl, Wl, Cout, nslab, nullptr, C0);
         else k_conv_wgrad_mfma<1, true><<<combos * nslab, wg::NTHREADS, 0, st>>>(s, (const bf16_t*)dy, dwc, dbu, N, Dl, Hl, Wl, Cout, nslab, nullptr, C0);
     }
     // 2. fold them into the 27-tap gradient of the up-sampled input channels (columns [0, C0) of dw)

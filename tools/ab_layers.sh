@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-layer A/B on ONE box: bench.py --per-layer once per "VAR=value" argument (and once plain), then the exclusive ms of every conv x pass
-# side by side.   usage: bash tools/ab_layers.sh FMRI_FWD_ASYNC=0
+# side by side.   usage: bash tools/ab_layers.sh FMRI_FWD_WS=0
 mkdir -p gpurun_out/ab
 REPS=${REPS:-2}
 for rep in $(seq 1 $REPS); do

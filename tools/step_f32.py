@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """K training steps of configs[1] in the fp32 parity mode and nothing else (the program behind profiles/r06_f32_kernel_stats.csv: which
-kernels the fp32 mode runs - the fp32 instantiations of the benchmarked MFMA kernels, `k_conv_fwd_ws<1, …, true>` / `k_conv_wgrad_kd<32, false, true>`).
+kernels the fp32 mode runs - the fp32 instantiations of the benchmarked MFMA kernels, `k_conv_fwd_ws<1, …, true>` / `k_conv_wgrad_kd<true>`).
 usage: step_f32.py [K] [batch]"""
 import os
 import sys
