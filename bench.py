@@ -5,15 +5,20 @@ per GPU, synthetic data resident in HBM, random-init (glorot) weights.
 
   python bench.py --gpus N --steps K --warmup W
   python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR      (also writes what the last timed step computed: dump_outputs)
+  python bench.py --gpus 1 --steps K --warmup W --full                  (also every measurement the headline figure does not need)
 
 N > 1: one rank per GPU over RCCL.  Under a launcher (torch.distributed.run sets RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*) this
 process IS one rank; started bare (`python bench.py --gpus 8`) it becomes a parent that starts the N ranks as child processes - before
 anything touches the GPU - relays rank 0's JSON line and exits non-zero when any rank fails.  A rank whose WORLD_SIZE differs from
 --gpus refuses to run (a single-GPU number can no longer be labelled as a scaling run).
 
-Prints ONE JSON line on rank 0.  Besides the driver contract it carries
+Prints ONE JSON line on rank 0.  A plain run sets up, pre-warms, warms up, times the K steps, writes --dump-outputs and prints the line:
+besides the driver contract it carries
   "roofline"     for the dominant kernel (live HIP-event timing of its launches in the timed region: every launch of every 10th timed
-                 step - event brackets on every step cost 2.3 % of the step, see --launch-timing-every), and
+                 step - event brackets on every step cost 2.3 % of the step, see --launch-timing-every).
+With --full (see full_legs) the run goes on after the timed region - the figures below take runs of their own - and the line also carries
+  "roofline_exclusive"  the same kernels timed in a second pass of the K steps on one stream,
+  "continuity", "val_dice", "reference_api", "secondary"  (N = 1) the legs of the functions of those names,
   "cpu_baseline" the CPU oracle (torch-CPU restatement; Keras/TF are absent here and on the GPU box) timed on the host (the only leg that
                  touches oracle/; its first step's forward pass is also the reference of the next item),
   "parity_mode"  what FMRI_DTYPE=fp32 costs and delivers at this configuration: patches/s of the fp32 step on the fp32 instantiation of the
@@ -690,7 +695,18 @@ def selftest_cpu(a, rank, world):
                                                                            "parallelism": "dp%d" % world}}))
 
 
-def main():
+def full_legs(a, world):
+    """What a run measures after its timed region: nothing without --full; with it every leg that its --no-* switches leave on, the
+    single-GPU legs at N = 1 only.  `exclusive` (the one-stream second pass) also needs the engine's second stream: main() checks that."""
+    one = a.full and world == 1
+    return {"exclusive": a.full and not a.no_launch_timing and not a.no_exclusive_pass,
+            "continuity": one and a.data == "learnable" and not a.no_secondary,
+            "val_dice": one and a.val_dice_steps > 0,
+            "secondary": one and not a.no_secondary,          # reference_api, configs[4], configs[3] and parity_mode
+            "cpu_baseline": one and not a.no_cpu_baseline}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)      # 50 steps = 0.8 s: the first ten run ~2 % slower than the steady state
@@ -704,7 +720,11 @@ def main():
                     help="learnable (default): a pool of batches of tools/learnable_task.py, walked round-robin; survey: rounds 1-3's ONE batch with labels "
                          "independent of the image (the net collapses to all-foreground and the backward kernels multiply ~0 gradients: a faster clock)")
     ap.add_argument("--pool", type=int, default=8, help="batches in the resident pool (learnable data)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline figure does not need (see full_legs): the one-stream "
+                         "second pass (roofline_exclusive) and, at N = 1, the continuity / val-Dice / reference-API / configs[3] / configs[4] "
+                         "legs, the CPU baseline and the fp32 parity mode.  The --no-* switches below leave single legs out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-launch-timing", action="store_true")
     ap.add_argument("--launch-timing-every", type=int, default=None,
                     help="HIP-event brackets on every n-th step of the timed region (1 = every step; they cost 2.3 %% of the step time when on every "
@@ -713,31 +733,38 @@ def main():
                     help="cfg1 (default): the headline configs[1] training step.  cfg3 / cfg4: ONE line for BASELINE configs[3] (2-D training step) "
                          "or configs[4] (sliding-window inference of a 160x256x256 volume), N = 1")
     ap.add_argument("--val-dice-steps", type=int, default=150,
-                    help="Adam steps of the val-Dice leg (after the timed region, N = 1 only; 0 = skip): see val_dice_leg")
+                    help="with --full: Adam steps of the val-Dice leg (after the timed region, N = 1 only; 0 = skip): see val_dice_leg")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short configs[3] / configs[4] / reference-API measurements that the default N = 1 line carries after the timed region")
+                    help="with --full: skip the short continuity / configs[3] / configs[4] / reference-API / parity-mode measurements that the "
+                         "N = 1 line carries after the timed region")
     ap.add_argument("--no-exclusive-pass", action="store_true",
-                    help="skip the second (single-stream) pass that measures exclusive kernel durations (used when profiling the timed region alone)")
+                    help="with --full: skip the second (single-stream) pass that measures exclusive kernel durations")
     ap.add_argument("--serialize-streams", action="store_true",
                     help="run the conv weight gradients on the main stream (no concurrent kernels): per-kernel durations become exclusive")
     ap.add_argument("--per-layer", default=None, metavar="JSON",
                     help="also write the per-layer table (every 3x3x3 conv x fwd/dgrad/wgrad: exclusive ms, TFLOP/s / 2.5 PF, algorithmic "
-                         "GB/s / 8 TB/s; SURVEY 8d) to this file")
+                         "GB/s / 8 TB/s; SURVEY 8d) to this file.  Exclusive times come from the second pass of --full or from --serialize-streams; "
+                         "otherwise the table holds the two-stream brackets and says so (\"exclusive\": false)")
     ap.add_argument("--selftest-cpu", action="store_true", help="exercise the N-rank launcher on the CPU (gloo); measures nothing")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs).  That last step then starts "
                          "from the seeded initial weights, zero Adam moments and the first pool batch (restored outside the clock), so that the "
                          "same arguments give the same inputs on every run")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
     if a.steps < 1:
         ap.error("--steps must be >= 1")
     if a.launch_timing_every is None:
         a.launch_timing_every = 5 if a.steps <= 20 else 10
+    if a.config != "cfg1" and a.gpus != 1:
+        ap.error("--config cfg3|cfg4 are single-GPU lines")
+    return a
+
+
+def main():
+    a = parse_args()
     if a.config != "cfg1":
-        if a.gpus != 1:
-            ap.error("--config cfg3|cfg4 are single-GPU lines")
         return secondary_line(a.config)
 
     if a.gpus > 1 and "RANK" not in os.environ:
@@ -755,6 +782,7 @@ def main():
     if a.selftest_cpu:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         return selftest_cpu(a, rank, world)
+    legs = full_legs(a, world)
     if local_rank >= torch.cuda.device_count():
         sys.stderr.write("bench.py: rank %d: LOCAL_RANK %d but only %d device(s) visible\n" % (rank, local_rank, torch.cuda.device_count()))
         sys.exit(2)
@@ -947,7 +975,7 @@ def main():
     tot_timed = timer.totals_ms()
     detail = timer.detail_ms()          # exclusive only when everything ran on one stream (replaced by the second pass below otherwise)
     tot_excl = None
-    if not a.no_launch_timing and not a.no_exclusive_pass and eng._wg_stream is not None:
+    if legs["exclusive"] and eng._wg_stream is not None:
         # The engine runs the weight-gradient kernels on a second stream, concurrently with the input-gradient chain: inside the timed
         # region a kernel's event bracket (and its rocprofv3 duration) includes the time it shares the CUs with the other stream's kernel.
         # A second pass of the same K steps with that stream switched off gives the EXCLUSIVE durations (every rank runs it: the steps
@@ -1057,9 +1085,9 @@ def main():
         with open(a.per_layer, "w") as f:
             json.dump(tab, f, indent=1)
         out["per_layer_total"] = tab["total"]
-    if world == 1 and (a.val_dice_steps > 0 or not a.no_secondary):
+    if legs["val_dice"] or legs["secondary"]:
         # after the timed region, never inside it: the bench engine's buffers go first (each leg builds its own model)
-        if a.data == "learnable" and not a.no_secondary:
+        if legs["continuity"]:
             # continuity with rounds 1-3: the same engine, re-initialised, on the old recipe (one batch, independent labels), >= 2 s of
             # untimed steps (by then it has collapsed and the clock has settled), then 50 timed steps (round 4: 1.5 s + 20 steps scattered
             # 306-337 patches/s from box to box)
@@ -1090,9 +1118,9 @@ def main():
         del eng, pool
         torch.cuda.empty_cache()
         model = None
-        if a.val_dice_steps > 0:
+        if legs["val_dice"]:
             out["val_dice"], model = val_dice_leg(a.batch, a.val_dice_steps)
-        if not a.no_secondary:
+        if legs["secondary"]:
             import fetal_net.metrics as FM
             import fetal_net.model as fmodel
             if model is None:
@@ -1103,9 +1131,9 @@ def main():
             del model
             torch.cuda.empty_cache()
     ref = None
-    if world == 1 and not a.no_cpu_baseline:
+    if legs["cpu_baseline"]:
         out["cpu_baseline"], ref = cpu_baseline()
-    if world == 1 and not a.no_secondary:
+    if legs["secondary"]:
         out["parity_mode"] = parity_mode_leg(a.batch, ref)
     print(json.dumps(out))
 

@@ -116,13 +116,13 @@ def test_full_size_parity_form_equals_27_tap_kernels():
 
 
 def test_bench_contract_smoke():
-    """bench.py runs end to end on one GPU and prints the driver's JSON contract (+ roofline with live HIP-event timing)."""
+    """bench.py --full runs end to end on one GPU and prints the driver's JSON contract (+ roofline with live HIP-event timing)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.check_output([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                                   stderr=subprocess.STDOUT, timeout=600).decode()
     line = [l for l in out.splitlines() if l.startswith("{")][-1]
     j = json.loads(line)
@@ -215,11 +215,11 @@ def test_warp_specialised_kernel_is_bit_identical_to_the_symmetric_one(tmp_path)
 
 
 def test_bench_contract_line(tmp_path):
-    """`python bench.py --steps 3 --warmup 1` prints ONE JSON line with the driver's contract keys, the two roofline objects of the
-    two-stream step and a cpu-free run when asked (the CPU baseline itself takes ~25 s and is exercised by the default bench run)."""
+    """`python bench.py --steps 3 --warmup 1 --full` prints ONE JSON line with the driver's contract keys, the two roofline objects of the
+    two-stream step and a cpu-free run when asked (the CPU baseline itself takes ~25 s and is exercised by a --full bench run)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -236,3 +236,23 @@ def test_bench_contract_line(tmp_path):
         assert ro["launches_per_step"] == 32 and ro["avg_launch_ms"] > 0
     assert d["roofline_exclusive"]["frac"] > d["roofline"]["frac"]          # exclusive kernel time < the bracket inside the two-stream region
     assert 0.3 < d["step_mfma_frac"] < 1.0
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """a plain `python bench.py --gpus 1 --steps 3 --warmup 1` prints the contract keys and the timed region's roofline, and nothing that
+    takes a run of its own: the one-stream second pass and the legs after the timed region run with --full only"""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+              "roofline", "step_mfma_frac", "kernel_ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "patches/s" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("roofline_exclusive", "continuity", "val_dice", "reference_api", "secondary", "cpu_baseline", "parity_mode"):
+        assert k not in d, k

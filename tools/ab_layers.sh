@@ -1,23 +1,25 @@
 #!/bin/bash
 # Per-layer A/B on ONE box: bench.py --per-layer once per "VAR=value" argument (and once plain), then the exclusive ms of every conv x pass
-# side by side.   usage: bash tools/ab_layers.sh FMRI_FWD_WS=0
-mkdir -p gpurun_out/ab
+# side by side.   usage: bash tools/ab_layers.sh FMRI_FWD_WS=0   (AB_DIR: where the runs' JSON files go, default a fresh temporary directory)
+AB_DIR=${AB_DIR:-$(mktemp -d)}
+mkdir -p "$AB_DIR"
 REPS=${REPS:-2}
 for rep in $(seq 1 $REPS); do
   i=0
   for cfg in "" "$@"; do
-    env $cfg python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --val-dice-steps 0 --no-secondary --per-layer gpurun_out/ab/pl_${i}_$rep.json > gpurun_out/ab/bench_${i}_$rep.json 2>/dev/null
+    env $cfg python3 bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --val-dice-steps 0 --no-secondary --per-layer "$AB_DIR/pl_${i}_$rep.json" > "$AB_DIR/bench_${i}_$rep.json" 2>/dev/null
     i=$((i+1))
   done
 done
-export REPS
+export REPS AB_DIR
 python3 - "$@" <<'PY'
 import json, sys
 import os
 cfgs = ["default"] + sys.argv[1:]
 reps = int(os.environ.get("REPS", "2"))
-tabs = [[json.load(open("gpurun_out/ab/pl_%d_%d.json" % (i, r))) for r in range(1, reps + 1)] for i in range(len(cfgs))]
-lines = [[json.loads(open("gpurun_out/ab/bench_%d_%d.json" % (i, r)).read().strip().splitlines()[-1]) for r in range(1, reps + 1)] for i in range(len(cfgs))]
+ab = os.environ["AB_DIR"]
+tabs = [[json.load(open(os.path.join(ab, "pl_%d_%d.json" % (i, r)))) for r in range(1, reps + 1)] for i in range(len(cfgs))]
+lines = [[json.loads(open(os.path.join(ab, "bench_%d_%d.json" % (i, r))).read().strip().splitlines()[-1]) for r in range(1, reps + 1)] for i in range(len(cfgs))]
 fmt = lambda vs: "%22s" % (" ".join("%.4g" % v for v in vs))
 print("(each cell: one value per interleaved repetition)")
 print("%-22s" % "" + "".join("%22s" % c[-22:] for c in cfgs))
