@@ -9,6 +9,8 @@
 // every gather address is register + immediate, ReLU is a template parameter, the weight gradient loads its next tile
 // while it multiplies the current one and gets the bias gradient from a padding column of the same product
 // (round 6, 4 x 64x128x128: forward 77 -> 56 us, weight gradient 89 -> 59 us; 5 slices x 64 x 256x256: 194 -> 77, 161 -> 102).
+// The 2-D instantiations take 1-7 channels: slice stacks, and stacks plus previous-slice truth channels (5 + 1 slices x 64 x 256x256:
+// 83 / 102 us, where the generic kernels took 964 / 1886; tools/bench_cascade.py).
 //
 // Reference ops replaced: the first Conv3D(+BiasAdd+Relu) of unet_model_3d (unet3d/unet.py:45-46,102,113) and its
 // Conv3DBackpropFilterV2 / BiasAddGrad.
@@ -346,10 +348,12 @@ k_conv_first_wgrad(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, 
 
 }  // namespace
 
-// single-channel 3-D volumes, and the few-slice stacks of the 2-D models (reference config_utils.py:53-56: 5 slices by default)
+// single-channel 3-D volumes, and the few-slice stacks of the 2-D models (reference config_utils.py:53-56: 5 slices by default).  The even
+// planar counts are those stacks plus one previous-slice truth channel (reference config_utils.py:128-131, generator.py:272-305): 1, 3 or 5
+// slices + 1 = 2, 4, 6 channels, K = 18 / 36 / 54 = 2 / 3 / 4 k-steps, still two waves per SIMD (first_fwd_waves).
 bool conv3d_first_ok(int C0, int C1, int Cout, int D, int H, int W, int dtype, int up0, int planar) {
     if (dtype != FMRI_BF16 || C1 != 0 || up0 || (Cout % 32) || (D % 4) || (H % 16) || (W % 32)) return false;
-    return planar ? (C0 == 1 || C0 == 3 || C0 == 5 || C0 == 7) : (C0 >= 1 && C0 <= 4);     // 3-D: up to 4 modalities (BraTS-style inputs)
+    return planar ? (C0 >= 1 && C0 <= 7) : (C0 >= 1 && C0 <= 4);     // 3-D: up to 4 modalities (BraTS-style inputs)
 }
 
 #define FMRI_FIRST_DISPATCH(LAUNCH)                   \
@@ -359,8 +363,11 @@ bool conv3d_first_ok(int C0, int C1, int Cout, int D, int H, int W, int dtype, i
         else if (!planar && C0 == 3) { LAUNCH(3, false); } \
         else if (!planar) { LAUNCH(4, false); }       \
         else if (C0 == 1) { LAUNCH(1, true); }        \
+        else if (C0 == 2) { LAUNCH(2, true); }        \
         else if (C0 == 3) { LAUNCH(3, true); }        \
+        else if (C0 == 4) { LAUNCH(4, true); }        \
         else if (C0 == 5) { LAUNCH(5, true); }        \
+        else if (C0 == 6) { LAUNCH(6, true); }        \
         else { LAUNCH(7, true); }                     \
     } while (0)
 

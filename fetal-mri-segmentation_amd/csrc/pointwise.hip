@@ -855,6 +855,69 @@ extern "C" int fmri_tile_gather(const float* vol, int X, int Y, int Z, const int
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
+// Tiles of a 2-D model with previous-slice truth channels (reference prediction.py:98-114, batch_iterator): the pz image slices of a tile
+// followed by aux_nz truth slices starting aux_dz slices from the tile's corner, every coordinate clamped into the volume.  One thread per
+// (tile, x, y) row gathers the row's pz + aux_nz channels in chunks of 8 and stores each chunk with the widest vector the row pitch allows (SW
+// bytes; the lanes of a wave cover consecutive rows, so a wave writes one contiguous span).  aux_nz = 0 gives k_tile_gather's bytes.
+template <typename T, int SW>
+__global__ void __launch_bounds__(256) k_tile_gather_stack(const float* __restrict__ vol, const float* __restrict__ aux, int X, int Y, int Z,
+                                                           const int32_t* __restrict__ idx, int B, int px, int py, int pz, int aux_dz, int aux_nz,
+                                                           T* __restrict__ tiles) {
+    constexpr int CH = 8, CHB = CH * (int)sizeof(T);
+    const int C = pz + aux_nz;
+    const int64_t rows = (int64_t)B * px * py;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {
+        const int b = (int)(i / ((int64_t)px * py));
+        const int r = (int)(i % ((int64_t)px * py));
+        const int x = r / py, y = r % py;
+        const int gx = min(max(idx[3 * b] + x, 0), X - 1), gy = min(max(idx[3 * b + 1] + y, 0), Y - 1), z0 = idx[3 * b + 2];
+        const int64_t col = ((int64_t)gx * Y + gy) * Z;
+        unsigned char* const row = reinterpret_cast<unsigned char*>(tiles + i * C);
+        for (int c0 = 0; c0 < C; c0 += CH) {
+            T v[CH];
+#pragma unroll
+            for (int j = 0; j < CH; ++j) {
+                const int c = c0 + j;
+                float f = 0.f;
+                if (c < pz) f = vol[col + min(max(z0 + c, 0), Z - 1)];
+                else if (c < C) f = aux[col + min(max(z0 + aux_dz + (c - pz), 0), Z - 1)];
+                v[j] = from_f<T>(f);
+            }
+            const int nb = min(CH, C - c0) * (int)sizeof(T);        // a multiple of SW (the launch picks SW from the row pitch)
+            unsigned char* const dst = row + c0 * (int)sizeof(T);
+            const unsigned char* const src = reinterpret_cast<const unsigned char*>(v);
+#pragma unroll
+            for (int q = 0; q < CHB / SW; ++q) {
+                if (q * SW >= nb) break;
+                if (SW == 16) { uint4 u; __builtin_memcpy(&u, src + 16 * q, 16); *reinterpret_cast<uint4*>(dst + 16 * q) = u; }
+                else if (SW == 8) { uint2 u; __builtin_memcpy(&u, src + 8 * q, 8); *reinterpret_cast<uint2*>(dst + 8 * q) = u; }
+                else if (SW == 4) { unsigned u; __builtin_memcpy(&u, src + 4 * q, 4); *reinterpret_cast<unsigned*>(dst + 4 * q) = u; }
+                else { unsigned short u; __builtin_memcpy(&u, src + 2 * q, 2); *reinterpret_cast<unsigned short*>(dst + 2 * q) = u; }
+            }
+        }
+    }
+}
+extern "C" int fmri_tile_gather_stack(const float* vol, const float* aux, int X, int Y, int Z, const int32_t* idx, int B, int px, int py, int pz,
+                                      int aux_dz, int aux_nz, void* tiles, int dtype, fmri_stream_t stream) {
+    if (B <= 0 || px <= 0 || py <= 0 || pz <= 0 || aux_nz < 0 || X <= 0 || Y <= 0 || Z <= 0) return FMRI_E_SHAPE;
+    if (!vol || !idx || !tiles || (aux_nz > 0 && !aux)) return FMRI_E_SHAPE;
+    if (dtype != FMRI_F32 && dtype != FMRI_BF16) return FMRI_E_DTYPE;
+    const int esz = dtype == FMRI_F32 ? 4 : 2;
+    if ((uintptr_t)tiles % esz) return FMRI_E_ALIGN;
+    // store width: the largest of 16 / 8 / 4 / 2 bytes that divides both the row pitch and the base address
+    const uintptr_t a = (uintptr_t)tiles | (uintptr_t)((pz + aux_nz) * esz);
+    const int sw = (a & 15) == 0 ? 16 : (a & 7) == 0 ? 8 : (a & 3) == 0 ? 4 : 2;
+    const int grid = grid_for((int64_t)B * px * py, 256, 4096);
+#define L_(T_, SW_) k_tile_gather_stack<T_, SW_><<<grid, 256, 0, as_stream(stream)>>>(vol, aux, X, Y, Z, idx, B, px, py, pz, aux_dz, aux_nz, (T_*)tiles)
+    if (dtype == FMRI_F32) {
+        if (sw == 16) L_(float, 16); else if (sw == 8) L_(float, 8); else L_(float, 4);
+    } else {
+        if (sw == 16) L_(bf16_t, 16); else if (sw == 8) L_(bf16_t, 8); else if (sw == 4) L_(bf16_t, 4); else L_(bf16_t, 2);
+    }
+#undef L_
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
 extern "C" int fmri_tile_scatter_accumulate(const float* pred, const int32_t* idx, int B, int px, int py, int pz, int C,
                                             double* acc, int32_t* cnt, int X, int Y, int Z, fmri_stream_t stream) {
     if (B <= 0 || px <= 0 || py <= 0 || pz <= 0 || C <= 0) return FMRI_E_SHAPE;

@@ -23,8 +23,8 @@ between the affine sampling and the elastic transform (augment.py:344-347), on t
 The noise fields (normal, uniform and Poisson draws) are made inside the kernels by a counter-based generator (Philox4x32-10 keyed by
 `noise_seed`; csrc/augment.hip), not by numpy: same distributions, other streams.  The patches of a batch are PLANNED one after the other
 on the host (every draw of the reference, in its order) and then LAUNCHED together, one launch per step of the chain (`_Sampler.plan` /
-`launch_batch`); configurations the batch kernels do not cover (previous-slice truth channels, piecewise affine, the Gaussian filter,
-drop_easy_patches' interleaved draws) go patch by patch (`launch_one`) - same draws, same batches (tests/test_gpu_augment.py).
+`launch_batch`, previous-slice truth channels included); configurations the batch kernels do not cover (piecewise affine, the Gaussian
+filter, drop_easy_patches' interleaved draws) go patch by patch (`launch_one`) - same draws, same batches (tests/test_gpu_augment.py).
 """
 import random
 import warnings
@@ -205,10 +205,8 @@ class _Sampler(object):
         self.launch_one(self.plan(index), x_slot, y_slot, m_slot)
 
     def batchable(self, plans):
-        """can launch_batch take these plans?  Not: previous-slice truth channels, piecewise affine, a Gaussian filter on some patch, an
-        elastic kernel wider than the one-launch field kernel - those go patch by patch (launch_one)"""
-        if self.prev_truth_index is not None or self.n_chan != self.patch_shape[2]:
-            return False
+        """can launch_batch take these plans?  Not: piecewise affine, a Gaussian filter on some patch, an elastic kernel wider than the
+        one-launch field kernel - those go patch by patch (launch_one)"""
         return all(q["corners"] is None and q["elastic_seq"] >= 0 and not (q["p"] is not None and q["p"]["apply_gaussian_filter"]) for q in plans)
 
     def launch(self, plans, x, y, m=None):
@@ -222,9 +220,13 @@ class _Sampler(object):
     def launch_batch(self, plans, x, y, m=None):
         """the patches of a batch with ONE launch per step of the chain (fmri_*_batch): 2-3 gathers, the elastic fields and 2-3 warps, the
         min / max, then only the intensity steps some patch of the batch drew.  Same arithmetic, same draws as launch_one patch by patch
-        (tests/test_gpu_augment.py)."""
+        (tests/test_gpu_augment.py).  With previous-slice truth channels the image slices are sampled, warped and augmented in a dense
+        (B, X, Y, slices) staging tensor - launch_one works on a contiguous copy as well, so the kernels see the same layout and draw the same
+        counters - and copied in front of the truth channels, which are sampled (nearest, outside = 0) and warped with the same fields."""
         ops, ddf, torch, ps = self.ops, self.ddf, self.torch, self.patch_shape
         B = len(plans)
+        prev = self.prev_truth_index is not None
+        xd = torch.empty((B,) + tuple(ps), device=x.device, dtype=torch.float32) if prev else x        # the image slices, dense
         idx = [q["index"] for q in plans]
         tshape = (ps[0], ps[1], self.truth_size)
         warped = any(q["elastic_seq"] for q in plans)
@@ -238,12 +240,12 @@ class _Sampler(object):
                                              self.augment["elastic_transform"]["sigma"], self.seed, [q["elastic_seq"] for q in plans], device=x.device)
         corners_t = [(q["corner"][0], q["corner"][1], q["corner"][2] + self.truth_index) for q in plans]
         # image: trilinear, outside = the volume's minimum; labels: nearest, outside = 0 (identity affine = the plain crop)
-        xt = target(x, ps, torch.float32)
+        xt = target(xd, ps, torch.float32)
         ops.affine_sample_batch([ddf.data[i] for i in idx], [q["A"] for q in plans], [q["corner"] for q in plans], ps, xt, 1, [ddf.min[i] for i in idx])
         yt = target(y, tshape, torch.uint8)
         ops.affine_sample_batch([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_t, tshape, yt, 0, [0.0] * B)
         if warped:
-            ops.elastic_warp_batch(xt, d, 1, x)
+            ops.elastic_warp_batch(xt, d, 1, xd)
             ops.elastic_warp_batch(yt, d, 0, y)
         if m is not None:
             # augmented: outside the mask = 0 (interpolate_affine_range, cval 0); plain crop: edge values
@@ -252,8 +254,24 @@ class _Sampler(object):
             ops.affine_sample_batch(src, [q["Am"] for q in plans], corners_t, tshape, mt, 0, [0.0] * B)
             if warped:
                 ops.elastic_warp_batch(mt, d, 0, m)
-        if not any(q["p"] is not None and q["need_intensity"] for q in plans):
-            return
+        if prev:
+            pshape = (ps[0], ps[1], self.prev_truth_size)
+            corners_p = [(q["corner"][0], q["corner"][1], q["corner"][2] + self.prev_truth_index) for q in plans]
+            xp = x[..., ps[2]:]
+            pt = torch.empty((B,) + pshape, device=x.device, dtype=torch.float32) if warped else xp
+            ops.affine_sample_batch([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_p, pshape, pt, 0, [0.0] * B,
+                                    out_ld=None if warped else self.n_chan)
+            if warped:
+                ops.elastic_warp_batch(pt, d, 0, xp)
+        if any(q["p"] is not None and q["need_intensity"] for q in plans):
+            self._intensity_batch(plans, xd)
+        if prev:
+            x[..., :ps[2]] = xd
+
+    def _intensity_batch(self, plans, x):
+        """the intensity steps of launch_batch on the dense image slices x (B, X, Y, slices)"""
+        ops = self.ops
+        B = len(plans)
         stats, ws = self._workspace(B)
         ops.minmax_ws_batch(x, stats, ws)
         params = []

@@ -4,7 +4,9 @@
 index set, mean of overlapping tiles in float64).  With a model built by this package the whole tile loop stays on the
 MI355X: the padded volume is uploaded once, tiles are gathered on the device (fmri_tile_gather), pushed through the
 engine and overlap-added in float64 on the device (fmri_tile_scatter_accumulate / fmri_tile_finalize); one hipGraph per
-tile-batch size replays gather -> network -> scatter.  Any other object with `.output_shape` / `.predict(ndarray)` (the
+tile-batch size replays gather -> network -> scatter.  A 2-D model with previous-slice truth channels (`truth_data` with
+`prev_truth_index` / `prev_truth_size`) stays on the device as well: the padded truth volume goes up beside the data and the gather appends
+its slices to every tile (fmri_tile_gather_stack).  Any other object with `.output_shape` / `.predict(ndarray)` (the
 reference's duck-typing contract) is driven through the same geometry with host-side tiles.
 """
 import gc
@@ -83,10 +85,18 @@ def patch_wise_prediction(model, data, patch_shape, overlap_factor=0, batch_size
                           prev_truth_index=None, prev_truth_size=None):
     """data (1,X,Y,Z) -> (X,Y,Z,C) float64 mean of all tiles covering each voxel."""
     is3d, pad0, pad_for_fit, data_0, indices, data_shape = _geometry(model, data, patch_shape, overlap_factor)
-    on_device = isinstance(model, Model) and truth_data is None and not permute and model._unsupported is None and \
-        (is3d or getattr(model, "_input_layout", "") == "channels_last_2d")
+    layout2d = getattr(model, "_input_layout", "") == "channels_last_2d"
+    # previous-slice truth on the device: 2-D models only (a 3-D model's truth channels are concatenated along z, reference prediction.py:100-110)
+    truth_ok = truth_data is None or (not is3d and layout2d and prev_truth_index is not None and bool(prev_truth_size))
+    on_device = isinstance(model, Model) and truth_ok and not permute and model._unsupported is None and (is3d or layout2d)
     if on_device:
-        out, count_ok = _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d)
+        truth_0 = None
+        if truth_data is not None:
+            truth_0 = np.pad(truth_data[0], pad0, mode='constant', constant_values=0)
+            truth_0 = np.pad(truth_0, pad_for_fit, 'constant', constant_values=0)
+        out, count_ok = _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d, truth_0=truth_0,
+                                            aux_dz=int(prev_truth_index) if truth_0 is not None else 0,
+                                            aux_nz=int(prev_truth_size) if truth_0 is not None else 0)
         assert count_ok, 'Found zeros in count'
         out = _unpad(out, pad_for_fit)
         assert np.array_equal(out.shape[:-1], data[0].shape), 'prediction shape wrong'
@@ -118,11 +128,13 @@ def patch_wise_prediction(model, data, patch_shape, overlap_factor=0, batch_size
     return predicted_output / predicted_count
 
 
-def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d=True):
+def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d=True, truth_0=None, aux_dz=0, aux_nz=0):
     """Upload once, then per tile batch: gather -> network -> float64 overlap-add, all on the device.  The static buffers
     (volume, accumulators, tile batch, index list) and one captured hipGraph per distinct batch size are cached on the
     model and re-used for every following volume of the same padded shape.  2-D models: a tile (px, py, slices) IS the
-    channels-last input of the network (the slice stack is the channel axis) and its output is one slice (px, py, 1)."""
+    channels-last input of the network (the slice stack is the channel axis) and its output is one slice (px, py, 1).
+    truth_0 (2-D models): the padded truth volume (data_0's extent); every tile then carries aux_nz more channels, its truth slices from
+    aux_dz slices past the tile's corner (reference batch_iterator, prediction.py:98-114)."""
     import torch
     from fmri_hip import ops
     patch = tuple(int(p) for p in patch_shape)
@@ -141,23 +153,30 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
         groups = -(-n // max(batch_size, 12))
         batch_size = -(-n // groups)
     sizes = sorted({min(batch_size, n - i) for i in range(0, n, batch_size)}, reverse=True)
-    key = (vshape, ashape, patch, tuple(sizes), use_graph)
+    aux_nz = int(aux_nz) if truth_0 is not None else 0
+    aux_dz = int(aux_dz) if aux_nz else 0
+    assert aux_nz == 0 or (not is3d and tuple(truth_0.shape) == vshape)
+    key = (vshape, ashape, patch, tuple(sizes), use_graph, aux_dz, aux_nz)
     st = model.__dict__.get("_tile_state")
     if st is None or st["key"] != key:
         st = dict(key=key, vol=torch.empty(vshape, dtype=torch.float32, device="cuda"),
+                  aux=torch.empty(vshape, dtype=torch.float32, device="cuda") if aux_nz else None,
                   acc=torch.zeros(ashape, dtype=torch.float64, device="cuda"),
                   cnt=torch.zeros(ashape[:3], dtype=torch.int32, device="cuda"), per_b={})
         for B in sizes:
             eng = model.engine(B)
-            # 3-D: (B, px, py, pz, 1) = NDHWC with one channel; 2-D: (1, B, px, py, slices) = the planar layout, slices as channels
-            tshape = (B,) + patch + (1,) if is3d else (1, B) + patch
+            # 3-D: (B, px, py, pz, 1) = NDHWC with one channel; 2-D: (1, B, px, py, slices [+ truth slices]) = the planar layout, slices as channels
+            tshape = (B,) + patch + (1,) if is3d else (1, B, patch[0], patch[1], patch[2] + aux_nz)
             opatch = patch if is3d else (patch[0], patch[1], 1)
             pb = dict(idx=torch.zeros((B, 3), dtype=torch.int32, device="cuda"),
                       tiles=torch.empty(tshape, dtype=eng.dtype, device="cuda"), graph=None)
 
             def body(pb=pb, B=B, opatch=opatch):
                 e = model.engine(B)
-                ops.tile_gather(st["vol"], pb["idx"], patch, pb["tiles"])
+                if aux_nz:
+                    ops.tile_gather_stack(st["vol"], st["aux"], pb["idx"], patch, aux_dz, aux_nz, pb["tiles"])
+                else:
+                    ops.tile_gather(st["vol"], pb["idx"], patch, pb["tiles"])
                 e.predict(pb["tiles"])
                 ops.tile_scatter_accumulate(e.probs, pb["idx"], opatch, st["acc"], st["cnt"])
 
@@ -196,6 +215,8 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
     if st.get("up_stream") is None:
         st["up_stream"], st["down_stream"] = torch.cuda.Stream(), torch.cuda.Stream()
         st["pin_in"] = torch.empty(vshape, dtype=torch.float32, pin_memory=True)
+    if aux_nz and st.get("pin_aux") is None:
+        st["pin_aux"] = torch.empty(vshape, dtype=torch.float32, pin_memory=True)
     up, down = st["up_stream"], st["down_stream"]
     main = torch.cuda.current_stream()
     st["acc"].zero_()
@@ -212,6 +233,7 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
     out_host = torch.empty(ashape, dtype=torch.float64, pin_memory=True)
     bad = torch.zeros(1, dtype=torch.int32, device="cuda")
     pin_np, src = st["pin_in"].numpy(), np.asarray(data_0)
+    pin_aux, src_aux = (st["pin_aux"].numpy(), np.asarray(truth_0)) if aux_nz else (None, None)
     starts_x = [int(ix[0]) for ix in indices]
     up_to = 0                                   # x-planes uploaded so far
     done_to = 0                                 # x-planes finalised and on their way down
@@ -221,8 +243,12 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
         need = min(vshape[0], max(starts_x[i:hi]) + patch[0])
         if need > up_to:
             np.copyto(pin_np[up_to:need], src[up_to:need], casting="unsafe")
+            if aux_nz:
+                np.copyto(pin_aux[up_to:need], src_aux[up_to:need], casting="unsafe")
             with torch.cuda.stream(up):
                 st["vol"][up_to:need].copy_(st["pin_in"][up_to:need], non_blocking=True)
+                if aux_nz:
+                    st["aux"][up_to:need].copy_(st["pin_aux"][up_to:need], non_blocking=True)
             up_to = need
             main.wait_stream(up)
         bidx = idx_all[i:hi]

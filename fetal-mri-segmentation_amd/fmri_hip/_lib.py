@@ -79,6 +79,7 @@ SIGNATURES = {
     "fmri_set_deterministic": [p, p, i64],
     "fmri_deterministic_finish": [p, p, i64, p],
     "fmri_tile_gather": [p, i32, i32, i32, p, i32, i32, i32, i32, p, i32, p],
+    "fmri_tile_gather_stack": [p, p, i32, i32, i32, p, i32, i32, i32, i32, i32, i32, p, i32, p],
     "fmri_tile_scatter_accumulate": [p, p, i32, i32, i32, i32, i32, p, p, i32, i32, i32, p],
     "fmri_tile_finalize": [p, p, p, p, i64, i32, p],
     "fmri_cast": [p, i32, p, i32, i64, p],

@@ -214,6 +214,21 @@ def tile_gather(vol, idx, patch, tiles):
     return tiles
 
 
+def tile_gather_stack(vol, aux, idx, patch, aux_dz, aux_nz, tiles):
+    """tiles (..., B, px, py, pz + aux_nz): the pz slices of vol at each corner of idx, then aux_nz slices of aux starting aux_dz slices from the
+    corner (fmri_tile_gather_stack; the previous-slice truth channels of reference prediction.py:98-114).  aux: fp32 (X, Y, Z) or None if aux_nz = 0"""
+    _need_cuda(vol, aux, idx, tiles)
+    X, Y, Z = vol.shape
+    if aux_nz:
+        assert aux is not None and tuple(aux.shape) == (X, Y, Z) and aux.dtype == torch.float32
+    assert vol.dtype == torch.float32 and idx.dtype == torch.int32
+    B = idx.shape[0]
+    assert tiles.numel() == B * patch[0] * patch[1] * (patch[2] + aux_nz)
+    check(lib().fmri_tile_gather_stack(_p(vol), _p(aux if aux_nz else None), X, Y, Z, _p(idx), B, patch[0], patch[1], patch[2], int(aux_dz),
+                                       int(aux_nz), _p(tiles), dt(tiles), _s()), "fmri_tile_gather_stack")
+    return tiles
+
+
 def tile_scatter_accumulate(pred, idx, patch, acc, cnt):
     _need_cuda(pred, idx, acc, cnt)
     X, Y, Z, Cc = acc.shape
@@ -1044,14 +1059,21 @@ def coarse_dropout_rng_batch(xb, grids, rate, stats, per_channel, seed, seqs):
     return xb
 
 
-def affine_sample_batch(vols, affines, corners, size, out, order, cvals):
+def affine_sample_batch(vols, affines, corners, size, out, order, cvals, out_ld=None):
     """out[b] (dense (nx, ny, nz) patches, equally spaced) = vols[b] sampled at affines[b] . (corners[b] + (i, j, k), 1): fmri_affine_sample for the
-    patches of a batch in one launch.  vols: device tensors of one dtype (float32 or uint8), each (X, Y, Z) contiguous; affines (B, 4, 4) or (B, 3, 4)"""
+    patches of a batch in one launch.  vols: device tensors of one dtype (float32 or uint8), each (X, Y, Z) contiguous; affines (B, 4, 4) or (B, 3, 4).
+    out_ld: row length of out when its last axis is a view into wider rows (the previous-slice truth channels behind the image slices)"""
     import ctypes
     import numpy as np
     B = len(vols)
     nx, ny, nz = (int(v) for v in size)
-    assert out.is_cuda and tuple(out.shape) == (B, nx, ny, nz) and out[0].is_contiguous()
+    if out_ld is None:
+        assert out.is_cuda and tuple(out.shape) == (B, nx, ny, nz) and out[0].is_contiguous()
+        out_ld = nz
+    else:
+        out_ld = int(out_ld)
+        assert out.is_cuda and tuple(out.shape) == (B, nx, ny, nz) and out_ld >= nz
+        assert out.stride(3) == 1 and out.stride(2) == out_ld and out.stride(1) == ny * out_ld, "rows of out_ld elements, channels contiguous"
     for v in vols:
         if not v.is_cuda or not v.is_contiguous() or v.dtype != vols[0].dtype or v.dim() != 3:
             raise RuntimeError("fmri_hip ops need contiguous device volumes of one dtype")
@@ -1062,7 +1084,7 @@ def affine_sample_batch(vols, affines, corners, size, out, order, cvals):
     cv = np.ascontiguousarray(cvals, dtype=np.float32)
     assert A.shape == (B, 3, 4) and cr.shape == (B, 3) and cv.shape == (B,)
     check(lib().fmri_affine_sample_batch(B, ctypes.cast(ptrs, ctypes.c_void_p), dims.ctypes.data, A.ctypes.data, cr.ctypes.data, cv.ctypes.data,
-                                         _dt_any(vols[0]), nx, ny, nz, int(order), _p(out), _dt_any(out), nz, int(out.stride(0)), _s()),
+                                         _dt_any(vols[0]), nx, ny, nz, int(order), _p(out), _dt_any(out), out_ld, int(out.stride(0)), _s()),
           "fmri_affine_sample_batch")
     return out
 

@@ -357,6 +357,12 @@ int fmri_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
  * [B][px][py][pz] (C = 1, NDHWC == NCDHW). */
 int fmri_tile_gather(const float* vol, int X, int Y, int Z, const int32_t* idx, int B, int px, int py, int pz, void* tiles,
                      int dtype, fmri_stream_t stream);
+/* 2-D models with previous-slice truth channels (reference prediction.py:98-114: batch_iterator concatenates the truth slices behind the
+ * image slices of every tile).  tiles out (dtype) [B][px][py][pz + aux_nz]: channel c < pz = vol at idx[b] + (x, y, c), channel pz + j = aux
+ * at (idx[b].x + x, idx[b].y + y, idx[b].z + aux_dz + j); every coordinate clamped into [0, X-1] x [0, Y-1] x [0, Z-1]; aux fp32 of vol's
+ * extent (may be NULL when aux_nz = 0, which gives fmri_tile_gather's output). */
+int fmri_tile_gather_stack(const float* vol, const float* aux, int X, int Y, int Z, const int32_t* idx, int B, int px, int py, int pz,
+                           int aux_dz, int aux_nz, void* tiles, int dtype, fmri_stream_t stream);
 /* acc (double) [X][Y][Z][C] += pred[b][px][py][pz][C] (fp32); cnt (int32) [X][Y][Z] += 1 */
 int fmri_tile_scatter_accumulate(const float* pred, const int32_t* idx, int B, int px, int py, int pz, int C, double* acc,
                                  int32_t* cnt, int X, int Y, int Z, fmri_stream_t stream);
