@@ -13,7 +13,6 @@ MI355X layout decisions
   * the up-sampled tensor and the concat are never materialised (the conv kernels read two sources);
   * every tensor is allocated once at build time (288 GB HBM: no re-computation, no allocator traffic in the step).
 """
-import math
 import os
 from collections import OrderedDict
 
@@ -22,6 +21,7 @@ import torch
 
 from . import ops
 from ._lib import lib, ACT_NONE, ACT_RELU, IMPL_AUTO
+from .engine_base import EngineBase, flat_to_kernel, glorot_uniform, kernel_to_flat
 
 
 class UNetPlan:
@@ -89,20 +89,14 @@ class UNetPlan:
         return (slices,) + tuple(s >> level for s in self.spatial)
 
 
-class UNetEngine:
+class UNetEngine(EngineBase):
     def __init__(self, plan, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None):
-        from ._lib import lib
-        lib()  # fail loudly if the HIP library is missing
-        self.plan, self.N, self.dtype, self.dev, self.training = plan, batch, dtype, torch.device(device), training
-        self.planar = plan.ndim == 2      # 2-D: tensors are [1][slices][H][W][C], every op is planar (no coupling along D)
-        self.dist = dist_ctx
-        self.t = 0                       # Adam step counter
-        self._pack_stream, self._pack_events, self._pack_event_dec, self._pack_pending = None, None, None, []
         # FMRI_WGRAD_PRIO (A/B): HIP priority of the weight-gradient stream (0 = default, positive = lower): with a lower one the dispatcher hands free
         # CUs to the input-gradient chain first and the weight-gradient backlog fills in behind the HBM-bound kernels of the main stream
-        self._wg_stream = (torch.cuda.Stream(device=self.dev, priority=int(os.environ.get("FMRI_WGRAD_PRIO", "0")))
-                           if (training and self.dev.type == "cuda" and os.environ.get("FMRI_WGRAD_STREAM", "1") != "0") else None)
-        self.loss_kind, self.loss_param = 0, 1.0      # ops.LOSS_KINDS: 0 = dice_coefficient_loss
+        super().__init__(dtype, device, training, dist_ctx, wg_priority=int(os.environ.get("FMRI_WGRAD_PRIO", "0")))
+        self.plan, self.N = plan, batch
+        self.planar = plan.ndim == 2      # 2-D: tensors are [1][slices][H][W][C], every op is planar (no coupling along D)
+        self._pack_stream, self._pack_events, self._pack_event_dec, self._pack_pending = None, None, None, []
         # FMRI_DETERMINISTIC=1: bit-reproducible training steps (same weights + same batch -> the same bits in every gradient and metric):
         # gradient partial sums meet as fixed-point integers in a shadow of G (ops.set_deterministic), the parity-form weight gradient -
         # whose scratch is filled by fp32 atomics - gives way to the fused-upsample 27-tap one.  One engine per process at a time.
@@ -138,18 +132,14 @@ class UNetEngine:
             self.layout[c["name"]] = L
         self.n_flat = (off + 3) & ~3
         dev = self.dev
-        self.P = torch.zeros(self.n_flat, dtype=torch.float32, device=dev)
-        if self.training:
-            self.G = torch.zeros_like(self.P)
-            self.M = torch.zeros_like(self.P)
-            self.V = torch.zeros_like(self.P)
-            if self.deterministic:
-                if p.norm is not None or p.deconvolution:
-                    raise NotImplementedError("FMRI_DETERMINISTIC=1 covers the plain unet_model_3d / unet_model_2d step (no normalisation layers, "
-                                              "UpSampling up-convolution): the normalisation statistics and the folded transposed conv still "
-                                              "accumulate with floating-point atomics")
-                self.G64 = torch.zeros(self.n_flat, dtype=torch.int64, device=dev)
-                _register_deterministic(self)
+        self._alloc_params()
+        if self.deterministic:
+            if p.norm is not None or p.deconvolution:
+                raise NotImplementedError("FMRI_DETERMINISTIC=1 covers the plain unet_model_3d / unet_model_2d step (no normalisation layers, "
+                                          "UpSampling up-convolution): the normalisation statistics and the folded transposed conv still "
+                                          "accumulate with floating-point atomics")
+            self.G64 = torch.zeros(self.n_flat, dtype=torch.int64, device=dev)
+            _register_deterministic(self)
         # compute-dtype copies of the 3x3x3 filters
         self.Wf, self.Wd, self.Wup = {}, {}, {}
         self.upcat = self._upcat_layers()
@@ -284,16 +274,16 @@ class UNetEngine:
             seq += lv
         for c in seq:
             if c.get("transpose"):
-                W[c["name"] + "/kernel"] = _glorot(rs, k2 + (c["cout"], c["cin"]))      # Keras: (k,k,k,Cout,Cin)
+                W[c["name"] + "/kernel"] = glorot_uniform(rs, k2 + (c["cout"], c["cin"]))      # Keras: (k,k,k,Cout,Cin)
                 W[c["name"] + "/bias"] = np.zeros(c["cout"], np.float32)
                 continue
-            W[c["name"] + "/kernel"] = _glorot(rs, k3 + (c["cin"], c["cout"]))
+            W[c["name"] + "/kernel"] = glorot_uniform(rs, k3 + (c["cin"], c["cout"]))
             W[c["name"] + "/bias"] = np.zeros(c["cout"], np.float32)
             if c.get("norm"):
                 W[c["norm"] + "/gamma"] = np.ones(c["cout"], np.float32)
                 W[c["norm"] + "/beta"] = np.zeros(c["cout"], np.float32)
         f = self.plan.final
-        W[f["name"] + "/kernel"] = _glorot(rs, k1 + (f["cin"], f["cout"]))
+        W[f["name"] + "/kernel"] = glorot_uniform(rs, k1 + (f["cin"], f["cout"]))
         W[f["name"] + "/bias"] = np.zeros(f["cout"], np.float32)
         self.load_keras_weights(W)
 
@@ -303,20 +293,18 @@ class UNetEngine:
         host = np.zeros(self.n_flat, np.float32)
         for name, L in self.layout.items():
             k = np.asarray(W[name + "/kernel"], np.float32)
-            if k.ndim == 4 and L["kind"] != "deconv":  # 2-D kernel (kH,kW,Cin,Cout) -> centre plane of a 3x3x3 / 1x1x1 kernel
-                k = _embed_2d_kernel(k)
             o, n = L["w"]
+            cio = (L["cin"], L["cout"])
             if L["kind"] == "deconv":
-                kk = np.asarray(W[name + "/kernel"], np.float32)
-                if kk.ndim == 4:                                              # (2,2,Cout,Cin) -> taps 0..3 of the 8
-                    kk = np.concatenate([kk.reshape(4, L["cout"], L["cin"]), np.zeros((4, L["cout"], L["cin"]), np.float32)])
-                host[o:o + n] = kk.reshape(8, L["cout"], L["cin"]).reshape(-1)
-            elif L["kind"] == "conv":
-                assert k.shape == (3, 3, 3, L["cin"], L["cout"]), (name, k.shape)
-                host[o:o + n] = k.transpose(0, 1, 2, 4, 3).reshape(-1)        # -> [27][Cout][Cin]
+                if k.ndim == 4:                                               # (2,2,Cout,Cin) -> taps 0..3 of the 8
+                    k = np.concatenate([k.reshape(4, L["cout"], L["cin"]), np.zeros((4, L["cout"], L["cin"]), np.float32)])
+                host[o:o + n] = k.reshape(8, L["cout"], L["cin"]).reshape(-1)
+            elif L["kind"] == "conv":                                         # 2-D kernels (kH,kW,Cin,Cout) fill the centre kd plane
+                assert k.shape in ((3, 3, 3) + cio, (3, 3) + cio), (name, k.shape)
+                host[o:o + n] = kernel_to_flat(k, 3)                          # -> [27][Cout][Cin]
             else:
-                assert k.shape[-2:] == (L["cin"], L["cout"]), (name, k.shape)
-                host[o:o + n] = k.reshape(L["cin"], L["cout"]).T.reshape(-1)  # -> [L][C]
+                assert k.shape[-2:] == cio, (name, k.shape)
+                host[o:o + n] = kernel_to_flat(k, 1)                          # -> [L][C]
             ob, nb = L["b"]
             host[ob:ob + nb] = np.asarray(W[name + "/bias"], np.float32)
             if L.get("norm"):
@@ -325,12 +313,12 @@ class UNetEngine:
         return host
 
     def load_keras_weights(self, W):
-        self.P.copy_(torch.from_numpy(self.keras_to_flat(W)))
+        """the Keras weights into P (EngineBase.load_keras_weights), then the batch-norm moving statistics where W has them"""
+        super().load_keras_weights(W)
         for name, L in self.layout.items():
             if L.get("norm") and name in self.moving and (L["norm"] + "/moving_mean") in W:
                 self.moving[name][0].copy_(torch.from_numpy(np.asarray(W[L["norm"] + "/moving_mean"], np.float32)))
                 self.moving[name][1].copy_(torch.from_numpy(np.asarray(W[L["norm"] + "/moving_variance"], np.float32)))
-        self.refresh_weight_copies()
 
     def flat_to_keras(self, host, moving=True):
         """inverse of keras_to_flat for any vector in the parameter layout (weights, Adam m, Adam v)"""
@@ -343,12 +331,8 @@ class UNetEngine:
                 k = host[o:o + n].reshape(8, L["cout"], L["cin"])
                 W[name + "/kernel"] = (k.reshape(2, 2, 2, L["cout"], L["cin"]) if self.plan.ndim == 3
                                        else k[:4].reshape(2, 2, L["cout"], L["cin"])).copy()
-            elif L["kind"] == "conv":
-                k = host[o:o + n].reshape(3, 3, 3, L["cout"], L["cin"]).transpose(0, 1, 2, 4, 3)
-                W[name + "/kernel"] = (k if self.plan.ndim == 3 else k[1]).copy()          # 2-D: the centre kd plane is the 3x3 kernel
             else:
-                k = host[o:o + n].reshape(L["cout"], L["cin"]).T
-                W[name + "/kernel"] = k.reshape(((1, 1, 1) if self.plan.ndim == 3 else (1, 1)) + (L["cin"], L["cout"])).copy()
+                W[name + "/kernel"] = flat_to_kernel(host[o:o + n], 3 if L["kind"] == "conv" else 1, L["cin"], L["cout"], self.plan.ndim)
             ob, nb = L["b"]
             W[name + "/bias"] = host[ob:ob + nb].copy()
             if L.get("norm"):
@@ -358,9 +342,6 @@ class UNetEngine:
                     mv = self.moving[name].cpu().numpy()
                     W[L["norm"] + "/moving_mean"], W[L["norm"] + "/moving_variance"] = mv[0].copy(), mv[1].copy()
         return W
-
-    def export_keras_weights(self):
-        return self.flat_to_keras(self.P.detach().cpu().numpy())
 
     def _upcat_layers(self):
         """decoder 'a' convs (UpSampling3D -> concatenate -> Conv3D, reference unet.py:132-138,61,102) that take the parity form:
@@ -546,10 +527,6 @@ class UNetEngine:
         nvox0 = int(np.prod(self._dims(0)))
         self.logits = torch.empty((nvox0, p.n_labels), dtype=torch.float32, device=dev)
         self.probs = torch.empty_like(self.logits)
-        if getattr(self, "sums", None) is None:
-            # ONE tensor for the engine's lifetime: captured hipGraphs of other batch sizes keep its address (re-creating it per buffer
-            # set left them writing into freed memory, which the allocator then handed to the tile index list of the next volume)
-            self.sums = torch.zeros(16, dtype=torch.float64, device=dev)
         if not self.training:
             self.grad, self.dlogits, self.wgrad_ws = None, None, None
             return
@@ -715,33 +692,6 @@ class UNetEngine:
             ops.conv1x1_fwd(h, self.w_view(f["name"]), self.b_view(f["name"]), self.logits)
         return self.logits
 
-    def loss_forward(self, y_true, weight=None):
-        """y_true uint8 [nvox*L] device.  probs + the 8 metric sums (accumulated into zeroed self.sums)."""
-        self.sums.zero_()
-        ops.sigmoid_dice_fwd(self.logits, y_true, self.probs, self.sums, weight=weight)
-        if self.loss_kind == ops.LOSS_WEIGHTED_DICE:
-            ns, nl = self._wdice_groups()
-            if getattr(self, "_gsums", None) is None or self._gsums.numel() < 3 * ns * nl:
-                self._gsums = torch.zeros(3 * ns * nl, dtype=torch.float64, device=self.dev)
-            ops.weighted_dice_fwd(self.probs, y_true, self._gsums, self.sums, ns, nl)
-        if self.dist is not None and self.dist.world > 1 and self.dist.global_dice:
-            self.dist.all_reduce_sums(self.sums)
-        return self.sums
-
-    def _wdice_groups(self):
-        """(groups along the batch axis, labels per group) of weighted_dice_coefficient's axis=(-3,-2,-1) (reference metrics.py:39): the 3-D
-        models' (N, labels, X, Y, Z) tensors give one Dice per (sample, label), the 2-D models' (N, X, Y, labels) one per slice"""
-        if self.plan.ndim == 2:
-            return self.N, 1
-        return self.N, self.plan.n_labels
-
-    def predict(self, x):
-        self.forward(x, bn_training=False)
-        self.sums.zero_()
-        # sigmoid only (y_true is irrelevant for probs): reuse the fused kernel with an all-zero label buffer
-        ops.sigmoid_dice_fwd(self.logits, self._dummy_y, self.probs, self.sums)
-        return self.probs
-
     # ------------------------------------------------------------------------------------------------ backward
     def _block_bwd(self, c, src0, src1, up0):
         """G[c] holds dL/d(output of the block) (already ReLU-masked when the block has no norm).  Leaves dL/d(conv output) in
@@ -768,15 +718,7 @@ class UNetEngine:
                                  workspace=self.wgrad_ws)
             self._grad_ready(name)
 
-        if self._wg_stream is None:
-            wgrad()
-            return
-        # the weight gradients are off the critical path of the backward pass (nothing reads them before the optimizer step): they run on
-        # their own stream, behind the event "dL/d(conv output) is final", next to the input-gradient chain of the main stream
-        # (a third stream for the first conv's weight gradient - HBM-bound, ready last - measured nothing: 13.09-13.13 ms either way)
-        self._wg_stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self._wg_stream):
-            wgrad()
+        self._wgrad(wgrad)                  # behind the event "dL/d(conv output) is final"
 
     def _folded_bwd(self, a, x_low, skip, cat, low):
         """backward of the folded transposed conv + conv of decoder block `a`: G[a] holds dL/d(conv output).  Weight gradients (side
@@ -801,12 +743,7 @@ class UNetEngine:
             self._grad_ready(name)
             self._grad_ready(F["u"])
 
-        if self._wg_stream is None:
-            wgrad()
-        else:
-            self._wg_stream.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(self._wg_stream):
-                wgrad()
+        self._wgrad(wgrad)
         ops.conv3d_upcat_dgrad(g, F["up_d"], F["sk_d"], self._mask_of(low), None, self.grad[low], cat)
 
     def _dgrad_into(self, b, a):
@@ -838,14 +775,7 @@ class UNetEngine:
         self._main_stream = torch.cuda.current_stream(self.dev) if self.dev.type == "cuda" else None
         self._dz_ready = set()
         self.G.zero_()
-        if seg_loss and self.loss_kind == ops.LOSS_WEIGHTED_DICE:
-            ns, nl = self._wdice_groups()
-            ops.weighted_dice_bwd(self.probs, y_true, self._gsums, self.sums, self.dlogits, ns, nl, grad_scale=grad_scale)
-        elif seg_loss:
-            ops.sigmoid_loss_bwd(self.probs, y_true, self.sums, self.dlogits, self.loss_kind, self.loss_param, smooth=1.0, grad_scale=grad_scale,
-                                 weight=weight)
-        if dprobs is not None:
-            ops.sigmoid_chain(self.probs, dprobs, self.dlogits, scale=dprobs_scale, accumulate=seg_loss)
+        self._seg_loss_bwd(y_true, grad_scale, weight, dprobs, dprobs_scale, seg_loss)
         f = p.final
         last = p.dec[-1][1] if p.dec else p.enc[-1][1]
         ops.conv1x1_bwd(A[last["name"]], self.w_view(f["name"]), self.dlogits, Gd[last["name"]], self.w_view(f["name"], self.G),
@@ -912,8 +842,7 @@ class UNetEngine:
             self._block_bwd(ca, xin, None, False)
             if ld > 0:
                 ops.conv3d_dgrad(Gd[ca["name"]], self.Wd[ca["name"]], Gd["pool_%d" % (ld - 1)], planar=self.planar)
-        if self._wg_stream is not None:
-            torch.cuda.current_stream(self.dev).wait_stream(self._wg_stream)
+        self._join_wgrad()
         if self.deterministic:
             ops.deterministic_finish(self.G, self.G64)       # G += the fixed-point sums of every gradient kernel of this pass
             if self.dist is not None:
@@ -951,40 +880,11 @@ class UNetEngine:
         if fin is not None:
             fin()
 
-    def grad_streams(self):
-        """streams that enqueue parameter-gradient kernels during backward (a gradient bucket is complete when all of them got there)"""
-        return [st for st in (getattr(self, "_main_stream", None), self._wg_stream) if st is not None]
-
     def _grad_ready(self, name):
         # deterministic mode: the gradients sit in the int64 shadow until deterministic_finish at the end of backward(), so no bucket of
         # G may be reduced before that - the whole buffer goes in dist.finish (ADVICE r3: early buckets all-reduced zeros)
         if self.dist is not None and not self.deterministic:
             self.dist.grad_ready(self, name)
-
-    # ------------------------------------------------------------------------------------------------ optimizer
-    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
-        self.t += 1
-        lr_t = lr * math.sqrt(1.0 - beta2 ** self.t) / (1.0 - beta1 ** self.t)
-        ops.adam_step(self.P, self.G, self.M, self.V, lr_t, beta1, beta2, eps, grad_scale)
-        self.refresh_weight_copies(overlap=True)
-
-    def train_step(self, x, y_true, lr, weight=None):
-        """one full step: forward, Dice, backward, (all-reduce), Adam.  Returns the device tensor of metric sums."""
-        self.forward(x)
-        self.loss_forward(y_true, weight)
-        # data parallel: with the global-batch Dice sums the ranks' gradients are summed (scale 1); with per-rank losses
-        # (global_dice=False) the all-reduce sum is turned into the mean by scaling each rank's loss gradient by 1/world
-        self.backward(y_true, grad_scale=(self.dist.grad_scale if self.dist is not None else 1.0), weight=weight)
-        self.adam_step(lr)
-        return self.sums
-
-    @staticmethod
-    def metrics_from_sums(s, smooth=1.0, loss_kind=0, loss_param=1.0):
-        s = [float(v) for v in s]
-        dice = (2.0 * s[0] + smooth) / (s[1] + s[2] + smooth)
-        vod = (s[3] + smooth) / (s[4] + s[5] - s[3] + smooth)
-        return dict(loss=ops.loss_value_from_sums(s, loss_kind, loss_param, smooth), dice_coefficient=dice, vod_coefficient=vod,
-                    binary_accuracy=s[6] / max(s[7], 1.0))
 
 
 _DET_OWNER = []          # [weakref to the engine that holds the process-wide fmri_set_deterministic registration]
@@ -1011,18 +911,3 @@ def _register_deterministic(eng):
     _DET_OWNER.append(ref)
     ops.set_deterministic(eng.G, eng.G64)
     eng._det_finalizer = weakref.finalize(eng, _release_deterministic, ref)
-
-
-def _glorot(rs, shape):
-    rf = int(np.prod(shape[:-2]))
-    lim = math.sqrt(6.0 / (rf * shape[-2] + rf * shape[-1]))
-    return rs.uniform(-lim, lim, size=shape).astype(np.float32)
-
-
-def _embed_2d_kernel(k):
-    kh, kw, ci, co = k.shape
-    if kh == 1:
-        return k.reshape(1, 1, 1, ci, co)
-    out = np.zeros((3, 3, 3, ci, co), np.float32)
-    out[1] = k
-    return out

@@ -1,0 +1,160 @@
+"""What the two engines share: `UNetEngine` (engine.py, the hand-scheduled U-Net) and `LayerGraphEngine` (graph_engine.py, the layer-graph
+interpreter) differ in how they schedule a step, not in what surrounds the schedule.
+
+`EngineBase` holds that part: the flat fp32 parameter store (P, its gradient G and the Adam moments M / V, all in the engine's `layout`),
+the loss head (sigmoid + metric sums, the seg-loss gradient), Keras Adam, Keras weight export / import and the weight-gradient side
+stream.  An engine sets `layout` / `n_flat` and calls `_alloc_params`, keeps `logits` / `probs` / `dlogits` / `_dummy_y` of the current
+batch, and provides `forward`, `backward`, `refresh_weight_copies(overlap)`, `keras_to_flat` and `flat_to_keras`.
+
+The module-level helpers convert Keras kernels: a Glorot-uniform draw, and a conv kernel (k,)*nd + (Cin, Cout) <-> the flat
+[k^3][Cout][Cin] image the engines keep in P (a 2-D kernel is the centre kd plane of that image).
+"""
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import lib
+
+
+class EngineBase(object):
+    def __init__(self, dtype, device, training, dist_ctx, wg_priority=0):
+        lib()  # fail loudly if the HIP library is missing
+        self.dtype, self.dev, self.training, self.dist = dtype, torch.device(device), training, dist_ctx
+        self.t = 0                       # Adam step counter
+        self.beta1 = 0.9                 # Adam's beta_1 when adam_step is given none (fetal_net.adversarial sets the optimizer's)
+        self.loss_kind, self.loss_param = 0, 1.0      # ops.LOSS_KINDS: 0 = dice_coefficient_loss
+        # the weight gradients run on their own stream (FMRI_WGRAD_STREAM=0: on the main stream); wg_priority = its HIP priority
+        self._wg_stream = (torch.cuda.Stream(device=self.dev, priority=wg_priority)
+                           if (training and self.dev.type == "cuda" and os.environ.get("FMRI_WGRAD_STREAM", "1") != "0") else None)
+        # ONE tensor for the engine's lifetime: captured hipGraphs of other batch sizes keep its address (re-creating it per buffer
+        # set left them writing into freed memory, which the allocator then handed to the tile index list of the next volume)
+        self.sums = torch.zeros(16, dtype=torch.float64, device=self.dev)
+
+    def _alloc_params(self):
+        """P in the engine's layout (n_flat fp32 values) and, when training, G, M and V of the same size"""
+        self.P = torch.zeros(self.n_flat, dtype=torch.float32, device=self.dev)
+        if self.training:
+            self.G, self.M, self.V = torch.zeros_like(self.P), torch.zeros_like(self.P), torch.zeros_like(self.P)
+
+    # ------------------------------------------------------------------------------------------------ Keras weights
+    def load_keras_weights(self, W):
+        self.P.copy_(torch.from_numpy(self.keras_to_flat(W)))
+        self.refresh_weight_copies()
+
+    def export_keras_weights(self):
+        return self.flat_to_keras(self.P.detach().cpu().numpy())
+
+    # ------------------------------------------------------------------------------------------------ loss
+    def loss_forward(self, y_true, weight=None):
+        """y_true uint8 [nvox*L] device.  probs + the 8 metric sums (accumulated into zeroed self.sums)."""
+        self.sums.zero_()
+        ops.sigmoid_dice_fwd(self.logits, y_true, self.probs, self.sums, weight=weight)
+        if self.loss_kind == ops.LOSS_WEIGHTED_DICE:
+            ns, nl = self._wdice_groups()
+            if getattr(self, "_gsums", None) is None or self._gsums.numel() < 3 * ns * nl:
+                self._gsums = torch.zeros(3 * ns * nl, dtype=torch.float64, device=self.dev)
+            ops.weighted_dice_fwd(self.probs, y_true, self._gsums, self.sums, ns, nl)
+        if self.dist is not None and self.dist.world > 1 and self.dist.global_dice:
+            self.dist.all_reduce_sums(self.sums)
+        return self.sums
+
+    def _wdice_groups(self):
+        """(groups along the batch axis, labels per group) of weighted_dice_coefficient's axis=(-3,-2,-1) (reference metrics.py:39): the 3-D
+        models' (N, labels, X, Y, Z) tensors give one Dice per (sample, label), the 2-D models' (N, X, Y, labels) one per slice"""
+        if self.plan.ndim == 2:
+            return self.N, 1
+        return self.N, self.plan.n_labels
+
+    def predict(self, x):
+        self.forward(x, bn_training=False)
+        self.sums.zero_()
+        # sigmoid only (y_true is irrelevant for probs): reuse the fused kernel with an all-zero label buffer
+        ops.sigmoid_dice_fwd(self.logits, self._dummy_y, self.probs, self.sums)
+        return self.probs
+
+    def _seg_loss_bwd(self, y_true, grad_scale, weight, dprobs, dprobs_scale, seg_loss):
+        """dlogits of the segmentation loss (after loss_forward), plus the chain of an outside gradient `dprobs` on the probabilities"""
+        if seg_loss and self.loss_kind == ops.LOSS_WEIGHTED_DICE:
+            ns, nl = self._wdice_groups()
+            ops.weighted_dice_bwd(self.probs, y_true, self._gsums, self.sums, self.dlogits, ns, nl, grad_scale=grad_scale)
+        elif seg_loss:
+            ops.sigmoid_loss_bwd(self.probs, y_true, self.sums, self.dlogits, self.loss_kind, self.loss_param, smooth=1.0, grad_scale=grad_scale,
+                                 weight=weight)
+        if dprobs is not None:
+            ops.sigmoid_chain(self.probs, dprobs, self.dlogits, scale=dprobs_scale, accumulate=seg_loss)
+
+    # ------------------------------------------------------------------------------------------------ weight-gradient stream
+    def _wgrad(self, fn):
+        """run fn, which enqueues weight-gradient kernels, on the side stream behind everything the main stream has enqueued so far
+        (inline without a side stream).  The weight gradients are off the critical path of the backward pass (nothing reads them before
+        the optimizer step): they run next to the input-gradient chain of the main stream.  (A third stream for the U-Net's first conv's
+        weight gradient - HBM-bound, ready last - measured nothing: 13.09-13.13 ms either way.)"""
+        if self._wg_stream is None:
+            fn()
+            return
+        self._wg_stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self._wg_stream):
+            fn()
+
+    def _join_wgrad(self):
+        """end of backward: the main stream waits for the side stream's weight gradients"""
+        if self._wg_stream is not None:
+            torch.cuda.current_stream(self.dev).wait_stream(self._wg_stream)
+
+    def grad_streams(self):
+        """streams that enqueue parameter-gradient kernels during backward (a gradient bucket is complete when all of them got there)"""
+        return [st for st in (getattr(self, "_main_stream", None), self._wg_stream) if st is not None]
+
+    # ------------------------------------------------------------------------------------------------ optimizer
+    def adam_step(self, lr, beta1=None, beta2=0.999, eps=1e-7, grad_scale=1.0):
+        beta1 = self.beta1 if beta1 is None else beta1
+        self.t += 1
+        lr_t = lr * math.sqrt(1.0 - beta2 ** self.t) / (1.0 - beta1 ** self.t)
+        ops.adam_step(self.P, self.G, self.M, self.V, lr_t, beta1, beta2, eps, grad_scale)
+        self.refresh_weight_copies(overlap=True)
+
+    def train_step(self, x, y_true, lr, weight=None):
+        """one full step: forward, Dice, backward, (all-reduce), Adam.  Returns the device tensor of metric sums."""
+        self.forward(x)
+        self.loss_forward(y_true, weight)
+        # data parallel: with the global-batch Dice sums the ranks' gradients are summed (scale 1); with per-rank losses
+        # (global_dice=False) the all-reduce sum is turned into the mean by scaling each rank's loss gradient by 1/world
+        self.backward(y_true, grad_scale=(self.dist.grad_scale if self.dist is not None else 1.0), weight=weight)
+        self.adam_step(lr)
+        return self.sums
+
+    @staticmethod
+    def metrics_from_sums(s, smooth=1.0, loss_kind=0, loss_param=1.0):
+        s = [float(v) for v in s]
+        dice = (2.0 * s[0] + smooth) / (s[1] + s[2] + smooth)
+        vod = (s[3] + smooth) / (s[4] + s[5] - s[3] + smooth)
+        return dict(loss=ops.loss_value_from_sums(s, loss_kind, loss_param, smooth), dice_coefficient=dice, vod_coefficient=vod,
+                    binary_accuracy=s[6] / max(s[7], 1.0))
+
+
+def glorot_uniform(rs, shape):
+    """Keras glorot_uniform kernel of `shape` = receptive field + (fan-in channels, fan-out channels), drawn from RandomState rs"""
+    rf = int(np.prod(shape[:-2]))
+    lim = math.sqrt(6.0 / (rf * shape[-2] + rf * shape[-1]))
+    return rs.uniform(-lim, lim, size=shape).astype(np.float32)
+
+
+def kernel_to_flat(k, size):
+    """Keras conv kernel (size,)*3 + (Cin, Cout) -> the flat [size^3][Cout][Cin] image; a 2-D kernel (size, size, Cin, Cout) becomes the
+    centre kd plane of the size^3 image (the caller checks the shape)"""
+    k = np.asarray(k, np.float32)
+    cin, cout = k.shape[-2:]
+    if k.ndim == 4:
+        k3 = np.zeros((size,) * 3 + (cin, cout), np.float32)
+        k3[size // 2] = k
+        k = k3
+    return k.reshape((size,) * 3 + (cin, cout)).transpose(0, 1, 2, 4, 3).reshape(-1)
+
+
+def flat_to_kernel(flat, size, cin, cout, nd):
+    """inverse of kernel_to_flat: the Keras kernel (size,)*nd + (Cin, Cout) of a flat [size^3][Cout][Cin] image (2-D: its centre kd plane)"""
+    k = flat.reshape((size,) * 3 + (cout, cin)).transpose(0, 1, 2, 4, 3)
+    return (k[size // 2] if nd == 2 else k).copy()

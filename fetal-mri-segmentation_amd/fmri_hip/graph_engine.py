@@ -18,9 +18,9 @@ Compile-time fusions (nothing of the fused kind is ever materialised):
   * Norm -> LeakyReLU | Activation('relu') => fmri_norm_act_fwd/bwd
   * Conv3D -> Activation('relu')           => activation in the conv epilogue
 Backward walks the op list in reverse; a tensor with several consumers receives its gradient contributions through
-`first writes, later ones accumulate`.  Parameters/gradients/Adam state are flat fp32 buffers like in UNetEngine.
+`first writes, later ones accumulate`.  Parameters, gradients, Adam state, the loss head and the weight-gradient side stream are
+engine_base.EngineBase's.
 """
-import math
 import os
 from collections import OrderedDict
 
@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, lib
+from ._lib import ACT_LEAKY, ACT_NONE, ACT_RELU
+from .engine_base import EngineBase, flat_to_kernel, glorot_uniform, kernel_to_flat
 
 LEAKY_ALPHA = 0.3      # keras.layers.LeakyReLU default (reference isensee2017.py:12)
 
@@ -41,28 +42,20 @@ class _Dims(object):
         return tuple(s >> level for s in self.spatial)
 
 
-class LayerGraphEngine(object):
+class LayerGraphEngine(EngineBase):
     def __init__(self, layers, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None, input_grad=False):
-        lib()
+        super().__init__(dtype, device, training, dist_ctx)
         self.input_grad = bool(input_grad)      # keep dL/d(input) (channel-padded in bf16 mode: the caller hands over cp(C) channels)
-        self.beta1 = 0.9
         self.layers = list(layers)
         self.by_name = OrderedDict((l.name, l) for l in self.layers)
-        self.dtype, self.dev, self.training, self.dist = dtype, torch.device(device), training, dist_ctx
         self.planar = any(l.class_name == "Conv2D" for l in self.layers)      # 2-D graph: slices ride the kernels' D axis
         self.nd = 2 if self.planar else 3
         # bf16: every tensor carries its channels padded to a multiple of 32 (zero weights / zero activations in the padding) so that
         # all convolutions - including the 16- and 32-channel levels, the stride-2 and the 1x1x1 ones - run on the MFMA kernels:
         # stride 2 = the stride-1 conv sampled at every second voxel, 1x1x1 = the centre tap of a 27-tap filter.  fp32 (parity mode)
         # keeps the exact-size tensors and the fp32 VALU kernels.  FMRI_GRAPH_PAD=0 switches the padding off.
-        import os
         self.pad = dtype == torch.bfloat16 and os.environ.get("FMRI_GRAPH_PAD", "1") != "0"
-        self.t = 0
-        self._wg_stream = (torch.cuda.Stream(device=self.dev) if (training and self.dev.type == "cuda" and os.environ.get("FMRI_WGRAD_STREAM", "1") != "0")
-                           else None)
         self._fixed_drop = None
-        self.loss_kind, self.loss_param = 0, 1.0
-        self.sums = torch.zeros(16, dtype=torch.float64, device=self.dev)
         self._compile()
         self._build_params(seed)
         self._bufsets = {}
@@ -228,9 +221,7 @@ class LayerGraphEngine(object):
             self.layout[name] = dict(kind="dense", w=(off, K * M), b=((off + K * M + 3) & ~3, M), K=K, M=M)
             off = ((off + K * M + 3) & ~3) + M
         self.n_flat = (off + 3) & ~3
-        self.P = torch.zeros(self.n_flat, dtype=torch.float32, device=self.dev)
-        if self.training:
-            self.G, self.M, self.V = torch.zeros_like(self.P), torch.zeros_like(self.P), torch.zeros_like(self.P)
+        self._alloc_params()
         self.Wf, self.Wd, self.Wup, self._dy64_buf = {}, {}, {}, {}
         self.Ws2, self._s2 = {}, None
         if self.pad:
@@ -398,17 +389,14 @@ class LayerGraphEngine(object):
         for l in self.layers:                                # Keras creation order
             if l.name in self.convs:
                 Lc = self.layout[l.name]
-                k = Lc["k"]
-                lim = math.sqrt(6.0 / (k ** self.nd * (Lc["cin"] + Lc["cout"])))
-                W[l.name + "/kernel"] = rs.uniform(-lim, lim, size=(k,) * self.nd + (Lc["cin"], Lc["cout"])).astype(np.float32)
+                W[l.name + "/kernel"] = glorot_uniform(rs, (Lc["k"],) * self.nd + (Lc["cin"], Lc["cout"]))
                 W[l.name + "/bias"] = np.zeros(Lc["cout"], np.float32)
             elif l.name in self.norms:
                 W[l.name + "/gamma"] = np.ones(self.layout[l.name]["c"], np.float32)
                 W[l.name + "/beta"] = np.zeros(self.layout[l.name]["c"], np.float32)
             elif l.name in self.denses:
                 Lc = self.layout[l.name]
-                lim = math.sqrt(6.0 / (Lc["K"] + Lc["M"]))
-                W[l.name + "/kernel"] = rs.uniform(-lim, lim, size=(Lc["K"], Lc["M"])).astype(np.float32)
+                W[l.name + "/kernel"] = glorot_uniform(rs, (Lc["K"], Lc["M"]))
                 W[l.name + "/bias"] = np.zeros(Lc["M"], np.float32)
         self.load_keras_weights(W)
 
@@ -418,12 +406,8 @@ class LayerGraphEngine(object):
             if Lc["kind"] == "conv":
                 k = np.asarray(W[name + "/kernel"], np.float32)
                 assert k.shape == (Lc["k"],) * self.nd + (Lc["cin"], Lc["cout"]), (name, k.shape)
-                if self.nd == 2:                          # (kh,kw,Cin,Cout) -> centre kd plane of the k^3 image (k = 1: the single tap)
-                    k3 = np.zeros((Lc["k"],) * 3 + (Lc["cin"], Lc["cout"]), np.float32)
-                    k3[Lc["k"] // 2] = k
-                    k = k3
                 o, n = Lc["w"]
-                host[o:o + n] = k.transpose(0, 1, 2, 4, 3).reshape(-1)
+                host[o:o + n] = kernel_to_flat(k, Lc["k"])       # 2-D: the centre kd plane of the k^3 image (k = 1: the single tap)
                 ob, nb = Lc["b"]
                 host[ob:ob + nb] = np.asarray(W[name + "/bias"], np.float32)
             elif Lc["kind"] == "dense":
@@ -439,10 +423,6 @@ class LayerGraphEngine(object):
                     host[o:o + n] = np.asarray(W[name + "/" + key], np.float32)
         return host
 
-    def load_keras_weights(self, W):
-        self.P.copy_(torch.from_numpy(self.keras_to_flat(W)))
-        self.refresh_weight_copies()
-
     def flat_to_keras(self, host, moving=True):
         W = OrderedDict()
         for l in self.layers:
@@ -450,8 +430,7 @@ class LayerGraphEngine(object):
             if name in self.convs:
                 Lc = self.layout[name]
                 o, n = Lc["w"]
-                k = host[o:o + n].reshape((Lc["k"],) * 3 + (Lc["cout"], Lc["cin"])).transpose(0, 1, 2, 4, 3)
-                W[name + "/kernel"] = (k[Lc["k"] // 2] if self.nd == 2 else k).copy()
+                W[name + "/kernel"] = flat_to_kernel(host[o:o + n], Lc["k"], Lc["cin"], Lc["cout"], self.nd)
                 ob, nb = Lc["b"]
                 W[name + "/bias"] = host[ob:ob + nb].copy()
             elif name in self.norms:
@@ -466,10 +445,8 @@ class LayerGraphEngine(object):
                 W[name + "/bias"] = host[ob:ob + nb].copy()
         return W
 
-    def export_keras_weights(self):
-        return self.flat_to_keras(self.P.detach().cpu().numpy())
-
-    def refresh_weight_copies(self):
+    def refresh_weight_copies(self, overlap=False):
+        """the compute-dtype images of P, all on the current stream (`overlap`, which adam_step passes, changes nothing here)"""
         if self.pad:
             self.Pp.index_copy_(0, self.map_p, self.P)       # every logical parameter into its place in the padded fp32 images (one kernel)
             for name, op in self.convs.items():
@@ -645,37 +622,12 @@ class LayerGraphEngine(object):
         """testing hook: fix the SpatialDropout3D masks ({layer name: [N,C] fp32 tensor}) instead of drawing them"""
         self._fixed_drop = masks
 
-    def loss_forward(self, y_true, weight=None):
-        self.sums.zero_()
-        ops.sigmoid_dice_fwd(self.logits, y_true, self.probs, self.sums, weight=weight)
-        if self.loss_kind == ops.LOSS_WEIGHTED_DICE:
-            ns, nl = self._wdice_groups()
-            if getattr(self, "_gsums", None) is None or self._gsums.numel() < 3 * ns * nl:
-                self._gsums = torch.zeros(3 * ns * nl, dtype=torch.float64, device=self.dev)
-            ops.weighted_dice_fwd(self.probs, y_true, self._gsums, self.sums, ns, nl)
-        if self.dist is not None and self.dist.world > 1 and self.dist.global_dice:
-            self.dist.all_reduce_sums(self.sums)
-        return self.sums
-
-    def _wdice_groups(self):
-        """(groups along the batch axis, labels per group) of weighted_dice_coefficient's axis=(-3,-2,-1) (reference metrics.py:39): the 3-D
-        models' (N, labels, X, Y, Z) tensors give one Dice per (sample, label), the 2-D models' (N, X, Y, labels) one per slice"""
-        if self.plan.ndim == 2:
-            return self.N, 1
-        return self.N, self.plan.n_labels
-
     def bce_forward(self, target):
         """dense head: probs = sigmoid(logits); sums = [sum of binary cross-entropy terms, sum |p - t|, n] (loss = [0] / [2], mae = [1] / [2])"""
         assert self.head == "dense"
         self.sums.zero_()
         ops.sigmoid_bce_fwd(self.logits.reshape(-1), target.reshape(-1), self.probs.reshape(-1), self.sums)
         return self.sums
-
-    def predict(self, x):
-        self.forward(x, bn_training=False)
-        self.sums.zero_()
-        ops.sigmoid_dice_fwd(self.logits, self._dummy_y, self.probs, self.sums)
-        return self.probs
 
     # ------------------------------------------------------------------------------------------------ backward
     def _accum(self, name, write):
@@ -690,9 +642,6 @@ class LayerGraphEngine(object):
                 self.tmp[name] = torch.empty_like(self.Gt[name])
             write(self.tmp[name])
             ops.add(self.Gt[name], self.tmp[name], self.Gt[name])
-
-    def grad_streams(self):
-        return [st for st in (getattr(self, "_main_stream", None), self._wg_stream) if st is not None]
 
     def backward(self, y_true, grad_scale=1.0, weight=None, dprobs=None, dprobs_scale=1.0, seg_loss=True, params=True):
         """seg head: y_true = uint8 labels; `dprobs` (optional, [..., ld >= n_labels]) is an extra gradient that arrives on the probabilities
@@ -712,14 +661,7 @@ class LayerGraphEngine(object):
         if self.head == "dense":
             ops.sigmoid_bce_bwd(self.probs.reshape(-1), y_true.reshape(-1), self.dlogits.reshape(-1), grad_scale / self.probs.numel())
         else:
-            if seg_loss and self.loss_kind == ops.LOSS_WEIGHTED_DICE:
-                ns, nl = self._wdice_groups()
-                ops.weighted_dice_bwd(self.probs, y_true, self._gsums, self.sums, self.dlogits, ns, nl, grad_scale=grad_scale)
-            elif seg_loss:
-                ops.sigmoid_loss_bwd(self.probs, y_true, self.sums, self.dlogits, self.loss_kind, self.loss_param, smooth=1.0, grad_scale=grad_scale,
-                                     weight=weight)
-            if dprobs is not None:
-                ops.sigmoid_chain(self.probs, dprobs, self.dlogits, scale=dprobs_scale, accumulate=seg_loss)
+            self._seg_loss_bwd(y_true, grad_scale, weight, dprobs, dprobs_scale, seg_loss)
         gsrc = self.Gt[self.logits_src]
         if gsrc.shape[-1] != self.plan.n_labels:
             gsrc.zero_()
@@ -771,14 +713,8 @@ class LayerGraphEngine(object):
                         else:
                             ops.conv3d_wgrad(s0, s1, g, dw, db, up0=o["up0"], planar=self.planar)
 
-                    if not params:
-                        pass
-                    elif self._wg_stream is None:
-                        wgrad()
-                    else:          # weight gradients beside the input-gradient chain (see UNetEngine._block_bwd)
-                        self._wg_stream.wait_stream(torch.cuda.current_stream(self.dev))
-                        with torch.cuda.stream(self._wg_stream):
-                            wgrad()
+                    if params:
+                        self._wgrad(wgrad)
                     if name in self.Wup and self.training:
                         self._accum(ins[0], lambda dst: ops.conv3d_upcat_dgrad(g, self.Wup[name]["up_d"], None, None, None, dst, None))
                     elif s2 is not None:
@@ -855,8 +791,7 @@ class LayerGraphEngine(object):
                         dst.zero_()
                         dst[:, :x.shape[1]] = dx
                 self._accum(o["ins"][0], write)
-        if self._wg_stream is not None:
-            torch.cuda.current_stream(self.dev).wait_stream(self._wg_stream)
+        self._join_wgrad()
         if self.pad and params:
             torch.index_select(self.Gp, 0, self.map_g, out=self.G)       # the logical gradients out of the padded images (one kernel)
         if self.dist is not None and params:
@@ -882,23 +817,3 @@ class LayerGraphEngine(object):
         first = name not in self._has_grad
         ops.slice_channels(src, off, self.Gt[name], accumulate=not first)
         self._has_grad.add(name)
-
-    # ------------------------------------------------------------------------------------------------ optimizer
-    def adam_step(self, lr, beta1=None, beta2=0.999, eps=1e-7, grad_scale=1.0):
-        beta1 = self.beta1 if beta1 is None else beta1
-        self.t += 1
-        lr_t = lr * math.sqrt(1.0 - beta2 ** self.t) / (1.0 - beta1 ** self.t)
-        ops.adam_step(self.P, self.G, self.M, self.V, lr_t, beta1, beta2, eps, grad_scale)
-        self.refresh_weight_copies()
-
-    def train_step(self, x, y_true, lr, weight=None):
-        self.forward(x)
-        self.loss_forward(y_true, weight)
-        self.backward(y_true, grad_scale=(self.dist.grad_scale if getattr(self, "dist", None) is not None else 1.0), weight=weight)
-        self.adam_step(lr)
-        return self.sums
-
-    @staticmethod
-    def metrics_from_sums(s, smooth=1.0, loss_kind=0, loss_param=1.0):
-        from .engine import UNetEngine
-        return UNetEngine.metrics_from_sums(s, smooth, loss_kind, loss_param)
