@@ -82,7 +82,7 @@ def assert_close(got, ref, rtol, atol_rel, what=""):
     if os.environ.get("FMRI_MEASURE", "0") == "1":
         _record(what, rtol, atol_rel, float((err / tol).max()))
         return float(err.max()) / scale
-    bad = err > tol
+    bad = ~(err <= tol)                    # a NaN fails (err > tol is False for it)
     if bool(bad.any()):
         idx = torch.nonzero(bad)[:5].tolist()
         raise AssertionError("%s: %d/%d elements off; max err %.3e (scale %.3e); first idx %s got %s ref %s" % (

@@ -387,6 +387,74 @@ def test_weight_gradient_is_exact_on_dyadic_data_at_full_size(case):
     assert torch.equal(db.cpu(), exp_db)
 
 
+# (N, D, H, W, Cin, planar): enc0a of the benchmarked step; 3 x 60: 5,760 weight-gradient tiles over 512 workgroups (11 or 12 each);
+# the 2-D first layer of configs[3] (5 slices; 6 = 5 + a previous-slice truth channel)
+FIRST_FULL = {"enc0a_n4": (4, 64, 128, 128, 1, False), "enc0a_n3_d60": (3, 60, 128, 128, 1, False),
+              "cfg3_2d_c5": (1, 64, 256, 256, 5, True), "cfg3_2d_c6": (1, 64, 256, 256, 6, True)}
+
+
+def _cpu_first_pre(x, w27, bias, planar):
+    """fp32 'same' conv without activation; planar: the centre kd plane of w27 as a 2-D conv of every slice"""
+    if not planar:
+        return _cpu_conv_ndhwc(x, w27, bias)
+    N, S, H, W, Cin = x.shape
+    Cout = w27.shape[1]
+    k = w27[9:18].reshape(3, 3, Cout, Cin).permute(2, 3, 0, 1).contiguous()
+    y = F.conv2d(x.reshape(N * S, H, W, Cin).permute(0, 3, 1, 2).contiguous(), k, bias, padding=1)
+    return y.permute(0, 2, 3, 1).reshape(N, S, H, W, Cout).contiguous()
+
+
+@pytest.mark.parametrize("case", list(FIRST_FULL))
+def test_first_layer_is_exact_on_dyadic_data_at_full_size(case):
+    """the first-layer kernels (conv3d_first.hip) at the sizes the models run them: forward with ReLU, without activation and with
+    LeakyReLU(0.25) - the RELU = false instantiation; alpha = 2^-2 keeps alpha * o exact - and the weight and bias gradients, whose
+    workgroups walk 16 (enc0a_n4), 11-12 (enc0a_n3_d60) or 16 (2-D) tiles each with the next tile's loads in flight.  Forward: x = k/4,
+    w = k/8, bias = k/4, at most 27 x 6 terms that are multiples of 1/32: exact in fp32, one bf16 rounding.  Weight gradient: dy sparse
+    (1/16) k/2, x = k/4: multiples of 1/8 whose sum stays below 2^24 / 8 (asserted): exact in any order, atomics included."""
+    from fmri_hip import ops
+    from fmri_hip._lib import ACT_LEAKY, ACT_NONE, ACT_RELU, BF16, IMPL_AUTO, IMPL_MFMA, lib
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    N, D, H, W, Cin, planar = FIRST_FULL[case]
+    Cout = 32
+    bf = torch.bfloat16
+    if not planar:
+        assert lib().fmri_conv3d_uses_mfma(Cin, 0, Cout, D, H, W, BF16) & 4, "not routed to the first-layer kernels"
+    impl = IMPL_MFMA if planar else IMPL_AUTO            # planar: impl=MFMA is refused unless the first-layer kernels take the shape
+    g = torch.Generator().manual_seed(14)
+    x = _dyadic((N, D, H, W, Cin), -4, 4, 4, g)
+    w = _dyadic((27, Cout, Cin), -2, 2, 8, g)
+    if planar:
+        w[:9] = 0
+        w[18:] = 0
+    bias = _dyadic((Cout,), -4, 4, 4, g)
+    xd, wd = x.to(bf).cuda(), w.to(bf).cuda()
+    pre = _cpu_first_pre(x, w, bias, planar)
+    assert float(pre.abs().max()) * 32 < 2 ** 24
+    y = torch.empty((N, D, H, W, Cout), dtype=bf, device="cuda")
+    for act, alpha, expect in ((ACT_RELU, 0.0, F.relu(pre)), (ACT_NONE, 0.0, pre), (ACT_LEAKY, 0.25, F.leaky_relu(pre, 0.25))):
+        y.fill_(float("nan"))
+        ops.conv3d_fwd(xd, None, wd, bias.cuda(), y, act=act, alpha=alpha, impl=impl, planar=planar)
+        torch.cuda.synchronize()
+        bad = int((y.cpu().float() != expect.to(bf).float()).sum())            # (by value: +0 and -0 of an exact zero sum both pass)
+        assert bad == 0, "%s act %d: %d of %d outputs differ from the exact value" % (case, act, bad, y.numel())
+    del y, pre, expect
+    dy = _dyadic((N, D, H, W, Cout), -2, 2, 2, g, density=1.0 / 16)
+    assert float(dy.abs().sum(dim=(0, 1, 2, 3)).max()) * 8 < 2 ** 24
+    dw, db = torch.zeros((27, Cout, Cin), device="cuda"), torch.zeros(Cout, device="cuda")
+    ops.conv3d_wgrad(xd, None, dy.to(bf).cuda(), dw, db, impl=impl, planar=planar)
+    if planar:
+        xc = x.reshape(N * D, H, W, Cin).permute(0, 3, 1, 2).contiguous()
+        gw = torch.nn.grad.conv2d_weight(xc, (Cout, Cin, 3, 3), dy.reshape(N * D, H, W, Cout).permute(0, 3, 1, 2).contiguous(), padding=1)
+        exp_dw = torch.zeros((27, Cout, Cin))
+        exp_dw[9:18] = gw.permute(2, 3, 0, 1).reshape(9, Cout, Cin)
+    else:
+        gw = torch.nn.grad.conv3d_weight(x.permute(0, 4, 1, 2, 3).contiguous(), (Cout, Cin, 3, 3, 3), dy.permute(0, 4, 1, 2, 3).contiguous(), padding=1)
+        exp_dw = gw.permute(2, 3, 4, 0, 1).reshape(27, Cout, Cin)
+    torch.cuda.synchronize()
+    assert torch.equal(dw.cpu(), exp_dw), "%s: max |diff| %.3e" % (case, float((dw.cpu() - exp_dw).abs().max()))
+    assert torch.equal(db.cpu(), dy.sum(dim=(0, 1, 2, 3)))
+
+
 # ------------------------------------------------------------------------------------------- configs[3]: 2-D mode at full size
 def test_cfg3_2d_full_size_step_bf16_vs_fp32_engine():
     """BASELINE configs[3]: 64 slices of 256x256x5, depth 4 / 32 filters, one full training step (planar kernels, planar parity form,

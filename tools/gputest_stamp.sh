@@ -14,6 +14,14 @@ LOG=gpurun_out/${TAG}_gputest_final.log
 } > $LOG
 python -m pytest tests -x -q -m gpu -p no:cacheprovider --durations=10 >> $LOG 2>&1
 RC=$?
+# paths relative to the repository root: the log is committed, where the tree was checked out is not part of it
+python3 - "$LOG" <<'PY'
+import os, sys
+text = open(sys.argv[1]).read()
+for root in {os.getcwd(), os.path.realpath("."), os.environ.get("PWD", os.getcwd())}:
+    text = text.replace(root.rstrip("/") + "/", "")
+open(sys.argv[1], "w").write(text)
+PY
 echo "# rc=$RC" >> $LOG
 tail -8 $LOG
 exit $RC
