@@ -523,7 +523,10 @@ __global__ void __launch_bounds__(256) k_sigmoid_dice_fwd(const float* __restric
         {   // binary cross-entropy with Keras' clipping, and the reference focal term (metrics.py:80-87: alpha .5, gamma 2)
             const float pc = fminf(fmaxf(p, 1e-7f), 1.f - 1e-7f);
             s[7] += (double)(w * (t > 0.5f ? -__logf(pc) : -__logf(1.f - pc)));   // weight_mask * xent (metrics.py:72-76)
-            s[8] += (double)(t > 0.5f ? -0.5f * (1.f - p) * (1.f - p) * __logf(p) : -0.5f * p * p * __logf(1.f - p));
+            // log p and log(1 - p) differ by the logit (1 - p = p e^-z): take the logarithm whose argument stays away from 0 and add z, so that
+            // the term is finite at saturated logits (p = 1.0f from z = 17 upward, where log(1 - p) = -inf; the exact value there is z / 2)
+            const float lg = (z > 0.f) == (t > 0.5f) ? __logf(t > 0.5f ? p : 1.f - p) : __logf(t > 0.5f ? 1.f - p : p) + (t > 0.5f ? z : -z);
+            s[8] += (double)(t > 0.5f ? -0.5f * (1.f - p) * (1.f - p) * lg : -0.5f * p * p * lg);
         }
         s[0] += (double)(t * p);
         s[1] += (double)t;
@@ -614,15 +617,21 @@ __global__ void k_sigmoid_loss_bwd(const float* __restrict__ probs, const uint8_
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float p = probs[i], t = (float)y[i];
         const float sg = p * (1.f - p);
+        // Keras clips p to [1e-7, 1 - 1e-7] inside binary_crossentropy (tf.clip_by_value): no gradient passes where the clip is active
+        // (k_sigmoid_bce_bwd of the discriminator does the same)
+        const float xg = (p > 1e-7f && p < 1.f - 1e-7f) ? 1.f : 0.f;
         float g;                                               // dL/dlogit
         if (kind == 0) g = -(a * t - c) * sg;
-        else if (kind == 1) g = (wgt ? wgt[i] : 1.f) * (p - t) * invn;
-        else if (kind == 2) g = -(a * t - c) * sg + p0 * (wgt ? wgt[i] : 1.f) * (p - t) * invn;
+        else if (kind == 1) g = xg * (wgt ? wgt[i] : 1.f) * (p - t) * invn;
+        else if (kind == 2) g = -(a * t - c) * sg + p0 * xg * (wgt ? wgt[i] : 1.f) * (p - t) * invn;
         else if (kind == 3) {
-            float dp;
-            if (t > 0.5f) dp = -0.5f * (-2.f * (1.f - p) * __logf(p) + (1.f - p) * (1.f - p) / p);
-            else dp = -0.5f * (2.f * p * __logf(1.f - p) - p * p / (1.f - p));
-            g = dp * sg;
+            // dL/dp * p (1 - p) with the factor folded in: q^2 p log p - q^3 / 2 (t = 1, q = 1 - p) and its mirror image; u log u -> 0 as
+            // u -> 0 is taken at its limit below the normal range.  (dL/dp alone is -inf at p = 1, t = 0, and inf * p (1 - p) = inf * 0 was
+            // NaN there, while the gradient is 1/2; the reference's TensorFlow formula has the same singularity - DESIGN.md.)
+            const float u = t > 0.5f ? p : 1.f - p, q = 1.f - u;          // u: the probability of the true class
+            const float ulu = u >= 1.17549435e-38f ? u * __logf(u) : 0.f;
+            g = q * q * ulu - 0.5f * q * q * q;
+            if (!(t > 0.5f)) g = -g;
         } else if (kind == 4) g = -(t * vu - (1.f - t) * vc) * sg;
         else g = (-(a * t - c) + p0 * (a2 * (1.f - t) - c2)) * sg;
         dl[i] = grad_scale * g;
@@ -735,7 +744,7 @@ extern "C" int fmri_sigmoid_dice_fwd(const float* logits, const uint8_t* y_true,
                                      fmri_stream_t stream) {
     if (n <= 0) return FMRI_E_SHAPE;
     {
-        const bool v4 = n % 4 == 0 && !((((uintptr_t)logits) | ((uintptr_t)probs) | ((uintptr_t)logits)) & 15) && !(((uintptr_t)y_true) & 3);
+        const bool v4 = n % 4 == 0 && !((((uintptr_t)logits) | ((uintptr_t)probs)) & 15) && !(((uintptr_t)y_true) & 3);
         if (v4) k_sigmoid_dice_fwd<4><<<grid_for(n / 4, 256, 512), 256, 0, as_stream(stream)>>>(logits, y_true, nullptr, probs, sums, n);
         else k_sigmoid_dice_fwd<1><<<grid_for(n, 256, 512), 256, 0, as_stream(stream)>>>(logits, y_true, nullptr, probs, sums, n);
     }

@@ -111,3 +111,48 @@ def bar(name, value, limit):
         return value
     assert value <= limit, "%s: %.3e > %.3e" % (name, value, limit)
     return value
+
+
+def drnd(shape, seed, dtype, scale=1.0, shift=0.0):
+    """rnd() drawn on the device (a seeded device generator): for tensors of 10^7-10^8 elements, where the host generator and the copy
+    would dominate the test"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    t = torch.randn(*shape, generator=g, device="cuda")
+    if scale != 1.0:
+        t *= scale
+    if shift != 0.0:
+        t += shift
+    return t.to(dtype)
+
+
+def dev_close(got, ref, rtol, atol_rel, what=""):
+    """assert_close with its arithmetic on the device (float64 there): tensors of 10^7-10^8 elements"""
+    import os
+    got, ref = got.reshape(ref.shape).double(), ref.double()
+    scale = float(ref.abs().max()) + 1e-30
+    err = (got - ref).abs()
+    tol = atol_rel * scale + rtol * ref.abs()
+    if os.environ.get("FMRI_MEASURE", "0") == "1":
+        # (an element that is exactly right under a bar of exactly 0 uses none of it: 0 / 0 must not hide the others behind a NaN)
+        frac = torch.where(tol > 0, err / tol, torch.where(err > 0, float("inf"), 0.0).to(err.dtype))
+        _record(what, rtol, atol_rel, float(torch.nan_to_num(frac, nan=float("inf")).max()))
+        return float(err.max()) / scale
+    bad = ~(err <= tol)                    # a NaN fails
+    if bool(bad.any()):
+        idx = torch.nonzero(bad)[:5].tolist()
+        raise AssertionError("%s: %d/%d elements off; max err %.3e (scale %.3e); first idx %s got %s ref %s" % (
+            what, int(bad.sum()), bad.numel(), float(err.max()), scale, idx,
+            [float(got[tuple(i)]) for i in idx], [float(ref[tuple(i)]) for i in idx]))
+    return float(err.max()) / scale
+
+
+def assert_same(got, ref, what=""):
+    """bit-for-bit equality of two tensors of one dtype and shape (-0.0 differs from 0.0, a NaN equals the same NaN)"""
+    assert got.dtype == ref.dtype and tuple(got.shape) == tuple(ref.shape), (what, got.dtype, ref.dtype, tuple(got.shape), tuple(ref.shape))
+    view = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[got.element_size()]
+    a, b = got.contiguous().view(view), ref.contiguous().view(view)
+    if not torch.equal(a, b):
+        bad = a != b
+        idx = torch.nonzero(bad)[:5].tolist()
+        raise AssertionError("%s: %d/%d elements differ; first idx %s got %s ref %s" % (
+            what, int(bad.sum()), bad.numel(), idx, [float(got[tuple(i)]) for i in idx], [float(ref[tuple(i)]) for i in idx]))
