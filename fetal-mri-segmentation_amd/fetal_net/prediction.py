@@ -222,13 +222,6 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
     st["acc"].zero_()
     st["cnt"].zero_()
     idx_all = torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).cuda()
-    # A captured graph holds no dependency on the engine's weight-repack side stream (it was captured after a warm-up that had already
-    # joined it), but an optimizer step since then may have left a repack of the deeper layers' filter images in flight there: make THIS
-    # stream wait for it before any replay reads those images.
-    for B in sizes:
-        join = getattr(model.engine(B), "_join_packs", None)
-        if join is not None:
-            join()
     out_dev = torch.empty_like(st["acc"])
     out_host = torch.empty(ashape, dtype=torch.float64, pin_memory=True)
     bad = torch.zeros(1, dtype=torch.int32, device="cuda")

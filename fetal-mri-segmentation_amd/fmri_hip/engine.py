@@ -13,7 +13,6 @@ MI355X layout decisions
   * the up-sampled tensor and the concat are never materialised (the conv kernels read two sources);
   * every tensor is allocated once at build time (288 GB HBM: no re-computation, no allocator traffic in the step).
 """
-import os
 from collections import OrderedDict
 
 import numpy as np
@@ -91,16 +90,15 @@ class UNetPlan:
 
 class UNetEngine(EngineBase):
     def __init__(self, plan, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None):
-        # FMRI_WGRAD_PRIO (A/B): HIP priority of the weight-gradient stream (0 = default, positive = lower): with a lower one the dispatcher hands free
-        # CUs to the input-gradient chain first and the weight-gradient backlog fills in behind the HBM-bound kernels of the main stream
-        super().__init__(dtype, device, training, dist_ctx, wg_priority=int(os.environ.get("FMRI_WGRAD_PRIO", "0")))
+        # every switch of this engine, read here and nowhere else; what each one does stands where self.sw[...] is used
+        super().__init__(dtype, device, training, dist_ctx, DETERMINISTIC=False, DECONV_FOLD=True, FWD_WS=True, UPCAT=True, TAIL_FUSE=True,
+                         TAIL_FUSE_2D=True, NORM_FUSE=1, NORM_FUSE_MAXLEVEL=1 if plan.norm == "batch" else 0)
         self.plan, self.N = plan, batch
         self.planar = plan.ndim == 2      # 2-D: tensors are [1][slices][H][W][C], every op is planar (no coupling along D)
-        self._pack_stream, self._pack_events, self._pack_event_dec, self._pack_pending = None, None, None, []
         # FMRI_DETERMINISTIC=1: bit-reproducible training steps (same weights + same batch -> the same bits in every gradient and metric):
         # gradient partial sums meet as fixed-point integers in a shadow of G (ops.set_deterministic), the parity-form weight gradient -
         # whose scratch is filled by fp32 atomics - gives way to the fused-upsample 27-tap one.  One engine per process at a time.
-        self.deterministic = bool(training and self.dev.type == "cuda" and os.environ.get("FMRI_DETERMINISTIC", "0") == "1")
+        self.deterministic = bool(training and self.dev.type == "cuda" and self.sw["DETERMINISTIC"])
         self._bufsets = {}
         self._build_params(seed)
         self.set_batch(batch)
@@ -140,8 +138,8 @@ class UNetEngine(EngineBase):
                                           "accumulate with floating-point atomics")
             self.G64 = torch.zeros(self.n_flat, dtype=torch.int64, device=dev)
             _register_deterministic(self)
-        # compute-dtype copies of the 3x3x3 filters
-        self.Wf, self.Wd, self.Wup = {}, {}, {}
+        # compute-dtype copies of the 3x3x3 filters (and no pack table yet: it holds their addresses)
+        self.Wf, self.Wd, self.Wup, self._ptab = {}, {}, {}, None
         self.upcat = self._upcat_layers()
         self.Wt = {}                      # compute-dtype copies of the transposed-conv filters [8][Cout][Cin]
         self.moving = {}                  # batch-norm moving mean / variance (inference statistics), fp32 [2][C]
@@ -205,8 +203,7 @@ class UNetEngine(EngineBase):
         # on its up-sampled channels, exactly as in the UpSampling3D variant - with pre-MULTIPLIED instead of pre-summed filters.  Keyed by the
         # 'a' conv's name.  FMRI_DECONV_FOLD=0 keeps the two-step form (transposed conv as one-tap parity form, then the plain 27-tap conv).
         self.Wfd, self.fold = {}, None
-        if (not self.planar and self.dtype == torch.bfloat16 and p.norm is None and os.environ.get("FMRI_DECONV_FOLD", "1") != "0"
-                and os.environ.get("FMRI_FWD_WS", "1") != "0"):
+        if (not self.planar and self.dtype == torch.bfloat16 and p.norm is None and self.sw["DECONV_FOLD"] and self.sw["FWD_WS"]):
             from .deconv_fold import DeconvFold
             for lv in p.dec:
                 a = lv[0]
@@ -346,13 +343,12 @@ class UNetEngine(EngineBase):
     def _upcat_layers(self):
         """decoder 'a' convs (UpSampling3D -> concatenate -> Conv3D, reference unet.py:132-138,61,102) that take the parity form:
         name -> (up-sampled channels, skip channels).  FMRI_UPCAT=0 keeps the 27-tap fused-upsample kernel (A/B switch)."""
-        import os
         p = self.plan
         out = {}
         self.upcat_wgrad = set()                           # ... of which the weight gradient takes the parity form too (never in deterministic mode)
         # (fp32, round 6: the parity form runs on the fp32 instantiation of the same MFMA kernels where fmri_conv3d_upcat_ok says so - 3-D,
         # channels in multiples of 16; FMRI_F32_MFMA=0 keeps fp32 on the VALU kernels and with them on the 27-tap fused-upsample form)
-        if (self.dtype != torch.bfloat16 and self.planar) or os.environ.get("FMRI_UPCAT", "1") == "0":
+        if (self.dtype != torch.bfloat16 and self.planar) or not self.sw["UPCAT"]:
             return out
         for lv in p.dec:
             a = lv[0]
@@ -371,77 +367,28 @@ class UNetEngine(EngineBase):
 
     def _use_upcat(self, name):
         """parity form for this layer at the CURRENT batch size (2-D: the slice count must be a multiple of the 4-slice tile)"""
-        return name in self.Wup and (not self.planar or self.N % 4 == 0)
-
-    def refresh_weight_copies(self, overlap=False):
-        """compute-dtype images of the fp32 parameters (forward filters, tap-flipped transposed filters for the input gradients, parity
-        filters).  Default (round 6): ONE launch for all of them on the current stream (ops.pack_weights_batched).  The scheme it replaced,
-        kept behind FMRI_PACK_BATCHED=0: overlap=True (the optimizer step): only the first encoder level is repacked on the current stream; the other layers -
-        whose weights are the large ones and are first read a whole level later - are repacked on a side stream, in order of first use,
-        with one event per encoder level and one for the decoder: `forward` waits for a level's event in front of that level, i.e. the
-        repack runs under the first convolutions of the NEXT step instead of in front of them.  (One event for the whole encoder made the
-        level-1 convs wait for the 256 -> 512 image, whose kernel - like every kernel next to a persistent conv launch, which fills all
-        CUs - only gets CUs between two conv launches: 74 us of stall behind the first level in the rocprofv3 timeline; un-profiled the
-        step does not notice: 13.09-13.15 ms either way.)"""
-        if self.dev.type == "cuda" and os.environ.get("FMRI_PACK_BATCHED", "1") != "0":
-            # round 6: one launch on the current stream for all plain / parity-form images (FMRI_PACK_BATCHED=0: the per-layer launches, on the
-            # side stream when overlap=True - the round-2 ... round-5 scheme below)
-            self._join_packs()
-            self._repack(lambda name: True, batched=True)
-            return
-        early = set(c["name"] for c in self.plan.enc[0])
-        if overlap and self.dev.type == "cuda" and os.environ.get("FMRI_PACK_OVERLAP", "1") != "0":
-            if self._pack_stream is None:
-                self._pack_stream = torch.cuda.Stream(device=self.dev)
-                self._pack_events = {ld: torch.cuda.Event() for ld in range(1, len(self.plan.enc))}
-                self._pack_event_dec = torch.cuda.Event()
-            self._repack(lambda name: name in early)
-            main = torch.cuda.current_stream(self.dev)
-            self._pack_stream.wait_stream(main)
-            enc = set(c["name"] for lv in self.plan.enc for c in lv) - early
-            with torch.cuda.stream(self._pack_stream):
-                # in order of first use: the encoder's images (joined after level 0), then the decoder's (joined in front of the decoder)
-                for ld in range(1, len(self.plan.enc)):
-                    lvl = set(c["name"] for c in self.plan.enc[ld])
-                    self._repack(lambda name: name in lvl)
-                    self._pack_events[ld].record(self._pack_stream)
-                self._repack(lambda name: name not in early and name not in enc)
-                self._pack_event_dec.record(self._pack_stream)
-            self._pack_pending = list(range(1, len(self.plan.enc))) + ["dec"]
-            return
-        self._join_packs()
-        self._repack(lambda name: True)
-
-    def _join_packs(self, level=None):
-        """make the current stream wait for the side-stream repack: the images of encoder level `level` (and of the levels before it), or
-        (level=None) all of them"""
-        while self._pack_pending and (level is None or (self._pack_pending[0] != "dec" and self._pack_pending[0] <= level)):
-            k = self._pack_pending.pop(0)
-            torch.cuda.current_stream(self.dev).wait_event(self._pack_event_dec if k == "dec" else self._pack_events[k])
+        return self.route["up"].get(name) == "upcat"
 
     def _pack_table(self):
-        """the images of _repack's first and third loop (plain layers, parity-form layers) as one table for ops.pack_weights_batched"""
-        if getattr(self, "_ptab", None) is None:
+        """the plain and the parity-form images as one table for ops.pack_weights_batched: (table, blocks, the tensors whose raw addresses the
+        table holds, P's address when it was built) - rebuilt when P has moved since, dropped wherever Wf / Wd / Wup are allocated"""
+        if self._ptab is None or self._ptab[3] != self.P.data_ptr():
             ent = [("plain", self.w_view(n), self.Wf[n], self.Wd.get(n)) for n in self.Wf if n not in self.Wfd]
             for n, W in self.Wup.items():
                 c0, c1 = self.upcat[n]
                 ent.append(("up", self.w_view(n), c0, c1, W["up_f"], W["up_d"], W["sk_f"], W["sk_d"], self.planar))
-            self._ptab = ops.pack_table(ent, self.dev) if ent else (None, 0)
+            self._ptab = (ops.pack_table(ent, self.dev) if ent else (None, 0)) + (ent, self.P.data_ptr())
         return self._ptab
 
-    def _repack(self, want, batched=False):
-        """batched: every plain / parity-form image in ONE launch (want must then accept every layer); the per-layer launches are
-        launch-bound - 14 of them cost the configs[1] step 0.12 ms wherever they run (tools/r06/pack_cost.py)"""
-        if batched:
-            tab, nb = self._pack_table()
-            if tab is not None:
-                ops.pack_weights_batched(tab, nb, self.dtype)
-        for name in self.Wf:
-            if not batched and want(name) and name not in self.Wfd:
-                ops.pack_weights(self.w_view(name), self.Wf[name], self.Wd.get(name))
+    def refresh_weight_copies(self):
+        """compute-dtype images of the fp32 parameters (forward filters, tap-flipped transposed filters for the input gradients, parity
+        filters), on the current stream.  Every plain / parity-form image in ONE launch: per-layer launches are launch-bound - 14 of them
+        cost the configs[1] step 0.12 ms wherever they run, also on a side stream under the next step's first convolutions (rounds 2-5,
+        retired: profiles/r06_pack_batched_ab.log, tools/r06/pack_cost.py).  Folded layers and transposed-conv images: per layer."""
+        tab, nb = self._pack_table()[:2]
+        if tab is not None:
+            ops.pack_weights_batched(tab, nb, self.dtype)
         for name, F in self.Wfd.items():
-            if not want(name):
-                continue
             w3 = self.w_view(name)
             weff, b27 = self.fold.effective(w3, self.w_view(F["u"]), self.b_view(name), self.b_view(F["u"]), F["cmid"], gemm_dtype=F["gd"])
             F["up_f"].copy_(weff)
@@ -450,12 +397,8 @@ class UNetEngine(EngineBase):
             if F["up_d"] is not None:
                 F["up_d"].copy_(weff[:, self.fold.mirror].transpose(-1, -2))            # Wc[p][1 - t']^T (fmri_conv3d_pack_up_weights' w_up_dgrad)
                 F["sk_d"].copy_(w3[:, :, F["cmid"]:].flip(0).transpose(1, 2))           # tap-flipped transposed skip filters
-        for name, W in self.Wup.items():
-            if not batched and want(name):
-                c0, c1 = self.upcat[name]
-                ops.conv3d_pack_up_weights(self.w_view(name), c0, c1, W["up_f"], W["up_d"], W["sk_f"], W["sk_d"], planar=self.planar)
         for name, wt in self.Wt.items():
-            if not want(name) or name in self._folded_up:
+            if name in self._folded_up:
                 continue
             if name in self.Wd2:
                 Wd_, L = self.Wd2[name], self.layout[name]
@@ -480,11 +423,12 @@ class UNetEngine(EngineBase):
             self._build_buffers()
             self._bufsets[key] = dict(act=self.act, grad=getattr(self, "grad", None), logits=self.logits, probs=self.probs,
                                       dlogits=getattr(self, "dlogits", None), pre=self.pre, nstats=self.nstats, nss=self.nss, norm_ws=self.norm_ws,
-                                      wgrad_ws=getattr(self, "wgrad_ws", None),
+                                      wgrad_ws=getattr(self, "wgrad_ws", None), route=self.route,
                                       dummy_y=torch.zeros(self.logits.numel(), dtype=torch.uint8, device=self.dev))
         b = self._bufsets[key]
         self.N, self.act, self.grad, self.logits, self.probs, self.dlogits = N, b["act"], b["grad"], b["logits"], b["probs"], b["dlogits"]
         self.pre, self.nstats, self.nss, self.norm_ws, self.wgrad_ws = b["pre"], b["nstats"], b["nss"], b["norm_ws"], b["wgrad_ws"]
+        self.route = b["route"]
         self._dummy_y = b["dummy_y"]       # per buffer set and never freed: captured hipGraphs keep raw pointers to it
 
     def _dims(self, level):
@@ -493,8 +437,61 @@ class UNetEngine(EngineBase):
             return (1,) + self.plan.level_dims(level, self.N)
         return (self.N,) + self.plan.level_dims(level)
 
+    def _plan_routes(self):
+        """Which kernel form every launch of a step takes at the CURRENT batch size, decided once per buffer set: the buffers are sized from
+        it, and forward and backward dispatch on it and on nothing else.
+          tail[block]   bits of ops.conv3d_fwd_tail_ok: what the epilogue of a plain single-source bf16 block without a normalisation layer
+                        produces besides its output (1: MaxPooling, 2: the final 1x1x1 conv's logits).  FMRI_TAIL_FUSE=0 switches it off,
+                        FMRI_TAIL_FUSE_2D=0 the same for the 2-D models only (A/B).
+          stats[block]  the block's forward launch sums its own output for the statistics of its normalisation layer;
+          dz[block]     the input-gradient launch that writes the block's gradient forms the reductions of its normalisation backward -
+                        both in the asynchronous epilogue of the 3-D bf16 MFMA launch (ops.conv3d_fwd_ntail_ok).  FMRI_NORM_FUSE = bit mask
+                        (1: stats, 2: dz), FMRI_NORM_FUSE_MAXLEVEL = deepest level that uses them.  Defaults from the interleaved A/B inside
+                        the configs[1] step (tools/ab_norm_tails.py, profiles/r03_norm_tails_ab.log): the statistics tail down to level 1
+                        (batch norm: 19.91 -> 19.55 ms) or on level 0 only (instance norm: a workgroup's sums are flushed whenever the sample
+                        changes; 20.65 -> 20.47 ms); the backward tail is built and tested but off: it saves 170-340 us of reduction passes
+                        per full-resolution layer and costs the input-gradient launch 100-180 us (tools/bench_ntail.py) - a launch that
+                        shares the chip with the weight-gradient stream, under which the HBM-bound reduction passes were already hidden
+                        (step +0.2 ... 0.5 ms with it).
+          up[a]         how decoder block `a` gets its up-sampled input: "fold" (transposed conv folded into a), "d2s" (2-D transposed conv as
+                        planar conv + depth-to-space; the slices must tile by 4), "onetap" (one-tap parity transposed conv), "deconv" (direct
+                        k2s2 transposed conv), "upcat" (parity-form up-sample + concat; 2-D: the slices must tile by 4) or "upsample" (the
+                        fused-upsample 27- / 9-tap conv);
+          upcat_wgrad[a]  a's weight gradient takes the parity form too."""
+        p, sw = self.plan, self.sw
+        r = dict(tail={}, stats={}, dz={}, up={}, upcat_wgrad={})
+
+        def ntail(c0, c1, cout, level, kind):
+            if p.norm is None or self.planar or self.dtype != torch.bfloat16 or not (sw["NORM_FUSE"] & kind) or level > sw["NORM_FUSE_MAXLEVEL"]:
+                return False
+            return ops.conv3d_fwd_ntail_ok(c0, c1, cout, *self._dims(level), self.dtype)
+
+        for lv in p.dec:
+            a, u = lv[0], p.up.get(lv[0]["level"])
+            if a["name"] in self.Wfd:
+                r["up"][a["name"]] = "fold"
+            elif u is not None:
+                r["up"][a["name"]] = ("d2s" if u["name"] in self.Wd2 and self.N % 4 == 0 else "onetap" if u["name"] in self.Wdc else "deconv")
+            else:
+                r["up"][a["name"]] = "upcat" if a["name"] in self.Wup and (not self.planar or self.N % 4 == 0) else "upsample"
+            r["upcat_wgrad"][a["name"]] = r["up"][a["name"]] == "upcat" and a["name"] in self.upcat_wgrad
+        tails = self.dtype == torch.bfloat16 and sw["TAIL_FUSE"] and (sw["TAIL_FUSE_2D"] or not self.planar)
+        for lv in p.enc + p.dec:
+            a, b = lv
+            for c in lv:
+                r["tail"][c["name"]] = (ops.conv3d_fwd_tail_ok(c["cin"], c["cout"], *self._dims(c["level"]), self.dtype, planar=self.planar)
+                                        if tails and not c.get("norm") else 0)
+                c0, c1 = (c["c_up"], c["c_skip"]) if "c_up" in c else (c["cin"], 0)
+                if r["up"].get(c["name"]) == "upcat":       # the parity form's skip launch writes the output
+                    c0, c1 = c1, 0
+                r["stats"][c["name"]] = ntail(c0, c1, c["cout"], c["level"], 1)
+            r["dz"][a["name"]] = ntail(b["cout"], 0, a["cout"], a["level"], 2)
+            r["dz"][b["name"]] = False                      # its gradient comes from a pooling / up-sampling / 1x1x1 backward, not from a conv launch
+        return r
+
     def _build_buffers(self):
         p, N, dt, dev = self.plan, self.N, self.dtype, self.dev
+        self.route = self._plan_routes()
         A = self.act = {}
         self.pre, self.nstats = {}, {}            # conv outputs before normalisation; saved statistics {mean, 1/s, 1/sigma}
         self.nss = {}                             # {scale, shift} of the apply pass, for the normalisation tail of the input-gradient launches
@@ -537,7 +534,7 @@ class UNetEngine(EngineBase):
             a = lv[0]
             # gradient of the concatenated conv input; the parity form writes the up-sampled part straight at low resolution,
             # so only the skip channels remain
-            ccat = self.upcat[a["name"]][1] if self._use_upcat(a["name"]) else (a["c_skip"] if a["name"] in self.Wfd else a["cin"])
+            ccat = a["c_skip"] if self.route["up"][a["name"]] in ("upcat", "fold") else a["cin"]
             Gd["cat_%d" % a["level"]] = torch.empty(self._dims(a["level"]) + (ccat,), dtype=dt, device=dev)
         self.dlogits = torch.empty_like(self.logits)
         # scratch for the slab flush of the MFMA weight-gradient kernel (max over the layers of this plan)
@@ -560,44 +557,13 @@ class UNetEngine(EngineBase):
         return t.reshape((t.shape[1],) + tuple(t.shape[2:])) if self.planar else t
 
     def _tail_ok(self, c):
-        """what the epilogue of conv block `c` can produce besides its output (ops.conv3d_fwd_tail_ok bits): only plain single-source
-        blocks without a normalisation layer (the consumer then reads the block's OUTPUT); FMRI_TAIL_FUSE=0 switches it off (A/B).  2-D
-        (round 6): MaxPooling2D / the final Conv2D out of the planar kernel's epilogue, FMRI_TAIL_FUSE_2D=0 switches that off."""
-        if c.get("norm") or self.dtype != torch.bfloat16 or os.environ.get("FMRI_TAIL_FUSE", "1") == "0":
-            return 0
-        if self.planar and os.environ.get("FMRI_TAIL_FUSE_2D", "1") == "0":
-            return 0
-        key = (c["name"], self.N)
-        cache = self.__dict__.setdefault("_tail_cache", {})
-        if key not in cache:                                   # a host-side query per (layer, batch size), not per step
-            d = self._dims(c["level"])
-            cache[key] = ops.conv3d_fwd_tail_ok(c["cin"], c["cout"], d[0], d[1], d[2], d[3], self.dtype, planar=self.planar)
-        return cache[key]
-
-    def _ntail_ok(self, c0, c1, cout, level, kind=1):
-        """does the 3-D MFMA launch (c0 | c1) -> cout at `level` carry a normalisation tail (kind 1: statistics of its output, kind 2: the
-        backward reductions - in its asynchronous epilogue: ops.conv3d_fwd_ntail_ok)?  FMRI_NORM_FUSE = bit mask of the kinds in use,
-        FMRI_NORM_FUSE_MAXLEVEL = deepest level that uses them.  Defaults from the interleaved A/B inside the configs[1] step
-        (tools/ab_norm_tails.py, profiles/r03_norm_tails_ab.log): the statistics tail down to level 1 (batch norm: 19.91 -> 19.55 ms) or on
-        level 0 only (instance norm: a workgroup's sums are flushed whenever the sample changes; 20.65 -> 20.47 ms); the backward tail is
-        built and tested but off: it saves 170-340 us of reduction passes per full-resolution layer and costs the input-gradient launch
-        100-180 us (tools/bench_ntail.py) - a launch that shares the chip with the weight-gradient stream, under which the HBM-bound
-        reduction passes were already hidden (step +0.2 ... 0.5 ms with it)."""
-        if self.plan.norm is None or self.planar or self.dtype != torch.bfloat16 or not (int(os.environ.get("FMRI_NORM_FUSE", "1")) & kind):
-            return False
-        if level > int(os.environ.get("FMRI_NORM_FUSE_MAXLEVEL", "1" if self.plan.norm == "batch" else "0")):
-            return False
-        key = (c0, c1, cout, level, self.N)
-        cache = self.__dict__.setdefault("_ntail_cache", {})
-        if key not in cache:
-            d = self._dims(level)
-            cache[key] = ops.conv3d_fwd_ntail_ok(c0, c1, cout, d[0], d[1], d[2], d[3], self.dtype)
-        return cache[key]
+        """what the epilogue of conv block `c` produces besides its output (_plan_routes)"""
+        return self.route["tail"][c["name"]]
 
     def _block_fwd(self, c, src0, src1, up0, bn_training, pool=None, final=None):
         """one [conv -> (norm) -> ReLU] block (reference create_convolution_block, unet.py:89-115).  pool: tensor that receives
         MaxPooling3D(2) of the block's output; final: the final 1x1x1 conv descriptor whose logits the epilogue computes - both only
-        when _tail_ok(c) says so (the caller checks)."""
+        when the route plan's tail bits say so (the caller checks)."""
         name = c["name"]
         out, act = (self.pre[name], ACT_NONE) if c.get("norm") else (self.act[name], ACT_RELU)
         if pool is not None or final is not None:
@@ -609,18 +575,15 @@ class UNetEngine(EngineBase):
         # normalised block with training statistics: the conv sums its own output in its epilogue where the launch allows it
         per, eos = self._norm_mode()
         want_sums = bool(c.get("norm")) and not (self.plan.norm == "batch" and not bn_training)
-        c0, c1 = src0.shape[-1], (0 if src1 is None else src1.shape[-1])
-        summed = False
-        if up0 and self._use_upcat(name):
+        summed = want_sums and self.route["stats"][name]
+        if self.route["up"].get(name) == "upcat":
             W = self.Wup[name]
-            if want_sums and src1 is not None and self._ntail_ok(c1, 0, c["cout"], c["level"]):
+            if summed:
                 ops.conv3d_upcat_fwd_stats(src0, src1, W["up_f"], W["sk_f"], self.b_view(name), out, self.norm_ws, per, act=act)
-                summed = True
             else:
                 ops.conv3d_upcat_fwd(src0, src1, W["up_f"], W["sk_f"], self.b_view(name), out, act=act, planar=self.planar)
-        elif want_sums and self._ntail_ok(c0, c1, c["cout"], c["level"]):
+        elif summed:
             ops.conv3d_fwd_stats(src0, src1, self.Wf[name], self.b_view(name), out, self.norm_ws, per, up0=up0, act=act)
-            summed = True
         else:
             ops.conv3d_fwd(src0, src1, self.Wf[name], self.b_view(name), out, up0=up0, act=act, planar=self.planar)
         if not c.get("norm"):
@@ -655,29 +618,27 @@ class UNetEngine(EngineBase):
         self.x_in = x
         h = x
         for ld, lv in enumerate(p.enc):
-            if ld > 0:                                      # this level's weight images were repacked on the side stream (FMRI_PACK_LEVELS=0: A/B,
-                self._join_packs(level=ld if os.environ.get("FMRI_PACK_LEVELS", "1") != "0" else len(p.enc))     # wait for the whole encoder's)
             h = self._block_fwd(lv[0], h, None, False, bn_training)
             # MaxPooling3D behind the level's second block comes out of that conv's epilogue when the kernel can do it
-            fuse_pool = ld < p.depth - 1 and (self._tail_ok(lv[1]) & 1)
+            fuse_pool = ld < p.depth - 1 and (self.route["tail"][lv[1]["name"]] & 1)
             h = self._block_fwd(lv[1], h, None, False, bn_training, pool=A["pool_%d" % ld] if fuse_pool else None)
             if ld < p.depth - 1:
                 h = A["pool_%d" % ld] if fuse_pool else ops.maxpool_fwd(h, A["pool_%d" % ld], planar=self.planar)
-        self._join_packs()
         for lv in p.dec:
             a, b = lv
             skip = A[p.enc[a["level"]][1]["name"]]
-            if a["name"] in self.Wfd:
+            up = self.route["up"][a["name"]]
+            if up == "fold":
                 F = self.Wfd[a["name"]]
                 ops.conv3d_upcat_fwd_bias27(h, skip, F["up_f"], F["sk_f"], F["bias27"], A[a["name"]], act=ACT_RELU)
-            elif a["level"] in p.up:
+            elif up in ("d2s", "onetap", "deconv"):
                 u = p.up[a["level"]]
-                if u["name"] in self.Wd2 and h.shape[1] % 4 == 0:
+                if up == "d2s":
                     Wd_ = self.Wd2[u["name"]]
                     t4 = self._d2s_tmp(u["name"], h, Wd_)
                     ops.conv3d_fwd(h, None, Wd_["wf"], Wd_["b4"], t4, act=ACT_NONE, planar=True)
                     self._d2s_views(A[u["name"]], t4)[0].copy_(self._d2s_views(A[u["name"]], t4)[1])
-                elif u["name"] in self.Wdc:
+                elif up == "onetap":
                     ops.conv3d_upcat_fwd(h, None, self.Wdc[u["name"]]["up_f"], None, self.b_view(u["name"]), A[u["name"]], act=ACT_NONE)
                 else:
                     ops.deconv_fwd(h, self.Wt[u["name"]], self.b_view(u["name"]), A[u["name"]], planar=self.planar)
@@ -685,7 +646,7 @@ class UNetEngine(EngineBase):
             else:
                 self._block_fwd(a, h, skip, True, bn_training)
             # the last block also produces the logits of the final 1x1x1 conv (one label) in its epilogue when the kernel can do it
-            fuse_final = lv is p.dec[-1] and p.n_labels == 1 and (self._tail_ok(b) & 2)
+            fuse_final = lv is p.dec[-1] and p.n_labels == 1 and (self.route["tail"][b["name"]] & 2)
             h = self._block_fwd(b, A[a["name"]], None, False, bn_training, final=p.final if fuse_final else None)
         f = p.final
         if not (p.dec and fuse_final):
@@ -710,7 +671,7 @@ class UNetEngine(EngineBase):
                              self.gb_view(name, "gamma"), self.nstats[name], self._as_samples(g), self.gb_view(name, "gamma", self.G),
                              self.gb_view(name, "beta", self.G), self.norm_ws, per, act=ACT_RELU, beta=self.gb_view(name, "beta"))
         def wgrad():
-            if up0 and name in self.upcat_wgrad and self._use_upcat(name):
+            if self.route["upcat_wgrad"].get(name):
                 ops.conv3d_upcat_wgrad(src0, src1, g, self.w_view(name, self.G), self.b_view(name, self.G), self.dwc_scratch,
                                        workspace=self.wgrad_ws, planar=self.planar)
             else:
@@ -751,7 +712,7 @@ class UNetEngine(EngineBase):
         applies a's ReLU mask (recomputed from a's conv output) and sums dz and dz * x for a's normalisation backward where it can."""
         Gd = self.grad
         an, bn = a["name"], b["name"]
-        if an in self.pre and self._ntail_ok(b["cout"], 0, a["cout"], a["level"], kind=2):
+        if self.route["dz"][an]:
             per = self._norm_mode()[0]
             ops.norm_scale_shift(self.nstats[an], self.gb_view(an, "gamma"), self.gb_view(an, "beta"), self.nss[an])
             ops.conv3d_dgrad_norm(Gd[bn], self.Wd[bn], self.pre[an], self.nss[an], Gd[an], self.norm_ws, per, act=ACT_RELU)
@@ -790,13 +751,14 @@ class UNetEngine(EngineBase):
             self._block_bwd(b, A[a["name"]], None, False)
             self._dgrad_into(b, a)
             cat = Gd["cat_%d" % ld]
-            if a["name"] in self.Wfd:
+            up = self.route["up"][a["name"]]
+            if up == "fold":
                 self._folded_bwd(a, A[low], skip, cat, low)
-            elif ld in p.up:
+            elif up in ("d2s", "onetap", "deconv"):
                 u = p.up[ld]
                 self._block_bwd(a, A[u["name"]], skip, False)
                 ops.conv3d_dgrad(Gd[a["name"]], self.Wd[a["name"]], cat, planar=self.planar)
-                if u["name"] in self.Wd2 and A[low].shape[1] % 4 == 0:
+                if up == "d2s":
                     Wd_, L = self.Wd2[u["name"]], self.layout[u["name"]]
                     dyc = ops.slice_channels(cat, 0, Gd[u["name"]])
                     t4 = self._d2s_tmp(u["name"], A[low], Wd_)
@@ -808,7 +770,7 @@ class UNetEngine(EngineBase):
                     ops.conv3d_wgrad(A[low], None, t4, Wd_["dw"], Wd_["db"], planar=True)
                     self.w_view(u["name"], self.G)[:4].add_(Wd_["dw"][13].view(4, L["cout"], L["cin"]))
                     self.b_view(u["name"], self.G).add_(Wd_["db"].view(4, L["cout"]).sum(0))
-                elif u["name"] in self.Wdc:
+                elif up == "onetap":
                     Wd_ = self.Wdc[u["name"]]
                     dyc = ops.slice_channels(cat, 0, Gd[u["name"]])          # the transposed conv's own slice of the concat gradient
                     ops.conv3d_upcat_dgrad(dyc, Wd_["up_d"], None, self._mask_of(low), None, Gd[low], None)
@@ -820,7 +782,7 @@ class UNetEngine(EngineBase):
                     ops.deconv_bwd(A[low], self.Wt[u["name"]], cat, Gd[low], self.w_view(u["name"], self.G), self.b_view(u["name"], self.G),
                                    dy_off=0, xmask=self._mask_of(low), planar=self.planar)
                 self._grad_ready(u["name"])
-            elif self._use_upcat(a["name"]):
+            elif up == "upcat":
                 self._block_bwd(a, A[low], skip, True)
                 W = self.Wup[a["name"]]
                 ops.conv3d_upcat_dgrad(Gd[a["name"]], W["up_d"], W["sk_d"], self._mask_of(low), None, Gd[low], cat, planar=self.planar)

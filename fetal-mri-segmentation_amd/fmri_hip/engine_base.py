@@ -4,7 +4,10 @@ interpreter) differ in how they schedule a step, not in what surrounds the sched
 `EngineBase` holds that part: the flat fp32 parameter store (P, its gradient G and the Adam moments M / V, all in the engine's `layout`),
 the loss head (sigmoid + metric sums, the seg-loss gradient), Keras Adam, Keras weight export / import and the weight-gradient side
 stream.  An engine sets `layout` / `n_flat` and calls `_alloc_params`, keeps `logits` / `probs` / `dlogits` / `_dummy_y` of the current
-batch, and provides `forward`, `backward`, `refresh_weight_copies(overlap)`, `keras_to_flat` and `flat_to_keras`.
+batch, and provides `forward`, `backward`, `refresh_weight_copies`, `keras_to_flat` and `flat_to_keras`.
+
+`read_switches` is the one place where the engines look at their FMRI_* environment switches: once, in `__init__`, into `self.sw`.  Buffers
+are sized and kernel routes planned from those values, so a switch that changes afterwards changes nothing (nor under a captured hipGraph).
 
 The module-level helpers convert Keras kernels: a Glorot-uniform draw, and a conv kernel (k,)*nd + (Cin, Cout) <-> the flat
 [k^3][Cout][Cin] image the engines keep in P (a 2-D kernel is the centre kd plane of that image).
@@ -19,16 +22,27 @@ from . import ops
 from ._lib import lib
 
 
+def read_switches(**defaults):
+    """FMRI_<NAME> for every NAME=default given.  A True default is on unless the variable is "0", a False one is off unless it is "1",
+    an int default is replaced by int(value)."""
+    out = {}
+    for name, d in defaults.items():
+        v = os.environ.get("FMRI_" + name)
+        out[name] = d if v is None else (v != "0") if d is True else (v == "1") if d is False else int(v)
+    return out
+
+
 class EngineBase(object):
-    def __init__(self, dtype, device, training, dist_ctx, wg_priority=0):
+    def __init__(self, dtype, device, training, dist_ctx, **switches):
+        """switches: the engine's own FMRI_* switches and their defaults (read_switches), next to FMRI_WGRAD_STREAM which both engines have"""
         lib()  # fail loudly if the HIP library is missing
         self.dtype, self.dev, self.training, self.dist = dtype, torch.device(device), training, dist_ctx
+        self.sw = read_switches(WGRAD_STREAM=True, **switches)
         self.t = 0                       # Adam step counter
         self.beta1 = 0.9                 # Adam's beta_1 when adam_step is given none (fetal_net.adversarial sets the optimizer's)
         self.loss_kind, self.loss_param = 0, 1.0      # ops.LOSS_KINDS: 0 = dice_coefficient_loss
-        # the weight gradients run on their own stream (FMRI_WGRAD_STREAM=0: on the main stream); wg_priority = its HIP priority
-        self._wg_stream = (torch.cuda.Stream(device=self.dev, priority=wg_priority)
-                           if (training and self.dev.type == "cuda" and os.environ.get("FMRI_WGRAD_STREAM", "1") != "0") else None)
+        # the weight gradients run on their own stream (FMRI_WGRAD_STREAM=0: on the main stream)
+        self._wg_stream = torch.cuda.Stream(device=self.dev) if (training and self.dev.type == "cuda" and self.sw["WGRAD_STREAM"]) else None
         # ONE tensor for the engine's lifetime: captured hipGraphs of other batch sizes keep its address (re-creating it per buffer
         # set left them writing into freed memory, which the allocator then handed to the tile index list of the next volume)
         self.sums = torch.zeros(16, dtype=torch.float64, device=self.dev)
@@ -114,7 +128,7 @@ class EngineBase(object):
         self.t += 1
         lr_t = lr * math.sqrt(1.0 - beta2 ** self.t) / (1.0 - beta1 ** self.t)
         ops.adam_step(self.P, self.G, self.M, self.V, lr_t, beta1, beta2, eps, grad_scale)
-        self.refresh_weight_copies(overlap=True)
+        self.refresh_weight_copies()
 
     def train_step(self, x, y_true, lr, weight=None):
         """one full step: forward, Dice, backward, (all-reduce), Adam.  Returns the device tensor of metric sums."""

@@ -21,7 +21,6 @@ Backward walks the op list in reverse; a tensor with several consumers receives 
 `first writes, later ones accumulate`.  Parameters, gradients, Adam state, the loss head and the weight-gradient side stream are
 engine_base.EngineBase's.
 """
-import os
 from collections import OrderedDict
 
 import numpy as np
@@ -44,7 +43,7 @@ class _Dims(object):
 
 class LayerGraphEngine(EngineBase):
     def __init__(self, layers, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None, input_grad=False):
-        super().__init__(dtype, device, training, dist_ctx)
+        super().__init__(dtype, device, training, dist_ctx, GRAPH_PAD=True, S2_PARITY=True)
         self.input_grad = bool(input_grad)      # keep dL/d(input) (channel-padded in bf16 mode: the caller hands over cp(C) channels)
         self.layers = list(layers)
         self.by_name = OrderedDict((l.name, l) for l in self.layers)
@@ -54,7 +53,7 @@ class LayerGraphEngine(EngineBase):
         # all convolutions - including the 16- and 32-channel levels, the stride-2 and the 1x1x1 ones - run on the MFMA kernels:
         # stride 2 = the stride-1 conv sampled at every second voxel, 1x1x1 = the centre tap of a 27-tap filter.  fp32 (parity mode)
         # keeps the exact-size tensors and the fp32 VALU kernels.  FMRI_GRAPH_PAD=0 switches the padding off.
-        self.pad = dtype == torch.bfloat16 and os.environ.get("FMRI_GRAPH_PAD", "1") != "0"
+        self.pad = dtype == torch.bfloat16 and self.sw["GRAPH_PAD"]
         self._fixed_drop = None
         self._compile()
         self._build_params(seed)
@@ -333,7 +332,7 @@ class LayerGraphEngine(EngineBase):
         # Conv3D(3x3x3, strides 2) (reference isensee2017.py:51): on the parity kernels (fmri_hip/strided_parity.py) where the shapes allow -
         # forward + input gradient (bit 0), weight gradient (bit 1: 64-wide blocks of the input's channels); FMRI_S2_PARITY=0: A/B
         self.Ws2, self._s2 = {}, None
-        if self.pad and not self.planar and self.dtype == torch.bfloat16 and os.environ.get("FMRI_S2_PARITY", "1") != "0":
+        if self.pad and not self.planar and self.dtype == torch.bfloat16 and self.sw["S2_PARITY"]:
             for name, op in self.convs.items():
                 if op.get("sub") != (2, 2, 2) or op["k"] != 3 or op["act"] != ACT_NONE or len(op["ins"]) != 1:
                     continue
@@ -445,8 +444,8 @@ class LayerGraphEngine(EngineBase):
                 W[name + "/bias"] = host[ob:ob + nb].copy()
         return W
 
-    def refresh_weight_copies(self, overlap=False):
-        """the compute-dtype images of P, all on the current stream (`overlap`, which adam_step passes, changes nothing here)"""
+    def refresh_weight_copies(self):
+        """the compute-dtype images of P, all on the current stream"""
         if self.pad:
             self.Pp.index_copy_(0, self.map_p, self.P)       # every logical parameter into its place in the padded fp32 images (one kernel)
             for name, op in self.convs.items():

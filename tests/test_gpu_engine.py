@@ -357,9 +357,9 @@ def test_norm_tails_match_the_separate_passes_bf16(norm, monkeypatch):
         eng.loss_forward(yd)
         eng.backward(yd)
         torch.cuda.synchronize()
-        fused = sorted(k for k, v in eng._ntail_cache.items() if v) if fuse == "3" else []
+        fused = sorted((kind, k) for kind in ("stats", "dz") for k, v in eng.route[kind].items() if v) if fuse == "3" else []
         out.append((eng.logits.double().cpu(), eng.G.double().cpu(), fused))
-    assert len(out[0][2]) >= 3, out[0][2]             # (32,0,64): enc0b forward; (64,0,64): dec0a skip launch, dec0b forward, dec0b input gradient; (64,0,32): enc0b input gradient
+    assert len(out[0][2]) >= 3, out[0][2]             # level 0: stats of enc0b, dec0a (skip launch) and dec0b; dz of dec0a (dec0b's input gradient) and enc0a (enc0b's)
     el = float((out[0][0] - out[1][0]).norm() / out[1][0].norm())
     eg = float((out[0][1] - out[1][1]).norm() / out[1][1].norm())
     print("%s: fused launches %s; logits rel L2 %.2e, gradient buffer rel L2 %.2e" % (norm, out[0][2], el, eg))

@@ -968,30 +968,32 @@ def test_pack_weights_batched_equals_the_per_layer_launches(ops, dtype):
             assert torch.equal(view(r), view(o)), k
 
 
-def test_engine_batched_repack_equals_the_per_layer_repack(monkeypatch):
-    """the engine's weight images after an optimizer step with FMRI_PACK_BATCHED=1 (default) and =0: the same bits, 3-D and 2-D"""
+def test_engine_batched_repack_equals_the_per_layer_repack(ops):
+    """the engine's weight images after its (batched) repack against the per-layer launches (ops.pack_weights / ops.conv3d_pack_up_weights)
+    applied to the same parameters, into fresh images of the same shapes: the same bits, 3-D and 2-D"""
     from fmri_hip.engine import UNetEngine, UNetPlan
     for ndim in (3, 2):
-        imgs = {}
-        for mode in ("1", "0"):
-            monkeypatch.setenv("FMRI_PACK_BATCHED", mode)
-            if ndim == 3:
-                eng = UNetEngine(UNetPlan(1, (16, 32, 32), depth=3, n_base_filters=32), 1, dtype=torch.bfloat16, seed=5)
-                x = torch.randn((1, 16, 32, 32, 1), generator=torch.Generator().manual_seed(1)).cuda().to(torch.bfloat16)
-                nv = 16 * 32 * 32
-            else:
-                eng = UNetEngine(UNetPlan(5, (64, 64), depth=3, n_base_filters=32, ndim=2), 8, dtype=torch.bfloat16, seed=5)
-                x = torch.randn((1, 8, 64, 64, 5), generator=torch.Generator().manual_seed(1)).cuda().to(torch.bfloat16)
-                nv = 8 * 64 * 64
-            y = (torch.rand((nv,), generator=torch.Generator().manual_seed(2)) > 0.7).to(torch.uint8).cuda()
-            eng.P.copy_(torch.randn(eng.P.shape, generator=torch.Generator().manual_seed(3)) * 0.05)     # the same parameters in both arms
-            eng.refresh_weight_copies(overlap=True)
-            eng._join_packs()
-            torch.cuda.synchronize()
-            imgs[mode] = {("f", k): v.clone() for k, v in eng.Wf.items()}
-            imgs[mode].update({("d", k): v.clone() for k, v in eng.Wd.items()})
-            for k, W in eng.Wup.items():
-                imgs[mode].update({(kk, k): v.clone() for kk, v in W.items() if v is not None})
+        if ndim == 3:
+            eng = UNetEngine(UNetPlan(1, (16, 32, 32), depth=3, n_base_filters=32), 1, dtype=torch.bfloat16, seed=5)
+        else:
+            eng = UNetEngine(UNetPlan(5, (64, 64), depth=3, n_base_filters=32, ndim=2), 8, dtype=torch.bfloat16, seed=5)
+        eng.P.copy_(torch.randn(eng.P.shape, generator=torch.Generator().manual_seed(3)) * 0.05)     # the same parameters in both arms
+        eng.refresh_weight_copies()
+        em = lambda t: None if t is None else torch.full_like(t, float("nan"))
+        imgs = {"1": {}, "0": {}}
+        for k in eng.Wf:
+            f, d = em(eng.Wf[k]), em(eng.Wd.get(k))
+            ops.pack_weights(eng.w_view(k), f, d)
+            imgs["1"][("f", k)], imgs["0"][("f", k)] = eng.Wf[k], f
+            if d is not None:
+                imgs["1"][("d", k)], imgs["0"][("d", k)] = eng.Wd[k], d
+        for k, W in eng.Wup.items():
+            c0, c1 = eng.upcat[k]
+            R = {kk: em(v) for kk, v in W.items()}
+            ops.conv3d_pack_up_weights(eng.w_view(k), c0, c1, R["up_f"], R["up_d"], R["sk_f"], R["sk_d"], planar=eng.planar)
+            imgs["1"].update({(kk, k): v for kk, v in W.items() if v is not None})
+            imgs["0"].update({(kk, k): v for kk, v in R.items() if v is not None})
+        torch.cuda.synchronize()
         assert imgs["1"].keys() == imgs["0"].keys() and len(imgs["1"]) > 10
         for k in imgs["1"]:
             assert torch.equal(imgs["1"][k].view(torch.int16), imgs["0"][k].view(torch.int16)), (ndim, k)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of engine switches on ONE box (boxes of the pool differ by several %): runs bench.py once per "VAR=value" argument (and once plain),
-# interleaved twice, and prints patches/s + the exclusive per-kernel table.   usage: bash tools/ab_bench.sh FMRI_TAIL_FUSE=0 FMRI_PACK_OVERLAP=0
+# interleaved twice, and prints patches/s + the exclusive per-kernel table.   usage: bash tools/ab_bench.sh FMRI_TAIL_FUSE=0 FMRI_WGRAD_STREAM=0
 mkdir -p gpurun_out
 for rep in 1 2; do
   for cfg in "" "$@"; do
