@@ -1,4 +1,4 @@
-// Post-processing of a predicted probability volume on the device (reference fetal_net/postprocess.py:7-19):
+// scipy.ndimage on the device.  First: post-processing of a predicted probability volume (reference fetal_net/postprocess.py:7-19):
 //   scipy.ndimage.gaussian_filter -> "> threshold" -> binary_fill_holes -> largest connected component (scipy.ndimage.label).
 // The production flow of the reference (prod/predict_nifti2.py:77-95) runs this once per stage on a whole 160x256x256-class volume; with
 // the sliding-window result already in HBM it costs four small HBM-bound passes and two label-propagation loops instead of a download
@@ -8,7 +8,9 @@
 // ni_filters.c NI_Correlate1D symmetric branch) in fp64 with host-computed weights, so the smoothed volume - and therefore the
 // thresholded mask - is bit-identical to scipy's; hole filling and labelling are integer algorithms with scipy's default 6-connectivity,
 // and ties between equally large components go to the one scipy numbers first (smallest linear index of its first voxel).
+// Second, at the end of the file: distance_transform_edt (the distance masks of the mask-weighted loss).
 #include "common.h"
+#include <math.h>
 
 namespace {
 
@@ -207,4 +209,245 @@ extern "C" int fmri_largest_component_step(const uint8_t* mask, int32_t* labels,
     }
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Exact Euclidean distance transform of a label volume on the device (reference fetal_net/utils/create_distance_masks.py: the distance
+// masks of the mask-weighted loss, scipy.ndimage.distance_transform_edt(mask, sampling) + distance_transform_edt(1 - mask, sampling)).
+// uint8 volume [X][Y][Z], z contiguous, per-axis voxel spacing, fp64: every nonzero voxel gets the distance to the nearest zero voxel,
+// zero voxels get 0 (scipy's definition).
+//
+// Separable form on SQUARED distances: f0 = 0 on zero voxels and +inf elsewhere, then one min-plus pass per axis,
+//   g(j) = min_i f(i) + (s * (i - j))^2,   axis order z, y, x;   the last pass takes the square root.
+//   z (contiguous lines): a [rows x Z] tile of the mask in LDS, one forward and one backward scan per row for the nearest voxel of the
+//     other class, (s_z * k)^2 written with coalesced stores.
+//   y, x (strided lines): a workgroup owns the whole line for a slab of 16 contiguous z (one 128-byte line of fp64 per line element),
+//     f[n][16] and w[k] = (s * k)^2 in LDS; thread (j, z) walks outwards from i = j in both directions and stops when w[k] >= best.
+//     Exact: f >= 0, so no candidate beyond k can be smaller; on real labels the walk is a few tens of steps, not n.
+// Arithmetic: products and sums separately rounded (fp contract off), w[k] = fl(fl(k * s) * fl(k * s)) as numpy forms it.  With unit
+// spacing every squared distance is an integer below 2^53: the result equals scipy's bit for bit.  Other spacings: the two agree to a
+// few ulp (another summation order, and offsets of equal true distance round differently) - tests/test_gpu_distance.py derives the bound.
+//
+// Two-class mode: the reference's mask is edt(m) + edt(1 - m); one summand is 0 at every voxel, so the sum is the distance to the
+// nearest voxel of the OTHER class.  Both fields (f_fg: distance of the nonzero voxels to the zeros, f_bg: of the zeros to the nonzeros)
+// go through the three passes of one launch each - one mask read - and the last pass computes and writes, per voxel, only the field
+// of the voxel's own class.
+//
+// Degenerate input: a volume without a zero voxel gives +inf everywhere (there is no nearest zero; scipy returns numbers that are not
+// distances there), in two-class mode a volume of one class is +inf everywhere; a volume without a nonzero voxel gives 0.
+// Lines longer than EDT_LDS_MAX on an axis take k_edt_line_global for that axis: the same walk on global memory, one thread per voxel.
+
+namespace {
+
+constexpr int EDT_LDS_MAX = 1024;        // longest line of the LDS kernels (f[1024][16] fp64 + w[1024] = 136 KiB of the CU's 160)
+constexpr int EDT_TZ = 16;               // z per slab of the strided passes: 16 fp64 = one 128-byte line
+constexpr int EDT_ZTILE = 32768;         // uint16 entries of the z pass's tile (64 KiB)
+constexpr int EDT_NONE = 0x7fff;         // "no voxel of the other class in this row"
+
+__device__ __forceinline__ double edt_w(int k, double s) {
+#pragma clang fp contract(off)
+    const double d = (double)k * s;
+    return d * d;
+}
+
+// ---- pass along z.  tile[r * pitch + z]: bit 15 = the voxel's class, bits 0-14 = distance in voxels to the nearest voxel of the other
+// class in the row (EDT_NONE: there is none).  pitch (in uint16) is twice an odd number: the 32 lanes of a half wave scanning 32 rows at
+// the same z touch 32 different banks.
+template <bool BOTH>
+__global__ __launch_bounds__(256) void k_edt_z(const uint8_t* __restrict__ mask, double* __restrict__ f_fg, double* __restrict__ f_bg,
+                                               int64_t rows, int Z, double sz, int R, int pitch) {
+    __shared__ uint16_t tile[EDT_ZTILE];
+    const int64_t tiles = (rows + R - 1) / R;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int64_t row0 = t * R;
+        const int nr = (int)min((int64_t)R, rows - row0);
+        const int64_t g0 = row0 * Z;
+        const int cnt = nr * Z;
+        for (int e = threadIdx.x; e < cnt; e += blockDim.x) tile[(e / Z) * pitch + e % Z] = mask[g0 + e] ? 0x8000 : 0;
+        __syncthreads();
+        for (int r = threadIdx.x; r < nr; r += blockDim.x) {
+            uint16_t* const row = tile + r * pitch;
+            int l0 = -1, l1 = -1;                        // position of the latest voxel of class 0 / 1
+            for (int z = 0; z < Z; ++z) {
+                const int c = row[z] >> 15;
+                l0 = c ? l0 : z;
+                l1 = c ? z : l1;
+                const int o = c ? l0 : l1;
+                row[z] = (uint16_t)((c << 15) | (o < 0 ? EDT_NONE : z - o));
+            }
+            l0 = l1 = -1;
+            for (int z = Z - 1; z >= 0; --z) {
+                const int v = row[z], c = v >> 15;
+                l0 = c ? l0 : z;
+                l1 = c ? z : l1;
+                const int o = c ? l0 : l1;
+                const int k = min(v & 0x7fff, o < 0 ? EDT_NONE : o - z);
+                row[z] = (uint16_t)((c << 15) | k);
+            }
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
+            const int v = tile[(e / Z) * pitch + e % Z], c = v >> 15, k = v & 0x7fff;
+            const double w = k == EDT_NONE ? (double)INFINITY : edt_w(k, sz);
+            f_fg[g0 + e] = c ? w : 0.0;
+            if (BOTH) f_bg[g0 + e] = c ? 0.0 : w;
+        }
+        __syncthreads();
+    }
+}
+
+// the min-plus walk of one output element: f(i) at i = j, then j -+ k for k = 1, 2, ... while w(k) < best.  [lo, hi] holds every finite
+// f(i) of the line (lo > hi: there is none): an element outside starts at the range's near end, nobody looks past its far end.
+template <typename F, typename W>
+__device__ __forceinline__ double edt_walk(int j, int lo, int hi, F f, W w) {
+#pragma clang fp contract(off)
+    if (lo > hi) return (double)INFINITY;
+    double best = f(j);
+    const int kmax = max(j - lo, hi - j);
+    for (int k = max(1, max(lo - j, j - hi)); k <= kmax; ++k) {
+        const double wk = w(k);
+        if (wk >= best) break;
+        if (j - k >= lo) best = fmin(best, f(j - k) + wk);
+        if (j + k <= hi) best = fmin(best, f(j + k) + wk);
+    }
+    return best;
+}
+
+// ---- pass along a strided axis.  Element j of line (o, c) is at o * ostride + c + j * stride, c in [0, inner) contiguous: y: o = x,
+// inner = Z, stride = Z; x: one o, inner = Y * Z, stride = Y * Z.  A workgroup takes slab after slab of EDT_TZ consecutive c and, in
+// two-class mode, the two fields one after the other through the same LDS.  Work item e = j * 16 + z: a wave is 4 neighbouring j x 16 z
+// (similar trip counts, conflict-free 512-byte LDS rows).  lo[z] / hi[z]: the range of finite f of line z of the slab - after the z pass
+// most lines of a volume with a small label have none, and without the range every element of such a line would walk all of it.
+// LAST: write sqrt; in two-class mode only where the voxel is of the field's class.
+template <int NMAX, bool LAST>
+__global__ __launch_bounds__(NMAX) void k_edt_line(const double* __restrict__ src0, const double* __restrict__ src1, double* __restrict__ dst0,
+                                                   double* __restrict__ dst1, const uint8_t* __restrict__ mask, int nf, int64_t outer,
+                                                   int64_t ostride, int64_t inner, int64_t stride, int n, double s) {
+    __shared__ double f[NMAX * EDT_TZ];
+    __shared__ double w[NMAX];
+    __shared__ int lo[EDT_TZ], hi[EDT_TZ];
+    for (int k = threadIdx.x; k < n; k += blockDim.x) w[k] = edt_w(k, s);
+    const int64_t spo = (inner + EDT_TZ - 1) / EDT_TZ;
+    const int cnt = n * EDT_TZ;
+    for (int64_t slab = blockIdx.x; slab < outer * spo; slab += gridDim.x) {
+        const int64_t c0 = (slab % spo) * EDT_TZ;
+        const int64_t base = (slab / spo) * ostride + c0;
+        const int tz = (int)min((int64_t)EDT_TZ, inner - c0);
+        for (int fld = 0; fld < nf; ++fld) {
+            const double* const src = fld ? src1 : src0;
+            double* const dst = (LAST || !fld) ? dst0 : dst1;
+            __syncthreads();                                   // w is written / the previous round's reads of f, lo, hi are done
+            if (threadIdx.x < EDT_TZ) lo[threadIdx.x] = n, hi[threadIdx.x] = -1;
+            int mylo = n, myhi = -1;                           // blockDim is a multiple of 16: a thread stays on one z, its j ascend
+            for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
+                const int z = e % EDT_TZ, j = e / EDT_TZ;
+                if (z >= tz) continue;
+                const double v = src[base + (int64_t)j * stride + z];
+                f[e] = v;
+                if (v < (double)INFINITY) mylo = min(mylo, j), myhi = j;
+            }
+            __syncthreads();
+            if (myhi >= 0) atomicMin(&lo[threadIdx.x % EDT_TZ], mylo), atomicMax(&hi[threadIdx.x % EDT_TZ], myhi);
+            __syncthreads();
+            for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
+                const int z = e % EDT_TZ, j = e / EDT_TZ;
+                if (z >= tz) continue;
+                const int64_t at = base + (int64_t)j * stride + z;
+                if (LAST && nf == 2 && (mask[at] != 0) != (fld == 0)) continue;
+                const double best = edt_walk(j, lo[z], hi[z], [&](int i) { return f[i * EDT_TZ + z]; }, [&](int k) { return w[k]; });
+                dst[at] = LAST ? sqrt(best) : best;
+            }
+        }
+    }
+}
+
+// ---- the slow, always applicable pass: one thread per voxel, the same walk on global memory.  FIRST: the source is the mask itself
+// (field 0: f0 = mask ? inf : 0, field 1: the complement).
+template <bool FIRST, bool LAST>
+__global__ void k_edt_line_global(const void* __restrict__ src, double* __restrict__ dst, const uint8_t* __restrict__ mask, int fld, int two,
+                                  int X, int Y, int Z, int axis, double s) {
+    const int64_t total = (int64_t)X * Y * Z;
+    const int n = axis == 0 ? X : (axis == 1 ? Y : Z);
+    const int64_t stride = axis == 0 ? (int64_t)Y * Z : (axis == 1 ? Z : 1);
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        if (LAST && two && (mask[t] != 0) != (fld == 0)) continue;
+        const int64_t q = t / Z;
+        const int j = axis == 0 ? (int)(q / Y) : (axis == 1 ? (int)(q % Y) : (int)(t % Z));
+        const int64_t base = t - (int64_t)j * stride;
+        const double best = edt_walk(j, 0, n - 1,
+            [&](int i) {
+                if (FIRST) return ((((const uint8_t*)src)[base + (int64_t)i * stride] != 0) != (fld != 0)) ? (double)INFINITY : 0.0;
+                return ((const double*)src)[base + (int64_t)i * stride];
+            },
+            [&](int k) { return edt_w(k, s); });
+        dst[t] = LAST ? sqrt(best) : best;
+    }
+}
+
+template <bool LAST>
+void launch_line(const double* s0, const double* s1, double* d0, double* d1, const uint8_t* mask, int nf, int X, int Y, int Z, int axis, double s,
+                 hipStream_t st) {
+    const int n = axis == 0 ? X : Y;
+    const int64_t total = (int64_t)X * Y * Z;
+    if (n > EDT_LDS_MAX) {
+        const int grid = grid_for(total, 256, 8192);
+        k_edt_line_global<false, LAST><<<grid, 256, 0, st>>>(s0, d0, mask, 0, nf == 2, X, Y, Z, axis, s);
+        if (nf == 2) k_edt_line_global<false, LAST><<<grid, 256, 0, st>>>(s1, LAST ? d0 : d1, mask, 1, 1, X, Y, Z, axis, s);
+        return;
+    }
+    const int64_t outer = axis == 0 ? 1 : X, inner = axis == 0 ? (int64_t)Y * Z : Z, stride = inner, ostride = (int64_t)Y * Z;
+    const int64_t slabs = outer * ceil_div64(inner, EDT_TZ);
+    const int grid = (int)(slabs < 65536 ? slabs : 65536);
+    if (n <= 256) k_edt_line<256, LAST><<<grid, 256, 0, st>>>(s0, s1, d0, d1, mask, nf, outer, ostride, inner, stride, n, s);
+    else if (n <= 512) k_edt_line<512, LAST><<<grid, 512, 0, st>>>(s0, s1, d0, d1, mask, nf, outer, ostride, inner, stride, n, s);
+    else k_edt_line<1024, LAST><<<grid, 1024, 0, st>>>(s0, s1, d0, d1, mask, nf, outer, ostride, inner, stride, n, s);
+}
+
+// the three passes; a0/a1 = the fields after z, b0/b1 after y (two-class: a0 = out, the rest scratch; one class: a0 = out, b0 = scratch)
+int edt_run(const uint8_t* mask, double* out, double* scratch, int X, int Y, int Z, double sx, double sy, double sz, int nf, hipStream_t st) {
+    const int64_t total = (int64_t)X * Y * Z, rows = (int64_t)X * Y;
+    double* const a0 = out;
+    double* const a1 = nf == 2 ? scratch : nullptr;
+    double* const b0 = nf == 2 ? scratch + total : scratch;
+    double* const b1 = nf == 2 ? scratch + 2 * total : nullptr;
+    if (Z > EDT_LDS_MAX) {
+        const int grid = grid_for(total, 256, 8192);
+        k_edt_line_global<true, false><<<grid, 256, 0, st>>>(mask, a0, mask, 0, nf == 2, X, Y, Z, 2, sz);
+        if (nf == 2) k_edt_line_global<true, false><<<grid, 256, 0, st>>>(mask, a1, mask, 1, 1, X, Y, Z, 2, sz);
+    } else {
+        int pitch = (Z + 1) & ~1;
+        if (!((pitch >> 1) & 1)) pitch += 2;
+        int R = EDT_ZTILE / pitch;
+        if (R > 256) R = 256;
+        const int64_t tiles = ceil_div64(rows, R);
+        const int grid = (int)(tiles < 65536 ? tiles : 65536);
+        if (nf == 2) k_edt_z<true><<<grid, 256, 0, st>>>(mask, a0, a1, rows, Z, sz, R, pitch);
+        else k_edt_z<false><<<grid, 256, 0, st>>>(mask, a0, nullptr, rows, Z, sz, R, pitch);
+    }
+    FMRI_LAUNCH_CHECK();
+    launch_line<false>(a0, a1, b0, b1, mask, nf, X, Y, Z, 1, sy, st);
+    FMRI_LAUNCH_CHECK();
+    launch_line<true>(b0, b1, out, nullptr, mask, nf, X, Y, Z, 0, sx, st);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+bool edt_args_ok(const uint8_t* mask, const double* out, const double* scratch, int X, int Y, int Z, double sx, double sy, double sz) {
+    return mask && out && scratch && X > 0 && Y > 0 && Z > 0 && sx > 0 && sy > 0 && sz > 0 && isfinite(sx) && isfinite(sy) && isfinite(sz);
+}
+
+}  // namespace
+
+extern "C" int fmri_edt_lds_max_line(void) { return EDT_LDS_MAX; }
+
+extern "C" int fmri_edt_u8(const uint8_t* mask, double* out, double* scratch, int X, int Y, int Z, double sx, double sy, double sz,
+                           fmri_stream_t stream) {
+    if (!edt_args_ok(mask, out, scratch, X, Y, Z, sx, sy, sz)) return FMRI_E_SHAPE;
+    return edt_run(mask, out, scratch, X, Y, Z, sx, sy, sz, 1, as_stream(stream));
+}
+
+extern "C" int fmri_edt_two_class_u8(const uint8_t* mask, double* out, double* scratch, int X, int Y, int Z, double sx, double sy, double sz,
+                                     fmri_stream_t stream) {
+    if (!edt_args_ok(mask, out, scratch, X, Y, Z, sx, sy, sz)) return FMRI_E_SHAPE;
+    return edt_run(mask, out, scratch, X, Y, Z, sx, sy, sz, 2, as_stream(stream));
 }

@@ -9,7 +9,13 @@ into the batch tensors, then the elementwise intensity passes.  The generator yi
 layouts ((N,1,X,Y,Z) / (N,X,Y,C) float32 images, uint8 labels); Model.train_on_batch / fit_generator take them as they are.
 A data file with a non-empty `mask` array (the distance masks of the mask-weighted loss, reference generator.py:18-21) makes the generator
 yield ([x, masks], y) like the reference's convert_data (generator.py:397-401): the mask patch is sampled like the labels (nearest, outside
-= 0, same transformation) at the label slices.  As in the reference the masks are NOT padded with the volumes.
+= 0, same transformation) at the label slices.  As in the reference the masks of a FILE are not padded with the volumes.
+`distance_masks=sampling` makes the masks at load time instead, for a file that has none: the exact Euclidean distance of every voxel
+to the nearest voxel of the other class (fetal_net/utils/create_distance_masks.py, csrc/postprocess.hip), computed on the device from the
+PADDED label volume - the grid the sampler draws its corners on, so mask and labels line up voxel for voxel and no crop leaves the mask.
+The padding is background.  It changes no background voxel's distance (it adds no foreground), and no foreground voxel's as long as
+the labels do not touch the volume's border: a padded voxel clamped to the original extent is a border voxel, background as well, and
+no farther along any axis.  Labels that do touch the border see the padding as background there - as the sampled label patches do.
 
 `device_data_generator` keeps the keyword arguments of the reference's `data_generator` (generator.py:222-225).
 Applied augmenters: flip, scale, iso_scale, rotate, translate, piecewise_affine, elastic_transform (imgaug), contrast,
@@ -38,9 +44,11 @@ _UNSUPPORTED = ()                          # every augmenter of reference augmen
 
 class DeviceDataFile(object):
     """The volumes of a data file, padded as the reference pads them for training (generator.py:13-57: DataFileDummy with
-    `samples_pad`, then pad_samples), resident in HBM: .data[i] float32 (X,Y,Z), .truth[i] uint8 (X,Y,Z), .stats min / max."""
+    `samples_pad`, then pad_samples), resident in HBM: .data[i] float32 (X,Y,Z), .truth[i] uint8 (X,Y,Z), .stats min / max.
+    .mask[i] float32: the file's masks (unpadded), or with `distance_masks` (a voxel spacing per axis, or True for the reference's
+    (0.4, 0.4, 3.0)) the distance mask of the padded labels, made on the device; None when there are neither."""
 
-    def __init__(self, data_file, patch_shape, samples_pad=3, truth_downsample=None, indices=None, device="cuda"):
+    def __init__(self, data_file, patch_shape, samples_pad=3, truth_downsample=None, indices=None, device="cuda", distance_masks=None):
         import torch
         ds = truth_downsample or 1
         root = data_file.root
@@ -48,10 +56,17 @@ class DeviceDataFile(object):
         self.indices = list(range(n)) if indices is None else list(indices)
         self.data, self.truth, self.min, self.max, self.mask = {}, {}, {}, {}, None
         if hasattr(root, "mask") and root.mask is not None and len(root.mask):
+            if distance_masks is not None:
+                raise ValueError("the data file already has masks: distance_masks would replace them")
             self.mask = {}
+        elif distance_masks is not None:
+            from .utils.create_distance_masks import sampling as default_sampling
+            from fmri_hip import ops
+            spacing = default_sampling if distance_masks is True else distance_masks
         self.subject_ids = [s for s in root.subject_ids] if hasattr(root, "subject_ids") else None
         out_shape = [patch_shape[0] // ds, patch_shape[1] // ds, 1]
         padding = np.ceil(np.subtract(patch_shape, out_shape) / 2).astype(int)
+        made = {}
         for i in self.indices:
             d = np.asarray(root.data[i])
             t = np.asarray(root.truth[i])
@@ -69,6 +84,10 @@ class DeviceDataFile(object):
             self.min[i], self.max[i] = dmin, dmax
             if self.mask is not None:
                 self.mask[i] = torch.from_numpy(np.ascontiguousarray(np.asarray(root.mask[i]), dtype=np.float32)).to(device)
+            elif distance_masks is not None:
+                made[i] = ops.distance_mask_u8((self.truth[i] != 0).to(torch.uint8), spacing).float()
+        if distance_masks is not None:
+            self.mask = made
         self.device = device
         self._mask_edge = {}
 
@@ -382,11 +401,14 @@ class _Sampler(object):
 def device_data_generator(data_file, index_list, batch_size=1, n_labels=1, labels=None, augment=None, patch_shape=None,
                           shuffle_index_list=True, skip_blank=True, truth_index=-1, truth_size=1, truth_downsample=None, truth_crop=True,
                           categorical=True, prev_truth_index=None, prev_truth_size=None, drop_easy_patches=False, is3d=False,
-                          samples_pad=3, strict=False, noise_seed=0, device="cuda", prefetch=0, batched=True):
+                          samples_pad=3, strict=False, noise_seed=0, device="cuda", prefetch=0, batched=True, distance_masks=None):
     """Endless generator of (x, y) CUDA tensors.  `data_file`: a DeviceDataFile, or anything with .root.data / .root.truth
     (uploaded here).  3-D: x (N,1,X,Y,Z), y (N,1,X,Y,truth_size); 2-D: x (N,X,Y,C), y (N,X,Y,truth_size).  skip_blank and
     drop_easy_patches read one scalar back per patch (they decide on the host whether the patch is kept), everything else is
     enqueue-only.
+
+    distance_masks (None | True | spacing per axis): for a data file without masks, make the distance masks of the mask-weighted loss on
+    the device when the volumes are uploaded (DeviceDataFile) and yield ([x, masks], y); a DeviceDataFile handed in was built with its own.
 
     batched: launch the patches of a batch together, one launch per step of the sampling / augmentation chain (the default; configurations
     the batch kernels do not cover go patch by patch on their own); False: always patch by patch - same draws, same batches.
@@ -408,7 +430,8 @@ def device_data_generator(data_file, index_list, batch_size=1, n_labels=1, label
     if patch_shape is None:
         raise ValueError("the device generator samples patches; patch_shape is required")
     ddf = data_file if isinstance(data_file, DeviceDataFile) else DeviceDataFile(data_file, patch_shape, samples_pad, truth_downsample,
-                                                                                 indices=sorted(set(index_list)), device=device)
+                                                                                 indices=sorted(set(index_list)), device=device,
+                                                                                 distance_masks=distance_masks)
     sampler = _Sampler(ddf, patch_shape, augment, truth_index, truth_size, prev_truth_index, prev_truth_size, strict, noise_seed)
     sampler.batched = bool(batched)
     index_generator = random_list_generator(index_list) if shuffle_index_list else list_generator(index_list)

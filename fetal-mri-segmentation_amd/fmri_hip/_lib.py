@@ -71,6 +71,9 @@ SIGNATURES = {
     "fmri_threshold_f64": [p, p, i64, C.c_double, p],
     "fmri_fill_holes_step": [p, p, p, i32, i32, i32, i32, i32, p, p],
     "fmri_largest_component_step": [p, p, p, p, p, i32, i32, i32, i32, i32, p, p],
+    "fmri_edt_lds_max_line": [],
+    "fmri_edt_u8": [p, p, p, i32, i32, i32, C.c_double, C.c_double, C.c_double, p],
+    "fmri_edt_two_class_u8": [p, p, p, i32, i32, i32, C.c_double, C.c_double, C.c_double, p],
     "fmri_add": [p, p, p, i64, i32, p],
     "fmri_act_bwd": [p, p, p, i32, f32, i64, i32, p],
     "fmri_slice_channels": [p, i32, i32, p, i32, i64, i32, i32, p],

@@ -745,6 +745,45 @@ def largest_component_u8(mask):
     return out
 
 
+def _edt_sampling(sampling):
+    import numpy as np
+    if sampling is None:
+        return (1.0, 1.0, 1.0)
+    sp = [float(sampling)] * 3 if np.isscalar(sampling) else [float(v) for v in sampling]     # a scalar is broadcast, as scipy does
+    if len(sp) != 3 or not all(v > 0 and np.isfinite(v) for v in sp):
+        raise ValueError("sampling: one positive number, or one per axis of the 3-D volume (got %r)" % (sampling,))
+    return tuple(sp)
+
+
+def _edt(mask, sampling, two_class):
+    _need_cuda(mask)
+    assert mask.dtype == torch.uint8 and mask.dim() == 3
+    X, Y, Z = mask.shape
+    sx, sy, sz = _edt_sampling(sampling)
+    out = torch.empty(mask.shape, dtype=torch.float64, device=mask.device)
+    if mask.numel() == 0:
+        return out
+    scratch = torch.empty((3 if two_class else 1) * mask.numel(), dtype=torch.float64, device=mask.device)
+    name = "fmri_edt_two_class_u8" if two_class else "fmri_edt_u8"
+    with torch.cuda.device(mask.device):
+        check(getattr(lib(), name)(_p(mask), _p(out), _p(scratch), X, Y, Z, sx, sy, sz, _s()), name)
+    return out
+
+
+def distance_transform_edt_u8(mask, sampling=None):
+    """scipy.ndimage.distance_transform_edt(mask, sampling) of a uint8 device volume [X,Y,Z] (nonzero = foreground) -> float64 device
+    tensor: the distance of every foreground voxel to the nearest zero voxel, 0 on zero voxels.  Identical to scipy with unit spacing,
+    within a few ulp otherwise (csrc/postprocess.hip).  A volume without a zero voxel gives +inf everywhere."""
+    return _edt(mask, sampling, False)
+
+
+def distance_mask_u8(truth, sampling=None):
+    """edt(truth) + edt(1 - truth) - the distance of every voxel to the nearest voxel of the other class, the reference's distance mask
+    (fetal_net/utils/create_distance_masks.py) - with both fields carried through one set of passes.  +inf everywhere when the volume
+    holds a single class."""
+    return _edt(truth, sampling, True)
+
+
 # ---------------------------------------------------------------------------------------------------- discriminator head (discriminator.hip)
 def avgpool_fwd(x, y, planar=False):
     """x [N,D,H,W,C] -> y [N,D//2,H//2,W//2,C] (planar: [N,D,H//2,W//2,C]); AveragePooling3D() / AveragePooling2D()"""

@@ -483,6 +483,23 @@ int fmri_fill_holes_step(const uint8_t* mask, uint8_t* reached, uint8_t* out, in
 int fmri_largest_component_step(const uint8_t* mask, int32_t* labels, int32_t* counts, unsigned long long* best, uint8_t* out, int X, int Y,
                                 int Z, int phase, int sweeps, int* changed, fmri_stream_t stream);
 
+/* ---- exact Euclidean distance transform of a label volume [X][Y][Z] (uint8, z contiguous) with per-axis voxel spacing, fp64: the distance
+ * masks of the mask-weighted loss (reference fetal_net/utils/create_distance_masks.py: scipy.ndimage.distance_transform_edt(mask,
+ * sampling) + distance_transform_edt(1 - mask, sampling)).  Separable min-plus passes on squared distances along z, y, x with separately
+ * rounded products and sums, square root in the last pass: identical to scipy with unit spacing, within a few ulp otherwise.
+ * fmri_edt_u8: out[v] = distance of a nonzero voxel to the nearest zero voxel, 0 on zero voxels (scipy's definition); scratch = X*Y*Z
+ *   doubles.
+ * fmri_edt_two_class_u8: out[v] = distance to the nearest voxel of the other class (= edt(mask) + edt(1 - mask)), both fields carried
+ *   through the same three launches; scratch = 3*X*Y*Z doubles.
+ * Degenerate input: no zero voxel -> +inf everywhere (scipy returns numbers that are not distances there); two-class form with a single
+ *   class -> +inf everywhere; fmri_edt_u8 without a nonzero voxel -> 0.  Any X, Y, Z >= 1; spacings > 0 and finite.  out, scratch and mask
+ *   must not overlap.
+ * fmri_edt_lds_max_line: the longest line (1024) the LDS kernels take; a longer axis runs a slower pass on global memory, same result. */
+int fmri_edt_lds_max_line(void);
+int fmri_edt_u8(const uint8_t* mask, double* out, double* scratch, int X, int Y, int Z, double sx, double sy, double sz, fmri_stream_t stream);
+int fmri_edt_two_class_u8(const uint8_t* mask, double* out, double* scratch, int X, int Y, int Z, double sx, double sy, double sz,
+                          fmri_stream_t stream);
+
 /* ---- PatchGAN discriminator head and the adversarial coupling.  Reference
  * fetal_net/model/discriminator/all_dis_3d.py:11-72 (conv blocks of the segmentation path's layer kinds + AveragePooling3D,
  * GlobalAveragePooling3D, Dense(128, LeakyReLU) x fc_layers, Dense(1, 'sigmoid'), loss binary_crossentropy, metric 'mae') and
