@@ -451,3 +451,289 @@ extern "C" int fmri_edt_two_class_u8(const uint8_t* mask, double* out, double* s
     if (!edt_args_ok(mask, out, scratch, X, Y, Z, sx, sy, sz)) return FMRI_E_SHAPE;
     return edt_run(mask, out, scratch, X, Y, Z, sx, sy, sz, 2, as_stream(stream));
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// scipy.ndimage's quadratic / cubic B-spline resampling on the device, fp64 (ndimage.zoom / rotate / affine_transform with
+// mode='constant': the resolution change and its inverse of fetal_net.pipeline.Zoom, the in-plane rotations of predict_augment), and the
+// voxel-wise median over a stack of test-time variants.  The arithmetic is scipy's C code restated (ni_splines.c, ni_interpolation.c),
+// every product and sum separately rounded:
+//   prefilter (spline_filter1d, mode 'mirror' - what scipy filters with for 'constant'): one pole z = sqrt(8) - 3 (order 2) or
+//     sqrt(3) - 2 (order 3); c *= (1 - z)(1 - 1/z); c[0] = (c[0] + z^(n-1) c[n-1] + sum_{i=1..n-2} z^i (c[i] + z^(n-1) c[n-1-i])) /
+//     (1 - z^(2n-2)); c[i] += z c[i-1]; c[n-1] = (z c[n-2] + c[n-1]) z / (z^2 - 1); c[i] = z (c[i+1] - c[i]).  One lane owns one line.
+//     Strided axes: consecutive lanes sit on consecutive z, so every step of the recursion reads and writes a coalesced row.  The
+//     contiguous axis: a [rows x Z] tile in LDS (coalesced both ways), one lane per row; the row pitch is an odd number of doubles, so
+//     the 32 lanes of a half wave, all at the same z of 32 rows, hit 32 different 8-byte bank pairs.  The tile is 72 KiB: two workgroups
+//     per CU.  A contiguous line longer than SPL_LDS_MAX runs the strided kernel with stride 1 (uncoalesced, same result).
+//   interpolation: input coordinate c_a = ((M_a0 i + M_a1 j) + M_a2 k) + t_a; a coordinate outside [0, n_a - 1] on any axis gives cval
+//     (it decides whole voxels - a fused multiply-add here would move voxels in and out); footprint of order + 1 taps per axis from
+//     floor(c) - order/2 (odd order) or floor(c + 0.5) - order/2 (even), indices beyond the edge mirrored about the end samples, scipy's
+//     weights; value = sum over the footprint, last axis fastest, of ((v w0) w1) w2.  The spline order is a template argument per axis:
+//     weights and indices live in registers (no scratch memory).  Lanes run along the contiguous output axis; neighbouring outputs share
+//     their footprints, so most of the up to 64 gathers per output hit in cache.
+//   median: one lane per voxel, the K <= 64 values in registers (padded with +inf to 8 / 16 / 32 / 64), a fully unrolled bitonic
+//     network, the middle element or the two middle elements added and halved (np.median).  NaN is not specified.
+
+namespace {
+
+constexpr int SPL_LDS_MAX = 1024;        // longest contiguous line of the LDS kernel (at least 8 rows per tile)
+constexpr int SPL_TILE = 9216;           // doubles in the tile: 72 KiB
+
+// the recursion on one line.  first(i): element i as stored, times the gain (the gain pass of scipy folded into the first read);
+// get(i) / put(i, v): element i after it has been rewritten.  n >= 2.
+template <typename First, typename Get, typename Put>
+__device__ __forceinline__ void spline_line(int n, double z, double zn1, First first, Get get, Put put) {
+#pragma clang fp contract(off)
+    double c0 = first(0) + zn1 * first(n - 1);
+    double zi = z;
+    for (int i = 1; i < n - 1 && zi != 0.0; ++i) {          // z^i underflows to 0 after some hundred elements: the rest adds nothing
+        c0 += zi * (first(i) + zn1 * first(n - 1 - i));
+        zi *= z;
+    }
+    c0 /= 1.0 - zn1 * zn1;
+    put(0, c0);
+    double prev = c0, prev2 = c0;
+    for (int i = 1; i < n; ++i) {
+        prev2 = prev;
+        prev = first(i) + z * prev;
+        put(i, prev);
+    }
+    double next = (z * prev2 + prev) * z / (z * z - 1.0);
+    put(n - 1, next);
+    for (int i = n - 2; i >= 0; --i) {
+        next = z * (next - get(i));
+        put(i, next);
+    }
+}
+
+// line t of `lines`: element j at (t / inner) * ostride + t % inner + j * stride
+__global__ __launch_bounds__(64) void k_spline_lines(double* __restrict__ vol, int64_t lines, int64_t inner, int64_t ostride, int64_t stride, int n,
+                                                     double z, double gain, double zn1) {
+#pragma clang fp contract(off)
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < lines; t += (int64_t)gridDim.x * blockDim.x) {
+        double* const p = vol + (t / inner) * ostride + t % inner;
+        spline_line(n, z, zn1, [&](int i) { return p[i * stride] * gain; }, [&](int i) { return p[i * stride]; },
+                    [&](int i, double v) { p[i * stride] = v; });
+    }
+}
+
+__global__ __launch_bounds__(256) void k_spline_z(double* __restrict__ vol, int64_t rows, int Z, int R, int pitch, double z, double gain,
+                                                  double zn1) {
+#pragma clang fp contract(off)
+    __shared__ double tile[SPL_TILE];
+    const int64_t tiles = (rows + R - 1) / R;
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int64_t row0 = t * R;
+        const int nr = (int)min((int64_t)R, rows - row0);
+        const int64_t g0 = row0 * Z;
+        const int cnt = nr * Z;
+        for (int e = threadIdx.x; e < cnt; e += blockDim.x) tile[(e / Z) * pitch + e % Z] = vol[g0 + e] * gain;
+        __syncthreads();
+        for (int r = threadIdx.x; r < nr; r += blockDim.x) {
+            double* const row = tile + r * pitch;
+            spline_line(Z, z, zn1, [&](int i) { return row[i]; }, [&](int i) { return row[i]; }, [&](int i, double v) { row[i] = v; });
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < cnt; e += blockDim.x) vol[g0 + e] = tile[(e / Z) * pitch + e % Z];
+        __syncthreads();
+    }
+}
+
+struct Affine12 { double m[12]; };
+
+// footprint of one axis: ORDER + 1 taps, first index and weights as scipy forms them, indices mirrored into [0, n)
+template <int ORDER>
+__device__ __forceinline__ void spline_taps(double c, int n, int (&idx)[4], double (&w)[4]) {
+#pragma clang fp contract(off)
+    const double f = (ORDER & 1) ? floor(c) : floor(c + 0.5);
+    const double y = c - f;
+    if (ORDER == 0) {
+        w[0] = 1.0;
+    } else if (ORDER == 1) {
+        w[0] = 1.0 - y;
+        w[1] = y;
+    } else if (ORDER == 2) {
+        w[0] = 0.5 * ((0.5 - y) * (0.5 - y));
+        w[1] = 0.75 - y * y;
+        w[2] = 0.5 * ((0.5 + y) * (0.5 + y));
+    } else {
+        const double u = 1.0 - y;
+        w[0] = u * u * u / 6.0;
+        w[1] = (y * y * (y - 2.0) * 3.0 + 4.0) / 6.0;
+        w[2] = (u * u * (u - 2.0) * 3.0 + 4.0) / 6.0;
+        w[3] = y * y * y / 6.0;
+    }
+    const int start = (int)f - ORDER / 2;
+    const int s2 = 2 * n - 2;
+#pragma unroll
+    for (int a = 0; a <= ORDER; ++a) {
+        int m = 0;
+        if (n > 1) {
+            m = (start + a) % s2;
+            m = m < 0 ? m + s2 : m;
+            m = m >= n ? s2 - m : m;
+        }
+        idx[a] = m;
+    }
+}
+
+template <int O0, int O1, int O2>
+__global__ __launch_bounds__(256) void k_spline_affine(const double* __restrict__ coef, int X, int Y, int Z, Affine12 A, double* __restrict__ out,
+                                                       int NX, int NY, int NZ, double cval) {
+#pragma clang fp contract(off)
+    const int64_t total = (int64_t)NX * NY * NZ;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t q = t / NZ;
+        const double k = (double)(int)(t % NZ), j = (double)(int)(q % NY), i = (double)(int)(q / NY);
+        const double c0 = ((A.m[0] * i + A.m[1] * j) + A.m[2] * k) + A.m[3];
+        const double c1 = ((A.m[4] * i + A.m[5] * j) + A.m[6] * k) + A.m[7];
+        const double c2 = ((A.m[8] * i + A.m[9] * j) + A.m[10] * k) + A.m[11];
+        if (c0 < 0.0 || c0 > (double)(X - 1) || c1 < 0.0 || c1 > (double)(Y - 1) || c2 < 0.0 || c2 > (double)(Z - 1)) {
+            out[t] = cval;
+            continue;
+        }
+        int i0[4], i1[4], i2[4];
+        double w0[4], w1[4], w2[4];
+        spline_taps<O0>(c0, X, i0, w0);
+        spline_taps<O1>(c1, Y, i1, w1);
+        spline_taps<O2>(c2, Z, i2, w2);
+        double acc = 0.0;
+#pragma unroll
+        for (int a = 0; a <= O0; ++a)
+#pragma unroll
+            for (int b = 0; b <= O1; ++b) {
+                const double* const line = coef + ((int64_t)i0[a] * Y + i1[b]) * Z;
+#pragma unroll
+                for (int c = 0; c <= O2; ++c) {
+                    double v = line[i2[c]];
+                    if (O0 > 0) v *= w0[a];
+                    if (O1 > 0) v *= w1[b];
+                    if (O2 > 0) v *= w2[c];
+                    acc += v;
+                }
+            }
+        out[t] = acc;
+    }
+}
+
+struct AffineLaunch {
+    const double* coef;
+    int X, Y, Z;
+    Affine12 A;
+    double* out;
+    int NX, NY, NZ;
+    double cval;
+    hipStream_t st;
+};
+template <int O0, int O1, int O2>
+void affine_go(const AffineLaunch& a) {
+    k_spline_affine<O0, O1, O2><<<grid_for((int64_t)a.NX * a.NY * a.NZ, 256, 65536), 256, 0, a.st>>>(a.coef, a.X, a.Y, a.Z, a.A, a.out, a.NX, a.NY,
+                                                                                                     a.NZ, a.cval);
+}
+template <int O0, int O1>
+void affine_pick2(int o2, const AffineLaunch& a) {
+    switch (o2) {
+        case 0: affine_go<O0, O1, 0>(a); break;
+        case 1: affine_go<O0, O1, 1>(a); break;
+        case 2: affine_go<O0, O1, 2>(a); break;
+        default: affine_go<O0, O1, 3>(a); break;
+    }
+}
+template <int O0>
+void affine_pick1(int o1, int o2, const AffineLaunch& a) {
+    switch (o1) {
+        case 0: affine_pick2<O0, 0>(o2, a); break;
+        case 1: affine_pick2<O0, 1>(o2, a); break;
+        case 2: affine_pick2<O0, 2>(o2, a); break;
+        default: affine_pick2<O0, 3>(o2, a); break;
+    }
+}
+
+// compare-exchange network on KB registers; K of them hold values, the rest +inf
+template <int KB>
+__global__ __launch_bounds__(256) void k_median_stack(const double* __restrict__ stack, int K, int64_t n, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        double v[KB];
+#pragma unroll
+        for (int k = 0; k < KB; ++k) v[k] = k < K ? stack[(int64_t)k * n + t] : (double)INFINITY;
+#pragma unroll
+        for (int size = 2; size <= KB; size <<= 1)
+#pragma unroll
+            for (int d = size >> 1; d > 0; d >>= 1)
+#pragma unroll
+                for (int a = 0; a < KB; ++a) {
+                    const int b = a ^ d;
+                    if (b > a) {
+                        const double lo = fmin(v[a], v[b]), hi = fmax(v[a], v[b]);
+                        const bool up = (a & size) == 0;
+                        v[a] = up ? lo : hi;
+                        v[b] = up ? hi : lo;
+                    }
+                }
+        double m0 = 0.0, m1 = 0.0;
+        const int k0 = (K - 1) / 2, k1 = K / 2;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+            m0 = k == k0 ? v[k] : m0;
+            m1 = k == k1 ? v[k] : m1;
+        }
+        out[t] = (m0 + m1) / 2.0;
+    }
+}
+
+}  // namespace
+
+extern "C" int fmri_spline_lds_max_line(void) { return SPL_LDS_MAX; }
+
+extern "C" int fmri_spline_filter1d_f64(double* vol, int X, int Y, int Z, int axis, int order, fmri_stream_t stream) {
+    if (!vol || X <= 0 || Y <= 0 || Z <= 0 || axis < 0 || axis > 2 || (order != 2 && order != 3)) return FMRI_E_SHAPE;
+    const int n = axis == 0 ? X : (axis == 1 ? Y : Z);
+    if (n < 2) return FMRI_OK;                               // scipy leaves a line of one sample as it is
+    const double z = order == 2 ? sqrt(8.0) - 3.0 : sqrt(3.0) - 2.0;
+    const double gain = (1.0 - z) * (1.0 - 1.0 / z), zn1 = pow(z, (double)(n - 1));
+    hipStream_t st = as_stream(stream);
+    const int64_t yz = (int64_t)Y * Z, rows = (int64_t)X * Y;
+    if (axis == 2 && Z <= SPL_LDS_MAX) {
+        const int pitch = Z | 1;
+        int R = SPL_TILE / pitch;
+        if (R > 256) R = 256;
+        const int64_t tiles = ceil_div64(rows, R);
+        k_spline_z<<<(int)(tiles < 65536 ? tiles : 65536), 256, 0, st>>>(vol, rows, Z, R, pitch, z, gain, zn1);
+    } else {
+        const int64_t lines = axis == 0 ? yz : (axis == 1 ? (int64_t)X * Z : rows);
+        const int64_t inner = axis == 0 ? yz : (axis == 1 ? Z : 1), ostride = axis == 2 ? Z : yz, stride = axis == 0 ? yz : (axis == 1 ? Z : 1);
+        k_spline_lines<<<grid_for(lines, 64, 65536), 64, 0, st>>>(vol, lines, inner, ostride, stride, n, z, gain, zn1);
+    }
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_spline_affine_f64(const double* coef, int X, int Y, int Z, const double* affine12_host, const int* orders3, double* out,
+                                      int NX, int NY, int NZ, double cval, fmri_stream_t stream) {
+    if (!coef || !affine12_host || !orders3 || !out || coef == out || X <= 0 || Y <= 0 || Z <= 0 || NX <= 0 || NY <= 0 || NZ <= 0)
+        return FMRI_E_SHAPE;
+    for (int a = 0; a < 3; ++a)
+        if (orders3[a] < 0 || orders3[a] > 3) return FMRI_E_SHAPE;
+    AffineLaunch a{coef, X, Y, Z, {}, out, NX, NY, NZ, cval, as_stream(stream)};
+    for (int e = 0; e < 12; ++e) a.A.m[e] = affine12_host[e];
+    switch (orders3[0]) {
+        case 0: affine_pick1<0>(orders3[1], orders3[2], a); break;
+        case 1: affine_pick1<1>(orders3[1], orders3[2], a); break;
+        case 2: affine_pick1<2>(orders3[1], orders3[2], a); break;
+        default: affine_pick1<3>(orders3[1], orders3[2], a); break;
+    }
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_median_stack_f64(const double* stack, int K, int64_t n, double* out, fmri_stream_t stream) {
+    if (!stack || !out || K < 1 || K > 64 || n <= 0) return FMRI_E_SHAPE;
+    hipStream_t st = as_stream(stream);
+    const int grid = grid_for(n, 256, 65536);
+    if (K <= 8) k_median_stack<8><<<grid, 256, 0, st>>>(stack, K, n, out);
+    else if (K <= 16) k_median_stack<16><<<grid, 256, 0, st>>>(stack, K, n, out);
+    else if (K <= 32) k_median_stack<32><<<grid, 256, 0, st>>>(stack, K, n, out);
+    else k_median_stack<64><<<grid, 256, 0, st>>>(stack, K, n, out);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}

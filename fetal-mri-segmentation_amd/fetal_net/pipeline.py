@@ -6,15 +6,18 @@
     VolumePipeline a first Stage over the whole volume and, optionally, a second Stage over the padded bounding box of the first mask
 
 Each resampling applied on the way in is pushed on a stack and undone in reverse on the way out, so the prediction always comes back on
-the voxel grid of the input.  Only the model work runs on the device (the tile loop behind `patch_wise_prediction`, the TTA variants,
-the mask clean-up when `postprocess_prediction` takes its device path); windowing, normalisation, zoom, crop and paste are
-once-per-volume host passes.  File I/O is the caller's (`fetal_net.utils.nifti`).  `predict_volume(...)` keeps the keyword surface of
-the reference's `main()` for callers that want the one-call form.
+the voxel grid of the input.  On the device run the model work (the tile loop behind `patch_wise_prediction`, the TTA variants, the
+mask clean-up when `postprocess_prediction` takes its device path) and, when a GPU and the HIP library are there, the volume-sized
+resampling arithmetic: the spline zoom of `Zoom` in both directions and the median over the TTA variants (`fmri_hip.ops.zoom_f64`,
+`median_stack_f64`: scipy's and numpy's own arithmetic in float64, tests/test_gpu_resample.py).  The pipeline around them is numpy, so
+each of these calls still uploads its input and downloads its result; windowing (`np.percentile`), normalisation, border, crop and paste
+are once-per-volume host passes.  File I/O is the caller's (`fetal_net.utils.nifti`).  `predict_volume(...)` keeps the keyword surface
+of the reference's `main()` for callers that want the one-call form.
 """
 import numpy as np
 from scipy import ndimage
 
-from .postprocess import postprocess_prediction
+from .postprocess import _device_ok, postprocess_prediction
 from .prediction import patch_wise_prediction, predict_augment, predict_flips
 from .utils.cut_relevant_areas import check_bounding_box, find_bounding_box
 
@@ -52,21 +55,54 @@ class Resampling(object):
         raise NotImplementedError
 
 
+def _use_device(arr, device):
+    """the `device=` convention of postprocess_prediction for arrays with three trailing spatial axes: None = the device path when a
+    GPU and the library are there and the array is float64; True / False force one"""
+    if device is None:
+        return isinstance(arr, np.ndarray) and arr.ndim >= 3 and arr.size > 0 and _device_ok(arr[(0,) * (arr.ndim - 3)])
+    return bool(device)
+
+
+def _on_device(fn, arr):
+    import torch
+    return fn(torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float64)).cuda()).cpu().numpy()
+
+
+def median_of_variants(variants, device=None):
+    """np.median(variants, axis=0) of a stack [K, X, Y, Z]; on the device (same values) for K <= 64 under the `device=` rule of Zoom"""
+    variants = np.asarray(variants)
+    if variants.ndim == 4 and 1 <= variants.shape[0] <= 64 and _use_device(variants, device):
+        from fmri_hip import ops
+        return _on_device(ops.median_stack_f64, variants)
+    return np.median(variants, axis=0)
+
+
 class Zoom(Resampling):
     """scipy zoom by per-axis factors; predictions return with `order_back` (0 for the model-specific scaling, 1 for the resolution change,
-    as the reference does at predict_nifti2.py:139-143)"""
+    as the reference does at predict_nifti2.py:139-143).  device=None: `fmri_hip.ops.zoom_f64` (scipy's arithmetic on the device) when a
+    GPU and the library are there and the array is float64 with three trailing spatial axes, else scipy; True / False force one."""
 
-    def __init__(self, factors, order_back):
+    def __init__(self, factors, order_back, device=None):
         self.factors = [float(f) for f in np.broadcast_to(factors, (3,))]
         self.order_back = order_back
+        self.device = device
 
     def forward(self, vol):
+        if np.ndim(vol) == 3 and _use_device(vol, self.device):
+            from fmri_hip import ops
+            return _on_device(lambda v: ops.zoom_f64(v, self.factors, order=3), vol)
         return ndimage.zoom(vol, self.factors)
 
     def backward(self, pred):
         # leading axes (a stack of TTA variants) are left alone
+        back = [1.0 / f for f in self.factors]
+        if _use_device(pred, self.device):
+            from fmri_hip import ops
+            flat = pred.reshape((-1,) + pred.shape[-3:])
+            out = [_on_device(lambda v: ops.zoom_f64(v, back, order=self.order_back), one) for one in flat]
+            return np.stack(out).reshape(pred.shape[:-3] + out[0].shape)
         lead = [1.0] * (pred.ndim - 3)
-        return ndimage.zoom(pred, lead + [1.0 / f for f in self.factors], order=self.order_back)
+        return ndimage.zoom(pred, lead + back, order=self.order_back)
 
 
 class Border(Resampling):
@@ -100,9 +136,10 @@ class Box(Resampling):
 class Stage(object):
     """One model of the pipeline and everything that belongs to it.  `config`: the model's experiment config (`patch_shape`,
     `patch_depth`, optional `scale_data`, optional callable `preproc`); `intensity`: None or a key of INTENSITY_METHODS; `norm`: None or
-    {'mean', 'std'}; `augment`: None | 'flip' (the 8 flips) | 'all' (`n_augment` random variants)."""
+    {'mean', 'std'}; `augment`: None | 'flip' (the 8 flips) | 'all' (`n_augment` random variants); `device`: where the stage's zoom
+    and the median over its variants run (None / True / False as for `Zoom`)."""
 
-    def __init__(self, model, config, intensity=None, norm=None, augment=None, n_augment=0, overlap=0.9):
+    def __init__(self, model, config, intensity=None, norm=None, augment=None, n_augment=0, overlap=0.9, device=None):
         if intensity is not None and intensity not in INTENSITY_METHODS:
             raise Exception("Unknown preprocess: {}".format(intensity))
         if augment not in (None, "flip", "all"):
@@ -110,7 +147,7 @@ class Stage(object):
         if config.get("preproc") is not None and not callable(config["preproc"]):
             raise TypeError("config['preproc'] must be a callable here (the reference looks a name up in its own fetal_net.preprocess)")
         self.model, self.config, self.intensity, self.norm = model, config, intensity, norm
-        self.augment, self.n_augment, self.overlap = augment, n_augment, overlap
+        self.augment, self.n_augment, self.overlap, self.device = augment, n_augment, overlap, device
 
     @property
     def patch(self):
@@ -121,7 +158,7 @@ class Stage(object):
         if self.intensity is not None:
             vol = INTENSITY_METHODS[self.intensity](vol)
         if resamplings is not None and self.config.get("scale_data") is not None:
-            step = Zoom(self.config["scale_data"], order_back=0)
+            step = Zoom(self.config["scale_data"], order_back=0, device=self.device)
             resamplings.append(step)
             vol = step.forward(vol)
         if resamplings is not None and self.config.get("preproc") is not None:
@@ -139,7 +176,7 @@ class Stage(object):
         else:
             return np.asarray(patch_wise_prediction(model=self.model, data=vol[np.newaxis], overlap_factor=self.overlap,
                                                     patch_shape=self.patch)).squeeze()
-        return np.asarray(variants if keep_variants else np.median(variants, axis=0)).squeeze()
+        return np.asarray(variants if keep_variants else median_of_variants(variants, self.device)).squeeze()
 
 
 def _undo(pred, resamplings):
@@ -151,10 +188,10 @@ def _undo(pred, resamplings):
 class VolumePipeline(object):
     """first Stage on the whole volume; optional second Stage on the region of interest the first one finds.  `resolution`: (xy, z) zoom
     applied before the first model and undone (order 1) on its prediction; `mask_options`: arguments of the clean-up that turns the first
-    prediction into the region-of-interest mask."""
+    prediction into the region-of-interest mask; `device`: where the resolution zoom runs (None / True / False as for `Zoom`)."""
 
-    def __init__(self, first, second=None, resolution=(1.0, 1.0), roi_padding=ROI_PADDING, mask_options=None):
-        self.first, self.second = first, second
+    def __init__(self, first, second=None, resolution=(1.0, 1.0), roi_padding=ROI_PADDING, mask_options=None, device=None):
+        self.first, self.second, self.device = first, second, device
         self.resolution = tuple(1.0 if r is None else float(r) for r in resolution)
         self.roi_padding = roi_padding
         self.mask_options = dict(gaussian_std=0.5, threshold=0.5) if mask_options is None else dict(mask_options)
@@ -165,7 +202,7 @@ class VolumePipeline(object):
         vol = volume
         xy, z = self.resolution
         if (xy, z) != (1.0, 1.0):
-            steps.append(Zoom([xy, xy, z], order_back=1))
+            steps.append(Zoom([xy, xy, z], order_back=1, device=self.device))
             vol = steps[-1].forward(vol)
         vol = self.first.intensities(vol, steps)
         seen = vol
@@ -200,15 +237,17 @@ class VolumePipeline(object):
 
 def predict_volume(data, model, config, overlap_factor=0.9, preprocess_method=None, norm_params=None, augment=None, num_augment=0,
                    model2=None, config2=None, preprocess_method2=None, norm_params2=None, augment2=None, num_augment2=0,
-                   z_scale=None, xy_scale=None, return_all_preds=False):
+                   z_scale=None, xy_scale=None, return_all_preds=False, device=None):
     """One-call form with the argument names of the reference's `main()` (predict_nifti2.py:98-160), on arrays: `data` = the volume as read
     from the NIfTI file.  Returns a dict: 'data' (the prepared volume the first model saw, before its border), 'prediction' (first stage, on
-    the input grid) and, with model2 / config2, 'mask' and 'prediction_roi' (second stage on the padded bounding box, volume-sized)."""
+    the input grid) and, with model2 / config2, 'mask' and 'prediction_roi' (second stage on the padded bounding box, volume-sized).
+    `device` (not in the reference): where the zooms and the variant medians run - None / True / False as for `Zoom`."""
     if config2 is not None and model2 is None:
         raise ValueError("config2 given without model2")
-    first = Stage(model, config, preprocess_method, norm_params, augment, num_augment, overlap_factor)
-    second = None if config2 is None else Stage(model2, config2, preprocess_method2, norm_params2, augment2, num_augment2, overlap_factor)
-    return VolumePipeline(first, second, resolution=(xy_scale, z_scale))(data, keep_variants=return_all_preds)
+    first = Stage(model, config, preprocess_method, norm_params, augment, num_augment, overlap_factor, device)
+    second = None if config2 is None else Stage(model2, config2, preprocess_method2, norm_params2, augment2, num_augment2, overlap_factor,
+                                                device)
+    return VolumePipeline(first, second, resolution=(xy_scale, z_scale), device=device)(data, keep_variants=return_all_preds)
 
 
 def secondary_prediction(mask, vol, config2, model2, preprocess_method2=None, norm_params2=None, overlap_factor=0.9, augment2=None,

@@ -303,6 +303,18 @@ def predict_flips(data, model, overlap_factor, config):
     return predictions
 
 
+def _hip_rotate_ok():
+    try:
+        import torch
+        from fmri_hip._lib import lib
+        if not torch.cuda.is_available():
+            return False
+        lib()
+        return True
+    except Exception:
+        return False
+
+
 class _TTAVariant:
     """One random test-time variant of a volume: intensity window, mirror axes, optional x/y swap, in-plane rotation angle.
     `draw` consumes numpy's global RNG in the order the reference's loop does (two window draws, the angle, three mirror coins, the
@@ -322,11 +334,16 @@ class _TTAVariant:
 
     @staticmethod
     def _rotate(vol, angle, order, reshape):
-        """scipy.ndimage.rotate(vol, angle, order=order, reshape=reshape) - on the device through fetal_net.spline_rotate (scipy's own
-        arithmetic in float64 on torch tensors, equal to 1e-12; a 160x256x256 volume takes scipy 1-2 s per rotation, 64 rotations per
-        predict_augment call) when a GPU is there, FMRI_TTA_TORCH_ROTATE=1 forces the torch form on the host, =0 scipy"""
+        """scipy.ndimage.rotate(vol, angle, order=order, reshape=reshape) - scipy's own arithmetic in float64, equal to 1e-12; a
+        160x256x256 volume takes scipy 1-2 s per rotation, 64 rotations per predict_augment call.  FMRI_TTA_TORCH_ROTATE unset or
+        'auto': the HIP kernels (fmri_hip.ops.rotate_f64) when a GPU and the library are there, else scipy; =1 forces the torch form
+        (fetal_net.spline_rotate, on the GPU when there is one, else on the host), =0 scipy"""
         mode = os.environ.get("FMRI_TTA_TORCH_ROTATE", "auto")
         import torch
+        if mode == "auto" and vol.ndim == 3 and vol.size > 0 and _hip_rotate_ok():
+            from fmri_hip import ops
+            dvol = torch.from_numpy(np.ascontiguousarray(vol, dtype=np.float64)).cuda()
+            return ops.rotate_f64(dvol, angle, order=order, reshape=reshape).cpu().numpy()
         if mode == "0" or (mode == "auto" and not torch.cuda.is_available()) or vol.ndim != 3:
             from scipy import ndimage
             return ndimage.rotate(vol, angle, order=order, reshape=reshape)

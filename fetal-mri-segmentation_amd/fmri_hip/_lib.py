@@ -74,6 +74,10 @@ SIGNATURES = {
     "fmri_edt_lds_max_line": [],
     "fmri_edt_u8": [p, p, p, i32, i32, i32, C.c_double, C.c_double, C.c_double, p],
     "fmri_edt_two_class_u8": [p, p, p, i32, i32, i32, C.c_double, C.c_double, C.c_double, p],
+    "fmri_spline_lds_max_line": [],
+    "fmri_spline_filter1d_f64": [p, i32, i32, i32, i32, i32, p],
+    "fmri_spline_affine_f64": [p, i32, i32, i32, p, p, p, i32, i32, i32, C.c_double, p],
+    "fmri_median_stack_f64": [p, i32, i64, p, p],
     "fmri_add": [p, p, p, i64, i32, p],
     "fmri_act_bwd": [p, p, p, i32, f32, i64, i32, p],
     "fmri_slice_channels": [p, i32, i32, p, i32, i64, i32, i32, p],

@@ -784,6 +784,129 @@ def distance_mask_u8(truth, sampling=None):
     return _edt(truth, sampling, True)
 
 
+# ---------------------------------------------------------------------------------------------------- spline resampling, median (postprocess.hip)
+def _vol_f64(vol):
+    _need_cuda(vol)
+    if vol.dtype != torch.float64 or vol.dim() != 3 or vol.numel() == 0:
+        raise ValueError("a non-empty float64 volume [X,Y,Z] is needed (got %s %s)" % (vol.dtype, tuple(vol.shape)))
+
+
+def spline_filter_f64(vol, order, axes=(0, 1, 2)):
+    """scipy.ndimage.spline_filter1d(., order, axis, mode='mirror') along each of `axes` (ascending, as scipy.ndimage.spline_filter runs
+    them) of a float64 device volume [X,Y,Z] -> a new tensor: the B-spline coefficients scipy interpolates with for mode='constant'.
+    Orders 0 and 1 need no filter: a copy."""
+    _vol_f64(vol)
+    if order not in (0, 1, 2, 3):
+        raise NotImplementedError("spline order %r" % (order,))
+    out = vol.clone()
+    if order > 1:
+        X, Y, Z = out.shape
+        with torch.cuda.device(out.device):
+            for axis in sorted(set(int(a) for a in axes)):
+                check(lib().fmri_spline_filter1d_f64(_p(out), X, Y, Z, axis, order, _s()), "fmri_spline_filter1d_f64")
+    return out
+
+
+def affine_transform_f64(vol, matrix, offset, output_shape, order, prefilter=True, cval=0.0, axes_orders=None):
+    """scipy.ndimage.affine_transform(vol, matrix, offset, output_shape, order=order, mode='constant', cval=cval, prefilter=prefilter) of a
+    float64 device volume [X,Y,Z] -> float64 device tensor of `output_shape`.  matrix: 3x3, or 3 numbers for a diagonal one; offset: one
+    number or 3.  axes_orders: a spline order per axis instead of `order` for all three (rotate_f64 passes (o, o, 0)); the prefilter runs
+    along the axes whose order is above 1."""
+    import ctypes
+    import numpy as np
+    _vol_f64(vol)
+    orders = [int(order)] * 3 if axes_orders is None else [int(o) for o in axes_orders]
+    if len(orders) != 3 or not all(0 <= o <= 3 for o in orders):
+        raise NotImplementedError("spline orders %r" % (orders,))
+    if len(set(o for o in orders if o > 1)) > 1:
+        raise NotImplementedError("one prefilter order per volume (got %r)" % (orders,))
+    M = np.asarray(matrix, dtype=np.float64)
+    if M.shape == (3,):
+        M = np.diag(M)
+    if M.shape != (3, 3):
+        raise ValueError("matrix: 3x3 or 3 numbers")
+    t = np.broadcast_to(np.asarray(offset, dtype=np.float64), (3,))
+    shape = tuple(int(v) for v in output_shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError("output_shape: three positive extents")
+    coef = vol
+    if prefilter and max(orders) > 1:
+        coef = spline_filter_f64(vol, max(orders), [a for a in range(3) if orders[a] > 1])
+    A = (ctypes.c_double * 12)(*np.concatenate([M, t[:, None]], axis=1).ravel())
+    O = (ctypes.c_int * 3)(*orders)
+    out = torch.empty(shape, dtype=torch.float64, device=vol.device)
+    X, Y, Z = vol.shape
+    with torch.cuda.device(vol.device):
+        check(lib().fmri_spline_affine_f64(_p(coef), X, Y, Z, ctypes.addressof(A), ctypes.addressof(O), _p(out), shape[0], shape[1], shape[2],
+                                           float(cval), _s()), "fmri_spline_affine_f64")
+    return out
+
+
+def zoom_geometry(shape, factors):
+    """output shape and per-axis coordinate ratio of scipy.ndimage.zoom(., factors) (grid_mode=False): m = int(round(n * f)) with Python's
+    round (halves to even), ratio (n - 1) / (m - 1), 1 where m == 1.  Pure host arithmetic."""
+    import numpy as np
+    shape = tuple(int(n) for n in shape)
+    f = [float(v) for v in np.broadcast_to(factors, (len(shape),))]
+    out_shape = tuple(int(round(n * v)) for n, v in zip(shape, f))
+    ratios = tuple(float(n - 1) / float(m - 1) if m > 1 else 1.0 for n, m in zip(shape, out_shape))
+    return out_shape, ratios
+
+
+def zoom_f64(vol, factors, order=3):
+    """scipy.ndimage.zoom(vol, factors, order=order) (mode 'constant', cval 0) of a float64 device volume [X,Y,Z]: a diagonal matrix of
+    the ratios and a zero offset, so the kernel forms scipy's k * ratio; prefilter along all three axes when order > 1"""
+    _vol_f64(vol)
+    out_shape, ratios = zoom_geometry(vol.shape, factors)
+    if min(out_shape) < 1:
+        raise ValueError("zoom factors %r leave no voxel of %r" % (factors, tuple(vol.shape)))
+    return affine_transform_f64(vol, ratios, 0.0, out_shape, order)
+
+
+def rotate_f64(vol, angle, order=3, reshape=True):
+    """scipy.ndimage.rotate(vol, angle, axes=(1, 0), reshape=reshape, order=order) of a float64 device volume [n0,n1,slices]: scipy rotates
+    plane by plane, i.e. prefilter along axes 0 and 1 and a single tap along the slice axis.  Matrix, output shape and offset are those
+    of fetal_net.spline_rotate.rotate (ndimage.rotate's own)."""
+    import math
+    import numpy as np
+    _vol_f64(vol)
+    n0, n1, ns = (int(v) for v in vol.shape)
+    a = np.deg2rad(angle)
+    c, s = math.cos(a), math.sin(a)
+    if angle % 360 == 0:
+        c, s = 1.0, 0.0
+    elif angle % 360 == 90:
+        c, s = 0.0, 1.0
+    elif angle % 360 == 180:
+        c, s = -1.0, 0.0
+    elif angle % 360 == 270:
+        c, s = 0.0, -1.0
+    M = np.array([[c, s], [-s, c]])
+    in_shape = np.array([n0, n1])
+    if reshape:
+        bounds = M @ np.array([[0, 0, n0, n0], [0, n1, 0, n1]], dtype=np.float64)
+        out_shape = (np.ptp(bounds, axis=1) + 0.5).astype(int)
+    else:
+        out_shape = in_shape
+    offset = (in_shape - 1) / 2.0 - M @ ((out_shape - 1) / 2.0)
+    M3 = np.eye(3)
+    M3[:2, :2] = M
+    return affine_transform_f64(vol, M3, [offset[0], offset[1], 0.0], (int(out_shape[0]), int(out_shape[1]), ns), order,
+                                axes_orders=(order, order, 0))
+
+
+def median_stack_f64(stack):
+    """np.median(stack, axis=0) of a float64 device stack [K, ...], 1 <= K <= 64, finite values -> float64 device tensor"""
+    _need_cuda(stack)
+    if stack.dtype != torch.float64 or stack.dim() < 2 or stack.numel() == 0:
+        raise ValueError("a non-empty float64 stack [K, ...] is needed (got %s %s)" % (stack.dtype, tuple(stack.shape)))
+    K = int(stack.shape[0])
+    out = torch.empty(stack.shape[1:], dtype=torch.float64, device=stack.device)
+    with torch.cuda.device(stack.device):
+        check(lib().fmri_median_stack_f64(_p(stack), K, out.numel(), _p(out), _s()), "fmri_median_stack_f64")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- discriminator head (discriminator.hip)
 def avgpool_fwd(x, y, planar=False):
     """x [N,D,H,W,C] -> y [N,D//2,H//2,W//2,C] (planar: [N,D,H//2,W//2,C]); AveragePooling3D() / AveragePooling2D()"""

@@ -500,6 +500,25 @@ int fmri_edt_u8(const uint8_t* mask, double* out, double* scratch, int X, int Y,
 int fmri_edt_two_class_u8(const uint8_t* mask, double* out, double* scratch, int X, int Y, int Z, double sx, double sy, double sz,
                           fmri_stream_t stream);
 
+/* ---- scipy.ndimage's B-spline resampling of a contiguous fp64 volume [X][Y][Z] (ndimage.zoom / rotate / affine_transform with
+ * mode='constant', orders 0-3) and the voxel-wise median of a stack: the once-per-volume passes around whole-volume prediction (reference
+ * prod/predict_nifti2.py:98-160, fetal_net/prediction.py:25-62).  scipy's own arithmetic, every product and sum separately rounded.
+ * fmri_spline_filter1d_f64: scipy.ndimage.spline_filter1d(vol, order, axis, mode='mirror') in place, order 2 or 3 (one pole: sqrt(8) - 3
+ *   or sqrt(3) - 2); a line of one sample is left as it is.  The contiguous axis runs through an LDS tile up to
+ *   fmri_spline_lds_max_line() (1024) samples per line, a longer one on global memory with the same result.
+ * fmri_spline_affine_f64: out[i][j][k] ([NX][NY][NZ]) = the spline through the coefficients `coef` at c = M (i, j, k) + t, with
+ *   affine12_host = the 12 doubles of [M | t], row-major 3x4, in HOST memory, read at enqueue; c_a = ((M_a0 i + M_a1 j) + M_a2 k) + t_a.
+ *   c_a < 0 or c_a > n_a - 1 on any axis -> cval.  orders3 (host): the spline order of each axis, 0-3 (scipy has one order; an order-0
+ *   axis with an identity row is scipy's plane-by-plane form of rotate): order + 1 taps from floor(c) - order/2 (odd) or
+ *   floor(c + 0.5) - order/2 (even), indices beyond the edge mirrored about the end samples.  coef != out.
+ * fmri_median_stack_f64: out[v] = median of stack[k * n + v], k < K, 1 <= K <= 64 (else FMRI_E_SHAPE); even K: the two middle values
+ *   added, then halved (np.median).  The values must not be NaN: the result is unspecified if one is. */
+int fmri_spline_lds_max_line(void);
+int fmri_spline_filter1d_f64(double* vol, int X, int Y, int Z, int axis, int order, fmri_stream_t stream);
+int fmri_spline_affine_f64(const double* coef, int X, int Y, int Z, const double* affine12_host, const int* orders3, double* out, int NX,
+                           int NY, int NZ, double cval, fmri_stream_t stream);
+int fmri_median_stack_f64(const double* stack, int K, int64_t n, double* out, fmri_stream_t stream);
+
 /* ---- PatchGAN discriminator head and the adversarial coupling.  Reference
  * fetal_net/model/discriminator/all_dis_3d.py:11-72 (conv blocks of the segmentation path's layer kinds + AveragePooling3D,
  * GlobalAveragePooling3D, Dense(128, LeakyReLU) x fc_layers, Dense(1, 'sigmoid'), loss binary_crossentropy, metric 'mae') and
