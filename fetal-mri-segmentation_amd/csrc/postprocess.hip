@@ -8,7 +8,8 @@
 // ni_filters.c NI_Correlate1D symmetric branch) in fp64 with host-computed weights, so the smoothed volume - and therefore the
 // thresholded mask - is bit-identical to scipy's; hole filling and labelling are integer algorithms with scipy's default 6-connectivity,
 // and ties between equally large components go to the one scipy numbers first (smallest linear index of its first voxel).
-// Second, at the end of the file: distance_transform_edt (the distance masks of the mask-weighted loss).
+// Second: distance_transform_edt (the distance masks of the mask-weighted loss).  Third: the B-spline resampling and the variant median
+// around whole-volume prediction.  Fourth, at the end of the file: the intensity preparation in front of the model.
 #include "common.h"
 #include <math.h>
 
@@ -22,7 +23,9 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {          // scipy mod
 // T = double: the post-processing volume (bit-identical to scipy).  T = float: a training patch (skimage.filters.gaussian of the
 // augmentation chain, reference augment.py:113-114): the same sums in fp64, the result rounded once to the patch's fp32.
 // NEAREST = scipy mode 'nearest' (a a a a | a b c d | d d d d), what skimage.filters.gaussian passes; else 'reflect'.
-template <typename T, bool NEAREST>
+// ANTI = NI_Correlate1D's antisymmetric branch (weights with w[r + j] == -w[r - j]: the order-1 Gaussian of gaussian_gradient_magnitude):
+// the pairs are subtracted, x[l + jj] - x[l - jj], instead of added.
+template <typename T, bool NEAREST, bool ANTI = false>
 __global__ void k_correlate1d_sym(const T* __restrict__ src, T* __restrict__ dst, int X, int Y, int Z, int axis,
                                   const double* __restrict__ w, int radius) {
 #pragma clang fp contract(off)      // separately rounded multiply and add: scipy's C loop is compiled without fused operations
@@ -37,8 +40,10 @@ __global__ void k_correlate1d_sym(const T* __restrict__ src, T* __restrict__ dst
         const int l = axis == 0 ? x : (axis == 1 ? y : z);
         const int64_t base = t - (int64_t)l * stride;
         double acc = (double)src[t] * w[radius];
-        for (int jj = -radius; jj < 0; ++jj)
-            acc += ((double)src[base + (int64_t)at(l + jj) * stride] + (double)src[base + (int64_t)at(l - jj) * stride]) * w[jj + radius];
+        for (int jj = -radius; jj < 0; ++jj) {
+            const double lo = (double)src[base + (int64_t)at(l + jj) * stride], hi = (double)src[base + (int64_t)at(l - jj) * stride];
+            acc += (ANTI ? lo - hi : lo + hi) * w[jj + radius];
+        }
         dst[t] = (T)acc;
     }
 }
@@ -146,6 +151,14 @@ extern "C" int fmri_correlate1d_f64(const double* src, double* dst, int X, int Y
                                     fmri_stream_t stream) {
     if (!src || !dst || !weights || src == dst || X <= 0 || Y <= 0 || Z <= 0 || axis < 0 || axis > 2 || radius < 0) return FMRI_E_SHAPE;
     k_correlate1d_sym<double, false><<<grid_for((int64_t)X * Y * Z, 256, 8192), 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z, axis, weights, radius);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+extern "C" int fmri_correlate1d_asym_f64(const double* src, double* dst, int X, int Y, int Z, int axis, const double* weights, int radius,
+                                         fmri_stream_t stream) {
+    if (!src || !dst || !weights || src == dst || X <= 0 || Y <= 0 || Z <= 0 || axis < 0 || axis > 2 || radius < 0) return FMRI_E_SHAPE;
+    k_correlate1d_sym<double, false, true><<<grid_for((int64_t)X * Y * Z, 256, 8192), 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z, axis, weights,
+                                                                                                                  radius);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
@@ -734,6 +747,318 @@ extern "C" int fmri_median_stack_f64(const double* stack, int K, int64_t n, doub
     else if (K <= 16) k_median_stack<16><<<grid, 256, 0, st>>>(stack, K, n, out);
     else if (K <= 32) k_median_stack<32><<<grid, 256, 0, st>>>(stack, K, n, out);
     else k_median_stack<64><<<grid, 256, 0, st>>>(stack, K, n, out);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+// ---- Fourth: intensity preparation of a whole volume in front of the model (reference prod/predict_nifti2.py:57-74, fetal_net/preprocess.py): the
+// percentile window, scipy.ndimage.laplace, the combine step of gaussian_gradient_magnitude and the min-max / z-score maps, all on a
+// contiguous fp64 volume.  The antisymmetric 1-D correlation of the gradient is k_correlate1d_sym<., ., true> at the top of the file.
+//
+// Exactness: every kernel restates numpy's / scipy's own operation order with one rounding per operation (fp contract off; fp64 add,
+// multiply, divide and square root are correctly rounded on gfx950 and the Makefile passes no fast-math flag), so the device result is
+// the host result bit for bit.  Order statistics are exact by construction: a radix select on the bit patterns.
+namespace {
+
+// order-preserving 64-bit key of a double: negatives with all bits flipped, the others with the sign bit flipped.  Every NaN takes the
+// largest key (the pattern of a positive NaN with a full mantissa), so NaNs sort last whatever their sign, as np.sort puts them.
+constexpr unsigned long long KEY_NAN = ~0ull;
+__device__ __forceinline__ unsigned long long f64_key(double x) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    if (x != x) return KEY_NAN;
+    return (b >> 63) ? ~b : b ^ 0x8000000000000000ull;
+}
+__device__ __forceinline__ double key_f64(unsigned long long k) {
+    const unsigned long long b = (k >> 63) ? k ^ 0x8000000000000000ull : ~k;
+    return __longlong_as_double((long long)b);
+}
+
+// ---- order statistics: most-significant-digit radix select of up to 8 ranks at once.
+// State in the caller's workspace (all passes are separate launches on one stream: launch order is the only synchronisation):
+//   prefix[k]  the key bits of rank k decided so far (low bits zero)      rem[k]  rank k's position among the keys that share its prefix
+//   leader[k]  the smallest j with prefix[j] == prefix[k]: ranks that still share a prefix share ONE histogram, row leader[k] - the two
+//              ends of a percentile window part only a few digits down, and in the first pass every rank counts every voxel
+//   nan        the number of NaNs, counted in the first pass              hist[8][NB] (NB <= 2048) the global histogram of the pass
+// A pass = k_select_count (per-workgroup LDS histogram of the digit under the pass, of the keys that match a leader's prefix; its
+// non-empty bins are added to hist) then k_select_pick (one workgroup: for each rank the digit whose cumulative count passes rem, new
+// prefix / rem / leaders, hist zeroed for the next pass; the last pick writes the values).
+constexpr int SEL_MAXK = 8, SEL_MAXNB = 2048;
+struct SelState {
+    unsigned long long prefix[SEL_MAXK];
+    unsigned long long nan;
+    unsigned rem[SEL_MAXK];
+    int leader[SEL_MAXK];
+    unsigned hist[SEL_MAXK * SEL_MAXNB];
+};
+struct SelRanks {
+    unsigned r[SEL_MAXK];
+};
+
+__global__ __launch_bounds__(256) void k_select_init(SelState* __restrict__ st, SelRanks ranks, int K) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < SEL_MAXK * SEL_MAXNB; i += gridDim.x * blockDim.x) st->hist[i] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x < SEL_MAXK) {
+        const int k = threadIdx.x;
+        st->prefix[k] = 0ull;
+        st->rem[k] = k < K ? ranks.r[k] : 0u;
+        st->leader[k] = 0;                       // nothing decided yet: one histogram serves every rank
+        if (k == 0) st->nan = 0ull;
+    }
+}
+
+// hi = shift + (bits of this digit): keys match a prefix when they agree above bit `hi` (hi == 64: the first pass, every key matches)
+template <int NB, int THREADS, bool FIRST>
+__global__ __launch_bounds__(THREADS) void k_select_count(const double* __restrict__ src, int64_t n, SelState* __restrict__ st, int K, int shift,
+                                                          int hi) {
+    __shared__ unsigned h[SEL_MAXK * NB];
+    __shared__ unsigned long long s_prefix[SEL_MAXK];
+    __shared__ int s_lead[SEL_MAXK];
+    if (threadIdx.x < SEL_MAXK) {
+        s_prefix[threadIdx.x] = st->prefix[threadIdx.x];
+        s_lead[threadIdx.x] = threadIdx.x < K && st->leader[threadIdx.x] == (int)threadIdx.x ? 1 : 0;
+    }
+    __syncthreads();
+    for (int k = 0; k < K; ++k)
+        if (s_lead[k])
+            for (int b = threadIdx.x; b < NB; b += THREADS) h[k * NB + b] = 0u;
+    __syncthreads();
+    unsigned nans = 0;
+    const unsigned mask = (1u << (hi - shift)) - 1u;         // hi - shift <= log2(NB) bits in this digit
+    for (int64_t t = (int64_t)blockIdx.x * THREADS + threadIdx.x; t < n; t += (int64_t)gridDim.x * THREADS) {
+        const unsigned long long key = f64_key(src[t]);
+        if (FIRST) nans += key == KEY_NAN ? 1u : 0u;
+        const unsigned digit = (unsigned)(key >> shift) & mask;
+        for (int k = 0; k < K; ++k)
+            if (s_lead[k] && (FIRST || (key >> hi) == (s_prefix[k] >> hi))) atomicAdd(&h[k * NB + digit], 1u);
+    }
+    __syncthreads();
+    for (int k = 0; k < K; ++k)
+        if (s_lead[k])
+            for (int b = threadIdx.x; b < NB; b += THREADS) {
+                const unsigned c = h[k * NB + b];
+                if (c) atomicAdd(&st->hist[k * SEL_MAXNB + b], c);
+            }
+    if (FIRST) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) nans += __shfl_xor(nans, o);
+        if ((threadIdx.x & 63) == 0 && nans) atomicAdd(&st->nan, (unsigned long long)nans);
+    }
+}
+
+template <int NB>
+__global__ __launch_bounds__(256) void k_select_pick(SelState* __restrict__ st, int K, int shift, int last, double* __restrict__ out,
+                                                     long long* __restrict__ nan_count) {
+    constexpr int E = NB / 256;                  // bins per thread, contiguous
+    __shared__ unsigned scan[256];
+    __shared__ unsigned long long s_prefix[SEL_MAXK];
+    __shared__ unsigned s_rem[SEL_MAXK];
+    const int tid = threadIdx.x;
+    for (int lead = 0; lead < K; ++lead) {
+        if (st->leader[lead] != lead) continue;  // uniform: read from global by every thread
+        unsigned c[E], sum = 0;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            c[e] = st->hist[lead * SEL_MAXNB + tid * E + e];
+            sum += c[e];
+        }
+        scan[tid] = sum;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {      // inclusive scan of the per-thread sums
+            const unsigned v = tid >= o ? scan[tid - o] : 0u;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        const unsigned base = scan[tid] - sum;   // keys in the bins below this thread's
+        for (int k = lead; k < K; ++k) {
+            if (st->leader[k] != lead) continue;
+            const unsigned want = st->rem[k];
+            unsigned below = base;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                if (c[e] && want >= below && want - below < c[e]) {      // exactly one bin of one thread
+                    s_prefix[k] = st->prefix[k] | ((unsigned long long)(tid * E + e) << shift);
+                    s_rem[k] = want - below;
+                }
+                below += c[e];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < E; ++e) st->hist[lead * SEL_MAXNB + tid * E + e] = 0u;
+    }
+    __syncthreads();
+    if (tid < K) {
+        st->prefix[tid] = s_prefix[tid];
+        st->rem[tid] = s_rem[tid];
+        int lead = tid;
+        for (int j = tid - 1; j >= 0; --j)
+            if (s_prefix[j] == s_prefix[tid]) lead = j;
+        st->leader[tid] = lead;
+        if (last) out[tid] = key_f64(s_prefix[tid]);
+    }
+    if (last && tid == 0) *nan_count = (long long)st->nan;
+}
+
+template <int BITS>
+int select_run(const double* src, int64_t n, SelState* st, const SelRanks& ranks, int K, double* out, long long* nan_count, hipStream_t s) {
+    constexpr int NB = 1 << BITS, THREADS = BITS > 8 ? 1024 : 256;
+    k_select_init<<<16, 256, 0, s>>>(st, ranks, K);
+    const int grid = grid_for(n, THREADS, 256);              // one flush of up to K * NB atomics per workgroup and pass: one per CU
+    for (int hi = 64; hi > 0; hi -= BITS) {
+        const int shift = hi > BITS ? hi - BITS : 0;         // the last digit of the 11-bit form has 9 bits
+        if (hi == 64) k_select_count<NB, THREADS, true><<<grid, THREADS, 0, s>>>(src, n, st, K, shift, hi);
+        else k_select_count<NB, THREADS, false><<<grid, THREADS, 0, s>>>(src, n, st, K, shift, hi);
+        k_select_pick<NB><<<1, 256, 0, s>>>(st, K, shift, shift == 0 ? 1 : 0, out, nan_count);
+    }
+    return hipGetLastError() == hipSuccess ? FMRI_OK : FMRI_E_LAUNCH;
+}
+
+// ---- range of a volume: min / max through integer atomics on the ordered keys (fmin / fmax skip NaNs; they are counted instead)
+__global__ void k_minmax64_init(unsigned long long* mm, long long* nan_count) {
+    mm[0] = ~0ull;
+    mm[1] = 0ull;
+    *nan_count = 0;
+}
+__global__ __launch_bounds__(256) void k_minmax64(const double* __restrict__ x, int64_t n, unsigned long long* mm, long long* nan_count) {
+    unsigned long long lo = ~0ull, hi = 0ull;
+    unsigned nans = 0;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const double v = x[t];
+        if (v != v) {
+            ++nans;
+        } else {
+            const unsigned long long k = f64_key(v);
+            lo = k < lo ? k : lo;
+            hi = k > hi ? k : hi;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long l2 = __shfl_xor(lo, o), h2 = __shfl_xor(hi, o);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+        nans += __shfl_xor(nans, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (lo <= hi) {
+            atomicMin(&mm[0], lo);
+            atomicMax(&mm[1], hi);
+        }
+        if (nans) atomicAdd((unsigned long long*)nan_count, (unsigned long long)nans);
+    }
+}
+__global__ void k_minmax64_decode(unsigned long long* mm) {
+    const double lo = key_f64(mm[0]), hi = key_f64(mm[1]);      // no finite value at all: the initial keys decode to NaNs
+    reinterpret_cast<double*>(mm)[0] = lo;
+    reinterpret_cast<double*>(mm)[1] = hi;
+}
+
+// ---- element-wise maps, each in the host expression's own operation order
+//   FMRI_MAP_WINDOW   (min(max(x, lo), hi) - lo) * scale + out_min      np.clip's min / max: a NaN x stays, a NaN bound wins
+//   FMRI_MAP_MINMAX   -1 + (2 * (x - mn)) / (mx - mn)
+//   FMRI_MAP_ZSCORE   (x - mean) / std
+template <int KIND>
+__global__ __launch_bounds__(256) void k_intensity_map(const double* src, double* dst, int64_t n, double p0, double p1, double p2, double p3) {
+#pragma clang fp contract(off)
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const double x = src[t];
+        double y;
+        if (KIND == FMRI_MAP_WINDOW) {
+            const double a = x != x ? x : (x > p0 ? x : p0);
+            const double b = a != a ? a : (a < p1 ? a : p1);
+            y = (b - p0) * p2 + p3;
+        } else if (KIND == FMRI_MAP_MINMAX) {
+            y = -1.0 + (2.0 * (x - p0)) / (p1 - p0);
+        } else {
+            y = (x - p0) / p1;
+        }
+        dst[t] = y;
+    }
+}
+
+// scipy.ndimage.laplace, mode 'reflect': per axis correlate1d with [1, -2, 1] (NI_Correlate1D's symmetric branch, centre tap first), the
+// axes' results added in ascending order.  One thread per voxel, z fastest; the six neighbours come from cache.
+__global__ __launch_bounds__(256) void k_laplace(const double* __restrict__ src, double* __restrict__ dst, int X, int Y, int Z) {
+#pragma clang fp contract(off)
+    const int64_t total = (int64_t)X * Y * Z, sx = (int64_t)Y * Z;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int z = (int)(t % Z);
+        const int64_t q = t / Z;
+        const int y = (int)(q % Y), x = (int)(q / Y);
+        const double c = src[t];
+        const double l0 = c * -2.0 + (src[t + (int64_t)(reflect_idx(x - 1, X) - x) * sx] + src[t + (int64_t)(reflect_idx(x + 1, X) - x) * sx]) * 1.0;
+        const double l1 = c * -2.0 + (src[t + (int64_t)(reflect_idx(y - 1, Y) - y) * Z] + src[t + (int64_t)(reflect_idx(y + 1, Y) - y) * Z]) * 1.0;
+        const double l2 = c * -2.0 + (src[t + (reflect_idx(z - 1, Z) - z)] + src[t + (reflect_idx(z + 1, Z) - z)]) * 1.0;
+        dst[t] = (l0 + l1) + l2;
+    }
+}
+
+// the tail of scipy.ndimage.generic_gradient_magnitude: squares added in axis order, then the square root
+__global__ __launch_bounds__(256) void k_grad_combine(const double* d0, const double* d1, const double* d2, double* out, int64_t n) {
+#pragma clang fp contract(off)
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const double a = d0[t], b = d1[t], c = d2[t];
+        out[t] = sqrt((a * a + b * b) + c * c);
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t fmri_order_stats_workspace_bytes(void) { return (int64_t)sizeof(SelState); }
+
+extern "C" int fmri_order_stats_f64(const double* src, int64_t n, const int64_t* ranks_host, int K, double* out, int64_t* nan_count,
+                                    void* workspace, fmri_stream_t stream) {
+    if (!src || !ranks_host || !out || !nan_count || !workspace || n <= 0 || n >= ((int64_t)1 << 31) || K < 1 || K > SEL_MAXK)
+        return FMRI_E_SHAPE;
+    SelRanks ranks{};
+    for (int k = 0; k < K; ++k) {
+        if (ranks_host[k] < 0 || ranks_host[k] >= n) return FMRI_E_SHAPE;
+        ranks.r[k] = (unsigned)ranks_host[k];
+    }
+    // digit width: 6 passes of 11 bits, or 8 passes of 8 bits.  Measured on a 160x256x256 volume (tools/bench_intensity.py, which is why
+    // the switch is read per call: one process times both): 4 ranks in 0.31-0.39 ms with 11 bits, 1.0-1.07 ms with 8.
+    const int bits = env_int("FMRI_SELECT_BITS", 11, {8, 11});
+    SelState* st = static_cast<SelState*>(workspace);
+    long long* nc = reinterpret_cast<long long*>(nan_count);
+    return bits == 11 ? select_run<11>(src, n, st, ranks, K, out, nc, as_stream(stream))
+                      : select_run<8>(src, n, st, ranks, K, out, nc, as_stream(stream));
+}
+
+extern "C" int fmri_minmax_f64(const double* src, int64_t n, double* out2, int64_t* nan_count, fmri_stream_t stream) {
+    if (!src || !out2 || !nan_count || n <= 0) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    unsigned long long* mm = reinterpret_cast<unsigned long long*>(out2);
+    long long* nc = reinterpret_cast<long long*>(nan_count);
+    k_minmax64_init<<<1, 1, 0, s>>>(mm, nc);
+    k_minmax64<<<grid_for(n, 256, 2048), 256, 0, s>>>(src, n, mm, nc);
+    k_minmax64_decode<<<1, 1, 0, s>>>(mm);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_intensity_map_f64(const double* src, double* dst, int64_t n, int kind, double p0, double p1, double p2, double p3,
+                                      fmri_stream_t stream) {
+    if (!src || !dst || n <= 0 || kind < FMRI_MAP_WINDOW || kind > FMRI_MAP_ZSCORE) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    const int grid = grid_for(n, 256, 8192);
+    if (kind == FMRI_MAP_WINDOW) k_intensity_map<FMRI_MAP_WINDOW><<<grid, 256, 0, s>>>(src, dst, n, p0, p1, p2, p3);
+    else if (kind == FMRI_MAP_MINMAX) k_intensity_map<FMRI_MAP_MINMAX><<<grid, 256, 0, s>>>(src, dst, n, p0, p1, p2, p3);
+    else k_intensity_map<FMRI_MAP_ZSCORE><<<grid, 256, 0, s>>>(src, dst, n, p0, p1, p2, p3);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_laplace_f64(const double* src, double* dst, int X, int Y, int Z, fmri_stream_t stream) {
+    if (!src || !dst || src == dst || X <= 0 || Y <= 0 || Z <= 0) return FMRI_E_SHAPE;
+    k_laplace<<<grid_for((int64_t)X * Y * Z, 256, 8192), 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_grad_magnitude_combine_f64(const double* d0, const double* d1, const double* d2, double* out, int64_t n,
+                                               fmri_stream_t stream) {
+    if (!d0 || !d1 || !d2 || !out || n <= 0) return FMRI_E_SHAPE;
+    k_grad_combine<<<grid_for(n, 256, 8192), 256, 0, as_stream(stream)>>>(d0, d1, d2, out, n);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }

@@ -8,15 +8,19 @@
 Each resampling applied on the way in is pushed on a stack and undone in reverse on the way out, so the prediction always comes back on
 the voxel grid of the input.  On the device run the model work (the tile loop behind `patch_wise_prediction`, the TTA variants, the
 mask clean-up when `postprocess_prediction` takes its device path) and, when a GPU and the HIP library are there, the volume-sized
-resampling arithmetic: the spline zoom of `Zoom` in both directions and the median over the TTA variants (`fmri_hip.ops.zoom_f64`,
-`median_stack_f64`: scipy's and numpy's own arithmetic in float64, tests/test_gpu_resample.py).  The pipeline around them is numpy, so
-each of these calls still uploads its input and downloads its result; windowing (`np.percentile`), normalisation, border, crop and paste
-are once-per-volume host passes.  File I/O is the caller's (`fetal_net.utils.nifti`).  `predict_volume(...)` keeps the keyword surface
-of the reference's `main()` for callers that want the one-call form.
+arithmetic around it: the spline zoom of `Zoom` in both directions, the median over the TTA variants (`fmri_hip.ops.zoom_f64`,
+`median_stack_f64`, tests/test_gpu_resample.py) and the intensity preparation in front of the model - the percentile window, the named
+`preproc` filter of `fetal_net.preprocess` and the z-scoring (`fmri_hip.ops.window_intensities_f64`, `laplace_f64`,
+`gaussian_gradient_magnitude_f64`, `norm_minmax_f64`, `normalize_f64`, tests/test_gpu_intensity.py): scipy's and numpy's own arithmetic
+in float64, so host and device give the same values.  `Stage.intensities` uploads the volume once, runs window -> scaling zoom ->
+filter -> z-score on the device tensor and downloads once; the other calls upload their input and download their result.  Border, crop
+and paste are once-per-volume host passes.  File I/O is the caller's (`fetal_net.utils.nifti`).  `predict_volume(...)` keeps the keyword
+surface of the reference's `main()` for callers that want the one-call form.
 """
 import numpy as np
 from scipy import ndimage
 
+from . import preprocess
 from .postprocess import _device_ok, postprocess_prediction
 from .prediction import patch_wise_prediction, predict_augment, predict_flips
 from .utils.cut_relevant_areas import check_bounding_box, find_bounding_box
@@ -26,9 +30,23 @@ CONTEXT_MARGIN = 3                 # voxels of minimum-valued border the first m
 
 
 # ------------------------------------------------------------------------------------------------------------ intensity preparation
-def window_intensities_data(data, min_percent=1, max_percent=99, out_min=0.0, out_max=255.0):
+def _wants_device(data, device):
+    """the `device=` rule of fetal_net.preprocess: a CUDA tensor stays on the device; None = a float64 3-D ndarray with a GPU and the
+    library there"""
+    if preprocess._is_device_tensor(data):
+        if device is not None and not device:
+            raise ValueError("a device tensor cannot take the host form")
+        return True
+    return _device_ok(data) if device is None else bool(device)
+
+
+def window_intensities_data(data, min_percent=1, max_percent=99, out_min=0.0, out_max=255.0, device=None):
     """SimpleITK IntensityWindowing(image, p_lo, p_hi) restated (reference fetal/preprocess.py:50-55): the [p_lo, p_hi] percentile window
-    is mapped linearly onto [0, 255], values outside it are clamped"""
+    is mapped linearly onto [0, 255], values outside it are clamped.  device: as in `fetal_net.preprocess` (None / True / False; a
+    float64 CUDA tensor stays one) - the device form selects the percentiles' order statistics and maps on the GPU, same values."""
+    if _wants_device(data, device):
+        from fmri_hip import ops
+        return preprocess._dispatch(data, True, lambda t: ops.window_intensities_f64(t, min_percent, max_percent, out_min, out_max), None)
     data = np.asarray(data, dtype=np.float64)
     lo, hi = np.percentile(data, min_percent), np.percentile(data, max_percent)
     if hi == lo:
@@ -36,8 +54,14 @@ def window_intensities_data(data, min_percent=1, max_percent=99, out_min=0.0, ou
     return (np.clip(data, lo, hi) - lo) * ((out_max - out_min) / (hi - lo)) + out_min
 
 
-def normalize_data(data, mean, std):
-    """reference fetal_net/normalize.py:66-69"""
+def normalize_data(data, mean, std, device=None):
+    """reference fetal_net/normalize.py:66-69.  device: a float64 CUDA tensor stays one; True = the device form for an array.  None keeps
+    an array on the host: one subtraction and one division per voxel take less time there (13 ms at 160x256x256) than the transfer of
+    the volume to the device and back (16-24 ms end to end, profiles/r06_intensity_timing.log) - the device form pays inside a chain
+    that is already on the device (`Stage.intensities`)."""
+    if preprocess._is_device_tensor(data) or device:
+        from fmri_hip import ops
+        return preprocess._dispatch(data, True, lambda t: ops.normalize_f64(t, mean, std), None)
     return (np.asarray(data, dtype=np.float64) - mean) / std
 
 
@@ -135,17 +159,22 @@ class Box(Resampling):
 
 class Stage(object):
     """One model of the pipeline and everything that belongs to it.  `config`: the model's experiment config (`patch_shape`,
-    `patch_depth`, optional `scale_data`, optional callable `preproc`); `intensity`: None or a key of INTENSITY_METHODS; `norm`: None or
-    {'mean', 'std'}; `augment`: None | 'flip' (the 8 flips) | 'all' (`n_augment` random variants); `device`: where the stage's zoom
-    and the median over its variants run (None / True / False as for `Zoom`)."""
+    `patch_depth`, optional `scale_data`, optional `preproc`: a callable, or the name of a filter in `fetal_net.preprocess` as in the
+    reference's configs); `intensity`: None or a key of INTENSITY_METHODS; `norm`: None or {'mean', 'std'}; `augment`: None | 'flip' (the
+    8 flips) | 'all' (`n_augment` random variants); `device`: where the stage's intensity preparation, its zoom and the median over its
+    variants run (None / True / False as for `Zoom`)."""
 
     def __init__(self, model, config, intensity=None, norm=None, augment=None, n_augment=0, overlap=0.9, device=None):
         if intensity is not None and intensity not in INTENSITY_METHODS:
             raise Exception("Unknown preprocess: {}".format(intensity))
         if augment not in (None, "flip", "all"):
             raise ValueError("Unknown augmentation {}".format(augment))
-        if config.get("preproc") is not None and not callable(config["preproc"]):
-            raise TypeError("config['preproc'] must be a callable here (the reference looks a name up in its own fetal_net.preprocess)")
+        pre = config.get("preproc")
+        self.preproc, self.preproc_named = pre, False
+        if isinstance(pre, str) and pre in preprocess.__all__:
+            self.preproc, self.preproc_named = getattr(preprocess, pre), True       # reference predict_nifti2.py:67-69
+        elif pre is not None and not callable(pre):
+            raise TypeError("config['preproc'] must be a callable or one of %s of fetal_net.preprocess (got %r)" % (preprocess.__all__, pre))
         self.model, self.config, self.intensity, self.norm = model, config, intensity, norm
         self.augment, self.n_augment, self.overlap, self.device = augment, n_augment, overlap, device
 
@@ -154,18 +183,50 @@ class Stage(object):
         return list(self.config["patch_shape"]) + [self.config["patch_depth"]]
 
     def intensities(self, vol, resamplings=None):
-        """windowing -> the model-specific scaling (recorded in `resamplings`) -> the config's own hook -> z-scoring, in the reference's order"""
+        """windowing -> the model-specific scaling (recorded in `resamplings`) -> the config's own hook -> z-scoring, in the reference's
+        order.  Under the device rule (a float64 volume [X,Y,Z]) the steps run on ONE device tensor: one upload, one download; a caller's
+        own callable is handed a numpy array in between, as on the host."""
+        scale = self.config.get("scale_data") if resamplings is not None else None
+        pre = self.preproc if resamplings is not None else None
+        norm = self.norm if self.norm is not None and any(self.norm.values()) else None
+        # the z-score alone is quicker on the host than the volume's round trip to the device (normalize_data): under the default rule
+        # the chain goes to the device for the steps that pay there
+        work = self.intensity is not None or scale is not None or (pre is not None and self.preproc_named) or (
+            self.device and (pre is not None or norm is not None))
+        if work and isinstance(vol, np.ndarray) and vol.ndim == 3 and vol.dtype == np.float64 and vol.size and _use_device(vol, self.device):
+            return self._intensities_on_device(vol, resamplings, scale, pre, norm)
         if self.intensity is not None:
-            vol = INTENSITY_METHODS[self.intensity](vol)
-        if resamplings is not None and self.config.get("scale_data") is not None:
-            step = Zoom(self.config["scale_data"], order_back=0, device=self.device)
+            vol = INTENSITY_METHODS[self.intensity](vol, device=False)
+        if scale is not None:
+            step = Zoom(scale, order_back=0, device=self.device)
             resamplings.append(step)
             vol = step.forward(vol)
-        if resamplings is not None and self.config.get("preproc") is not None:
-            vol = self.config["preproc"](vol)
-        if self.norm is not None and any(self.norm.values()):
-            vol = normalize_data(vol, mean=self.norm["mean"], std=self.norm["std"])
+        if pre is not None:
+            vol = pre(vol, device=False) if self.preproc_named else pre(vol)
+        if norm is not None:
+            vol = normalize_data(vol, mean=norm["mean"], std=norm["std"], device=False)
         return vol
+
+    def _intensities_on_device(self, vol, resamplings, scale, pre, norm):
+        import torch
+        from fmri_hip import ops
+        t = torch.from_numpy(np.ascontiguousarray(vol)).cuda()
+        if self.intensity is not None:
+            t = INTENSITY_METHODS[self.intensity](t)
+        if scale is not None:
+            step = Zoom(scale, order_back=0, device=self.device)
+            resamplings.append(step)
+            t = ops.zoom_f64(t, step.factors, order=3)
+        if pre is not None and self.preproc_named:
+            t = pre(t)
+        elif pre is not None:
+            back = np.asarray(pre(t.cpu().numpy()))
+            if norm is None or not (back.ndim == 3 and back.dtype == np.float64 and back.size):
+                return back if norm is None else normalize_data(back, mean=norm["mean"], std=norm["std"], device=False)
+            t = torch.from_numpy(np.ascontiguousarray(back)).cuda()
+        if norm is not None:
+            t = ops.normalize_f64(t, norm["mean"], norm["std"])
+        return t.cpu().numpy()
 
     def infer(self, vol, keep_variants=False):
         """probabilities of `vol` [X,Y,Z]: tiled prediction, or the median over the stage's test-time augmentation variants"""
@@ -241,7 +302,8 @@ def predict_volume(data, model, config, overlap_factor=0.9, preprocess_method=No
     """One-call form with the argument names of the reference's `main()` (predict_nifti2.py:98-160), on arrays: `data` = the volume as read
     from the NIfTI file.  Returns a dict: 'data' (the prepared volume the first model saw, before its border), 'prediction' (first stage, on
     the input grid) and, with model2 / config2, 'mask' and 'prediction_roi' (second stage on the padded bounding box, volume-sized).
-    `device` (not in the reference): where the zooms and the variant medians run - None / True / False as for `Zoom`."""
+    `device` (not in the reference): where the intensity preparation, the zooms and the variant medians run - None / True / False as for
+    `Zoom`.  config['preproc'] may name a filter of `fetal_net.preprocess`, as the reference's configs do."""
     if config2 is not None and model2 is None:
         raise ValueError("config2 given without model2")
     first = Stage(model, config, preprocess_method, norm_params, augment, num_augment, overlap_factor, device)

@@ -78,6 +78,13 @@ SIGNATURES = {
     "fmri_spline_filter1d_f64": [p, i32, i32, i32, i32, i32, p],
     "fmri_spline_affine_f64": [p, i32, i32, i32, p, p, p, i32, i32, i32, C.c_double, p],
     "fmri_median_stack_f64": [p, i32, i64, p, p],
+    "fmri_order_stats_workspace_bytes": [],
+    "fmri_order_stats_f64": [p, i64, p, i32, p, p, p, p],
+    "fmri_minmax_f64": [p, i64, p, p, p],
+    "fmri_intensity_map_f64": [p, p, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, p],
+    "fmri_laplace_f64": [p, p, i32, i32, i32, p],
+    "fmri_correlate1d_asym_f64": [p, p, i32, i32, i32, i32, p, i32, p],
+    "fmri_grad_magnitude_combine_f64": [p, p, p, p, i64, p],
     "fmri_add": [p, p, p, i64, i32, p],
     "fmri_act_bwd": [p, p, p, i32, f32, i64, i32, p],
     "fmri_slice_channels": [p, i32, i32, p, i32, i64, i32, i32, p],

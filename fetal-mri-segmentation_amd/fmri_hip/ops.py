@@ -908,6 +908,178 @@ def median_stack_f64(stack):
 
 
 # ---------------------------------------------------------------------------------------------------- discriminator head (discriminator.hip)
+# ---------------------------------------------------------------------------------------------------- intensity preparation (postprocess.hip)
+MAP_WINDOW, MAP_MINMAX, MAP_ZSCORE = 0, 1, 2
+_MAX_RANKS = 8
+
+
+def order_stats_f64(vol, ranks):
+    """(np.sort(vol, axis=None)[ranks] as a float64 numpy array, the number of NaNs in vol) of a float64 device tensor of any shape: a
+    radix select on the device, all ranks in one sweep per digit; more than 8 ranks go in groups of 8.  One read-back at the end."""
+    import ctypes
+    import numpy as np
+    _need_cuda(vol)
+    if vol.dtype != torch.float64 or vol.numel() == 0:
+        raise ValueError("a non-empty float64 tensor is needed (got %s %s)" % (vol.dtype, tuple(vol.shape)))
+    n = vol.numel()
+    ranks = [int(r) for r in np.asarray(ranks).ravel()]
+    if not ranks:
+        raise ValueError("no ranks")
+    L = lib()
+    groups = (len(ranks) + _MAX_RANKS - 1) // _MAX_RANKS
+    with torch.cuda.device(vol.device):
+        ws = torch.empty(L.fmri_order_stats_workspace_bytes(), dtype=torch.uint8, device=vol.device)
+        out = torch.empty(groups * _MAX_RANKS, dtype=torch.float64, device=vol.device)
+        nan = torch.empty(groups, dtype=torch.int64, device=vol.device)
+        for g in range(groups):
+            part = ranks[g * _MAX_RANKS:(g + 1) * _MAX_RANKS]
+            R = (ctypes.c_int64 * len(part))(*part)
+            check(L.fmri_order_stats_f64(_p(vol), n, ctypes.addressof(R), len(part), out.data_ptr() + 8 * _MAX_RANKS * g,
+                                         nan.data_ptr() + 8 * g, _p(ws), _s()), "fmri_order_stats_f64")
+    vals = out.cpu().numpy().reshape(groups, _MAX_RANKS)
+    return np.concatenate([vals[g, :len(ranks[g * _MAX_RANKS:(g + 1) * _MAX_RANKS])] for g in range(groups)]), int(nan[0].item())
+
+
+def percentile_f64(vol, qs):
+    """np.percentile(vol, qs) (the default 'linear' method) of a float64 device tensor -> float64 numpy array of len(qs), or a numpy
+    scalar for a scalar q: the two neighbouring order statistics of every q from ONE order_stats_f64 call, then numpy's own _lerp on the
+    host in float64.  A NaN anywhere in vol gives NaN for every q, as numpy does."""
+    import numpy as np
+    scalar = np.ndim(qs) == 0
+    q = np.atleast_1d(np.asarray(qs, dtype=np.float64))
+    if not np.all((q >= 0) & (q <= 100)):
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    n = vol.numel()
+    vi = np.true_divide(q, 100) * (n - 1)                    # numpy's virtual index of method 'linear'
+    lo = np.floor(vi)
+    hi = np.minimum(lo + 1, n - 1)
+    t = np.subtract(vi, lo)
+    vals, nans = order_stats_f64(vol, np.concatenate([lo, hi]).astype(np.int64))
+    if nans:
+        res = np.full(q.shape, np.nan)
+    else:
+        a, b = vals[:q.size], vals[q.size:]
+        diff = b - a
+        with np.errstate(invalid="ignore", over="ignore"):
+            res = a + diff * t                                   # numpy.lib._function_base_impl._lerp
+            res = np.where(t >= 0.5, b - diff * (1 - t), res)
+    return res[0] if scalar else res
+
+
+def minmax_f64(vol):
+    """(vol.min(), vol.max()) of a float64 device tensor as Python floats; NaN for both when vol holds a NaN, as numpy gives"""
+    _need_cuda(vol)
+    if vol.dtype != torch.float64 or vol.numel() == 0:
+        raise ValueError("a non-empty float64 tensor is needed (got %s %s)" % (vol.dtype, tuple(vol.shape)))
+    with torch.cuda.device(vol.device):
+        out = torch.empty(2, dtype=torch.float64, device=vol.device)
+        nan = torch.empty(1, dtype=torch.int64, device=vol.device)
+        check(lib().fmri_minmax_f64(_p(vol), vol.numel(), _p(out), _p(nan), _s()), "fmri_minmax_f64")
+    lo, hi = out.tolist()
+    return (float("nan"), float("nan")) if int(nan.item()) else (lo, hi)
+
+
+def intensity_map_f64(vol, kind, p0, p1, p2=0.0, p3=0.0, out=None):
+    """out = map(vol) element by element (csrc/postprocess.hip: MAP_WINDOW, MAP_MINMAX, MAP_ZSCORE); out=None: a new tensor, out=vol: in
+    place"""
+    _need_cuda(vol, out)
+    if vol.dtype != torch.float64 or vol.numel() == 0:
+        raise ValueError("a non-empty float64 tensor is needed (got %s %s)" % (vol.dtype, tuple(vol.shape)))
+    if out is None:
+        out = torch.empty_like(vol)
+    assert out.dtype == torch.float64 and out.shape == vol.shape and out.device == vol.device
+    with torch.cuda.device(vol.device):
+        check(lib().fmri_intensity_map_f64(_p(vol), _p(out), vol.numel(), int(kind), float(p0), float(p1), float(p2), float(p3), _s()),
+              "fmri_intensity_map_f64")
+    return out
+
+
+def window_intensities_f64(vol, min_percent=1, max_percent=99, out_min=0.0, out_max=255.0):
+    """fetal_net.pipeline.window_intensities_data of a float64 device volume -> a new tensor"""
+    _vol_f64(vol)
+    lo, hi = (float(v) for v in percentile_f64(vol, [min_percent, max_percent]))
+    if hi == lo:
+        return torch.full_like(vol, float(out_min))
+    return intensity_map_f64(vol, MAP_WINDOW, lo, hi, (out_max - out_min) / (hi - lo), out_min)
+
+
+def norm_minmax_f64(vol):
+    """-1 + 2 * (d - d.min()) / (d.max() - d.min()) (reference fetal_net/preprocess.py:5-6) -> a new tensor; NaN everywhere for a
+    constant volume (0 / 0), as on the host"""
+    _vol_f64(vol)
+    mn, mx = minmax_f64(vol)
+    return intensity_map_f64(vol, MAP_MINMAX, mn, mx)
+
+
+def normalize_f64(vol, mean, std):
+    """(vol - mean) / std (reference fetal_net/normalize.py:66-69) -> a new tensor"""
+    _vol_f64(vol)
+    return intensity_map_f64(vol, MAP_ZSCORE, mean, std)
+
+
+def laplace_f64(vol):
+    """scipy.ndimage.laplace(vol) (mode 'reflect') of a float64 device volume [X,Y,Z] -> a new tensor"""
+    _vol_f64(vol)
+    X, Y, Z = vol.shape
+    out = torch.empty_like(vol)
+    with torch.cuda.device(vol.device):
+        check(lib().fmri_laplace_f64(_p(vol), _p(out), X, Y, Z, _s()), "fmri_laplace_f64")
+    return out
+
+
+def gaussian_kernel1d(sigma, order, radius):
+    """scipy.ndimage._filters._gaussian_kernel1d for orders 0 and 1, reversed as gaussian_filter1d reverses it before it correlates"""
+    import numpy as np
+    if order not in (0, 1):
+        raise NotImplementedError("gaussian derivative order %r" % (order,))
+    sigma2 = sigma * sigma
+    x = np.arange(-radius, radius + 1)
+    phi_x = np.exp(-0.5 / sigma2 * x ** 2)
+    phi_x = phi_x / phi_x.sum()
+    if order == 0:
+        return phi_x[::-1].copy()
+    exponent_range = np.arange(order + 1)
+    q = np.zeros(order + 1)
+    q[0] = 1
+    D = np.diag(exponent_range[1:], 1)
+    P = np.diag(np.ones(order) / -sigma2, -1)
+    q = (D + P).dot(q)
+    q = (x[:, None] ** exponent_range).dot(q)
+    return (q * phi_x)[::-1].copy()
+
+
+def gaussian_gradient_magnitude_f64(vol, sigma, truncate=4.0):
+    """scipy.ndimage.gaussian_gradient_magnitude(vol, sigma) (mode 'reflect') of a float64 device volume [X,Y,Z] -> a new tensor.
+    D_a = derivative along a, smoothing along the other two, the axes in ascending order as gaussian_filter runs them; the smoothed
+    prefixes are shared (g0 serves D_1 and D_2): 8 correlation passes instead of 9, then sqrt((D_0^2 + D_1^2) + D_2^2)."""
+    import numpy as np
+    _vol_f64(vol)
+    X, Y, Z = vol.shape
+    sig = [float(sigma)] * 3 if np.isscalar(sigma) else [float(v) for v in sigma]
+    if len(sig) != 3:
+        raise ValueError("sigma: one number, or one per axis")
+    if any(sd <= 1e-15 for sd in sig):
+        raise NotImplementedError("a sigma of ~0 (scipy skips that axis, its derivative included)")
+    L = lib()
+    with torch.cuda.device(vol.device):
+        radius = [int(truncate * sd + 0.5) for sd in sig]
+        w = [[torch.from_numpy(gaussian_kernel1d(sd, o, r)).to(vol.device) for o in (0, 1)] for sd, r in zip(sig, radius)]
+
+        def run(src, axis, order):
+            dst = torch.empty_like(vol)
+            name = "fmri_correlate1d_asym_f64" if order else "fmri_correlate1d_f64"
+            check(getattr(L, name)(_p(src), _p(dst), X, Y, Z, axis, _p(w[axis][order]), radius[axis], _s()), name)
+            return dst
+
+        d0 = run(run(run(vol, 0, 1), 1, 0), 2, 0)
+        g0 = run(vol, 0, 0)
+        d1 = run(run(g0, 1, 1), 2, 0)
+        d2 = run(run(g0, 1, 0), 2, 1)
+        del g0
+        check(L.fmri_grad_magnitude_combine_f64(_p(d0), _p(d1), _p(d2), _p(d0), vol.numel(), _s()), "fmri_grad_magnitude_combine_f64")
+    return d0
+
+
 def avgpool_fwd(x, y, planar=False):
     """x [N,D,H,W,C] -> y [N,D//2,H//2,W//2,C] (planar: [N,D,H//2,W//2,C]); AveragePooling3D() / AveragePooling2D()"""
     _need_cuda(x, y)

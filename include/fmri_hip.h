@@ -519,6 +519,38 @@ int fmri_spline_affine_f64(const double* coef, int X, int Y, int Z, const double
                            int NY, int NZ, double cval, fmri_stream_t stream);
 int fmri_median_stack_f64(const double* stack, int K, int64_t n, double* out, fmri_stream_t stream);
 
+/* ---- intensity preparation of a contiguous fp64 volume in front of the model (reference prod/predict_nifti2.py:57-74 and
+ * fetal_net/preprocess.py: the percentile window, laplace, gaussian_gradient_magnitude, min-max and z-score maps).  numpy's / scipy's own
+ * operation order, one rounding per operation: the device result is the host result bit for bit.
+ * fmri_order_stats_f64: out[k] (device) = sorted(src)[ranks_host[k]], k < K <= 8, by a most-significant-digit radix select on
+ *   order-preserving 64-bit keys (NaNs sort last, as np.sort puts them); *nan_count (device) = the number of NaNs in src.  ranks_host:
+ *   zero-based, HOST memory, read at enqueue.  workspace: fmri_order_stats_workspace_bytes() bytes on the device, any contents; the
+ *   passes are separate launches on `stream`, nothing is read back.  n >= 2^31, K > 8 or a rank outside [0, n): FMRI_E_SHAPE.
+ *   Environment switch FMRI_SELECT_BITS = 11 (default) | 8: the digit width (6 or 8 passes), read at every call.
+ * fmri_minmax_f64: out2 (device) = {min, max} of the values that are not NaN, *nan_count (device) = the number of NaNs.
+ * fmri_intensity_map_f64: dst[i] = map(src[i]); src == dst is allowed.
+ *   FMRI_MAP_WINDOW  (min(max(x, p0), p1) - p0) * p2 + p3      p0, p1 = window, p2 = scale, p3 = out_min; np.clip's NaN rules
+ *   FMRI_MAP_MINMAX  -1 + (2 * (x - p0)) / (p1 - p0)           p0, p1 = min, max
+ *   FMRI_MAP_ZSCORE  (x - p0) / p1                             p0, p1 = mean, std
+ * fmri_laplace_f64: scipy.ndimage.laplace(vol) (mode 'reflect') of [X][Y][Z] in one 7-point pass.  src != dst.
+ * fmri_correlate1d_asym_f64: fmri_correlate1d_f64 for antisymmetric weights (w[r + j] == -w[r - j]: scipy's branch for the order-1
+ *   Gaussian): acc = x[l] * w[r]; acc += (x[l + jj] - x[l - jj]) * w[jj + r] for jj = -r .. -1.
+ * fmri_grad_magnitude_combine_f64: out = sqrt((d0 * d0 + d1 * d1) + d2 * d2), the tail of gaussian_gradient_magnitude; out may be one
+ *   of the inputs. */
+#define FMRI_MAP_WINDOW 0
+#define FMRI_MAP_MINMAX 1
+#define FMRI_MAP_ZSCORE 2
+int64_t fmri_order_stats_workspace_bytes(void);
+int fmri_order_stats_f64(const double* src, int64_t n, const int64_t* ranks_host, int K, double* out, int64_t* nan_count, void* workspace,
+                         fmri_stream_t stream);
+int fmri_minmax_f64(const double* src, int64_t n, double* out2, int64_t* nan_count, fmri_stream_t stream);
+int fmri_intensity_map_f64(const double* src, double* dst, int64_t n, int kind, double p0, double p1, double p2, double p3,
+                           fmri_stream_t stream);
+int fmri_laplace_f64(const double* src, double* dst, int X, int Y, int Z, fmri_stream_t stream);
+int fmri_correlate1d_asym_f64(const double* src, double* dst, int X, int Y, int Z, int axis, const double* weights, int radius,
+                              fmri_stream_t stream);
+int fmri_grad_magnitude_combine_f64(const double* d0, const double* d1, const double* d2, double* out, int64_t n, fmri_stream_t stream);
+
 /* ---- PatchGAN discriminator head and the adversarial coupling.  Reference
  * fetal_net/model/discriminator/all_dis_3d.py:11-72 (conv blocks of the segmentation path's layer kinds + AveragePooling3D,
  * GlobalAveragePooling3D, Dense(128, LeakyReLU) x fc_layers, Dense(1, 'sigmoid'), loss binary_crossentropy, metric 'mae') and
