@@ -9,7 +9,8 @@
 // thresholded mask - is bit-identical to scipy's; hole filling and labelling are integer algorithms with scipy's default 6-connectivity,
 // and ties between equally large components go to the one scipy numbers first (smallest linear index of its first voxel).
 // Second: distance_transform_edt (the distance masks of the mask-weighted loss).  Third: the B-spline resampling and the variant median
-// around whole-volume prediction.  Fourth, at the end of the file: the intensity preparation in front of the model.
+// around whole-volume prediction.  Fourth: the intensity preparation in front of the model.  Fifth, at the end of the file: scoring a
+// predicted mask against the truth (overlap counts, surfaces, masked reductions over the distance field).
 #include "common.h"
 #include <math.h>
 
@@ -1059,6 +1060,269 @@ extern "C" int fmri_grad_magnitude_combine_f64(const double* d0, const double* d
                                                fmri_stream_t stream) {
     if (!d0 || !d1 || !d2 || !out || n <= 0) return FMRI_E_SHAPE;
     k_grad_combine<<<grid_for(n, 256, 8192), 256, 0, as_stream(stream)>>>(d0, d1, d2, out, n);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+// ---- Fifth: scoring a predicted mask against the truth (reference fetal/evaluate.py: hard Dice on "> 0" masks; the surface metrics are
+// medpy.metric.binary's hd / hd95 / assd restated).  Two uint8 volumes [X][Y][Z], a voxel belongs to a mask when its byte is nonzero.
+//   counts     |A|, |B|, |A n B|: the overlap scores (Dice, VOD, volume difference, sensitivity, precision) are ratios of these integers.
+//   surface    border = mask ^ binary_erosion(mask, generate_binary_structure(3, connectivity)), scipy's border_value = 0: a foreground
+//              voxel with a background neighbour, or with a neighbour outside the volume.  Written INVERTED (0 on the border, 1 elsewhere):
+//              that is the input of fmri_edt_u8, whose field is then the distance of every voxel to the nearest border voxel -
+//              distance_transform_edt(~border, sampling).
+//   distances  d(A -> B) = that field of B read at A's border voxels.  Its sum and maximum come from one masked reduction, the percentile
+//              from a stream compaction of both directions into one buffer followed by the radix select above.
+// Exactness: counts, borders and maxima are exact; the distances are the EDT's (identical to scipy at unit spacing).  The sum is
+// reproducible: the grid depends on n alone, every thread adds its voxels in index order, a wave adds by a fixed butterfly, the waves of a
+// workgroup and then the workgroups' partials are added in index order by a second launch.  No floating-point atomics anywhere.
+namespace {
+
+constexpr int EV_THREADS = 256;
+constexpr int EV_GRID = 2048;            // cap of the voxel kernels' grids (8 workgroups per CU); also the number of partials
+constexpr int EV_WAVES = EV_THREADS / 64;
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// bit 7 of every nonzero byte of w
+__device__ __forceinline__ unsigned long long nonzero_bytes(unsigned long long w) {
+    return (((w & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | w) & 0x8080808080808080ull;
+}
+
+// words = n / 8 when both pointers are 8-byte aligned (eight voxels per load), else 0; the remaining voxels go one per thread
+__global__ __launch_bounds__(EV_THREADS) void k_seg_counts(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int64_t n, int64_t words,
+                                                           unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long part[3][EV_WAVES];
+    unsigned long long ca = 0, cb = 0, cab = 0;
+    const int64_t tid = (int64_t)blockIdx.x * EV_THREADS + threadIdx.x, step = (int64_t)gridDim.x * EV_THREADS;
+    const unsigned long long* const a8 = reinterpret_cast<const unsigned long long*>(a);
+    const unsigned long long* const b8 = reinterpret_cast<const unsigned long long*>(b);
+    for (int64_t t = tid; t < words; t += step) {
+        const unsigned long long ma = nonzero_bytes(a8[t]), mb = nonzero_bytes(b8[t]);
+        ca += __popcll(ma);
+        cb += __popcll(mb);
+        cab += __popcll(ma & mb);
+    }
+    for (int64_t t = words * 8 + tid; t < n; t += step) {
+        const int va = a[t] != 0, vb = b[t] != 0;
+        ca += va;
+        cb += vb;
+        cab += va & vb;
+    }
+    ca = wave_sum_u64(ca);
+    cb = wave_sum_u64(cb);
+    cab = wave_sum_u64(cab);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[0][wave] = ca;
+        part[1][wave] = cb;
+        part[2][wave] = cab;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        unsigned long long s = 0;
+        for (int w = 0; w < EV_WAVES; ++w) s += part[threadIdx.x][w];
+        if (s) atomicAdd(&out[threadIdx.x], s);
+    }
+}
+
+// blockIdx.y selects the volume (one or two in a launch).  CONN = scipy's connectivity: the neighbours with 1 .. CONN nonzero offsets.
+template <int CONN>
+__global__ __launch_bounds__(EV_THREADS) void k_surface(const uint8_t* __restrict__ m0, const uint8_t* __restrict__ m1, uint8_t* __restrict__ i0,
+                                                        uint8_t* __restrict__ i1, int X, int Y, int Z, unsigned long long* __restrict__ count) {
+    __shared__ unsigned long long part[EV_WAVES];
+    const uint8_t* const __restrict__ mask = blockIdx.y ? m1 : m0;
+    uint8_t* const __restrict__ inv = blockIdx.y ? i1 : i0;
+    const int64_t total = (int64_t)X * Y * Z, sx = (int64_t)Y * Z;
+    unsigned long long found = 0;
+    for (int64_t t = (int64_t)blockIdx.x * EV_THREADS + threadIdx.x; t < total; t += (int64_t)gridDim.x * EV_THREADS) {
+        int border = 0;
+        if (mask[t]) {
+            const int z = (int)(t % Z);
+            const int64_t q = t / Z;
+            const int y = (int)(q % Y), x = (int)(q / Y);
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx)
+#pragma unroll
+                for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                    for (int dz = -1; dz <= 1; ++dz) {
+                        const int order = (dx != 0) + (dy != 0) + (dz != 0);
+                        if (order == 0 || order > CONN) continue;
+                        const int xx = x + dx, yy = y + dy, zz = z + dz;
+                        if (xx < 0 || xx >= X || yy < 0 || yy >= Y || zz < 0 || zz >= Z) border = 1;
+                        else if (!mask[t + dx * sx + dy * (int64_t)Z + dz]) border = 1;
+                    }
+        }
+        inv[t] = border ? 0 : 1;
+        found += border;
+    }
+    found = wave_sum_u64(found);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = found;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+        for (int w = 0; w < EV_WAVES; ++w) s += part[w];
+        if (s) atomicAdd(&count[blockIdx.y], s);
+    }
+}
+
+// partial[2 * blockIdx.x] = {sum, max} of the workgroup's selected values; the grid is a function of n alone (see above)
+__global__ __launch_bounds__(EV_THREADS) void k_masked_partials(const double* __restrict__ values, const uint8_t* __restrict__ inv_sel, int64_t n,
+                                                                double* __restrict__ partial) {
+    __shared__ double ps[EV_WAVES], pm[EV_WAVES];
+    double sum = 0.0, mx = -(double)INFINITY;
+    for (int64_t t = (int64_t)blockIdx.x * EV_THREADS + threadIdx.x; t < n; t += (int64_t)gridDim.x * EV_THREADS)
+        if (inv_sel[t] == 0) {
+            const double v = values[t];
+            sum += v;
+            mx = fmax(mx, v);
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sum += __shfl_xor(sum, o);
+        mx = fmax(mx, __shfl_xor(mx, o));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        ps[threadIdx.x >> 6] = sum;
+        pm[threadIdx.x >> 6] = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = ps[0], m = pm[0];
+        for (int w = 1; w < EV_WAVES; ++w) {
+            s += ps[w];
+            m = fmax(m, pm[w]);
+        }
+        partial[2 * blockIdx.x] = s;
+        partial[2 * blockIdx.x + 1] = m;
+    }
+}
+
+// one workgroup: thread i adds partials i, i + 256, ... in that order, then a fixed tree over the 256 threads
+__global__ __launch_bounds__(EV_THREADS) void k_masked_finish(const double* __restrict__ partial, int parts, double* __restrict__ out) {
+    __shared__ double ss[EV_THREADS], sm[EV_THREADS];
+    double sum = 0.0, mx = -(double)INFINITY;
+    for (int i = threadIdx.x; i < parts; i += EV_THREADS) {
+        sum += partial[2 * i];
+        mx = fmax(mx, partial[2 * i + 1]);
+    }
+    ss[threadIdx.x] = sum;
+    sm[threadIdx.x] = mx;
+    __syncthreads();
+    for (int o = EV_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            ss[threadIdx.x] += ss[threadIdx.x + o];
+            sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + o]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[0] = ss[0];
+        out[1] = sm[0];
+    }
+}
+
+// the selected values, dense, from out[*cursor] on.  Every wave owns one contiguous run of voxels (a multiple of 64, so its loads of
+// inv_sel are whole 64-byte lines) and walks it twice: first it counts its selected voxels by ballots; thread 0 then reserves the
+// workgroup's total with ONE integer atomic and hands every wave its start; the second walk (inv_sel now comes from cache) ballots
+// again and every selected lane stores at the wave's running start + the number of selected lanes below it.  One atomic per wave and
+// ballot, the first form of this kernel, put ~40 k atomics on the one cursor: 0.22 ms for a 160x256x256 volume, 15x the masked
+// reduction that reads the same bytes.  The loop bounds are uniform over a wave, so all 64 lanes reach every ballot.  A slot at or past
+// `capacity` is not written (the cursor still advances: the caller compares).
+__global__ __launch_bounds__(EV_THREADS) void k_masked_compact(const double* __restrict__ values, const uint8_t* __restrict__ inv_sel, int64_t n,
+                                                               double* __restrict__ out, int64_t capacity, unsigned long long* __restrict__ cursor) {
+    __shared__ unsigned long long wcount[EV_WAVES], wstart[EV_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t waves = (int64_t)gridDim.x * EV_WAVES;
+    const int64_t per = ((n + waves - 1) / waves + 63) / 64 * 64;
+    const int64_t w = (int64_t)blockIdx.x * EV_WAVES + wave;
+    const int64_t lo = min(w * per, n), hi = min(lo + per, n);
+    unsigned long long count = 0;
+    for (int64_t t0 = lo; t0 < hi; t0 += 64) {
+        const int64_t t = t0 + lane;
+        count += __popcll(__ballot(t < hi && inv_sel[t] == 0));
+    }
+    if (lane == 0) wcount[wave] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long total = 0;
+        for (int k = 0; k < EV_WAVES; ++k) total += wcount[k];
+        unsigned long long at = total ? atomicAdd(cursor, total) : 0ull;
+        for (int k = 0; k < EV_WAVES; ++k) {
+            wstart[k] = at;
+            at += wcount[k];
+        }
+    }
+    __syncthreads();
+    unsigned long long at = wstart[wave];
+    for (int64_t t0 = lo; t0 < hi; t0 += 64) {
+        const int64_t t = t0 + lane;
+        const bool sel = t < hi && inv_sel[t] == 0;
+        const unsigned long long vote = __ballot(sel);
+        if (sel) {
+            const int64_t slot = (int64_t)at + __popcll(vote & ((1ull << lane) - 1ull));
+            if (slot < capacity) out[slot] = values[t];
+        }
+        at += __popcll(vote);
+    }
+}
+
+}  // namespace
+
+extern "C" int fmri_seg_counts_u8(const uint8_t* a, const uint8_t* b, int64_t n, int64_t* out3, fmri_stream_t stream) {
+    if (!a || !b || !out3 || n <= 0) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    if (hipMemsetAsync(out3, 0, 3 * sizeof(int64_t), s) != hipSuccess) return FMRI_E_LAUNCH;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7u) == 0;
+    const int64_t words = aligned ? n / 8 : 0;
+    k_seg_counts<<<grid_for(aligned ? words : n, EV_THREADS, EV_GRID), EV_THREADS, 0, s>>>(a, b, n, words,
+                                                                                                  reinterpret_cast<unsigned long long*>(out3));
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_surface_u8(const uint8_t* mask, uint8_t* inv_border, const uint8_t* mask2, uint8_t* inv_border2, int X, int Y, int Z,
+                               int connectivity, int64_t* count, fmri_stream_t stream) {
+    if (!mask || !inv_border || mask == inv_border || !count || X <= 0 || Y <= 0 || Z <= 0 || connectivity < 1 || connectivity > 3)
+        return FMRI_E_SHAPE;
+    const int nvol = mask2 ? 2 : 1;
+    if (mask2 && (!inv_border2 || mask2 == inv_border2 || inv_border2 == inv_border || inv_border2 == mask || inv_border == mask2))
+        return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    if (hipMemsetAsync(count, 0, nvol * sizeof(int64_t), s) != hipSuccess) return FMRI_E_LAUNCH;
+    const dim3 grid(grid_for((int64_t)X * Y * Z, EV_THREADS, EV_GRID), nvol);
+    unsigned long long* const c = reinterpret_cast<unsigned long long*>(count);
+    if (connectivity == 1) k_surface<1><<<grid, EV_THREADS, 0, s>>>(mask, mask2, inv_border, inv_border2, X, Y, Z, c);
+    else if (connectivity == 2) k_surface<2><<<grid, EV_THREADS, 0, s>>>(mask, mask2, inv_border, inv_border2, X, Y, Z, c);
+    else k_surface<3><<<grid, EV_THREADS, 0, s>>>(mask, mask2, inv_border, inv_border2, X, Y, Z, c);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int64_t fmri_masked_stats_workspace_bytes(void) { return (int64_t)(2 * EV_GRID * sizeof(double)); }
+
+extern "C" int fmri_masked_stats_f64(const double* values, const uint8_t* inv_sel, int64_t n, double* out2, void* workspace,
+                                     fmri_stream_t stream) {
+    if (!values || !inv_sel || !out2 || !workspace || n <= 0) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    const int parts = grid_for(n, EV_THREADS, EV_GRID);
+    double* const partial = static_cast<double*>(workspace);
+    k_masked_partials<<<parts, EV_THREADS, 0, s>>>(values, inv_sel, n, partial);
+    k_masked_finish<<<1, EV_THREADS, 0, s>>>(partial, parts, out2);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_masked_compact_f64(const double* values, const uint8_t* inv_sel, int64_t n, double* out, int64_t capacity, int64_t* cursor,
+                                       fmri_stream_t stream) {
+    if (!values || !inv_sel || !out || !cursor || n <= 0 || capacity <= 0) return FMRI_E_SHAPE;
+    k_masked_compact<<<grid_for(n, EV_THREADS, EV_GRID), EV_THREADS, 0, as_stream(stream)>>>(values, inv_sel, n, out, capacity,
+                                                                                             reinterpret_cast<unsigned long long*>(cursor));
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }

@@ -85,6 +85,11 @@ SIGNATURES = {
     "fmri_laplace_f64": [p, p, i32, i32, i32, p],
     "fmri_correlate1d_asym_f64": [p, p, i32, i32, i32, i32, p, i32, p],
     "fmri_grad_magnitude_combine_f64": [p, p, p, p, i64, p],
+    "fmri_seg_counts_u8": [p, p, i64, p, p],
+    "fmri_surface_u8": [p, p, p, p, i32, i32, i32, i32, p, p],
+    "fmri_masked_stats_workspace_bytes": [],
+    "fmri_masked_stats_f64": [p, p, i64, p, p, p],
+    "fmri_masked_compact_f64": [p, p, i64, p, i64, p, p],
     "fmri_add": [p, p, p, i64, i32, p],
     "fmri_act_bwd": [p, p, p, i32, f32, i64, i32, p],
     "fmri_slice_channels": [p, i32, i32, p, i32, i64, i32, i32, p],

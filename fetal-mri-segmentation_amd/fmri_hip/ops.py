@@ -1080,6 +1080,136 @@ def gaussian_gradient_magnitude_f64(vol, sigma, truncate=4.0):
     return d0
 
 
+# ---------------------------------------------------------------------------------------------------- evaluation (postprocess.hip)
+def _masks_u8(*masks):
+    _need_cuda(*masks)
+    for m in masks:
+        if m.dtype != torch.uint8 or m.dim() != 3 or m.numel() == 0:
+            raise ValueError("a non-empty uint8 volume [X,Y,Z] is needed (got %s %s)" % (m.dtype, tuple(m.shape)))
+        if m.shape != masks[0].shape or m.device != masks[0].device:
+            raise ValueError("the two masks differ in shape or device (%s, %s)" % (tuple(masks[0].shape), tuple(m.shape)))
+
+
+def _connectivity(connectivity):
+    if connectivity not in (1, 2, 3):
+        raise ValueError("connectivity: 1, 2 or 3 (scipy.ndimage.generate_binary_structure(3, connectivity)), got %r" % (connectivity,))
+    return int(connectivity)
+
+
+def seg_counts_u8(a, b):
+    """(|A|, |B|, |A n B|) as Python ints of two uint8 device volumes (nonzero = in the mask): exact integer sums"""
+    _masks_u8(a, b)
+    with torch.cuda.device(a.device):
+        out = torch.empty(3, dtype=torch.int64, device=a.device)
+        check(lib().fmri_seg_counts_u8(_p(a), _p(b), a.numel(), _p(out), _s()), "fmri_seg_counts_u8")
+    return tuple(int(v) for v in out.tolist())
+
+
+def _surface(a, b, connectivity, counts):
+    """enqueue the border extraction of a (and b, or None) -> their inverted borders; counts: int64 device tensor of 1 (2) entries"""
+    X, Y, Z = a.shape
+    inv_a = torch.empty_like(a)
+    inv_b = None if b is None else torch.empty_like(b)
+    check(lib().fmri_surface_u8(_p(a), _p(inv_a), _p(b), _p(inv_b), X, Y, Z, connectivity, _p(counts), _s()), "fmri_surface_u8")
+    return inv_a, inv_b
+
+
+def surface_u8(mask, connectivity=1):
+    """(inv_border, count): inv_border is 0 on the surface voxels of a uint8 device volume and 1 elsewhere - the complement of
+    mask ^ scipy.ndimage.binary_erosion(mask, generate_binary_structure(3, connectivity)), so a foreground voxel on a volume face is
+    surface - which is the input distance_transform_edt_u8 turns into the distance to the nearest surface voxel; count = the number of
+    surface voxels."""
+    _masks_u8(mask)
+    connectivity = _connectivity(connectivity)
+    with torch.cuda.device(mask.device):
+        count = torch.empty(1, dtype=torch.int64, device=mask.device)
+        inv, _ = _surface(mask, None, connectivity, count)
+    return inv, int(count.item())
+
+
+def _compact(field, inv_sel, out, cursor):
+    check(lib().fmri_masked_compact_f64(_p(field), _p(inv_sel), field.numel(), _p(out), out.numel(), _p(cursor), _s()),
+          "fmri_masked_compact_f64")
+
+
+def surface_distances_f64(result, reference, sampling=None, connectivity=1):
+    """The distances from every surface voxel of `result` to the nearest surface voxel of `reference` (medpy's
+    __surface_distances: distance_transform_edt(~reference_border, sampling)[result_border]) as a dense float64 device tensor, in no
+    particular order.  `result` without a surface gives an empty tensor; `reference` without one gives +inf for every entry (there is
+    no nearest voxel) without running the distance transform."""
+    _masks_u8(result, reference)
+    connectivity = _connectivity(connectivity)
+    sampling = _edt_sampling(sampling)
+    dev = result.device
+    with torch.cuda.device(dev):
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        inv_r, inv_f = _surface(result, reference, connectivity, counts)
+        n_r, n_f = (int(v) for v in counts.tolist())
+        if n_r == 0 or n_f == 0:
+            return torch.full((n_r,), float("inf"), dtype=torch.float64, device=dev)
+        field = _edt(inv_f, sampling, False)
+        out = torch.empty(n_r, dtype=torch.float64, device=dev)
+        cursor = torch.zeros(1, dtype=torch.int64, device=dev)
+        _compact(field, inv_r, out, cursor)
+    return out
+
+
+_NAN = float("nan")
+
+
+def _scores(a, b, sampling, connectivity, percentile, with_counts):
+    _masks_u8(a, b)
+    connectivity = _connectivity(connectivity)
+    sampling = _edt_sampling(sampling)
+    L = lib()
+    dev = a.device
+    n = a.numel()
+    with torch.cuda.device(dev):
+        ints = torch.zeros(5, dtype=torch.int64, device=dev)                # |A|, |B|, |A n B|, surface voxels of A, of B
+        if with_counts:
+            check(L.fmri_seg_counts_u8(_p(a), _p(b), n, _p(ints), _s()), "fmri_seg_counts_u8")
+        inv_a, inv_b = _surface(a, b, connectivity, ints[3:])
+        c = [int(v) for v in ints.tolist()]                                 # the one read-back in front of the distance transforms
+        n_a, n_b = c[3], c[4]
+        res = {"hd": _NAN, "hd95": _NAN, "assd": _NAN, "n_surface": (n_a, n_b)}
+        if with_counts:
+            res["counts"] = tuple(c[:3])
+        if n_a == 0 or n_b == 0:                                             # an empty mask: no surface, the field would be +inf
+            return res
+        dist = torch.empty(n_a + n_b, dtype=torch.float64, device=dev)       # d(A -> B), then d(B -> A)
+        cursor = torch.zeros(1, dtype=torch.int64, device=dev)
+        stats = torch.empty(4, dtype=torch.float64, device=dev)
+        ws = torch.empty(L.fmri_masked_stats_workspace_bytes(), dtype=torch.uint8, device=dev)
+        for k, (sel, other) in enumerate(((inv_a, inv_b), (inv_b, inv_a))):
+            field = _edt(other, sampling, False)
+            check(L.fmri_masked_stats_f64(_p(field), _p(sel), n, stats.data_ptr() + 16 * k, _p(ws), _s()), "fmri_masked_stats_f64")
+            _compact(field, sel, dist, cursor)
+            del field
+        hd95 = float(percentile_f64(dist, percentile))
+        s_ab, m_ab, s_ba, m_ba = stats.tolist()
+        if int(cursor.item()) != n_a + n_b:
+            raise RuntimeError("the compaction kept %d distances, the surfaces hold %d" % (int(cursor.item()), n_a + n_b))
+    res.update(hd=max(m_ab, m_ba), hd95=hd95, assd=(s_ab / n_a + s_ba / n_b) / 2)
+    return res
+
+
+def surface_metrics_u8(a, b, sampling=None, connectivity=1, percentile=95):
+    """medpy.metric.binary's hd, hd95 and assd of two uint8 device volumes (nonzero = in the mask; sampling = the voxel spacing) ->
+    {"hd": max(max d(A->B), max d(B->A)), "hd95": np.percentile(hstack(d(A->B), d(B->A)), percentile), "assd": mean(mean d(A->B),
+    mean d(B->A)), "n_surface": (nA, nB)} with d(A->B) the distances of surface_distances_f64(a, b).  One surface launch for both
+    masks, a read-back of the two counts, then per direction a distance transform, a masked sum / max and a compaction, and the radix
+    select of percentile_f64 on the compacted distances.  hd and hd95 are exact functions of the distance field; the sum behind assd
+    is added in a fixed order (two calls agree bit for bit).  A mask without a voxel: the three metrics are NaN and no distance
+    transform runs."""
+    return _scores(a, b, sampling, connectivity, percentile, False)
+
+
+def segmentation_scores_u8(a, b, sampling=None, connectivity=1, percentile=95):
+    """surface_metrics_u8 plus "counts": (|A|, |B|, |A n B|), the integers every overlap score is a ratio of, counted in front of the
+    surface launch and read back with the surface counts (fetal_net.evaluate.evaluate_case)"""
+    return _scores(a, b, sampling, connectivity, percentile, True)
+
+
 def avgpool_fwd(x, y, planar=False):
     """x [N,D,H,W,C] -> y [N,D//2,H//2,W//2,C] (planar: [N,D,H//2,W//2,C]); AveragePooling3D() / AveragePooling2D()"""
     _need_cuda(x, y)

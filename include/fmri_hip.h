@@ -551,6 +551,27 @@ int fmri_correlate1d_asym_f64(const double* src, double* dst, int X, int Y, int 
                               fmri_stream_t stream);
 int fmri_grad_magnitude_combine_f64(const double* d0, const double* d1, const double* d2, double* out, int64_t n, fmri_stream_t stream);
 
+/* ---- scoring a predicted mask against the truth (reference fetal/evaluate.py; the surface metrics are medpy.metric.binary's hd, hd95
+ * and assd).  uint8 volumes [X][Y][Z], z contiguous; a voxel belongs to a mask when its byte is nonzero.  Every entry point needs n > 0.
+ * fmri_seg_counts_u8: out3 (device) = {|A|, |B|, |A n B|}, exact.
+ * fmri_surface_u8: inv_border[v] = 0 where mask[v] is foreground and one of its neighbours of
+ *   scipy.ndimage.generate_binary_structure(3, connectivity) (6 / 18 / 26 for connectivity 1 / 2 / 3) is background or lies outside the
+ *   volume, 1 elsewhere: the complement of mask ^ binary_erosion(mask, structure), scipy's border_value = 0.  fmri_edt_u8(inv_border) is
+ *   then the distance of every voxel to the nearest border voxel.  count[0] (device) = the number of border voxels.  mask2 / inv_border2
+ *   (both or neither; NULL = one volume): a second volume of the same shape in the same launch, its number in count[1].
+ * fmri_masked_stats_f64: out2 (device) = {sum, max} of values[i] over the i with inv_sel[i] == 0 ({0, -inf} when there is none).  The
+ *   max is exact; the sum is added in an order fixed by n (per-workgroup partials in `workspace`,
+ *   fmri_masked_stats_workspace_bytes() bytes on the device, then one workgroup over the partials): two calls agree bit for bit.
+ * fmri_masked_compact_f64: the same selection copied densely to out[*cursor], out[*cursor + 1], ... in unspecified order; *cursor
+ *   (device, set by the caller) ends advanced by the number selected.  Slots at or past `capacity` are not written. */
+int fmri_seg_counts_u8(const uint8_t* a, const uint8_t* b, int64_t n, int64_t* out3, fmri_stream_t stream);
+int fmri_surface_u8(const uint8_t* mask, uint8_t* inv_border, const uint8_t* mask2, uint8_t* inv_border2, int X, int Y, int Z,
+                    int connectivity, int64_t* count, fmri_stream_t stream);
+int64_t fmri_masked_stats_workspace_bytes(void);
+int fmri_masked_stats_f64(const double* values, const uint8_t* inv_sel, int64_t n, double* out2, void* workspace, fmri_stream_t stream);
+int fmri_masked_compact_f64(const double* values, const uint8_t* inv_sel, int64_t n, double* out, int64_t capacity, int64_t* cursor,
+                            fmri_stream_t stream);
+
 /* ---- PatchGAN discriminator head and the adversarial coupling.  Reference
  * fetal_net/model/discriminator/all_dis_3d.py:11-72 (conv blocks of the segmentation path's layer kinds + AveragePooling3D,
  * GlobalAveragePooling3D, Dense(128, LeakyReLU) x fc_layers, Dense(1, 'sigmoid'), loss binary_crossentropy, metric 'mae') and
