@@ -232,6 +232,199 @@ extern "C" int fmri_upsample_nearest2x_bwd(const void* dy, int dy_ld, int dy_off
     return FMRI_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ max-pool / nearest up-sampling, per-axis factors
+// MaxPooling3D(pool_size) / UpSampling3D(size) of the reference's builders with a window other than 2x2x2 - (2, 2, 1) for the anisotropic
+// fetal volumes - or, planar, MaxPooling2D / UpSampling2D as (1, ph, pw).  Factors 1..4 per axis, stride = window: every fine voxel belongs
+// to exactly one window, so one thread (one channel vector) owns a window and writes all of its children - no atomics.  Same arithmetic
+// as the 2x kernels above, in the same (d, h, w) scan order; the windows are walked by run-time loops, nothing window-sized is kept in
+// registers (a 4x4x4 window is 64 voxels): the backward max-pool reads x twice - find the maximum, then route.
+struct PoolDims {
+    int D, H, W;          // coarse dims
+    int pd, ph, pw;
+};
+__device__ __forceinline__ int64_t fine_vox(const PoolDims& p, int n, int d, int h, int w, int a, int b, int c) {
+    return (((int64_t)n * (p.D * p.pd) + d * p.pd + a) * (p.H * p.ph) + h * p.ph + b) * (p.W * p.pw) + w * p.pw + c;
+}
+
+template <typename T, int VEC>
+__global__ void __launch_bounds__(256) k_maxpool_p_fwd(const T* __restrict__ x, T* __restrict__ y, int N, int C, PoolDims p) {
+    const int CG = C / VEC;
+    const int64_t total = (int64_t)N * p.D * p.H * p.W * CG;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int cg = (int)(i % CG), n, d, h, w;
+        decode_vox(i / CG, p.D, p.H, p.W, n, d, h, w);
+        float m[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) m[k] = -INFINITY;
+        for (int a = 0; a < p.pd; ++a)
+            for (int b = 0; b < p.ph; ++b)
+                for (int c = 0; c < p.pw; ++c) {
+                    float xv[VEC];
+                    ldv<T, VEC>(x + fine_vox(p, n, d, h, w, a, b, c) * C + cg * VEC, xv);
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) m[k] = fmaxf(m[k], xv[k]);
+                }
+        stv<T, VEC>(y + (i / CG) * C + cg * VEC, m);
+    }
+}
+
+template <typename T, int VEC>
+__global__ void __launch_bounds__(256) k_maxpool_p_bwd(const T* __restrict__ x, const T* __restrict__ dy, const T* __restrict__ add, int add_ld,
+                                                       int add_off, T* __restrict__ dx, int N, int C, int relu_mask, PoolDims p) {
+    const int CG = C / VEC;
+    const int64_t total = (int64_t)N * p.D * p.H * p.W * CG;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int cg = (int)(i % CG), n, d, h, w;
+        decode_vox(i / CG, p.D, p.H, p.W, n, d, h, w);
+        float m[VEC], g[VEC];
+        bool taken[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) { m[k] = -INFINITY; taken[k] = false; }
+        for (int a = 0; a < p.pd; ++a)                       // pass 1: the window's maximum
+            for (int b = 0; b < p.ph; ++b)
+                for (int c = 0; c < p.pw; ++c) {
+                    float xv[VEC];
+                    ldv<T, VEC>(x + fine_vox(p, n, d, h, w, a, b, c) * C + cg * VEC, xv);
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) m[k] = fmaxf(m[k], xv[k]);
+                }
+        ldv<T, VEC>(dy + (i / CG) * C + cg * VEC, g);
+        for (int a = 0; a < p.pd; ++a)                       // pass 2: dy to the first maximum in scan order, + skip gradient, ReLU mask
+            for (int b = 0; b < p.ph; ++b)
+                for (int c = 0; c < p.pw; ++c) {
+                    const int64_t v = fine_vox(p, n, d, h, w, a, b, c);
+                    float xv[VEC], r[VEC], s[VEC];
+                    ldv<T, VEC>(x + v * C + cg * VEC, xv);
+                    if (add) ldv<T, VEC>(add + v * add_ld + add_off + cg * VEC, s);
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) {
+                        float rr = 0.f;
+                        if (!taken[k] && xv[k] == m[k]) { rr = g[k]; taken[k] = true; }
+                        if (add) rr += s[k];
+                        if (relu_mask && !(xv[k] > 0.f)) rr = 0.f;
+                        r[k] = rr;
+                    }
+                    stv<T, VEC>(dx + v * C + cg * VEC, r);
+                }
+    }
+}
+
+template <typename T, int VEC>
+__global__ void __launch_bounds__(256) k_upsample_p_fwd(const T* __restrict__ x, T* __restrict__ y, int y_ld, int y_off, int N, int C, PoolDims p) {
+    const int CG = C / VEC;
+    const int64_t total = (int64_t)N * p.D * p.H * p.W * CG;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int cg = (int)(i % CG), n, d, h, w;
+        decode_vox(i / CG, p.D, p.H, p.W, n, d, h, w);
+        float v[VEC];
+        ldv<T, VEC>(x + (i / CG) * C + cg * VEC, v);
+        for (int a = 0; a < p.pd; ++a)
+            for (int b = 0; b < p.ph; ++b)
+                for (int c = 0; c < p.pw; ++c) stv<T, VEC>(y + fine_vox(p, n, d, h, w, a, b, c) * y_ld + y_off + cg * VEC, v);
+    }
+}
+
+template <typename T, int VEC>
+__global__ void __launch_bounds__(256) k_upsample_p_bwd(const T* __restrict__ dy, int dy_ld, int dy_off, const T* __restrict__ xmask,
+                                                        T* __restrict__ dx, int N, int C, PoolDims p) {
+    const int CG = C / VEC;
+    const int64_t total = (int64_t)N * p.D * p.H * p.W * CG;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int cg = (int)(i % CG), n, d, h, w;
+        decode_vox(i / CG, p.D, p.H, p.W, n, d, h, w);
+        float acc[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+        for (int a = 0; a < p.pd; ++a)
+            for (int b = 0; b < p.ph; ++b)
+                for (int c = 0; c < p.pw; ++c) {
+                    float g[VEC];
+                    ldv<T, VEC>(dy + fine_vox(p, n, d, h, w, a, b, c) * dy_ld + dy_off + cg * VEC, g);
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) acc[k] += g[k];
+                }
+        if (xmask) {
+            float m[VEC];
+            ldv<T, VEC>(xmask + (i / CG) * C + cg * VEC, m);
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) if (!(m[k] > 0.f)) acc[k] = 0.f;
+        }
+        stv<T, VEC>(dx + (i / CG) * C + cg * VEC, acc);
+    }
+}
+
+// factors 1..4 per axis, not all 1 (that is a copy, not a pooling layer)
+static inline bool pool_factors_ok(int pd, int ph, int pw) {
+    if (pd < 1 || pd > 4 || ph < 1 || ph > 4 || pw < 1 || pw > 4) return false;
+    return pd * ph * pw > 1;
+}
+
+extern "C" int fmri_maxpool3d_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int pd, int ph, int pw, int dtype,
+                                  fmri_stream_t stream) {
+    if (N <= 0 || C <= 0 || D < 1 || H < 1 || W < 1 || !pool_factors_ok(pd, ph, pw) || D % pd || H % ph || W % pw) return FMRI_E_SHAPE;
+    const PoolDims p = {D / pd, H / ph, W / pw, pd, ph, pw};
+    int vec = pick_vec(C);
+    int grid = grid_for((int64_t)N * p.D * p.H * p.W * (C / vec));
+    hipStream_t s = as_stream(stream);
+    if (dtype == FMRI_F32) LAUNCH_TV(k_maxpool_p_fwd, float, vec, grid, 256, s, (const float*)x, (float*)y, N, C, p);
+    else if (dtype == FMRI_BF16) LAUNCH_TV(k_maxpool_p_fwd, bf16_t, vec, grid, 256, s, (const bf16_t*)x, (bf16_t*)y, N, C, p);
+    else return FMRI_E_DTYPE;
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_maxpool3d_bwd(const void* x, const void* dy, const void* add, int add_ld, int add_off, void* dx, int N, int D, int H,
+                                  int W, int C, int pd, int ph, int pw, int relu_mask, int dtype, fmri_stream_t stream) {
+    if (N <= 0 || C <= 0 || D < 1 || H < 1 || W < 1 || !pool_factors_ok(pd, ph, pw) || D % pd || H % ph || W % pw) return FMRI_E_SHAPE;
+    if (add && (add_off < 0 || add_ld < add_off + C)) return FMRI_E_SHAPE;
+    const PoolDims p = {D / pd, H / ph, W / pw, pd, ph, pw};
+    int vec = pick_vec(C);
+    if (add) { while (vec > 1 && ((add_ld % vec) || (add_off % vec))) vec >>= 1; }
+    int grid = grid_for((int64_t)N * p.D * p.H * p.W * (C / vec));
+    hipStream_t s = as_stream(stream);
+    if (dtype == FMRI_F32)
+        LAUNCH_TV(k_maxpool_p_bwd, float, vec, grid, 256, s, (const float*)x, (const float*)dy, (const float*)add, add_ld, add_off,
+                  (float*)dx, N, C, relu_mask, p);
+    else if (dtype == FMRI_BF16)
+        LAUNCH_TV(k_maxpool_p_bwd, bf16_t, vec, grid, 256, s, (const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)add, add_ld, add_off,
+                  (bf16_t*)dx, N, C, relu_mask, p);
+    else return FMRI_E_DTYPE;
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_upsample_nearest_fwd(const void* x, void* y, int y_ld, int y_off, int N, int D, int H, int W, int C, int pd, int ph,
+                                         int pw, int dtype, fmri_stream_t stream) {
+    if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || !pool_factors_ok(pd, ph, pw) || y_off < 0 || y_ld < y_off + C) return FMRI_E_SHAPE;
+    const PoolDims p = {D, H, W, pd, ph, pw};
+    int vec = pick_vec(C);
+    while (vec > 1 && ((y_ld % vec) || (y_off % vec))) vec >>= 1;
+    int grid = grid_for((int64_t)N * D * H * W * (C / vec));
+    hipStream_t s = as_stream(stream);
+    if (dtype == FMRI_F32) LAUNCH_TV(k_upsample_p_fwd, float, vec, grid, 256, s, (const float*)x, (float*)y, y_ld, y_off, N, C, p);
+    else if (dtype == FMRI_BF16) LAUNCH_TV(k_upsample_p_fwd, bf16_t, vec, grid, 256, s, (const bf16_t*)x, (bf16_t*)y, y_ld, y_off, N, C, p);
+    else return FMRI_E_DTYPE;
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_upsample_nearest_bwd(const void* dy, int dy_ld, int dy_off, const void* xmask, void* dx, int N, int D, int H, int W,
+                                         int C, int pd, int ph, int pw, int dtype, fmri_stream_t stream) {
+    if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || !pool_factors_ok(pd, ph, pw) || dy_off < 0 || dy_ld < dy_off + C) return FMRI_E_SHAPE;
+    const PoolDims p = {D, H, W, pd, ph, pw};
+    int vec = pick_vec(C);
+    while (vec > 1 && ((dy_ld % vec) || (dy_off % vec))) vec >>= 1;
+    int grid = grid_for((int64_t)N * D * H * W * (C / vec));
+    hipStream_t s = as_stream(stream);
+    if (dtype == FMRI_F32)
+        LAUNCH_TV(k_upsample_p_bwd, float, vec, grid, 256, s, (const float*)dy, dy_ld, dy_off, (const float*)xmask, (float*)dx, N, C, p);
+    else if (dtype == FMRI_BF16)
+        LAUNCH_TV(k_upsample_p_bwd, bf16_t, vec, grid, 256, s, (const bf16_t*)dy, dy_ld, dy_off, (const bf16_t*)xmask, (bf16_t*)dx, N, C, p);
+    else return FMRI_E_DTYPE;
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ final 1x1x1 conv
 // Reference: Conv3D(n_labels,(1,1,1)) at unet3d/unet.py:68.  AI ~ 1 flop/B: one pass over x, C small (<= 256).
 // One thread per voxel, channel loop vectorised; weights broadcast from LDS.

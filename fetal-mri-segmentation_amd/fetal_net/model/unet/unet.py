@@ -1,8 +1,10 @@
 """`unet_model_2d` with the reference signature and topology (reference fetal_net/model/unet/unet.py:22-141): the 2-D twin of
-unet_model_3d with channels-LAST input (X, Y, C) wrapped in Permute layers, optional SpatialDropout2D."""
+unet_model_3d with channels-LAST input (X, Y, C) wrapped in Permute layers, optional SpatialDropout2D.  pool_size (2, 2) without dropout
+runs on the hand-scheduled engine; other pool sizes (per-axis factors 1..4) and dropout_rate > 0 on the layer-graph engine (UpSampling2D only)."""
 from ...engine_model import Adam, Model
 from ...metrics import dice_coefficient, dice_coefficient_loss, vod_coefficient
 from ..graph import Graph
+from ..unet3d.unet import check_pool_divides, pool_route
 
 
 def _block(g, x, n_filters, batch_normalization):
@@ -17,6 +19,9 @@ def unet_model_2d(input_shape, pool_size=(2, 2), n_labels=1, initial_learning_ra
                   activation_name="sigmoid", loss_function=dice_coefficient_loss, dropout_rate=0, **kargs):
     input_shape = tuple(int(v) for v in input_shape)
     pool_size = tuple(pool_size)
+    graph_engine, refused = pool_route(pool_size, 2, deconvolution, dropout=dropout_rate > 0)
+    if not deconvolution and refused is None:
+        check_pool_divides(input_shape[:2], pool_size, depth)
     g = Graph()
     x = g.input(input_shape)
     h = g.permute(x, (3, 1, 2))
@@ -48,13 +53,13 @@ def unet_model_2d(input_shape, pool_size=(2, 2), n_labels=1, initial_learning_ra
     plan_args = dict(in_channels=input_shape[-1], spatial=input_shape[:2], depth=depth, n_base_filters=n_base_filters,
                      n_labels=n_labels, ndim=2, norm="batch" if batch_normalization else None, deconvolution=bool(deconvolution))
     model = Model(g.layers, plan_args, "unet_model_2d", builder_kwargs, "channels_last_2d")
+    if graph_engine:
+        model._graph_engine = True        # pool sizes other than (2, 2) and SpatialDropout2D: the layer-graph engine, planar
     unsupported = []
-    if pool_size != (2, 2):
-        unsupported.append("pool_size != (2,2)")
+    if refused:
+        unsupported.append(refused)
     if activation_name != "sigmoid":
         unsupported.append("activation_name != 'sigmoid'")
-    if dropout_rate > 0:
-        unsupported.append("dropout_rate > 0 (SpatialDropout2D)")
     if unsupported:
         model._unsupported = ", ".join(unsupported)
     metrics = ['binary_accuracy', vod_coefficient]

@@ -4,7 +4,8 @@ a Keras-Model duck type whose compute runs on the MI355X engine.
 Topology: `depth` encoder levels of two [Conv3D 3x3x3 'same' -> (BatchNorm | InstanceNorm)? -> ReLU] blocks with
 n_base_filters*2^level and twice that many filters, MaxPooling3D between levels; decoder levels of
 (UpSampling3D | Conv3DTranspose k2 s2) -> concatenate([up, skip], axis=1) -> two conv blocks with the skip's filter count;
-Conv3D(n_labels, 1x1x1) -> Activation(activation_name).  Compiled with Adam(lr) and metrics
+Conv3D(n_labels, 1x1x1) -> Activation(activation_name).  pool_size (2, 2, 2) runs on the hand-scheduled engine; any other pool size with
+per-axis factors 1..4 - (2, 2, 1) for anisotropic volumes - on the layer-graph engine (UpSampling3D only).  Compiled with Adam(lr) and metrics
 ['binary_accuracy', vod_coefficient] (+ dice_coefficient when the loss is not the Dice loss).
 """
 from ...engine_model import Adam, Model
@@ -34,11 +35,42 @@ def up_block(g, x, pool_size, deconvolution, kernel_size=(2, 2, 2), strides=(2, 
     return g.up_sample(x, pool_size)
 
 
+def pool_route(pool_size, nd, deconvolution, dropout=False):
+    """How a U-Net with these options runs.  -> (graph_engine, refused): graph_engine = True sends the model to the layer-graph engine -
+    a pool size other than all 2s (per-axis factors 1..4, its pooling / up-sampling kernels take the factors at run time) or, 2-D,
+    SpatialDropout2D (`dropout`); refused = why the model cannot run at all, or None.  All 2s without dropout keeps the hand-scheduled
+    engine."""
+    twos = tuple(pool_size) == (2,) * nd
+    if twos and not dropout:
+        return False, None
+    if len(pool_size) != nd or not all(float(p).is_integer() and 1 <= p <= 4 for p in pool_size):
+        return False, "pool_size %s: the pooling kernels take per-axis factors 1..4" % (pool_size,)
+    if all(p == 1 for p in pool_size):
+        return False, "pool_size %s pools nothing" % (pool_size,)
+    if deconvolution:
+        what = ([] if twos else ["pool_size %s" % (pool_size,)]) + (["dropout_rate > 0 (SpatialDropout2D)"] if dropout else [])
+        return False, ("%s with deconvolution=True: the reference's transposed convolution up-samples by 2 whatever the pool size, and the "
+                       "layer-graph engine that runs these options has no transposed-convolution op" % " and ".join(what))
+    return True, None
+
+
+def check_pool_divides(input_spatial, pool_size, depth):
+    """ValueError at build time when `depth - 1` poolings do not divide a spatial axis: Keras fails at the concatenate whose up-sampled
+    half has lost voxels; the message names the axis"""
+    for axis, (s, p) in enumerate(zip(input_spatial, pool_size)):
+        if s % (p ** (depth - 1)):
+            raise ValueError("input_shape: spatial axis %d has %d voxels, not divisible by pool_size %d ** (depth - 1) = %d: the "
+                             "concatenate of the shallowest decoder level would not match" % (axis, s, p, p ** (depth - 1)))
+
+
 def unet_model_3d(input_shape, pool_size=(2, 2, 2), n_labels=1, initial_learning_rate=0.00001, deconvolution=False, depth=4,
                   n_base_filters=32, include_label_wise_dice_coefficients=False, batch_normalization=False,
                   activation_name="sigmoid", loss_function=dice_coefficient_loss, **kargs):
     input_shape = tuple(int(v) for v in input_shape)
     pool_size = tuple(pool_size)
+    graph_engine, refused = pool_route(pool_size, 3, deconvolution)
+    if not deconvolution and refused is None:
+        check_pool_divides(input_shape[1:], pool_size, depth)
     g = Graph()
     x = g.input(input_shape)
     skips = []
@@ -58,8 +90,8 @@ def unet_model_3d(input_shape, pool_size=(2, 2, 2), n_labels=1, initial_learning
     g.activation(h, activation_name)
 
     unsupported = []
-    if pool_size != (2, 2, 2):
-        unsupported.append("pool_size != (2,2,2)")
+    if refused:
+        unsupported.append(refused)
     if activation_name != "sigmoid":
         unsupported.append("activation_name != 'sigmoid'")
     builder_kwargs = dict(input_shape=input_shape, pool_size=pool_size, n_labels=n_labels, initial_learning_rate=initial_learning_rate,
@@ -70,6 +102,8 @@ def unet_model_3d(input_shape, pool_size=(2, 2, 2), n_labels=1, initial_learning
     plan_args = dict(in_channels=input_shape[0], spatial=input_shape[1:], depth=depth, n_base_filters=n_base_filters,
                      n_labels=n_labels, ndim=3, norm="batch" if batch_normalization else None, deconvolution=bool(deconvolution))
     model = Model(g.layers, plan_args, "unet_model_3d", builder_kwargs, "channels_first_3d")
+    if graph_engine:
+        model._graph_engine = True
     if unsupported:
         model._unsupported = ", ".join(unsupported)
     metrics = ['binary_accuracy', vod_coefficient]

@@ -49,6 +49,10 @@ SIGNATURES = {
     "fmri_maxpool3d_2x_bwd": [p, p, p, i32, i32, p, i32, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_upsample_nearest2x_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_upsample_nearest2x_bwd": [p, i32, i32, p, p, i32, i32, i32, i32, i32, i32, i32, p],
+    "fmri_maxpool3d_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
+    "fmri_maxpool3d_bwd": [p, p, p, i32, i32, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
+    "fmri_upsample_nearest_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
+    "fmri_upsample_nearest_bwd": [p, i32, i32, p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_norm_act_fwd": [p, p, p, p, p, p, i32, i64, i32, i32, f32, i32, i32, f32, i32, p],
     "fmri_norm_act_bwd": [p, p, p, p, p, p, p, p, p, i32, i64, i32, i32, i32, f32, i32, p],
     "fmri_norm_act_bwd_x": [p, p, p, p, p, p, p, p, p, i32, i64, i32, i32, i32, f32, i32, p],

@@ -2,7 +2,7 @@
 
 The hand-scheduled `UNetEngine` stays the path of the headline U-Net; this interpreter runs any graph made of the layer
 classes the reference's builders emit — Conv3D (3x3x3 stride 1|2, 1x1x1), InstanceNormalization / BatchNormalization,
-LeakyReLU / Activation('relu'|'sigmoid'), MaxPooling3D, UpSampling3D, Concatenate, Add, SpatialDropout3D — i.e. the Isensee
+LeakyReLU / Activation('relu'|'sigmoid'), MaxPooling3D / UpSampling3D (per-axis factors 1..4), Concatenate, Add, SpatialDropout3D — i.e. the Isensee
 model of reference fetal_net/model/unet3d/isensee2017.py:15-111 (and, for cross-checking, unet_model_3d) — and their 2-D twins
 (Conv2D, UpSampling2D, SpatialDropout2D, MaxPooling2D between two Permute layers: reference fetal_net/model/unet/isensee.py:14-105).
 A graph may also end in Dense(1, 'sigmoid') on a GlobalAveragePooling3D (the PatchGAN discriminator of reference
@@ -13,7 +13,7 @@ adversarial experiments is trained with (reference fetal/experiments/train_adv.p
 the slice axis, pooling / up-sampling / stride in X and Y only), a 2-D filter is the centre kd plane of a 27-tap image.
 
 Compile-time fusions (nothing of the fused kind is ever materialised):
-  * UpSampling3D -> Conv3D(3x3x3)          => conv reads its source through the fused nearest x2 (up0)
+  * UpSampling3D(2) -> Conv3D(3x3x3)       => conv reads its source through the fused nearest x2 (up0); other sizes are materialised
   * Concatenate([a, b]) -> Conv3D(3x3x3)   => dual-source conv
   * Norm -> LeakyReLU | Activation('relu') => fmri_norm_act_fwd/bwd
   * Conv3D -> Activation('relu')           => activation in the conv epilogue
@@ -108,13 +108,20 @@ class LayerGraphEngine(EngineBase):
             c = consumers[name]
             return len(c) == 1 and (cls is None or self.by_name[c[0]].class_name in cls)
 
+        def window(l, key):
+            """per-axis factors of a pooling / up-sampling layer; None = all 2s, the path of the 2x kernels (and of the fused up0)"""
+            size = tuple(int(v) for v in (l.config.get(key) or (2,) * nd))
+            if len(size) != nd or not all(1 <= v <= 4 for v in size) or all(v == 1 for v in size):
+                raise NotImplementedError("%s %s of layer %s: per-axis factors 1..4, not all 1" % (key, size, l.name))
+            return None if size == (2,) * nd else size
+
         # producers that a later 3x3x3 stride-1 conv reads through (fused up-sampling / concatenation): decided up front because
         # they precede their consumer in the layer list
         for l in L:
             if l.class_name == CONV and tuple(l.config["kernel_size"]) == k3 and tuple(l.config.get("strides") or s1) == s1:
                 src = self.by_name[inb[l.name][0]]
-                if src.class_name == UPS and single_consumer(src.name):
-                    absorbed.add(src.name)
+                if src.class_name == UPS and single_consumer(src.name) and window(src, "size") is None:
+                    absorbed.add(src.name)        # (the convs' fused nearest up-sampling is x2 per axis: any other size is materialised)
                 elif src.class_name == "Concatenate" and len(src.inbound) == 2 and single_consumer(src.name):
                     absorbed.add(src.name)
         APOOL, GAP = "AveragePooling%dD" % nd, "GlobalAveragePooling%dD" % nd
@@ -138,7 +145,7 @@ class LayerGraphEngine(EngineBase):
                 op = dict(kind="conv", name=l.name, out=l.name, k=k[0], s=(1 if sub is not None else s[0]), sub=sub, act=ACT_NONE, up0=False,
                           ins=[inb[l.name][0]])
                 if k == k3 and s == s1:
-                    if src.class_name == UPS and single_consumer(src.name):
+                    if src.class_name == UPS and single_consumer(src.name) and window(src, "size") is None:
                         absorbed.add(src.name)
                         op["ins"], op["up0"] = [inb[src.name][0]], True
                     elif src.class_name == "Concatenate" and len(src.inbound) == 2 and single_consumer(src.name):
@@ -163,9 +170,9 @@ class LayerGraphEngine(EngineBase):
             elif cn == DROP:
                 self.ops.append(dict(kind="dropout", out=l.name, ins=[inb[l.name][0]], rate=float(l.config.get("rate", 0.0))))
             elif cn == UPS:
-                self.ops.append(dict(kind="upsample", out=l.name, ins=[inb[l.name][0]]))
+                self.ops.append(dict(kind="upsample", out=l.name, ins=[inb[l.name][0]], pool=window(l, "size")))
             elif cn == POOL:
-                self.ops.append(dict(kind="maxpool", out=l.name, ins=[inb[l.name][0]]))
+                self.ops.append(dict(kind="maxpool", out=l.name, ins=[inb[l.name][0]], pool=window(l, "pool_size")))
             elif cn == APOOL:
                 if tuple(l.config.get("pool_size")) != (2,) * nd:
                     raise NotImplementedError("AveragePooling with pool_size %s" % (l.config.get("pool_size"),))
@@ -588,9 +595,9 @@ class LayerGraphEngine(EngineBase):
                     self.drop[o["out"]] = None
                     ops.cast(src, out)                      # identity copy keeps the tensor table simple
             elif kind == "upsample":
-                ops.upsample_fwd(self._t(o["ins"][0]), out, planar=self.planar)
+                ops.upsample_fwd(self._t(o["ins"][0]), out, planar=self.planar, pool=o["pool"])
             elif kind == "maxpool":
-                ops.maxpool_fwd(self._t(o["ins"][0]), out, planar=self.planar)
+                ops.maxpool_fwd(self._t(o["ins"][0]), out, planar=self.planar, pool=o["pool"])
             elif kind == "avgpool":
                 ops.avgpool_fwd(self._t(o["ins"][0]), out, planar=self.planar)
             elif kind == "gap":
@@ -763,10 +770,10 @@ class LayerGraphEngine(EngineBase):
                 else:
                     self._accum(o["ins"][0], lambda dst: ops.channel_scale(self._smp(g), sc, self._smp(dst)))
             elif kind == "upsample":
-                self._accum(o["ins"][0], lambda dst: ops.upsample_bwd(g, dst, dy_off=0, planar=self.planar))
+                self._accum(o["ins"][0], lambda dst: ops.upsample_bwd(g, dst, dy_off=0, planar=self.planar, pool=o["pool"]))
             elif kind == "maxpool":
                 src = o["ins"][0]
-                self._accum(src, lambda dst: ops.maxpool_bwd(self._t(src), g, dst, relu_mask=False, planar=self.planar))
+                self._accum(src, lambda dst: ops.maxpool_bwd(self._t(src), g, dst, relu_mask=False, planar=self.planar, pool=o["pool"]))
             elif kind == "avgpool":
                 self._accum(o["ins"][0], lambda dst: ops.avgpool_bwd(g, dst, planar=self.planar))
             elif kind == "gap":

@@ -244,6 +244,21 @@ int fmri_upsample_nearest2x_fwd(const void* x, void* y, int y_ld, int y_off, int
 int fmri_upsample_nearest2x_bwd(const void* dy, int dy_ld, int dy_off, const void* xmask, void* dx, int N, int D, int H,
                                 int W, int C, int dtype, int planar, fmri_stream_t stream);
 
+/* ---- MaxPooling3D(pool_size) / UpSampling3D(size) with per-axis factors pd, ph, pw in 1..4 (not all 1), stride = window - the
+ * anisotropic (2, 2, 1) of reference configs; a 2-D layer of a planar tensor is (1, ph, pw).  Same arithmetic, tie rule (first maximum
+ * in (d, h, w) scan order), fused skip-gradient add / ReLU mask / xmask and fp32 child sum as the 2x entries above, which stay the path
+ * of 2x2x2 windows.  FMRI_E_SHAPE: a factor outside 1..4, all factors 1, a pooled dimension that is no multiple of its factor, a
+ * channel slice [off, off + C) that does not fit in ld.
+ * fmri_maxpool3d_*: D,H,W are the INPUT dims.  fmri_upsample_nearest_*: D,H,W are the LOW-resolution dims. */
+int fmri_maxpool3d_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int pd, int ph, int pw, int dtype,
+                       fmri_stream_t stream);
+int fmri_maxpool3d_bwd(const void* x, const void* dy, const void* add, int add_ld, int add_off, void* dx, int N, int D, int H,
+                       int W, int C, int pd, int ph, int pw, int relu_mask, int dtype, fmri_stream_t stream);
+int fmri_upsample_nearest_fwd(const void* x, void* y, int y_ld, int y_off, int N, int D, int H, int W, int C, int pd, int ph,
+                              int pw, int dtype, fmri_stream_t stream);
+int fmri_upsample_nearest_bwd(const void* dy, int dy_ld, int dy_off, const void* xmask, void* dx, int N, int D, int H, int W,
+                              int C, int pd, int ph, int pw, int dtype, fmri_stream_t stream);
+
 /* ---- BatchNormalization(axis=1) / keras-contrib InstanceNormalization(axis=1) fused with the block's activation — reference
  * unet.py:103-115.  x, y: [N][V][C] (V = D*H*W voxels).  per_instance = 0: statistics over all N*V voxels per channel (Keras
  * training-mode batch norm, eps inside the sqrt); 1: per (sample, channel) (instance norm; eps_on_std = 1 reproduces

@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Max-pooling / nearest up-sampling with per-axis factors (`fmri_maxpool3d_fwd / _bwd`, `fmri_upsample_nearest_fwd / _bwd`) next to the 2x
+kernels, and the models that use them.  Three sections (`--only kernels|model|bound`, default all):
+
+kernels  bf16, the headline level-0 tensor 4 x 64 x 128 x 128 x 64 as the FINE side of every launch: the 2x kernels, the new kernels at
+         pool (2, 2, 2) on the same tensors, the new kernels at pool (2, 2, 1).  Device events around 20 back-to-back launches, 7 rounds with
+         the variants alternated inside a round, 2 warm-up rounds; median of the rounds, their min and max, and the bytes the launch has to
+         move (every tensor once) over the median.  Nothing in the product switches to the new kernels for (2, 2, 2): a report, not a gate.
+model    ms per training step of unet_model_3d(pool_size=(2, 2, 1)) beside the (2, 2, 2) model, both bf16 at batch 4 x 128 x 128 x 16, depth 4,
+         32 filters, both on the layer-graph engine; 5 alternated rounds of 20 steps after 10 warm-up steps each.
+bound    the bf16 (channel-padded) layer-graph engine against the fp32 one on unet_model_3d(input_shape=(1, 16, 16, 16), depth=3,
+         n_base_filters=4), pool (2, 2, 2): max |logits_bf16 - logits_fp32| / max |logits_fp32| with the weights and the batch of
+         tests/test_gpu_pool_sizes.py::test_unet3d_anisotropic_pool_bf16_padded_engine, whose bound is twice this figure.  This section uses
+         nothing this pool-size work added: `--root` points it at a checkout of the commit before it.
+"""
+import argparse
+import os
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--only", choices=["kernels", "model", "bound"], default=None)
+ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="repository root to import from")
+args = ap.parse_args()
+sys.path.insert(0, args.root)
+sys.path.insert(0, os.path.join(args.root, "fetal-mri-segmentation_amd"))
+import numpy as np
+import torch
+import bench
+from fmri_hip import ops
+
+assert torch.cuda.is_available(), "needs the GPU: nothing here has a CPU form"
+print("# kernel_source_hash=%s" % bench.kernel_source_hash())
+
+
+def rounds(variants, calls=20, n_rounds=7, warm=2):
+    """variants: {name: fn}.  -> {name: [ms per call, one per timed round]}, the variants alternated inside every round"""
+    out = {k: [] for k in variants}
+    for r in range(warm + n_rounds):
+        for name, fn in variants.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            b.synchronize()
+            if r >= warm:
+                out[name].append(a.elapsed_time(b) / calls)
+    return out
+
+
+def report(title, times, nbytes=None):
+    for name, t in times.items():
+        med = float(np.median(t))
+        rate = "" if nbytes is None else "; %.3f GB -> %.2f TB/s" % (nbytes[name] / 1e9, nbytes[name] / (med * 1e-3) / 1e12)
+        print("%-22s %-28s median %.4f ms (min %.4f, max %.4f)%s" % (title, name, med, min(t), max(t), rate))
+
+
+def kernels():
+    dt, es = torch.bfloat16, 2
+    g = torch.Generator(device="cuda").manual_seed(1)
+    fine = (4, 64, 128, 128, 64)
+    x = torch.relu(torch.randn(fine, generator=g, device="cuda")).to(dt)           # post-ReLU, as the pooled tensors of the models are
+    dfine = torch.randn(fine, generator=g, device="cuda").to(dt)
+    out_fine = torch.empty(fine, dtype=dt, device="cuda")
+    nf = x.numel() * es
+    print("# bf16, fine tensor %s = %.3f GB; bytes = every tensor of the launch once" % (fine, nf / 1e9))
+    for pool in ((2, 2, 2), (2, 2, 1)):
+        low = (fine[0], fine[1] // pool[0], fine[2] // pool[1], fine[3] // pool[2], fine[4])
+        nl = nf // (pool[0] * pool[1] * pool[2])
+        y = torch.empty(low, dtype=dt, device="cuda")
+        dy = torch.randn(low, generator=g, device="cuda").to(dt)
+        forms = [("new", pool)] + ([("2x", None)] if pool == (2, 2, 2) else [])
+        tag = "pool %s" % (pool,)
+        report(tag, rounds({"maxpool fwd, %s" % f: (lambda p=p: ops.maxpool_fwd(x, y, pool=p)) for f, p in forms}),
+               {"maxpool fwd, %s" % f: nf + nl for f, _ in forms})
+        report(tag, rounds({"maxpool bwd, %s" % f: (lambda p=p: ops.maxpool_bwd(x, dy, out_fine, relu_mask=False, pool=p)) for f, p in forms}),
+               {"maxpool bwd, %s" % f: nf + nl + nf for f, _ in forms})
+        report(tag, rounds({"upsample fwd, %s" % f: (lambda p=p: ops.upsample_fwd(dy, out_fine, pool=p)) for f, p in forms}),
+               {"upsample fwd, %s" % f: nl + nf for f, _ in forms})
+        report(tag, rounds({"upsample bwd, %s" % f: (lambda p=p: ops.upsample_bwd(dfine, y, pool=p)) for f, p in forms}),
+               {"upsample bwd, %s" % f: nf + nl for f, _ in forms})
+
+
+def model():
+    import fetal_net.model as fmodel
+    from fmri_hip.graph_engine import LayerGraphEngine
+    N, sp = 4, (128, 128, 16)
+    g = torch.Generator(device="cuda").manual_seed(2)
+    x = torch.randn((N,) + sp + (1,), generator=g, device="cuda").to(torch.bfloat16)
+    yv = (torch.rand((N,) + sp, generator=g, device="cuda") > 0.7).to(torch.uint8).reshape(-1)
+    engines = {}
+    for pool in ((2, 2, 2), (2, 2, 1)):
+        m = fmodel.unet_model_3d(input_shape=(1,) + sp, pool_size=pool, depth=4, n_base_filters=32)
+        engines["pool %s" % (pool,)] = LayerGraphEngine(m.layers, N, dtype=torch.bfloat16)
+    for e in engines.values():
+        for _ in range(10):
+            e.train_step(x, yv, 1e-5)
+    torch.cuda.synchronize()
+    t = rounds({k: (lambda e=e: e.train_step(x, yv, 1e-5)) for k, e in engines.items()}, calls=20, n_rounds=5, warm=0)
+    report("unet_model_3d step", t)
+    print("# bf16, batch %d x %s, depth 4, 32 filters, layer-graph engine, ms per training step (forward, loss, backward, Adam)" % (N, sp))
+
+
+def bound():
+    import fetal_net.model as fmodel
+    from fmri_hip.graph_engine import LayerGraphEngine
+    from oracle import unet_oracle as O
+    N, sp = 2, (16, 16, 16)
+    m = fmodel.unet_model_3d(input_shape=(1,) + sp, depth=3, n_base_filters=4)
+    W = O.Spec((1,) + sp, depth=3, n_base_filters=4).init_weights(21)
+    r2 = np.random.RandomState(5)
+    for k in W:
+        if k.endswith("/bias"):
+            W[k] = (r2.randn(*W[k].shape) * 0.05).astype(np.float32)
+    x, _ = O.synthetic_batch((N, 1) + sp)
+    logits = {}
+    for dt in (torch.float32, torch.bfloat16):
+        e = LayerGraphEngine(m.layers, N, dtype=dt)
+        e.load_keras_weights(W)
+        e.forward(torch.from_numpy(x).cuda().reshape(N, *sp, 1).to(dt).contiguous())
+        torch.cuda.synchronize()
+        logits[dt] = e.logits.cpu().numpy().copy()
+    lf, lb = logits[torch.float32], logits[torch.bfloat16]
+    print("bf16 padded vs fp32 logits, pool (2, 2, 2): unet_model_3d(input_shape=%s, depth=3, n_base_filters=4), batch %d: "
+          "max |bf16 - fp32| / max |fp32| = %.3e" % ((1,) + sp, N, float(np.abs(lb - lf).max() / np.abs(lf).max())))
+
+
+for name, fn in (("kernels", kernels), ("model", model), ("bound", bound)):
+    if args.only in (None, name):
+        fn()
