@@ -37,6 +37,8 @@ int conv3d_fwd_ntail_slots();
 bool conv3d_first_ok(int C0, int C1, int Cout, int D, int H, int W, int dtype, int up0, int planar);
 int conv3d_first_fwd(const void*, int, int, const void*, const float*, void*, int, int, int, int, int, int, float, hipStream_t);
 int conv3d_first_wgrad(const void*, int, int, const void*, float*, float*, int, int, int, int, int, hipStream_t);
+bool conv3d_first_dgrad_ok(int Cin, int Cout, int D, int H, int W, int dtype);
+int conv3d_first_dgrad(const void*, int, const void*, float*, int, int, int, int, int, hipStream_t);
 
 static int check_common(const void* src0, int C0, int up0, int planar, const void* src1, int C1, int N, int D, int H, int W, int Cout) {
     if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0 || C0 <= 0 || C1 < 0) return FMRI_E_SHAPE;
@@ -105,6 +107,17 @@ extern "C" int fmri_conv3d_dgrad(const void* dy, int Cout, const void* w_dgrad, 
     // input gradient = the same direct convolution over dy with the tap-flipped transposed filters
     return fmri_conv3d_fwd(dy, Cout, 0, nullptr, 0, w_dgrad, nullptr, mask, dx, N, D, H, W, Cin, FMRI_ACT_NONE, 0.f, dtype, impl,
                            planar, stream);
+}
+
+// Input gradient of the network's FIRST convolution (1-4 input channels) in fp32, from the forward filter image: what a network in front of
+// a frozen segmenter is trained with.  A call of its own, so that fmri_conv3d_dgrad's dispatch stays what it is for every other caller.
+extern "C" int fmri_conv3d_first_dgrad_ok(int Cin, int Cout, int D, int H, int W, int dtype) {
+    return conv3d_first_dgrad_ok(Cin, Cout, D, H, W, dtype) ? 1 : 0;
+}
+extern "C" int fmri_conv3d_first_dgrad(const void* dy, int Cout, const void* w, float* dx, int N, int D, int H, int W, int Cin, int dtype,
+                                       fmri_stream_t stream) {
+    if (!dy || !w || !dx || N <= 0 || !conv3d_first_dgrad_ok(Cin, Cout, D, H, W, dtype)) return FMRI_E_SHAPE;
+    return conv3d_first_dgrad(dy, Cout, w, dx, N, D, H, W, Cin, as_stream(stream));
 }
 
 extern "C" int fmri_conv3d_wgrad(const void* src0, int C0, int up0, const void* src1, int C1, const void* dy, float* dw, float* db,

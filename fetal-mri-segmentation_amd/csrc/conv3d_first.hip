@@ -12,8 +12,11 @@
 // The 2-D instantiations take 1-7 channels: slice stacks, and stacks plus previous-slice truth channels (5 + 1 slices x 64 x 256x256:
 // 83 / 102 us, where the generic kernels took 964 / 1886; tools/bench_cascade.py).
 //
-// Reference ops replaced: the first Conv3D(+BiasAdd+Relu) of unet_model_3d (unet3d/unet.py:45-46,102,113) and its
-// Conv3DBackpropFilterV2 / BiasAddGrad.
+// The input gradient (k_conv_first_dgrad: what a network IN FRONT of a frozen segmenter is trained with, reference model/norm/NormNet.py) turns
+// the product round: the channels are the contraction, the 27 taps the rows, and its operand comes straight from global memory - see there.
+//
+// Reference ops replaced: the first Conv3D(+BiasAdd+Relu) of unet_model_3d (unet3d/unet.py:45-46,102,113), its
+// Conv3DBackpropFilterV2 / BiasAddGrad and, for NormNet, its Conv3DBackpropInputV2.
 #include "common.h"
 
 FMRI_DET_TU(first)
@@ -346,6 +349,180 @@ k_conv_first_wgrad(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, 
     if (db && t < 32) fmri_grad_add(dc, &db[cot * 32 + t], red[K * 32 + t]);
 }
 
+
+// ---------------------------------------------------------------------------------------------------------- input gradient
+// dx[v][c] = sum_tap sum_co dy[v - off(tap)][co] * w[tap][co][c] in fp32, from the FORWARD filter image.  Of the two ways to put this on the
+// matrix cores the kernel takes the second:
+//   (a) [voxels x 27 Cout] x [27 Cout x CIN], gathered from an LDS halo tile of dy: 54 k-steps per 32 voxels at Cout = 32 for ONE useful
+//       column of 32, and every voxel's A operand is 27 x 64 B of LDS reads (7 GB per launch at 4 x 64x128x128) from a halo tile that, with
+//       Cout channels per voxel, only fits LDS in small pieces (re-read factor 2.7);
+//   (b) [27 CIN x Cout] x [Cout x voxels]: two k-steps per 32 voxels, whose B operand - 8 consecutive channels of the lane's voxel - is a
+//       16-byte GLOBAL load: dy never passes through LDS at all.  The product P[tap][v] is the contribution of voxel v to dx[v + off(tap)];
+//       what goes through LDS is P (27 floats per voxel), summed col2im-style: dx[u] = sum_tap P[tap][u - off(tap)].
+// A workgroup owns a 16 x 32 (h, w) column of a sample and marches along d through `dchunk` output planes.  Per input plane it forms P for the
+// 18 x 34 halo plane (612 voxels = 20 column tiles of 32, five per wave; voxels outside the volume are zero operands), stores it tap-major
+// [27][640] in LDS (69 KB: two workgroups per CU; consecutive lanes = consecutive voxels in the stores and in the reads, no bank conflicts),
+// and every thread sums, for its two (h, w) positions, the nine in-plane taps of each kd into s[kd].  The three planes that meet in an
+// output plane are combined in REGISTERS while the march goes on: dx[d] = (s2[d-1] + s1[d]) + s0[d+1] - so nothing is recomputed along d but
+// the two planes at a chunk's ends, the in-plane halo costs 612 / 512 of the reads, and the order of every sum is fixed: each dx element is
+// written once, by one lane, and does not depend on the chunking (no atomics; two runs give the same bits).  The next plane's operands are
+// loaded while this plane's P is summed.  More than one input channel: one pass over the LDS image per channel, the operands stay in
+// registers; more than 32 output channels: further k-steps on operands loaded in place.
+// Measured (tools/bench_norm_net.py, profiles/r07_first_dgrad.log; 4 x 64x128x128, Cout 32, Cin 1, one read of dy = 268 MB): 59.6 us per
+// launch = 4.5 TB/s, where the generic kernel - the only way to this tensor before - takes 2,366 us (the forward sibling: 56 us); the
+// NormNet step (Isensee depth 5 / 16 filters in front of the configs[1] U-Net, batch 2) 17.83 -> 16.69 ms.  Form (a) was not built.
+namespace fd {
+constexpr int TH = 16, TW = 32;
+constexpr int HH = TH + 2, HW = TW + 2;                 // 18 x 34 halo plane
+constexpr int NQ = HH * HW;                             // 612 voxels
+constexpr int NT = 5;                                   // column tiles of 32 voxels per wave (4 waves x 5 x 32 = 640 >= 612)
+constexpr int QP = 4 * NT * 32;                         // LDS pitch of a tap row
+constexpr int NTHREADS = 256;
+}  // namespace fd
+
+template <int CIN>
+__global__ void __launch_bounds__(fd::NTHREADS, 2)
+k_conv_first_dgrad(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ wt /*[27][Cout][CIN]*/, float* __restrict__ dx, int N, int D, int H,
+                   int W, int Cout, int dchunk) {
+    using namespace fd;
+    __shared__ float sp[27 * QP];
+    int tile = blockIdx.x;
+    const int twn = W / TW, thn = H / TH, tdn = D / dchunk;
+    const int w0 = (tile % twn) * TW; tile /= twn;
+    const int h0 = (tile % thn) * TH; tile /= thn;
+    const int d0 = (tile % tdn) * dchunk;
+    const int n = tile / tdn;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, r = lane & 31, hk = lane >> 5;
+    const int nchunk = Cout / 32;
+
+    // B operand: the lane's voxel of column tile wv + 4 i, channels 16 hk + 8 ks + j of a 32-channel chunk (k-step ks, element j): the lane
+    // reads 32 contiguous bytes per chunk.  Element offset inside a plane of dy, or -1 for a voxel outside the volume (a zero operand).
+    int boff[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        const int q = (wv + 4 * i) * 32 + r;
+        const int gh = h0 - 1 + q / HW, gw = w0 - 1 + q % HW;
+        boff[i] = (q < NQ && (unsigned)gh < (unsigned)H && (unsigned)gw < (unsigned)W) ? (gh * W + gw) * Cout + 16 * hk : -1;
+    }
+    const int64_t plane = (int64_t)H * W * Cout;
+    auto load_b = [&](const bf16_t* pl, int i, int ck, u32x4 (&b)[2]) {
+        b[0] = u32x4{0, 0, 0, 0};
+        b[1] = u32x4{0, 0, 0, 0};
+        if (boff[i] >= 0) {
+            const u32x4* const p = reinterpret_cast<const u32x4*>(pl + boff[i] + ck * 32);
+            b[0] = p[0];
+            b[1] = p[1];
+        }
+    };
+    // A operand: row r = tap (rows 27 ... 31 are zero), the same channels as B; the forward image holds a tap's 8 channels x CIN inputs as
+    // 16 CIN contiguous bytes
+    auto load_a = [&](int ck, u16x8 (&a)[CIN][2]) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            unsigned short e[8 * CIN];
+#pragma unroll
+            for (int k = 0; k < 8 * CIN; ++k) e[k] = 0;
+            if (r < 27) {
+                const u16x8* const p = reinterpret_cast<const u16x8*>(wt + ((int64_t)r * Cout + ck * 32 + 16 * hk + 8 * ks) * CIN);
+#pragma unroll
+                for (int m = 0; m < CIN; ++m) {
+                    const u16x8 v = p[m];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) e[8 * m + j] = v[j];
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CIN; ++c)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) a[c][ks][j] = e[j * CIN + c];
+        }
+    };
+    // the thread's two output positions (hl = t / 32 + 8 i, wl = t % 32): offset of tap (kh, kw) = (0, 0) in a tap row of the LDS image
+    const int wl = t & 31, hl = t >> 5;
+    const int g0 = (hl + 2) * HW + wl + 2;
+    float acc0[CIN][2], acc1[CIN][2];
+#pragma unroll
+    for (int c = 0; c < CIN; ++c)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) acc0[c][i] = acc1[c][i] = 0.f;
+
+    u32x4 bn[NT][2];                                    // chunk 0 of the plane that is processed next
+    const int din_first = d0 > 0 ? d0 - 1 : d0, din_last = d0 + dchunk < D ? d0 + dchunk : D - 1;
+    {
+        const bf16_t* const pl = dy + ((int64_t)n * D + din_first) * plane;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) load_b(pl, i, 0, bn[i]);
+    }
+    // planes d0 - 1 and D of the walk lie outside the volume: their sums are zero, the registers just move on
+    for (int din = d0 - 1; din <= d0 + dchunk; ++din) {
+        const bool inside = din >= din_first && din <= din_last;
+        const bf16_t* const pl = dy + ((int64_t)n * D + din) * plane;
+        u32x4 b0[NT][2];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) { b0[i][0] = bn[i][0]; b0[i][1] = bn[i][1]; }
+        if (inside && din < din_last) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) load_b(pl + plane, i, 0, bn[i]);
+        }
+#pragma unroll
+        for (int c = 0; c < CIN; ++c) {
+            float s[2][3];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) s[i][0] = s[i][1] = s[i][2] = 0.f;
+            if (inside) {
+                u16x8 a[CIN][2];
+                load_a(0, a);
+#pragma unroll
+                for (int i = 0; i < NT; ++i) {
+                    f32x16 acc;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) acc[k] = 0.f;
+                    u32x4 b[2];
+                    if (c == 0) { b[0] = b0[i][0]; b[1] = b0[i][1]; }
+                    else load_b(pl, i, 0, b);
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[c][ks]), __builtin_bit_cast(bf16x8_t, b[ks]), acc, 0, 0, 0);
+                    for (int ck = 1; ck < nchunk; ++ck) {
+                        u16x8 a2[CIN][2];
+                        load_a(ck, a2);
+                        load_b(pl, i, ck, b);
+#pragma unroll
+                        for (int ks = 0; ks < 2; ++ks)
+                            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a2[c][ks]), __builtin_bit_cast(bf16x8_t, b[ks]), acc, 0, 0, 0);
+                    }
+                    // D rows = tap (reg & 3) + 8 (reg >> 2) + 4 hk of voxel q = (wv + 4 i) * 32 + r
+                    const int q = (wv + 4 * i) * 32 + r;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        const int tap = (k & 3) + 8 * (k >> 2) + 4 * hk;
+                        if (tap < 27) sp[tap * QP + q] = acc[k];
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int kd = 0; kd < 3; ++kd)
+#pragma unroll
+                        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+                            for (int kw = 0; kw < 3; ++kw)
+                                s[i][kd] += sp[(kd * 9 + kh * 3 + kw) * QP + g0 + (8 * i - kh) * HW - kw];
+                __syncthreads();
+            }
+            const int dout = din - 1;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if (dout >= d0 && dout < d0 + dchunk)
+                    dx[((((int64_t)n * D + dout) * H + h0 + hl + 8 * i) * W + w0 + wl) * CIN + c] = acc0[c][i] + s[i][0];
+                acc0[c][i] = acc1[c][i] + s[i][1];
+                acc1[c][i] = s[i][2];
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // single-channel 3-D volumes, and the few-slice stacks of the 2-D models (reference config_utils.py:53-56: 5 slices by default).  The even
@@ -400,6 +577,30 @@ int conv3d_first_wgrad(const void* x, int C0, int planar, const void* dy, float*
 #define L_(CIN_, PL_) \
     k_conv_first_wgrad<CIN_, PL_><<<dim3(gx, Cout / 32), fg::NTHREADS, 0, st>>>((const bf16_t*)x, (const bf16_t*)dy, dw, db, N, D, H, W, Cout)
     FMRI_FIRST_DISPATCH(L_);
+#undef L_
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+// the 3-D range of conv3d_first_ok
+bool conv3d_first_dgrad_ok(int Cin, int Cout, int D, int H, int W, int dtype) {
+    return Cin >= 1 && Cout >= 32 && D >= 4 && H >= 16 && W >= 32 && conv3d_first_ok(Cin, 0, Cout, D, H, W, dtype, 0, 0);
+}
+
+int conv3d_first_dgrad(const void* dy, int Cout, const void* w, float* dx, int N, int D, int H, int W, int Cin, hipStream_t st) {
+    if ((((uintptr_t)dy) | ((uintptr_t)w)) & 15) return FMRI_E_ALIGN;
+    if (((uintptr_t)dx) & 3) return FMRI_E_ALIGN;
+    // planes per workgroup: a chunk re-reads its two end planes, a launch wants two workgroups per CU (512); D is a multiple of 4
+    const int cols = N * (H / fd::TH) * (W / fd::TW);
+    int dchunk = 4;
+    for (int c : {64, 32, 16, 8})
+        if (D % c == 0 && (int64_t)cols * (D / c) >= 512) { dchunk = c; break; }
+    const int grid = cols * (D / dchunk);
+#define L_(CIN_) k_conv_first_dgrad<CIN_><<<grid, fd::NTHREADS, 0, st>>>((const bf16_t*)dy, (const bf16_t*)w, dx, N, D, H, W, Cout, dchunk)
+    if (Cin == 1) L_(1);
+    else if (Cin == 2) L_(2);
+    else if (Cin == 3) L_(3);
+    else L_(4);
 #undef L_
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;

@@ -527,6 +527,7 @@ class Model(object):
         self._unsupported = None               # reason string when the engine cannot run this topology yet
         self._mask_shape = None                # shape of the second (distance-mask) input of a mask-weighted loss, when there is one
         self._pending_weights = None
+        self._engine_kwargs = {}               # extra keyword arguments of the engine (norm_net_model: input_grad=True for its frozen segmenter)
         self.history = None
 
     # -- Keras surface -----------------------------------------------------------------------------------------------
@@ -578,9 +579,11 @@ class Model(object):
                 dist_ctx = None
             if getattr(self, "_graph_engine", False):
                 from fmri_hip.graph_engine import LayerGraphEngine
-                self._engine = LayerGraphEngine(self.layers, batch, dtype=self._compute_dtype(), training=True, dist_ctx=dist_ctx)
+                self._engine = LayerGraphEngine(self.layers, batch, dtype=self._compute_dtype(), training=True, dist_ctx=dist_ctx,
+                                                **self._engine_kwargs)
             else:
-                self._engine = UNetEngine(UNetPlan(**self._plan_args), batch, dtype=self._compute_dtype(), training=True, dist_ctx=dist_ctx)
+                self._engine = UNetEngine(UNetPlan(**self._plan_args), batch, dtype=self._compute_dtype(), training=True, dist_ctx=dist_ctx,
+                                          **self._engine_kwargs)
             if self._pending_weights is not None:
                 self._engine.load_keras_weights(self._pending_weights)
                 self._pending_weights = None

@@ -52,7 +52,8 @@ class Graph(object):
         return self._add("instance_normalization", "InstanceNormalization", x.shape, [x], axis=axis, params=2 * x.shape[axis])
 
     def activation(self, x, name):
-        return self._add("activation", "Activation", x.shape, [x], activation=name)
+        """Activation(None) is the identity, which Keras records under the name 'linear'"""
+        return self._add("activation", "Activation", x.shape, [x], activation="linear" if name is None else name)
 
     def leaky_relu(self, x, alpha=0.3):
         return self._add("leaky_re_lu", "LeakyReLU", x.shape, [x], alpha=alpha)

@@ -76,7 +76,7 @@ def isensee2017_model(input_shape=(128, 128, 5), n_base_filters=16, depth=5, dro
     model._graph_engine = True
     model._created_layers = list(g.layers)       # incl. the heads Keras would drop: what the reference builder CREATED (name counters)
     if activation_name != "sigmoid":
-        model._unsupported = "activation_name != 'sigmoid'"
+        model._unsupported = "activation_name %r (only 'sigmoid', or None on isensee2017_model_3d)" % (activation_name,)
     metrics = ['binary_accuracy', vod_coefficient]
     if loss_function != dice_coefficient_loss:
         metrics += [dice_coefficient]

@@ -59,7 +59,7 @@ def unet_model_2d(input_shape, pool_size=(2, 2), n_labels=1, initial_learning_ra
     if refused:
         unsupported.append(refused)
     if activation_name != "sigmoid":
-        unsupported.append("activation_name != 'sigmoid'")
+        unsupported.append("activation_name %r (only 'sigmoid', or None on isensee2017_model_3d)" % (activation_name,))
     if unsupported:
         model._unsupported = ", ".join(unsupported)
     metrics = ['binary_accuracy', vod_coefficient]

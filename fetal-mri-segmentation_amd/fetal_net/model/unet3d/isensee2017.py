@@ -4,7 +4,8 @@ executed by the generic layer-graph engine (fmri_hip.graph_engine).
 Per level: in-conv block (3x3x3, stride 2 below the first level) + context module (block -> SpatialDropout3D -> block), summed;
 decoder: UpSampling3D -> block, concatenate([skip, up]), localisation (3x3x3 block -> 1x1x1 block); 1x1x1 segmentation heads on the
 `n_segmentation_levels` shallowest levels, summed bottom-up through UpSampling3D; Activation(activation_name).  Every block is
-Conv3D -> keras-contrib InstanceNormalization(axis=1) -> LeakyReLU.
+Conv3D -> keras-contrib InstanceNormalization(axis=1) -> LeakyReLU.  activation_name=None (Keras: 'linear') leaves the summed heads as the
+output: the network that `norm_net_model` trains in front of a frozen segmenter (reference fetal_net/model/norm/NormNet.py:14-16).
 """
 from ...engine_model import Adam, Model
 from ...metrics import dice_coefficient, dice_coefficient_loss, vod_coefficient
@@ -68,8 +69,8 @@ def isensee2017_model_3d(input_shape=(1, 128, 128, 128), n_base_filters=16, dept
         model._mask_shape = tuple(int(v) for v in mask_shape)
         if not getattr(loss_function, "mask_weighted", False):
             unsupported.append("mask_shape with a loss factory other than dice_and_xent_mask")
-    if activation_name != "sigmoid":
-        unsupported.append("activation_name != 'sigmoid'")
+    if activation_name not in ("sigmoid", None, "linear"):
+        unsupported.append("activation_name %r (only 'sigmoid', or None / 'linear': the output is then the logits)" % (activation_name,))
     if unsupported:
         model._unsupported = ", ".join(unsupported)
     metrics = ['binary_accuracy', vod_coefficient]

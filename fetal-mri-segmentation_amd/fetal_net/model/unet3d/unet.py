@@ -93,7 +93,7 @@ def unet_model_3d(input_shape, pool_size=(2, 2, 2), n_labels=1, initial_learning
     if refused:
         unsupported.append(refused)
     if activation_name != "sigmoid":
-        unsupported.append("activation_name != 'sigmoid'")
+        unsupported.append("activation_name %r (only 'sigmoid', or None on isensee2017_model_3d)" % (activation_name,))
     builder_kwargs = dict(input_shape=input_shape, pool_size=pool_size, n_labels=n_labels, initial_learning_rate=initial_learning_rate,
                           deconvolution=deconvolution, depth=depth, n_base_filters=n_base_filters,
                           batch_normalization=batch_normalization, activation_name=activation_name, loss_function=loss_function)

@@ -89,11 +89,14 @@ class UNetPlan:
 
 
 class UNetEngine(EngineBase):
-    def __init__(self, plan, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None):
+    def __init__(self, plan, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None, input_grad=False):
+        """input_grad: backward() also delivers dL/d(input) (input_gradient()) - the gradient a network in front of this one is trained
+        with while this one stays frozen (backward(params=False); reference fetal_net/model/norm/NormNet.py)."""
         # every switch of this engine, read here and nowhere else; what each one does stands where self.sw[...] is used
         super().__init__(dtype, device, training, dist_ctx, DETERMINISTIC=False, DECONV_FOLD=True, FWD_WS=True, UPCAT=True, TAIL_FUSE=True,
-                         TAIL_FUSE_2D=True, NORM_FUSE=1, NORM_FUSE_MAXLEVEL=1 if plan.norm == "batch" else 0)
+                         TAIL_FUSE_2D=True, NORM_FUSE=1, NORM_FUSE_MAXLEVEL=1 if plan.norm == "batch" else 0, FIRST_DGRAD=True)
         self.plan, self.N = plan, batch
+        self.input_grad = bool(input_grad and training)
         self.planar = plan.ndim == 2      # 2-D: tensors are [1][slices][H][W][C], every op is planar (no coupling along D)
         # FMRI_DETERMINISTIC=1: bit-reproducible training steps (same weights + same batch -> the same bits in every gradient and metric):
         # gradient partial sums meet as fixed-point integers in a shadow of G (ops.set_deterministic), the parity-form weight gradient -
@@ -167,7 +170,9 @@ class UNetEngine(EngineBase):
                 if not self.planar:
                     continue                             # 2-D keeps the 9-tap images too: batches whose slice count does not tile fall back
             self.Wf[name] = torch.empty((27, L["cout"], L["cin"]), dtype=self.dtype, device=dev)
-            if self.training and name != first:
+            # (the first conv's input-gradient image: only with input_grad, and only where fmri_conv3d_first_dgrad - which reads the forward
+            # image - does not take the shape)
+            if self.training and (name != first or (self.input_grad and not self._first_dgrad_ok())):
                 self.Wd[name] = torch.empty((27, L["cin"], L["cout"]), dtype=self.dtype, device=dev)
         # Deconvolution3D(k = 2, s = 2) (reference unet.py:135): output voxel 2g+p = W[p] . x[g] + b, i.e. the parity form with ONE
         # non-zero tap per parity class (low-res offset 0) - it rides the same MFMA kernels (fmri_conv3d_upcat_* with C1 = 0)
@@ -365,6 +370,13 @@ class UNetEngine(EngineBase):
                     self.upcat_wgrad.add(a["name"])
         return out
 
+    def _first_dgrad_ok(self):
+        """does fmri_conv3d_first_dgrad take the first convolution's input gradient? (3-D bf16 shapes of ops.conv3d_first_dgrad_ok; it does
+        not depend on the batch size).  FMRI_FIRST_DGRAD=0 keeps the generic route (A/B switch, tools/bench_norm_net.py)."""
+        c = self.plan.enc[0][0]
+        return (self.sw["FIRST_DGRAD"] and not self.planar and self.dtype == torch.bfloat16 and
+                ops.conv3d_first_dgrad_ok(c["cin"], c["cout"], *self.plan.level_dims(0), self.dtype))
+
     def _use_upcat(self, name):
         """parity form for this layer at the CURRENT batch size (2-D: the slice count must be a multiple of the 4-slice tile)"""
         return self.route["up"].get(name) == "upcat"
@@ -423,12 +435,12 @@ class UNetEngine(EngineBase):
             self._build_buffers()
             self._bufsets[key] = dict(act=self.act, grad=getattr(self, "grad", None), logits=self.logits, probs=self.probs,
                                       dlogits=getattr(self, "dlogits", None), pre=self.pre, nstats=self.nstats, nss=self.nss, norm_ws=self.norm_ws,
-                                      wgrad_ws=getattr(self, "wgrad_ws", None), route=self.route,
+                                      wgrad_ws=getattr(self, "wgrad_ws", None), route=self.route, dx_in=self.dx_in, dx_tmp=self.dx_tmp,
                                       dummy_y=torch.zeros(self.logits.numel(), dtype=torch.uint8, device=self.dev))
         b = self._bufsets[key]
         self.N, self.act, self.grad, self.logits, self.probs, self.dlogits = N, b["act"], b["grad"], b["logits"], b["probs"], b["dlogits"]
         self.pre, self.nstats, self.nss, self.norm_ws, self.wgrad_ws = b["pre"], b["nstats"], b["nss"], b["norm_ws"], b["wgrad_ws"]
-        self.route = b["route"]
+        self.route, self.dx_in, self.dx_tmp = b["route"], b["dx_in"], b["dx_tmp"]
         self._dummy_y = b["dummy_y"]       # per buffer set and never freed: captured hipGraphs keep raw pointers to it
 
     def _dims(self, level):
@@ -457,9 +469,13 @@ class UNetEngine(EngineBase):
                         planar conv + depth-to-space; the slices must tile by 4), "onetap" (one-tap parity transposed conv), "deconv" (direct
                         k2s2 transposed conv), "upcat" (parity-form up-sample + concat; 2-D: the slices must tile by 4) or "upsample" (the
                         fused-upsample 27- / 9-tap conv);
-          upcat_wgrad[a]  a's weight gradient takes the parity form too."""
+          upcat_wgrad[a]  a's weight gradient takes the parity form too;
+          first_dgrad   engines built with input_grad: "first" (fmri_conv3d_first_dgrad: fp32 straight from the forward filter image) or
+                        "generic" (fmri_conv3d_dgrad in the compute dtype on a [27][Cin][Cout] image, then a cast: fp32, 2-D, other shapes)."""
         p, sw = self.plan, self.sw
         r = dict(tail={}, stats={}, dz={}, up={}, upcat_wgrad={})
+        if self.input_grad:
+            r["first_dgrad"] = "first" if self._first_dgrad_ok() else "generic"
 
         def ntail(c0, c1, cout, level, kind):
             if p.norm is None or self.planar or self.dtype != torch.bfloat16 or not (sw["NORM_FUSE"] & kind) or level > sw["NORM_FUSE_MAXLEVEL"]:
@@ -524,6 +540,10 @@ class UNetEngine(EngineBase):
         nvox0 = int(np.prod(self._dims(0)))
         self.logits = torch.empty((nvox0, p.n_labels), dtype=torch.float32, device=dev)
         self.probs = torch.empty_like(self.logits)
+        # dL/d(input) in fp32 (what the network in front takes as the gradient on its output); the generic route in bf16 goes through dx_tmp
+        self.dx_in = torch.empty(self._dims(0) + (p.in_channels,), dtype=torch.float32, device=dev) if self.input_grad else None
+        self.dx_tmp = torch.empty_like(self.dx_in, dtype=dt) if (self.input_grad and dt != torch.float32 and
+                                                                 self.route["first_dgrad"] == "generic") else None
         if not self.training:
             self.grad, self.dlogits, self.wgrad_ws = None, None, None
             return
@@ -598,7 +618,7 @@ class UNetEngine(EngineBase):
         (ops.norm_act_fwd_pre if summed else ops.norm_act_fwd)(
             self._as_samples(self.pre[name]), self.gb_view(name, "gamma"), self.gb_view(name, "beta"),
             self._as_samples(self.act[name]), st, self.norm_ws, per, eps=1e-3, eps_on_std=eos, act=ACT_RELU)
-        if self.plan.norm == "batch" and bn_training:
+        if self.plan.norm == "batch" and bn_training and self._update_moving:
             # Keras moving statistics (momentum 0.99); the variance fed to the moving average is sample-size corrected
             M = float(self.pre[name].numel() // c["cout"])
             mv = self.moving[name]
@@ -610,11 +630,13 @@ class UNetEngine(EngineBase):
                 mv[1].mul_(0.99).add_(var, alpha=0.01)
         return self.act[name]
 
-    def forward(self, x, bn_training=None):
-        """x: [N,D,H,W,Cin] compute dtype, device.  Leaves logits (fp32 [nvox, L]) in self.logits."""
+    def forward(self, x, bn_training=None, update_moving=True):
+        """x: [N,D,H,W,Cin] compute dtype, device.  Leaves logits (fp32 [nvox, L]) in self.logits.  update_moving=False: a training-mode pass
+        of a FROZEN network - BatchNormalization normalises with the batch statistics but leaves its moving averages alone."""
         p, A = self.plan, self.act
         assert tuple(x.shape) == self._dims(0) + (p.in_channels,), (x.shape,)
         bn_training = self.training if bn_training is None else bn_training
+        self._update_moving = update_moving
         self.x_in = x
         h = x
         for ld, lv in enumerate(p.enc):
@@ -679,7 +701,8 @@ class UNetEngine(EngineBase):
                                  workspace=self.wgrad_ws)
             self._grad_ready(name)
 
-        self._wgrad(wgrad)                  # behind the event "dL/d(conv output) is final"
+        if self._params:
+            self._wgrad(wgrad)              # behind the event "dL/d(conv output) is final"
 
     def _folded_bwd(self, a, x_low, skip, cat, low):
         """backward of the folded transposed conv + conv of decoder block `a`: G[a] holds dL/d(conv output).  Weight gradients (side
@@ -704,7 +727,8 @@ class UNetEngine(EngineBase):
             self._grad_ready(name)
             self._grad_ready(F["u"])
 
-        self._wgrad(wgrad)
+        if self._params:
+            self._wgrad(wgrad)
         ops.conv3d_upcat_dgrad(g, F["up_d"], F["sk_d"], self._mask_of(low), None, self.grad[low], cat)
 
     def _dgrad_into(self, b, a):
@@ -727,12 +751,17 @@ class UNetEngine(EngineBase):
             return None
         return self.act.get(name)
 
-    def backward(self, y_true, grad_scale=1.0, weight=None, dprobs=None, dprobs_scale=1.0, seg_loss=True):
+    def backward(self, y_true, grad_scale=1.0, weight=None, dprobs=None, dprobs_scale=1.0, seg_loss=True, params=True):
         """`dprobs` ([..., ld >= n_labels], optional): a gradient that arrives on the probabilities from outside - the adversarial term of
         reference fetal/experiments/train_adv.py:177-180 (the frozen discriminator's input gradient); `seg_loss=False` leaves only that
-        term (the unlabelled pass of train_semi.py:176-183)."""
+        term (the unlabelled pass of train_semi.py:176-183).
+        params=False: the pass of a FROZEN network, of which only input_gradient() is wanted (engines built with input_grad=True): no
+        weight-gradient launch (the side stream stays idle), no data-parallel bucket, and no adam_step is to follow.  The kernels that form
+        a parameter gradient next to an input gradient (1x1x1 conv, transposed conv, normalisation backward) still write theirs into G,
+        which nobody applies; P, M, V, t and the moving statistics are untouched."""
         p, A, Gd = self.plan, self.act, self.grad
         normed = p.norm is not None
+        self._params = bool(params)
         self._main_stream = torch.cuda.current_stream(self.dev) if self.dev.type == "cuda" else None
         self._dz_ready = set()
         self.G.zero_()
@@ -765,19 +794,21 @@ class UNetEngine(EngineBase):
                     yv, tv = self._d2s_views(dyc, t4)
                     tv.copy_(yv)                                               # space-to-depth of the gradient
                     ops.conv3d_dgrad(t4, Wd_["wd"], Gd[low], mask=self._mask_of(low), planar=True)
-                    Wd_["dw"].zero_()
-                    Wd_["db"].zero_()
-                    ops.conv3d_wgrad(A[low], None, t4, Wd_["dw"], Wd_["db"], planar=True)
-                    self.w_view(u["name"], self.G)[:4].add_(Wd_["dw"][13].view(4, L["cout"], L["cin"]))
-                    self.b_view(u["name"], self.G).add_(Wd_["db"].view(4, L["cout"]).sum(0))
+                    if params:
+                        Wd_["dw"].zero_()
+                        Wd_["db"].zero_()
+                        ops.conv3d_wgrad(A[low], None, t4, Wd_["dw"], Wd_["db"], planar=True)
+                        self.w_view(u["name"], self.G)[:4].add_(Wd_["dw"][13].view(4, L["cout"], L["cin"]))
+                        self.b_view(u["name"], self.G).add_(Wd_["db"].view(4, L["cout"]).sum(0))
                 elif up == "onetap":
                     Wd_ = self.Wdc[u["name"]]
                     dyc = ops.slice_channels(cat, 0, Gd[u["name"]])          # the transposed conv's own slice of the concat gradient
                     ops.conv3d_upcat_dgrad(dyc, Wd_["up_d"], None, self._mask_of(low), None, Gd[low], None)
-                    ops.conv3d_upcat_wgrad(A[low], None, dyc, Wd_["dw27"], self.b_view(u["name"], self.G), self.dwc_scratch)
-                    L = self.layout[u["name"]]
-                    dwc = self.dwc_scratch[:64 * L["cout"] * L["cin"]].view(8, 8, L["cout"], L["cin"])
-                    self.w_view(u["name"], self.G).add_(dwc[self._par8, 7 - self._par8])
+                    if params:
+                        ops.conv3d_upcat_wgrad(A[low], None, dyc, Wd_["dw27"], self.b_view(u["name"], self.G), self.dwc_scratch)
+                        L = self.layout[u["name"]]
+                        dwc = self.dwc_scratch[:64 * L["cout"] * L["cin"]].view(8, 8, L["cout"], L["cin"])
+                        self.w_view(u["name"], self.G).add_(dwc[self._par8, 7 - self._par8])
                 else:
                     ops.deconv_bwd(A[low], self.Wt[u["name"]], cat, Gd[low], self.w_view(u["name"], self.G), self.b_view(u["name"], self.G),
                                    dy_off=0, xmask=self._mask_of(low), planar=self.planar)
@@ -804,13 +835,28 @@ class UNetEngine(EngineBase):
             self._block_bwd(ca, xin, None, False)
             if ld > 0:
                 ops.conv3d_dgrad(Gd[ca["name"]], self.Wd[ca["name"]], Gd["pool_%d" % (ld - 1)], planar=self.planar)
-        self._join_wgrad()
+            elif self.input_grad:
+                # dL/d(input), fp32: the first conv's input gradient on the route planned in _plan_routes
+                if self.route["first_dgrad"] == "first":
+                    ops.conv3d_first_dgrad(Gd[ca["name"]], self.Wf[ca["name"]], self.dx_in)
+                else:
+                    ops.conv3d_dgrad(Gd[ca["name"]], self.Wd[ca["name"]], self.dx_in if self.dx_tmp is None else self.dx_tmp, planar=self.planar)
+                    if self.dx_tmp is not None:
+                        ops.cast(self.dx_tmp, self.dx_in)
+        if params:
+            self._join_wgrad()
         if self.deterministic:
             ops.deterministic_finish(self.G, self.G64)       # G += the fixed-point sums of every gradient kernel of this pass
-            if self.dist is not None:
+            if self.dist is not None and params:
                 self.dist.begin()                            # nothing was reduced during this backward: one range, the whole buffer
-        if self.dist is not None:
+        if self.dist is not None and params:
             self.dist.finish(self)
+
+    def input_gradient(self):
+        """dL/d(input) of the last backward pass, [N][D][H][W][Cin] fp32 (engines built with input_grad=True)"""
+        if not self.input_grad:
+            raise RuntimeError("this engine was built without input_grad=True")
+        return self.dx_in
 
     def _d2s_tmp(self, name, x_low, Wd_):
         """(1, S, H, W, 4*Cout) scratch of the 2-D transposed conv for the current slice count"""
@@ -845,7 +891,7 @@ class UNetEngine(EngineBase):
     def _grad_ready(self, name):
         # deterministic mode: the gradients sit in the int64 shadow until deterministic_finish at the end of backward(), so no bucket of
         # G may be reduced before that - the whole buffer goes in dist.finish (early buckets all-reduced zeros)
-        if self.dist is not None and not self.deterministic:
+        if self.dist is not None and not self.deterministic and self._params:
             self.dist.grad_ready(self, name)
 
 

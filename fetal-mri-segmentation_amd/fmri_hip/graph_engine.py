@@ -5,6 +5,9 @@ classes the reference's builders emit — Conv3D (3x3x3 stride 1|2, 1x1x1), Inst
 LeakyReLU / Activation('relu'|'sigmoid'), MaxPooling3D / UpSampling3D (per-axis factors 1..4), Concatenate, Add, SpatialDropout3D — i.e. the Isensee
 model of reference fetal_net/model/unet3d/isensee2017.py:15-111 (and, for cross-checking, unet_model_3d) — and their 2-D twins
 (Conv2D, UpSampling2D, SpatialDropout2D, MaxPooling2D between two Permute layers: reference fetal_net/model/unet/isensee.py:14-105).
+A graph may end in Activation('linear') instead of the sigmoid (isensee2017_model_3d(activation_name=None): the network that reference
+fetal_net/model/norm/NormNet.py puts in front of a frozen segmenter): its output is the logits themselves, it has no loss of its own and is
+trained with a gradient handed to backward(dprobs=..., seg_loss=False).
 A graph may also end in Dense(1, 'sigmoid') on a GlobalAveragePooling3D (the PatchGAN discriminator of reference
 fetal_net/model/discriminator/all_dis_3d.py:11-72: + AveragePooling3D, Dense, anisotropic strides (2, 2, 1)); its loss is the binary
 cross-entropy on float targets, and with `input_grad=True` the backward pass also delivers dL/d(input) - what the generator of the
@@ -87,9 +90,10 @@ class LayerGraphEngine(EngineBase):
         inb = {l.name: [res(i) for i in l.inbound] for l in L}
         out_layer = L[-1] if L[-1].class_name != "Permute" else self.by_name[L[-1].inbound[0]]
         self.head = "dense" if (out_layer.class_name == "Dense" and out_layer.config.get("activation") == "sigmoid") else "seg"
-        if self.head == "seg" and not (out_layer.class_name == "Activation" and out_layer.config.get("activation") == "sigmoid"):
-            raise NotImplementedError("the graph must end in Activation('sigmoid') or Dense(n, 'sigmoid')")
-        # seg head: the sigmoid layer owns no tensor, its source holds the logits; dense head: the Dense op writes the logits itself
+        if self.head == "seg" and not (out_layer.class_name == "Activation" and out_layer.config.get("activation") in ("sigmoid", "linear", None)):
+            raise NotImplementedError("the graph must end in Activation('sigmoid' | 'linear') or Dense(n, 'sigmoid')")
+        self.linear = self.head == "seg" and out_layer.config.get("activation") != "sigmoid"       # linear head: the logits are the output
+        # seg head: the sigmoid / linear layer owns no tensor, its source holds the logits; dense head: the Dense op writes the logits itself
         self.logits_src = inb[out_layer.name][0] if self.head == "seg" else out_layer.name
         in_shape = L[0].output_shape                      # 3-D: (None, C, X, Y, Z); 2-D: (None, X, Y, C) channels-last
         if self.planar:
@@ -613,6 +617,20 @@ class LayerGraphEngine(EngineBase):
             ops.cast(src.reshape(-1), self.logits.reshape(-1))
         return self.logits
 
+    def predict(self, x):
+        """linear head: the output is the logits, handed on in `probs` unchanged (fp32)"""
+        if not self.linear:
+            return super().predict(x)
+        self.forward(x, bn_training=False)
+        ops.cast(self.logits.reshape(-1), self.probs.reshape(-1))
+        return self.probs
+
+    def loss_forward(self, y_true, weight=None):
+        if self.linear:
+            raise NotImplementedError("a network with a linear output has no segmentation loss of its own: it is trained inside a chain "
+                                      "(fetal_net.model.norm_net_model) through backward(dprobs=..., seg_loss=False)")
+        return super().loss_forward(y_true, weight)
+
     def _dense_x(self, o):
         """the Dense layer's input [N, K] fp32: its source tensor, or the logical channels of a channel-padded one"""
         src, K = self.T[o["ins"][0]], self.layout[o["name"]]["K"]
@@ -650,10 +668,13 @@ class LayerGraphEngine(EngineBase):
             ops.add(self.Gt[name], self.tmp[name], self.Gt[name])
 
     def backward(self, y_true, grad_scale=1.0, weight=None, dprobs=None, dprobs_scale=1.0, seg_loss=True, params=True):
-        """seg head: y_true = uint8 labels; `dprobs` (optional, [..., ld >= n_labels]) is an extra gradient that arrives on the probabilities
+        """linear head: `dprobs` is the gradient on the output, dlogits = dprobs_scale * dprobs (seg_loss must be False).
+        seg head: y_true = uint8 labels; `dprobs` (optional, [..., ld >= n_labels]) is an extra gradient that arrives on the probabilities
         (the adversarial term of reference train_adv.py:177-180), `seg_loss=False` leaves only that term (train_semi.py:176-183).
         dense head: y_true = float targets, the loss is their mean binary cross-entropy times grad_scale.
         params=False: only the input gradient is wanted (the frozen discriminator inside the combined model)."""
+        if self.linear and (seg_loss or dprobs is None):
+            raise NotImplementedError("a linear output head takes its gradient from outside: backward(dprobs=g, seg_loss=False)")
         self._main_stream = torch.cuda.current_stream(self.dev) if self.dev.type == "cuda" else None
         if self.pad:
             if params:
@@ -666,6 +687,12 @@ class LayerGraphEngine(EngineBase):
             self.dist.begin()
         if self.head == "dense":
             ops.sigmoid_bce_bwd(self.probs.reshape(-1), y_true.reshape(-1), self.dlogits.reshape(-1), grad_scale / self.probs.numel())
+        elif self.linear:
+            # linear head: dlogits = dprobs_scale * (the outside gradient on the output), no p (1 - p) factor
+            g = dprobs.reshape(self.dlogits.shape[0], -1)
+            self.dlogits.copy_(g[:, :self.plan.n_labels])
+            if dprobs_scale != 1.0:
+                self.dlogits.mul_(dprobs_scale)
         else:
             self._seg_loss_bwd(y_true, grad_scale, weight, dprobs, dprobs_scale, seg_loss)
         gsrc = self.Gt[self.logits_src]

@@ -85,6 +85,22 @@ def conv3d_dgrad(dy, w_dgrad, dx, mask=None, impl=IMPL_AUTO, planar=False):
     return dx
 
 
+def conv3d_first_dgrad_ok(Cin, Cout, D, H, W, dtype):
+    """does fmri_conv3d_first_dgrad take this first-layer shape? (bf16, 3-D, Cin 1..4, Cout % 32, D % 4, H % 16, W % 32)"""
+    return bool(lib().fmri_conv3d_first_dgrad_ok(Cin, Cout, D, H, W, BF16 if dtype == torch.bfloat16 else F32))
+
+
+def conv3d_first_dgrad(dy, w_fwd, dx):
+    """dx [N,D,H,W,Cin] fp32 (overwritten) = input gradient of the first convolution from dy [N,D,H,W,Cout] bf16 and the FORWARD filter
+    image w_fwd [27,Cout,Cin] bf16"""
+    _need_cuda(dy, w_fwd, dx)
+    N, D, H, W, Cin = dx.shape
+    Cout = dy.shape[-1]
+    assert tuple(dy.shape[:4]) == (N, D, H, W) and w_fwd.shape == (27, Cout, Cin) and dx.dtype == torch.float32 and w_fwd.dtype == dy.dtype
+    check(lib().fmri_conv3d_first_dgrad(_p(dy), Cout, _p(w_fwd), _p(dx), N, D, H, W, Cin, dt(dy), _s()), "fmri_conv3d_first_dgrad")
+    return dx
+
+
 def conv3d_wgrad(src0, src1, dy, dw, db, up0=False, impl=IMPL_AUTO, planar=False, workspace=None):
     _need_cuda(src0, src1, dy, dw, db)
     N, D, H, W, Cout = dy.shape

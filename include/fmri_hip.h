@@ -86,6 +86,18 @@ int fmri_conv3d_fwd_tail_planar(const void* src0, int C0, const void* w, const f
 int fmri_conv3d_dgrad(const void* dy, int Cout, const void* w_dgrad, const void* mask, void* dx, int N, int D, int H,
                       int W, int Cin, int dtype, int impl, int planar, fmri_stream_t stream);
 
+/* ---- Conv3DBackpropInputV2 of the network's FIRST convolution (1-4 input channels), in fp32: the gradient that leaves a frozen
+ * segmenter towards a network in front of it (reference fetal_net/model/norm/NormNet.py).
+ *   dy [N][D][H][W][Cout] bf16: the gradient at the convolution's output (the block's ReLU mask / normalisation backward applied);
+ *   w  [27][Cout][Cin] bf16: the FORWARD filter image (w_fwd of fmri_conv3d_pack_weights), tap = kd*9 + kh*3 + kw;
+ *   dx [N][D][H][W][Cin] FP32, overwritten: dx[v][c] = sum_tap sum_co dy[v - off(tap)][co] * w[tap][co][c], zeros outside the volume.
+ * Every dx element is written once by one lane in a fixed summation order (no atomics): two calls give the same bits.
+ * Shapes (fmri_conv3d_first_dgrad_ok == 1): FMRI_BF16, Cin 1..4, Cout % 32 == 0, D % 4 == 0, H % 16 == 0, W % 32 == 0 (3-D only);
+ * anything else, a NULL pointer or N <= 0: FMRI_E_SHAPE - callers then use fmri_conv3d_dgrad with a [27][Cin][Cout] image. */
+int fmri_conv3d_first_dgrad_ok(int Cin, int Cout, int D, int H, int W, int dtype);
+int fmri_conv3d_first_dgrad(const void* dy, int Cout, const void* w, float* dx, int N, int D, int H, int W, int Cin, int dtype,
+                            fmri_stream_t stream);
+
 /* ---- Conv3DBackpropFilterV2 + BiasAddGrad: dw[27][Cout][C0+C1] (fp32) += sum_v x[v+tap][ci]*dy[v][co];
  * db[Cout] (fp32) += sum_v dy[v][co] (db may be NULL).  ACCUMULATES: the caller zeroes dw/db once per step.
  * Same dual-source / fused-upsample input description as fmri_conv3d_fwd.
