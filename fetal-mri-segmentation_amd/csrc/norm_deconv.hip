@@ -4,13 +4,43 @@
 // All HBM-bound; channels-last, fp32 statistics accumulated in double.
 #include "common.h"
 
+FMRI_DET_TU(norm)
+
 namespace {
+
+// ---- ordered statistics (deterministic mode).  The reductions below end in one fp64 atomic per channel per workgroup, whose arrival order
+// moves the last bits of the totals.  With a slab given, a workgroup instead STORES its partial {sum, sum2} to row blockIdx.z * gridDim.x +
+// blockIdx.x of slab[rows][C][2] - a static index - and k_norm_slab_fold, a second launch, adds the rows of every (group, channel) in
+// ascending order.  No workgroup waits for another one.  fp64 partials: no range limit (a 2^-k fixed-point image of ws would leave a sum of
+// x^2 over 4 x 64x128x128 voxels too few fraction bits).
+__device__ __forceinline__ void norm_partial_out(double* __restrict__ ws, double* __restrict__ slab, int gi, int C, int c, double a, double b) {
+    if (slab) {
+        double* const r = slab + (((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * C + c) * 2;
+        r[0] = a;
+        r[1] = b;
+    } else {
+        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 0], a);
+        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 1], b);
+    }
+}
+// ws[g][c][k] += slab rows g * rows .. g * rows + rows - 1, in that order (rows = workgroups per group: gridDim.x per sample for instance
+// norm, N * gridDim.x for batch norm, whose single group owns every row)
+__global__ void k_norm_slab_fold(const double* __restrict__ slab, double* __restrict__ ws, int G, int C, int rows) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= G * C * 2) return;
+    const int g = i / (2 * C), r = i % (2 * C);
+    const double* p = slab + (int64_t)g * rows * C * 2 + r;
+    double a = 0.0;
+    for (int k = 0; k < rows; ++k) a += p[(int64_t)k * C * 2];
+    ws[i] += a;
+}
 
 // ---------------------------------------------------------------------------------------------------- statistics
 // ws[g][c][0..1] (double) += sum(x), sum(x^2) over the voxels of group g (g = sample for instance norm, 0 for batch norm).
 // Block = 256 threads = (256/CL) voxel lanes x CL channel lanes, CL = min(C,64) rounded to a power of two.
 template <typename T>
-__global__ void k_norm_reduce(const T* __restrict__ x, double* __restrict__ ws, int64_t V, int C, int per_instance, int vchunk) {
+__global__ void k_norm_reduce(const T* __restrict__ x, double* __restrict__ ws, double* __restrict__ slab, int64_t V, int C, int per_instance,
+                              int vchunk) {
     const int c = blockIdx.y * 64 + (threadIdx.x & 63);
     const int g = blockIdx.z;
     const int vl = threadIdx.x >> 6;                       // 0..3
@@ -32,15 +62,14 @@ __global__ void k_norm_reduce(const T* __restrict__ x, double* __restrict__ ws, 
     if (threadIdx.x < 64 && c < C) {
         double ds = (double)red[0][0][threadIdx.x] + red[0][1][threadIdx.x] + red[0][2][threadIdx.x] + red[0][3][threadIdx.x];
         double dq = (double)red[1][0][threadIdx.x] + red[1][1][threadIdx.x] + red[1][2][threadIdx.x] + red[1][3][threadIdx.x];
-        const int gi = per_instance ? g : 0;
-        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 0], ds);
-        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 1], dq);
+        norm_partial_out(ws, slab, per_instance ? g : 0, C, c, ds, dq);
     }
 }
 // Same reductions with 16-byte loads (bf16 x 8 channels per lane): C/8 lanes cover one voxel's channels, 256/(C/8) voxels per pass.
 // Used when C/8 is a power of two <= 256 (the scalar kernels above move 2 bytes per lane and reach ~1/4 of the HBM rate).
 template <typename T, int VEC>
-__global__ void __launch_bounds__(256) k_norm_reduce_v(const T* __restrict__ x, double* __restrict__ ws, int64_t V, int C, int per_instance, int vchunk) {
+__global__ void __launch_bounds__(256) k_norm_reduce_v(const T* __restrict__ x, double* __restrict__ ws, double* __restrict__ slab, int64_t V, int C,
+                                                       int per_instance, int vchunk) {
     const int CG = C / VEC, VL = 256 / CG;
     const int cg = threadIdx.x % CG, vl = threadIdx.x / CG;
     const int g = blockIdx.z;
@@ -63,9 +92,7 @@ __global__ void __launch_bounds__(256) k_norm_reduce_v(const T* __restrict__ x, 
     for (int c = threadIdx.x; c < C; c += 256) {          // (C up to 512: 64 channel groups x 4 voxel lanes)
         double ds = 0, dq = 0;
         for (int l = 0; l < VL; ++l) { ds += red[0][l * CG + c / VEC][c % VEC]; dq += red[1][l * CG + c / VEC][c % VEC]; }
-        const int gi = per_instance ? g : 0;
-        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 0], ds);
-        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 1], dq);
+        norm_partial_out(ws, slab, per_instance ? g : 0, C, c, ds, dq);
     }
 }
 // FROMX: the sign of the block's output is recomputed from x exactly as k_norm_apply formed it (z = fma(x, inv * gamma, beta - mean * inv *
@@ -74,7 +101,8 @@ __global__ void __launch_bounds__(256) k_norm_reduce_v(const T* __restrict__ x, 
 template <typename T, int VEC, bool FROMX>
 __global__ void __launch_bounds__(256) k_norm_bwd_reduce_v(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy, const float* __restrict__ stats,
                                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                                    double* __restrict__ ws, int64_t V, int C, int per_instance, int act, float alpha, int vchunk) {
+                                    double* __restrict__ ws, double* __restrict__ slab, int64_t V, int C, int per_instance, int act, float alpha,
+                                    int vchunk) {
     const int CG = C / VEC, VL = 256 / CG;
     const int cg = threadIdx.x % CG, vl = threadIdx.x / CG;
     const int g = blockIdx.z, gi = per_instance ? g : 0;
@@ -116,8 +144,7 @@ __global__ void __launch_bounds__(256) k_norm_bwd_reduce_v(const T* __restrict__
         double ds = 0, dq = 0;
         for (int l = 0; l < VL; ++l) { ds += red[0][l * CG + c / VEC][c % VEC]; dq += red[1][l * CG + c / VEC][c % VEC]; }
         const float* const st = stats + ((int64_t)gi * C + c) * 3;
-        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 0], ds);
-        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 1], (dq - (double)st[0] * ds) * (double)st[1]);      // sum dz * xhat, xhat = (x - mean) * inv
+        norm_partial_out(ws, slab, gi, C, c, ds, (dq - (double)st[0] * ds) * (double)st[1]);      // sum dz * xhat, xhat = (x - mean) * inv
     }
 }
 // voxels per reduction workgroup.  Every workgroup ends with one fp64 atomic per channel into its group's accumulators, so the number of
@@ -241,7 +268,8 @@ __global__ void __launch_bounds__(256) k_norm_apply(const T* __restrict__ x, con
 template <typename T>
 __global__ void k_norm_bwd_reduce(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy, const float* __restrict__ stats,
                                   const float* __restrict__ gamma, const float* __restrict__ beta,
-                                  double* __restrict__ ws, int64_t V, int C, int per_instance, int act, float alpha, int vchunk) {
+                                  double* __restrict__ ws, double* __restrict__ slab, int64_t V, int C, int per_instance, int act, float alpha,
+                                  int vchunk) {
     const int c = blockIdx.y * 64 + (threadIdx.x & 63);
     const int g = blockIdx.z;
     const int vl = threadIdx.x >> 6;
@@ -270,9 +298,7 @@ __global__ void k_norm_bwd_reduce(const T* __restrict__ x, const T* __restrict__
     if (threadIdx.x < 64 && c < C) {
         double ds = (double)red[0][0][threadIdx.x] + red[0][1][threadIdx.x] + red[0][2][threadIdx.x] + red[0][3][threadIdx.x];
         double dq = (double)red[1][0][threadIdx.x] + red[1][1][threadIdx.x] + red[1][2][threadIdx.x] + red[1][3][threadIdx.x];
-        const int gi = per_instance ? g : 0;
-        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 0], ds);
-        atomicAdd(&ws[((int64_t)gi * C + c) * 2 + 1], dq);
+        norm_partial_out(ws, slab, per_instance ? g : 0, C, c, ds, dq);
     }
 }
 // dgamma[c] += sum_g ws[g][c][1], dbeta[c] += sum_g ws[g][c][0]; the last reader of the backward sums (launched behind the apply pass)
@@ -442,6 +468,8 @@ __global__ void k_deconv_dgrad(const T* __restrict__ dy, int dy_ld, int dy_off, 
     }
 }
 // dw[a][co][ci] += sum_{n,i} dy[n,2i+a,co] * x[n,i,ci];  db[co] += sum dy.  One block per (a, co): threads over ci, loop voxels.
+// The nsplit voxel ranges are a static partition and every partial a fixed-order fma chain: flushed through fmri_grad_add, the sums are
+// bit-reproducible in deterministic mode.
 template <typename T>
 __global__ void k_deconv_wgrad(const T* __restrict__ x, const T* __restrict__ dy, int dy_ld, int dy_off, float* __restrict__ dw,
                                float* __restrict__ db, int N, int D, int H, int W, int Cin, int Cout, int pd, int nsplit) {
@@ -464,12 +492,41 @@ __global__ void k_deconv_wgrad(const T* __restrict__ x, const T* __restrict__ dy
             if (ci < Cin) acc = fmaf(g, to_f<T>(x[v * Cin + ci]), acc);
             if (ci0 == 0 && threadIdx.x == 0) bsum += g;
         }
-        if (ci < Cin) atomicAdd(&dw[((int64_t)a * Cout + co) * Cin + ci], acc);
+        if (ci < Cin) fmri_grad_add(g_det_cfg, &dw[((int64_t)a * Cout + co) * Cin + ci], acc);
     }
-    if (db && threadIdx.x == 0) atomicAdd(&db[co], bsum);
+    if (db && threadIdx.x == 0) fmri_grad_add(g_det_cfg, &db[co], bsum);
 }
 
 }  // namespace
+
+// ---- deterministic mode: the slab of the ordered statistics (fmri_set_deterministic_scratch)
+static double* h_norm_slab = nullptr;
+static int64_t h_norm_slab_bytes = 0;
+static inline int64_t norm_slab_doubles(int N, int64_t V, int C, int per_instance) {
+    return (int64_t)N * ceil_div64(V, norm_vchunk(V, N, per_instance, C)) * C * 2;
+}
+// the slab a reduction launch writes its partials to: nullptr in default mode (atomics); deterministic mode without a large enough slab is
+// an error (*rc), never a silent return to the atomics
+static inline double* norm_slab_for(int N, int64_t V, int C, int per_instance, int* rc) {
+    *rc = FMRI_OK;
+    if (!h_det_on) return nullptr;
+    if (!h_norm_slab || norm_slab_doubles(N, V, C, per_instance) * (int64_t)sizeof(double) > h_norm_slab_bytes) *rc = FMRI_E_SHAPE;
+    return h_norm_slab;
+}
+static inline void norm_slab_fold(const double* slab, double* ws, int N, int64_t V, int C, int per_instance, int vchunk, hipStream_t s) {
+    const int G = per_instance ? N : 1, gx = (int)ceil_div64(V, vchunk);
+    k_norm_slab_fold<<<(G * C * 2 + 255) / 256, 256, 0, s>>>(slab, ws, G, C, per_instance ? gx : N * gx);
+}
+extern "C" int fmri_set_deterministic_scratch(void* scratch, int64_t bytes) {
+    if ((scratch == nullptr) != (bytes <= 0) || ((uintptr_t)scratch & 7)) return FMRI_E_SHAPE;
+    h_norm_slab = (double*)scratch;
+    h_norm_slab_bytes = scratch ? bytes : 0;
+    return FMRI_OK;
+}
+extern "C" int64_t fmri_norm_det_workspace_bytes(int N, int64_t V, int C, int per_instance) {
+    if (N <= 0 || V <= 0 || C <= 0) return 0;
+    return norm_slab_doubles(N, V, C, per_instance ? 1 : 0) * (int64_t)sizeof(double);
+}
 
 int norm_ws_zero(double* ws, int n, hipStream_t s) {
     if (!ws || n <= 0) return FMRI_E_SHAPE;
@@ -511,10 +568,14 @@ static int norm_act_fwd_impl(const void* x, const float* gamma, const float* bet
         if (!have_sums) {
         const int vchunk = norm_vchunk(V, N, per_instance, C);
         dim3 grid((unsigned)ceil_div64(V, vchunk), (C + 63) / 64, N);
+        int rc;
+        double* const slab = norm_slab_for(N, V, C, per_instance, &rc);          // deterministic mode: ordered partials, folded below
+        if (rc) return rc;
         if (norm_vec_ok(C, dtype))
-            k_norm_reduce_v<bf16_t, 8><<<dim3(grid.x, 1, N), 256, 0, s>>>((const bf16_t*)x, ws, V, C, per_instance, vchunk);
-        else if (dtype == FMRI_F32) k_norm_reduce<float><<<grid, 256, 0, s>>>((const float*)x, ws, V, C, per_instance, vchunk);
-        else k_norm_reduce<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)x, ws, V, C, per_instance, vchunk);
+            k_norm_reduce_v<bf16_t, 8><<<dim3(grid.x, 1, N), 256, 0, s>>>((const bf16_t*)x, ws, slab, V, C, per_instance, vchunk);
+        else if (dtype == FMRI_F32) k_norm_reduce<float><<<grid, 256, 0, s>>>((const float*)x, ws, slab, V, C, per_instance, vchunk);
+        else k_norm_reduce<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)x, ws, slab, V, C, per_instance, vchunk);
+        if (slab) norm_slab_fold(slab, ws, N, V, C, per_instance, vchunk, s);
         }
         const double M = per_instance ? (double)V : (double)V * N;
         k_norm_finalize<<<(G * C + 255) / 256, 256, 0, s>>>(ws, stats, G, C, M, eps, eps_on_std);
@@ -568,6 +629,9 @@ static int norm_act_bwd_impl(const void* x, const void* y, const void* dy, const
     const int G = per_instance ? N : 1;
     const int vchunk = norm_vchunk(V, N, per_instance, C);
     dim3 grid((unsigned)ceil_div64(V, vchunk), (C + 63) / 64, N);
+    int rc = FMRI_OK;
+    double* const slab = pre ? nullptr : norm_slab_for(N, V, C, per_instance, &rc);     // deterministic mode: ordered partials
+    if (rc) return rc;
     if (pre) {
         if (dtype != FMRI_F32 && dtype != FMRI_BF16) return FMRI_E_DTYPE;
         k_norm_bwd_center<<<(G * C + 255) / 256, 256, 0, s>>>(ws, stats, G, C);
@@ -579,15 +643,16 @@ static int norm_act_bwd_impl(const void* x, const void* y, const void* dy, const
     } else if (norm_vec_ok(C, dtype)) {
         if (beta)
             k_norm_bwd_reduce_v<bf16_t, 8, true><<<dim3(grid.x, 1, N), 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, stats, gamma,
-                                                                                      beta, ws, V, C, per_instance, act, alpha, vchunk);
+                                                                                      beta, ws, slab, V, C, per_instance, act, alpha, vchunk);
         else
             k_norm_bwd_reduce_v<bf16_t, 8, false><<<dim3(grid.x, 1, N), 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, stats, gamma,
-                                                                                       beta, ws, V, C, per_instance, act, alpha, vchunk);
+                                                                                       beta, ws, slab, V, C, per_instance, act, alpha, vchunk);
     } else if (dtype == FMRI_F32)
-        k_norm_bwd_reduce<float><<<grid, 256, 0, s>>>((const float*)x, (const float*)y, (const float*)dy, stats, gamma, beta, ws, V, C, per_instance, act, alpha, vchunk);
+        k_norm_bwd_reduce<float><<<grid, 256, 0, s>>>((const float*)x, (const float*)y, (const float*)dy, stats, gamma, beta, ws, slab, V, C, per_instance, act, alpha, vchunk);
     else if (dtype == FMRI_BF16)
-        k_norm_bwd_reduce<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, stats, gamma, beta, ws, V, C, per_instance, act, alpha, vchunk);
+        k_norm_bwd_reduce<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, stats, gamma, beta, ws, slab, V, C, per_instance, act, alpha, vchunk);
     else return FMRI_E_DTYPE;
+    if (slab) norm_slab_fold(slab, ws, N, V, C, per_instance, vchunk, s);
     const double M = per_instance ? (double)V : (double)V * N;
     const int vec = pick_vec(C);
     const int64_t total = (int64_t)N * V * (C / vec);

@@ -896,6 +896,7 @@ extern "C" int fmri_weighted_dice_fwd(const float* probs, const uint8_t* y_true,
     if (hipMemsetAsync(gsums, 0, (size_t)G * 3 * sizeof(double), s) != hipSuccess) return FMRI_E_LAUNCH;
     int bx = (int)((vox + 256 * 16 - 1) / (256 * 16));
     if (bx > 256) bx = 256;
+    if (h_det_on) bx = 1;          // deterministic mode: one workgroup per sample, so no two workgroups meet in a group's fp64 sums
     k_wdice_sums<<<dim3(bx, nsamples), 256, 0, s>>>(probs, y_true, gsums, vox, L);
     k_wdice_finish<<<1, 64, 0, s>>>(gsums, sums, G, smooth);
     FMRI_LAUNCH_CHECK();
@@ -1159,6 +1160,7 @@ int fmri_det_set_mfma(const FmriDetCfg&);
 int fmri_det_set_first(const FmriDetCfg&);
 int fmri_det_set_generic(const FmriDetCfg&);
 int fmri_det_set_direct(const FmriDetCfg&);
+int fmri_det_set_norm(const FmriDetCfg&);
 extern "C" int fmri_set_deterministic(float* grad_base, void* shadow_i64, int64_t n) {
     if ((grad_base == nullptr) != (shadow_i64 == nullptr) || (grad_base && n <= 0)) return FMRI_E_SHAPE;
     const FmriDetCfg c{grad_base, (unsigned long long*)shadow_i64, grad_base ? (long long)n : 0};
@@ -1167,6 +1169,7 @@ extern "C" int fmri_set_deterministic(float* grad_base, void* shadow_i64, int64_
     if (!rc) rc = fmri_det_set_first(c);
     if (!rc) rc = fmri_det_set_generic(c);
     if (!rc) rc = fmri_det_set_direct(c);
+    if (!rc) rc = fmri_det_set_norm(c);
     return rc;
 }
 extern "C" int fmri_deterministic_finish(float* grad_base, void* shadow_i64, int64_t n, fmri_stream_t stream) {

@@ -577,13 +577,14 @@ class Model(object):
                     dist_ctx = DataParallel()
             except Exception:
                 dist_ctx = None
+            # trainable = False (norm_net_model sets it on its segmenter): the engine is built frozen - it is only ever run with
+            # backward(params=False), and under FMRI_DETERMINISTIC=1 it leaves the one registration to the network that is trained
+            kw = dict(self._engine_kwargs, frozen=True) if getattr(self, "trainable", True) is False else self._engine_kwargs
             if getattr(self, "_graph_engine", False):
                 from fmri_hip.graph_engine import LayerGraphEngine
-                self._engine = LayerGraphEngine(self.layers, batch, dtype=self._compute_dtype(), training=True, dist_ctx=dist_ctx,
-                                                **self._engine_kwargs)
+                self._engine = LayerGraphEngine(self.layers, batch, dtype=self._compute_dtype(), training=True, dist_ctx=dist_ctx, **kw)
             else:
-                self._engine = UNetEngine(UNetPlan(**self._plan_args), batch, dtype=self._compute_dtype(), training=True, dist_ctx=dist_ctx,
-                                          **self._engine_kwargs)
+                self._engine = UNetEngine(UNetPlan(**self._plan_args), batch, dtype=self._compute_dtype(), training=True, dist_ctx=dist_ctx, **kw)
             if self._pending_weights is not None:
                 self._engine.load_keras_weights(self._pending_weights)
                 self._pending_weights = None

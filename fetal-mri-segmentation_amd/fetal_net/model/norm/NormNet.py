@@ -95,10 +95,15 @@ def norm_net_model(input_shape=(1, 128, 128, 128), n_base_filters=16, depth=5, d
         seg_net = load_old_model(str(old_model_path))
     _check_segmenter(seg_net, n_labels, input_shape)
     seg_net.trainable = False
-    if seg_net._engine is not None and not getattr(seg_net._engine, "input_grad", False):
-        # an engine built for plain use: rebuild it (same weights) so that its backward pass ends in dL/d(input)
+    if seg_net._engine is not None and not (getattr(seg_net._engine, "input_grad", False) and getattr(seg_net._engine, "frozen", False)):
+        # an engine built for plain use: rebuild it (same weights) so that its backward pass ends in dL/d(input) - and, under
+        # FMRI_DETERMINISTIC=1, so that it gives the deterministic-gradient registration back: the norm net takes it
         seg_net._pending_weights = OrderedDict((k, np.asarray(v)) for k, v in seg_net._engine.export_keras_weights().items())
+        seg_net._engine.close()
         seg_net._engine = None
+    # (trainable = False above makes Model.engine build it frozen: the segmenter writes no parameter gradient anybody reads, so under
+    # FMRI_DETERMINISTIC=1 it takes no registration - one per process, the trainable norm net's - while its normalisation layers still
+    # sum in block order)
     seg_net._engine_kwargs = dict(seg_net._engine_kwargs, input_grad=True)
     builder_kwargs = dict(input_shape=input_shape, n_base_filters=n_base_filters, depth=depth, dropout_rate=dropout_rate,
                           n_segmentation_levels=n_segmentation_levels, n_labels=n_labels, initial_learning_rate=initial_learning_rate,

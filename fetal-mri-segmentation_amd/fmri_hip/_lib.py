@@ -103,6 +103,8 @@ SIGNATURES = {
     "fmri_adam_step": [p, p, p, p, i64, f32, f32, f32, f32, f32, p],
     "fmri_set_deterministic": [p, p, i64],
     "fmri_deterministic_finish": [p, p, i64, p],
+    "fmri_set_deterministic_scratch": [p, i64],
+    "fmri_norm_det_workspace_bytes": [i32, i64, i32, i32],
     "fmri_tile_gather": [p, i32, i32, i32, p, i32, i32, i32, i32, p, i32, p],
     "fmri_tile_gather_stack": [p, p, i32, i32, i32, p, i32, i32, i32, i32, i32, i32, p, i32, p],
     "fmri_tile_scatter_accumulate": [p, p, i32, i32, i32, i32, i32, p, p, i32, i32, i32, p],

@@ -25,7 +25,12 @@ class ChainEngine(object):
             raise ValueError("the network in front must have a linear output (isensee2017_model_3d(activation_name=None))")
         if not getattr(seg, "input_grad", False) or not seg.training:
             raise ValueError("the frozen segmenter's engine must be built with input_grad=True")
+        if getattr(norm, "deterministic", False) != getattr(seg, "deterministic", False) or (
+                getattr(seg, "deterministic", False) and not getattr(seg, "frozen", False)):
+            raise ValueError("FMRI_DETERMINISTIC=1: the network in front holds the deterministic-gradient registration, the segmenter's engine "
+                             "must be built frozen=True under the same switch")
         self.norm, self.seg = norm, seg
+        self.deterministic = bool(getattr(norm, "deterministic", False))       # both engines on ordered routes, the registration is norm's
         self.dtype, self.dev, self.training, self.dist = norm.dtype, norm.dev, norm.training, norm.dist
         self.plan = seg.plan                     # output geometry: labels and spatial dims of the segmenter
         self.sums = seg.sums                     # the metric sums are the segmenter's (one tensor for the engine's lifetime)
@@ -62,6 +67,9 @@ class ChainEngine(object):
 
     def export_keras_weights(self):
         return self.norm.export_keras_weights()
+
+    def close(self):
+        self.norm.close()
 
     def adam_step(self, lr, **kw):
         self.norm.adam_step(lr, **kw)

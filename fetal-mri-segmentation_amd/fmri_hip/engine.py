@@ -89,19 +89,24 @@ class UNetPlan:
 
 
 class UNetEngine(EngineBase):
-    def __init__(self, plan, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None, input_grad=False):
+    def __init__(self, plan, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None, input_grad=False, frozen=False):
         """input_grad: backward() also delivers dL/d(input) (input_gradient()) - the gradient a network in front of this one is trained
-        with while this one stays frozen (backward(params=False); reference fetal_net/model/norm/NormNet.py)."""
+        with while this one stays frozen (backward(params=False); reference fetal_net/model/norm/NormNet.py).  frozen: EngineBase."""
         # every switch of this engine, read here and nowhere else; what each one does stands where self.sw[...] is used
-        super().__init__(dtype, device, training, dist_ctx, DETERMINISTIC=False, DECONV_FOLD=True, FWD_WS=True, UPCAT=True, TAIL_FUSE=True,
+        super().__init__(dtype, device, training, dist_ctx, frozen=frozen, DECONV_FOLD=True, FWD_WS=True, UPCAT=True, TAIL_FUSE=True,
                          TAIL_FUSE_2D=True, NORM_FUSE=1, NORM_FUSE_MAXLEVEL=1 if plan.norm == "batch" else 0, FIRST_DGRAD=True)
         self.plan, self.N = plan, batch
         self.input_grad = bool(input_grad and training)
         self.planar = plan.ndim == 2      # 2-D: tensors are [1][slices][H][W][C], every op is planar (no coupling along D)
-        # FMRI_DETERMINISTIC=1: bit-reproducible training steps (same weights + same batch -> the same bits in every gradient and metric):
-        # gradient partial sums meet as fixed-point integers in a shadow of G (ops.set_deterministic), the parity-form weight gradient -
-        # whose scratch is filled by fp32 atomics - gives way to the fused-upsample 27-tap one.  One engine per process at a time.
-        self.deterministic = bool(training and self.dev.type == "cuda" and self.sw["DETERMINISTIC"])
+        if self.deterministic:
+            # FMRI_DETERMINISTIC=1 (EngineBase) keeps to routes whose sums are ordered, and gives these up:
+            #   * the parity-form weight gradient, whose scratch is filled by fp32 atomics (_upcat_layers): the fused-upsample 27-tap one;
+            #   * the statistics a conv launch forms in its epilogue (the four producer waves of a workgroup meet in its slot with fp64
+            #     atomics): the separate reductions, which add their workgroups' partials in block order - the FMRI_NORM_FUSE=0 path;
+            #   * every route of the transposed conv but the direct k2s2 kernels (the folded one sums border classes with fp32 atomics,
+            #     the one-tap parity form uses the parity-form weight gradient, the 2-D depth-to-space one accumulates outside G) - the
+            #     FMRI_DECONV_FOLD=0 path without the one-tap form.
+            self.sw["NORM_FUSE"], self.sw["DECONV_FOLD"] = 0, False
         self._bufsets = {}
         self._build_params(seed)
         self.set_batch(batch)
@@ -135,12 +140,13 @@ class UNetEngine(EngineBase):
         dev = self.dev
         self._alloc_params()
         if self.deterministic:
-            if p.norm is not None or p.deconvolution:
-                raise NotImplementedError("FMRI_DETERMINISTIC=1 covers the plain unet_model_3d / unet_model_2d step (no normalisation layers, "
-                                          "UpSampling up-convolution): the normalisation statistics and the folded transposed conv still "
-                                          "accumulate with floating-point atomics")
-            self.G64 = torch.zeros(self.n_flat, dtype=torch.int64, device=dev)
-            _register_deterministic(self)
+            cf = p.final["cin"]
+            if cf % 8 or (cf // 8) & (cf // 8 - 1) or cf // 8 > 64 or p.n_labels > 4:
+                raise NotImplementedError("FMRI_DETERMINISTIC=1: the final 1x1x1 convolution over %d channels / %d labels takes the generic "
+                                          "fmri_conv1x1_bwd kernel, whose waves meet in LDS with floating-point atomics (reproducible: "
+                                          "8 x 2^k <= 512 channels, at most 4 labels)" % (cf, p.n_labels))
+        if self.training:
+            self._det_register(self.G)
         # compute-dtype copies of the 3x3x3 filters (and no pack table yet: it holds their addresses)
         self.Wf, self.Wd, self.Wup, self._ptab = {}, {}, {}, None
         self.upcat = self._upcat_layers()
@@ -177,7 +183,7 @@ class UNetEngine(EngineBase):
         # Deconvolution3D(k = 2, s = 2) (reference unet.py:135): output voxel 2g+p = W[p] . x[g] + b, i.e. the parity form with ONE
         # non-zero tap per parity class (low-res offset 0) - it rides the same MFMA kernels (fmri_conv3d_upcat_* with C1 = 0)
         self.Wdc = {}
-        if not self.planar and self.dtype == torch.bfloat16:
+        if not self.planar and self.dtype == torch.bfloat16 and not self.deterministic:
             for lvl, u in p.up.items():
                 L = self.layout[u["name"]]
                 D, H, W = p.level_dims(lvl)
@@ -190,7 +196,7 @@ class UNetEngine(EngineBase):
         # 2-D twin (Deconvolution2D, reference unet/unet.py get_up_convolution): the 4 taps are 4 independent 1x1 convs, run as ONE planar
         # 3x3 MFMA conv to 4*Cout channels whose only non-zero tap is the centre one, followed by a depth-to-space copy
         self.Wd2 = {}
-        if self.planar and self.dtype == torch.bfloat16:
+        if self.planar and self.dtype == torch.bfloat16 and not self.deterministic:
             for lvl, u in p.up.items():
                 L = self.layout[u["name"]]
                 _, S, H, W = (1,) + p.level_dims(lvl + 1, 4)                  # low-res dims (the slice count does not matter here)
@@ -537,6 +543,9 @@ class UNetEngine(EngineBase):
         # scratch of the normalisation sums: [G][C][2] doubles - and, behind them, the per-workgroup blocks of the conv launches' tails
         self.norm_ws = torch.zeros(max(max(G, 1) * cmax * 2, ops.norm_tail_ws_doubles(max(G, 1), cmax) if dev.type == "cuda" else 0),
                                    dtype=torch.float64, device=dev) if p.norm else None
+        if p.norm:
+            self._det_reserve_norm([(N, int(np.prod(self._dims(c["level"])[1:])) // (N if self.planar else 1), c["cout"], self._norm_mode()[0])
+                                    for c in p.convs_forward_order()])
         nvox0 = int(np.prod(self._dims(0)))
         self.logits = torch.empty((nvox0, p.n_labels), dtype=torch.float32, device=dev)
         self.probs = torch.empty_like(self.logits)
@@ -762,6 +771,7 @@ class UNetEngine(EngineBase):
         p, A, Gd = self.plan, self.act, self.grad
         normed = p.norm is not None
         self._params = bool(params)
+        self._det_check_backward(params)
         self._main_stream = torch.cuda.current_stream(self.dev) if self.dev.type == "cuda" else None
         self._dz_ready = set()
         self.G.zero_()
@@ -846,7 +856,7 @@ class UNetEngine(EngineBase):
         if params:
             self._join_wgrad()
         if self.deterministic:
-            ops.deterministic_finish(self.G, self.G64)       # G += the fixed-point sums of every gradient kernel of this pass
+            self._det_finish()                               # G += the fixed-point sums of every gradient kernel of this pass
             if self.dist is not None and params:
                 self.dist.begin()                            # nothing was reduced during this backward: one range, the whole buffer
         if self.dist is not None and params:
@@ -882,40 +892,9 @@ class UNetEngine(EngineBase):
                 return lv[1]["name"]
         raise KeyError(ld)
 
-    def close(self):
-        """give up the process-wide deterministic registration (FMRI_DETERMINISTIC=1; also done when the engine is garbage-collected)"""
-        fin = self.__dict__.pop("_det_finalizer", None)
-        if fin is not None:
-            fin()
-
     def _grad_ready(self, name):
         # deterministic mode: the gradients sit in the int64 shadow until deterministic_finish at the end of backward(), so no bucket of
         # G may be reduced before that - the whole buffer goes in dist.finish (ADVICE r3: early buckets all-reduced zeros)
         if self.dist is not None and not self.deterministic and self._params:
             self.dist.grad_ready(self, name)
 
-
-_DET_OWNER = []          # [weakref to the engine that holds the process-wide fmri_set_deterministic registration]
-
-
-def _release_deterministic(token):
-    if _DET_OWNER and _DET_OWNER[0] is token:
-        _DET_OWNER.clear()
-        try:
-            ops.set_deterministic(None, None)
-        except Exception:                                    # interpreter shutdown: the library may be gone already
-            pass
-
-
-def _register_deterministic(eng):
-    """fmri_set_deterministic keeps raw device pointers process-wide: ONE engine may hold the registration, and it is given back when
-    that engine dies or is closed (a stale registration redirected a later engine's gradients into freed memory)"""
-    import weakref
-    if _DET_OWNER and _DET_OWNER[0]() is not None:
-        raise RuntimeError("FMRI_DETERMINISTIC=1: another engine of this process holds the deterministic-gradient registration "
-                           "(one deterministic engine per process at a time; call its close() first)")
-    _DET_OWNER.clear()
-    ref = weakref.ref(eng)
-    _DET_OWNER.append(ref)
-    ops.set_deterministic(eng.G, eng.G64)
-    eng._det_finalizer = weakref.finalize(eng, _release_deterministic, ref)

@@ -14,6 +14,7 @@ The module-level helpers convert Keras kernels: a Glorot-uniform draw, and a con
 """
 import math
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -32,12 +33,58 @@ def read_switches(**defaults):
     return out
 
 
+_DET_OWNER = []          # [weakref to the engine that holds the process-wide fmri_set_deterministic registration]
+_DET_SCRATCH = []        # [the slab of the ordered normalisation statistics, as registered with fmri_set_deterministic_scratch]
+
+
+def _release_deterministic(token):
+    if _DET_OWNER and _DET_OWNER[0] is token:
+        _DET_OWNER.clear()
+        _DET_SCRATCH.clear()
+        try:
+            ops.set_deterministic(None, None)                # (takes the scratch registration back as well)
+        except Exception:                                    # interpreter shutdown: the library may be gone already
+            pass
+
+
+def register_deterministic(eng, grad, shadow):
+    """fmri_set_deterministic keeps raw device pointers process-wide: ONE engine may hold the registration, and it is given back when
+    that engine dies or is closed (a stale registration redirected a later engine's gradients into freed memory).
+    grad: the buffer the engine's gradient kernels write (dw / db pointers), shadow: its zeroed int64 twin."""
+    if _DET_OWNER and _DET_OWNER[0]() is not None:
+        raise RuntimeError("FMRI_DETERMINISTIC=1: another engine of this process holds the deterministic-gradient registration "
+                           "(one deterministic engine per process at a time; call its close() first)")
+    _DET_OWNER.clear()
+    ref = weakref.ref(eng)
+    _DET_OWNER.append(ref)
+    ops.set_deterministic(grad, shadow, _DET_SCRATCH[0] if _DET_SCRATCH else None)
+    eng._det_finalizer = weakref.finalize(eng, _release_deterministic, ref)
+
+
+def reserve_deterministic_scratch(nbytes, dev):
+    """the process-wide slab of the ordered normalisation statistics holds at least nbytes from here on.  It only grows; every engine
+    of the process - the registered one and a frozen one next to it - shares it, their normalisation calls being ordered on one stream."""
+    if nbytes <= 0 or (_DET_SCRATCH and _DET_SCRATCH[0].numel() * 8 >= nbytes):
+        return
+    _DET_SCRATCH[:] = [torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)]
+    ops.set_deterministic_scratch(_DET_SCRATCH[0])
+
+
 class EngineBase(object):
-    def __init__(self, dtype, device, training, dist_ctx, **switches):
-        """switches: the engine's own FMRI_* switches and their defaults (read_switches), next to FMRI_WGRAD_STREAM which both engines have"""
+    def __init__(self, dtype, device, training, dist_ctx, frozen=False, **switches):
+        """switches: the engine's own FMRI_* switches and their defaults (read_switches), next to FMRI_WGRAD_STREAM and FMRI_DETERMINISTIC
+        which both engines have"""
         lib()  # fail loudly if the HIP library is missing
         self.dtype, self.dev, self.training, self.dist = dtype, torch.device(device), training, dist_ctx
-        self.sw = read_switches(WGRAD_STREAM=True, **switches)
+        self.sw = read_switches(WGRAD_STREAM=True, DETERMINISTIC=False, **switches)
+        # FMRI_DETERMINISTIC=1: bit-reproducible training steps (same weights + same batch -> the same bits in every gradient and metric).
+        # Gradient partial sums meet as fixed-point integers in a shadow of the buffer the gradient kernels write (_det_register), the
+        # normalisation reductions add their workgroups' partials in block order (_det_reserve_norm), and the engines keep to kernel
+        # routes whose sums are ordered.  One registered engine per process at a time.
+        # frozen: an engine that is only ever run with backward(params=False) next to the registered one (the segmenter of
+        # norm_net_model): it writes no parameter gradient anybody reads, so it takes no registration, but it runs the ordered routes.
+        self.deterministic = bool(training and self.dev.type == "cuda" and self.sw["DETERMINISTIC"])
+        self.frozen = bool(frozen)
         self.t = 0                       # Adam step counter
         self.beta1 = 0.9                 # Adam's beta_1 when adam_step is given none (fetal_net.adversarial sets the optimizer's)
         self.loss_kind, self.loss_param = 0, 1.0      # ops.LOSS_KINDS: 0 = dice_coefficient_loss
@@ -52,6 +99,37 @@ class EngineBase(object):
         self.P = torch.zeros(self.n_flat, dtype=torch.float32, device=self.dev)
         if self.training:
             self.G, self.M, self.V = torch.zeros_like(self.P), torch.zeros_like(self.P), torch.zeros_like(self.P)
+
+    # ------------------------------------------------------------------------------------------------ deterministic mode
+    def _det_register(self, grad):
+        """deterministic mode: the int64 shadow G64 of `grad` - the buffer the weight-gradient kernels of this engine write - and the
+        process-wide registration (a frozen engine takes none)"""
+        if not self.deterministic or self.frozen:
+            return
+        self._det_grad = grad
+        self.G64 = torch.zeros(grad.numel(), dtype=torch.int64, device=self.dev)
+        register_deterministic(self, grad, self.G64)
+
+    def _det_reserve_norm(self, calls):
+        """deterministic mode: room in the ordered-statistics slab for every normalisation call (N, V, C, per_instance) of a buffer set"""
+        if self.deterministic:
+            reserve_deterministic_scratch(max([ops.norm_det_workspace_bytes(*c) for c in calls] + [0]), self.dev)
+
+    def _det_finish(self):
+        """end of backward: the registered buffer += the fixed-point sums of every gradient kernel of this pass"""
+        if self.deterministic and not self.frozen:
+            ops.deterministic_finish(self._det_grad, self.G64)
+
+    def _det_check_backward(self, params):
+        if self.deterministic and self.frozen and params:
+            raise NotImplementedError("FMRI_DETERMINISTIC=1: this engine was built frozen (it holds no deterministic-gradient registration): "
+                                      "backward(params=False) only")
+
+    def close(self):
+        """give up the process-wide deterministic registration (FMRI_DETERMINISTIC=1; also done when the engine is garbage-collected)"""
+        fin = self.__dict__.pop("_det_finalizer", None)
+        if fin is not None:
+            fin()
 
     # ------------------------------------------------------------------------------------------------ Keras weights
     def load_keras_weights(self, W):

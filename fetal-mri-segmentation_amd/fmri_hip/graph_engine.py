@@ -45,8 +45,18 @@ class _Dims(object):
 
 
 class LayerGraphEngine(EngineBase):
-    def __init__(self, layers, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None, input_grad=False):
-        super().__init__(dtype, device, training, dist_ctx, GRAPH_PAD=True, S2_PARITY=True)
+    def __init__(self, layers, batch, dtype=torch.bfloat16, device="cuda", seed=42, training=True, dist_ctx=None, input_grad=False, frozen=False):
+        super().__init__(dtype, device, training, dist_ctx, frozen=frozen, GRAPH_PAD=True, S2_PARITY=True)
+        if self.deterministic:
+            # FMRI_DETERMINISTIC=1 (EngineBase): the engine is reproducible bit for bit or refuses here.  Routes it gives up: the parity-form
+            # weight gradients of the stride-2 and the up-sampling convolutions (their scratch is filled by fp32 atomics) - the stride-2 ones
+            # run as stride-1 convolutions sampled at every second voxel (the FMRI_S2_PARITY=0 form), the up-sampling ones keep the parity
+            # form forward and for the input gradient and take the fused-upsample 27-tap weight gradient.  Dropout masks are a function of
+            # torch's generator: a reproducible run also needs torch.manual_seed (or set_dropout_masks).
+            self.sw["S2_PARITY"] = False
+            if dist_ctx is not None:
+                raise NotImplementedError("FMRI_DETERMINISTIC=1 with a dist_ctx: multi-rank data parallel on the layer-graph engine is outside "
+                                          "the mode (its reduction behind the fold of the fixed-point shadow has not been shown reproducible)")
         self.input_grad = bool(input_grad)      # keep dL/d(input) (channel-padded in bf16 mode: the caller hands over cp(C) channels)
         self.layers = list(layers)
         self.by_name = OrderedDict((l.name, l) for l in self.layers)
@@ -59,6 +69,10 @@ class LayerGraphEngine(EngineBase):
         self.pad = dtype == torch.bfloat16 and self.sw["GRAPH_PAD"]
         self._fixed_drop = None
         self._compile()
+        if self.deterministic and self.denses:
+            raise NotImplementedError("FMRI_DETERMINISTIC=1: Dense layers (%s) - the dense / discriminator kernels and the binary "
+                                      "cross-entropy head are outside the mode: their step has not been made and shown bit-reproducible"
+                                      % ", ".join(self.denses))
         self._build_params(seed)
         self._bufsets = {}
         self.set_batch(batch)
@@ -236,7 +250,11 @@ class LayerGraphEngine(EngineBase):
         self.Ws2, self._s2 = {}, None
         if self.pad:
             self._build_padded_params()
+            if self.training:
+                self._det_register(self.Gp)                  # the weight-gradient kernels write the padded images
         else:
+            if self.training:
+                self._det_register(self.G)
             for name, op in self.convs.items():
                 Lc = self.layout[name]
                 self.Wf[name] = torch.empty((op["k"] ** 3, Lc["cout"], Lc["cin"]), dtype=self.dtype, device=self.dev)
@@ -368,7 +386,8 @@ class LayerGraphEngine(EngineBase):
                 coutp, cinp = self.shape[name][0], self.Wp32[name].shape[2]
                 ok = ops.conv3d_upcat_ok(cinp, 0, coutp, *self.shape[name][1:], self.dtype)
                 if ok & 1:
-                    W = dict(up_f=torch.empty((8, 8, coutp, cinp), dtype=self.dtype, device=dev), up_d=None, wgrad=bool(ok & 2))
+                    W = dict(up_f=torch.empty((8, 8, coutp, cinp), dtype=self.dtype, device=dev), up_d=None,
+                             wgrad=bool(ok & 2) and not self.deterministic)
                     if self.training:
                         W["up_d"] = torch.empty((8, 8, cinp, coutp), dtype=self.dtype, device=dev)
                     self.Wup[name] = W
@@ -510,6 +529,8 @@ class LayerGraphEngine(EngineBase):
                         full[o["name"]] = torch.empty(self._lead(N) + sp_in + (o["shape"][0],), dtype=self.dtype, device=self.dev)
                     if self.training:
                         gfull[o["name"]] = torch.zeros(self._lead(N) + sp_in + (o["shape"][0],), dtype=self.dtype, device=self.dev)
+            self._det_reserve_norm([(N, int(np.prod(self.shape[o["out"]][1:])), o["shape"][0], 1 if o["instance"] else 0)
+                                    for o in self.ops if o["kind"] == "norm"])
             cmax = max([self.shape[n][0] for n in self.norms] + [1])
             nvox = N * int(np.prod(self.plan.spatial)) if self.head == "seg" else N
             Lb = self.plan.n_labels
@@ -675,6 +696,7 @@ class LayerGraphEngine(EngineBase):
         params=False: only the input gradient is wanted (the frozen discriminator inside the combined model)."""
         if self.linear and (seg_loss or dprobs is None):
             raise NotImplementedError("a linear output head takes its gradient from outside: backward(dprobs=g, seg_loss=False)")
+        self._det_check_backward(params)
         self._main_stream = torch.cuda.current_stream(self.dev) if self.dev.type == "cuda" else None
         if self.pad:
             if params:
@@ -825,6 +847,8 @@ class LayerGraphEngine(EngineBase):
                         dst[:, :x.shape[1]] = dx
                 self._accum(o["ins"][0], write)
         self._join_wgrad()
+        if params:
+            self._det_finish()                                           # in front of the gather: the shadow covers Gp, not G
         if self.pad and params:
             torch.index_select(self.Gp, 0, self.map_g, out=self.G)       # the logical gradients out of the padded images (one kernel)
         if self.dist is not None and params:

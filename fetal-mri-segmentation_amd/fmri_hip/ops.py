@@ -549,15 +549,35 @@ def clock_ghz(stamp0, stamp1):
     return srt[len(srt) // 2], per
 
 
-def set_deterministic(grad, shadow):
+def set_deterministic(grad, shadow, scratch=None):
     """register (fp32 gradient buffer, zeroed int64 shadow of the same length) for bit-reproducible gradient accumulation, or (None, None)
-    to switch it off (include/fmri_hip.h: fmri_set_deterministic); process-wide"""
+    to switch it off (include/fmri_hip.h: fmri_set_deterministic); process-wide.  scratch: the slab of the ordered normalisation statistics
+    (any contiguous device tensor of norm_det_workspace_bytes; the caller keeps it alive) - without one the normalisation entry points
+    refuse to run while the registration is on"""
     if grad is None:
+        check(lib().fmri_set_deterministic_scratch(0, 0), "fmri_set_deterministic_scratch")
         check(lib().fmri_set_deterministic(0, 0, 0), "fmri_set_deterministic")
         return
-    _need_cuda(grad, shadow)
+    _need_cuda(grad, shadow, scratch)
     assert grad.dtype == torch.float32 and shadow.dtype == torch.int64 and shadow.numel() == grad.numel() and grad.is_contiguous() and shadow.is_contiguous()
+    set_deterministic_scratch(scratch)
     check(lib().fmri_set_deterministic(_p(grad), _p(shadow), grad.numel()), "fmri_set_deterministic")
+
+
+def set_deterministic_scratch(scratch):
+    """the slab of the ordered normalisation statistics on its own (None takes it back): a frozen network that holds no gradient
+    registration of its own grows the registered engine's slab through this"""
+    if scratch is None:
+        check(lib().fmri_set_deterministic_scratch(0, 0), "fmri_set_deterministic_scratch")
+        return
+    _need_cuda(scratch)
+    assert scratch.is_contiguous()
+    check(lib().fmri_set_deterministic_scratch(_p(scratch), scratch.numel() * scratch.element_size()), "fmri_set_deterministic_scratch")
+
+
+def norm_det_workspace_bytes(N, V, C, per_instance):
+    """bytes of the deterministic scratch one norm_act_fwd / norm_act_bwd call on [N][V][C] needs"""
+    return int(lib().fmri_norm_det_workspace_bytes(int(N), int(V), int(C), int(per_instance)))
 
 
 def deterministic_finish(grad, shadow):

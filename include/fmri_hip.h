@@ -368,11 +368,24 @@ int fmri_channel_scale(const void* x, const float* scale, void* y, int N, int64_
  * points into, shadow n zeroed int64 - those partial sums are rounded to 2^-40 fixed point and added with 64-bit integer atomics to
  * shadow[i] instead (integer adds commute exactly); fmri_deterministic_finish adds shadow * 2^-40 to G and clears it (call it once per
  * backward pass, after every gradient kernel, before the optimizer).  The metric sums of fmri_sigmoid_dice_fwd meet the same way (2^-20).
- * Process-wide state (one engine at a time); (NULL, NULL, 0) switches it off.  Covered: the 3x3x3 / first-layer / 1x1x1 / direct
- * weight and bias gradients of the plain U-Net step; NOT covered: the parity-form weight gradient's scratch (fmri_conv3d_upcat_wgrad*:
- * use fmri_conv3d_wgrad with up0), the normalisation statistics, fmri_weighted_dice_fwd, fmri_border_class_sums. */
+ * Process-wide state (one engine at a time); (NULL, NULL, 0) switches it off.  Covered: the 3x3x3 / first-layer / 1x1x1 / direct /
+ * transposed-conv (fmri_deconv3d_k2s2_bwd) weight and bias gradients, the normalisation statistics (below) and the group sums of
+ * fmri_weighted_dice_fwd (one workgroup per sample while a registration is on); NOT covered: the parity-form weight gradient's scratch
+ * (fmri_conv3d_upcat_wgrad*: use fmri_conv3d_wgrad with up0), the statistics a conv launch forms in its epilogue (fmri_conv3d_fwd_stats,
+ * fmri_conv3d_upcat_fwd_stats, fmri_conv3d_dgrad_norm: the four producer waves of a workgroup meet in its slot with fp64 atomics - use
+ * the separate reductions), fmri_border_class_sums, and fmri_conv1x1_bwd on its generic kernel (other than 8 x 2^k channels, or more
+ * than 4 labels: its waves meet in LDS with fp32 atomics).
+ *
+ * Ordered normalisation statistics.  While a registration is on, the reductions of fmri_norm_act_fwd / fmri_norm_act_bwd / fmri_norm_act_bwd_x
+ * do not add their workgroups' fp64 partial sums to ws with atomics: every workgroup stores its partial to a row of a scratch slab chosen by
+ * its block index, and a second launch adds the rows of each (group, channel) in ascending order into ws (`ws` keeps its size [G][C][2] and
+ * its meaning).  fmri_set_deterministic_scratch registers that slab (8-byte aligned device memory; (NULL, 0) takes it back); one call needs
+ * fmri_norm_det_workspace_bytes(N, V, C, per_instance) of it, and all calls that share it must be ordered on one stream.  With a
+ * registration on and no slab, or one too small, those entry points return FMRI_E_SHAPE - they never return to the atomics. */
 int fmri_set_deterministic(float* grad_base, void* shadow_i64, int64_t n);
 int fmri_deterministic_finish(float* grad_base, void* shadow_i64, int64_t n, fmri_stream_t stream);
+int fmri_set_deterministic_scratch(void* scratch, int64_t bytes);
+int64_t fmri_norm_det_workspace_bytes(int N, int64_t V, int C, int per_instance);
 
 /* ---- Keras Adam.get_updates — reference unet.py:85.  lr_t = lr*sqrt(1-b2^t)/(1-b1^t) is computed by the host.
  * g is multiplied by grad_scale first.  p -= lr_t * m/(sqrt(v)+eps). One launch over the flat parameter buffer. */
