@@ -101,6 +101,43 @@ static inline int pick_vec(int C, int maxvec = 8) {
     while (v > 1 && (C % v)) v >>= 1;
     return v;
 }
+// ---- label values of the multi-label kernels (fmri_labels_expand_u8, fmri_tile_finalize_labels, fmri_label_counts_u8): a HOST array of L
+// distinct nonzero bytes, read at enqueue and handed to the kernel by value as eight words (a kernel indexes them through LDS).
+constexpr int FMRI_MAX_LABELS = 32;
+struct FmriLabelValues {
+    uint32_t w[FMRI_MAX_LABELS / 4];
+};
+// FMRI_E_SHAPE: L outside 1..32, NULL, a zero among the values, or a value twice
+static inline int fmri_label_values(const uint8_t* values, int L, FmriLabelValues* out) {
+    if (!values || L < 1 || L > FMRI_MAX_LABELS) return FMRI_E_SHAPE;
+    bool seen[256] = {false};
+    uint8_t v[FMRI_MAX_LABELS] = {0};
+    for (int l = 0; l < L; ++l) {
+        if (values[l] == 0 || seen[values[l]]) return FMRI_E_SHAPE;
+        seen[values[l]] = true;
+        v[l] = values[l];
+    }
+    for (int i = 0; i < FMRI_MAX_LABELS / 4; ++i)
+        out->w[i] = (uint32_t)v[4 * i] | ((uint32_t)v[4 * i + 1] << 8) | ((uint32_t)v[4 * i + 2] << 16) | ((uint32_t)v[4 * i + 3] << 24);
+    return FMRI_OK;
+}
+#ifdef __HIPCC__
+// the values into LDS (vals[32]) and, when lut is given, the 256-entry byte -> index + 1 table (0 = not a label); blockDim.x >= 256 for
+// the table.  Ends in a barrier.
+__device__ __forceinline__ void fmri_label_tables(const FmriLabelValues& V, int L, uint8_t* vals, uint8_t* lut) {
+    uint32_t* const vw = reinterpret_cast<uint32_t*>(vals);
+#pragma unroll
+    for (int i = 0; i < FMRI_MAX_LABELS / 4; ++i)
+        if (threadIdx.x == i) vw[i] = V.w[i];
+    if (lut && threadIdx.x < 256) lut[threadIdx.x] = 0;
+    __syncthreads();
+    if (lut) {
+        if (threadIdx.x < L) lut[vals[threadIdx.x]] = (uint8_t)(threadIdx.x + 1);
+        __syncthreads();
+    }
+}
+#endif
+
 static inline int grid_for(int64_t total, int block = 256, int cap = 256 * 16) {
     int64_t g = ceil_div64(total, block);
     if (g > cap) g = cap;

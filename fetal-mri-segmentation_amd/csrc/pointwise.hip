@@ -954,6 +954,53 @@ extern "C" int fmri_sigmoid_dice_bwd(const float* probs, const uint8_t* y_true, 
     return FMRI_OK;
 }
 
+// ---- label-wise Dice while training (reference metrics.py:52-59, unet.py:75-80): lsums [L][3] = sum y*p, sum y, sum p per label over the
+// whole batch, element i of probs / y carrying label i % L.  The grid is a multiple of L workgroups, so the grid stride is a multiple of L
+// and a thread stays with ONE label: three float64 accumulators and coalesced 4-byte / 1-byte loads.  A workgroup's 256 x 3 partial sums meet in
+// LDS and thread (l, q) adds the partials of label l in thread order - a fixed order, wave after wave - then one atomic per (label, sum) and
+// workgroup: float64 by default; under a deterministic registration a 2^-20 fixed-point integer added to the SAME 8-byte slot, which
+// k_label_sums_finish converts in place.  No per-thread array, no dynamic register indexing.
+__global__ void __launch_bounds__(256) k_label_sums(const float* __restrict__ probs, const uint8_t* __restrict__ y, int64_t n, int L,
+                                                    double* __restrict__ lsums) {
+    __shared__ double part[3][256];
+    const int64_t tid = blockIdx.x * (int64_t)256 + threadIdx.x, step = (int64_t)gridDim.x * 256;      // step % L == 0
+    double a = 0, b = 0, c = 0;
+    for (int64_t i = tid; i < n; i += step) {
+        const float p = probs[i], t = (float)y[i];
+        a += (double)(t * p);
+        b += (double)t;
+        c += (double)p;
+    }
+    part[0][threadIdx.x] = a;
+    part[1][threadIdx.x] = b;
+    part[2][threadIdx.x] = c;
+    __syncthreads();
+    if (threadIdx.x < 3 * L) {
+        const int l = threadIdx.x / 3, q = threadIdx.x - 3 * l;
+        const int first = (int)((l + L - (int)((blockIdx.x * (int64_t)256) % L)) % L);                // first thread of the workgroup with label l
+        double r = 0;
+        for (int t = first; t < 256; t += L) r += part[q][t];
+        if (g_det_cfg.base != nullptr)
+            atomicAdd(reinterpret_cast<unsigned long long*>(lsums) + threadIdx.x, (unsigned long long)__double2ll_rn(r * 1048576.0));
+        else atomicAdd(&lsums[threadIdx.x], r);
+    }
+}
+__global__ void k_label_sums_finish(double* __restrict__ lsums, int n3) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n3) lsums[k] = (double)(long long)reinterpret_cast<unsigned long long*>(lsums)[k] * (1.0 / 1048576.0);
+}
+extern "C" int fmri_label_sums(const float* probs, const uint8_t* y_true, int64_t nvox, int L, double* lsums, fmri_stream_t stream) {
+    if (!probs || !y_true || !lsums || nvox <= 0 || L < 1 || L > FMRI_MAX_LABELS) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    if (hipMemsetAsync(lsums, 0, (size_t)3 * L * sizeof(double), s) != hipSuccess) return FMRI_E_LAUNCH;
+    const int64_t n = nvox * L;
+    const int grid = (grid_for(n, 256 * 8, 512) + L - 1) / L * L;
+    k_label_sums<<<grid, 256, 0, s>>>(probs, y_true, n, L, lsums);
+    if (h_det_on) k_label_sums_finish<<<1, 128, 0, s>>>(lsums, 3 * L);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ Keras Adam
 // Reference: Adam(lr=initial_learning_rate) at unet3d/unet.py:85; Keras 2.2 update rule (epsilon outside the sqrt).
 __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -1132,6 +1179,100 @@ extern "C" int fmri_tile_finalize(const double* acc, const int32_t* cnt, double*
                                   fmri_stream_t stream) {
     if (nvox <= 0 || C <= 0) return FMRI_E_SHAPE;
     k_tile_finalize<<<grid_for(nvox, 256, 4096), 256, 0, as_stream(stream)>>>(acc, cnt, out, bad, nvox, C);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+// ---- several labels: a label map straight from the overlap-add, and training targets from a label map
+// out[v] per voxel from q_c = acc[v][c] / cnt[v] (float64, fmri_tile_finalize's division).  C == 1: values[0] where q_0 > threshold
+// (reference prediction.py:257); C > 1: values[k], k the FIRST index of the maximum (np.argmax), 0 where max q < threshold (:219-222).
+__global__ void __launch_bounds__(256) k_tile_finalize_labels(const double* __restrict__ acc, const int32_t* __restrict__ cnt,
+                                                              uint8_t* __restrict__ out, int32_t* __restrict__ bad, int64_t nvox, int C,
+                                                              double threshold, FmriLabelValues V) {
+    __shared__ __attribute__((aligned(4))) uint8_t vals[FMRI_MAX_LABELS];
+    fmri_label_tables(V, C, vals, nullptr);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = cnt[i];
+        if (c <= 0) {
+            atomicAdd(bad, 1);
+            out[i] = 0;
+            continue;
+        }
+        const double* const row = acc + i * C;
+        double best = row[0] / (double)c;
+        int k = 0;
+        for (int j = 1; j < C; ++j) {
+            const double q = row[j] / (double)c;
+            if (q > best) { best = q; k = j; }
+        }
+        const bool keep = C == 1 ? best > threshold : !(best < threshold);
+        out[i] = keep ? vals[k] : (uint8_t)0;
+    }
+}
+extern "C" int fmri_tile_finalize_labels(const double* acc, const int32_t* cnt, uint8_t* out, int32_t* bad, int64_t nvox, int C,
+                                         double threshold, const uint8_t* values, fmri_stream_t stream) {
+    FmriLabelValues V;
+    if (!acc || !cnt || !out || !bad || nvox <= 0 || fmri_label_values(values, C, &V) != FMRI_OK) return FMRI_E_SHAPE;
+    k_tile_finalize_labels<<<grid_for(nvox, 256, 4096), 256, 0, as_stream(stream)>>>(acc, cnt, out, bad, nvox, C, threshold, V);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+// out[v][l] = (lab[v] == values[l]), channels last.  ROW: L is 1, 2, 4 or 8 and `out` is L-byte aligned - one thread per voxel, the row is one
+// store of L bytes (the set byte is a shift of the label's index).  Otherwise the output is written as the flat byte array it is, 8 bytes
+// per thread in one store (the byte at j belongs to voxel j / L, label j % L: one division per thread, then counted up), the bytes past
+// the last multiple of 8 one by one.  The label bytes are read through the 256-entry value -> index table in LDS.
+template <typename W>
+__global__ void __launch_bounds__(256) k_labels_expand_row(const uint8_t* __restrict__ lab, int64_t n, int L, W* __restrict__ out, FmriLabelValues V) {
+    __shared__ __attribute__((aligned(4))) uint8_t vals[FMRI_MAX_LABELS];
+    __shared__ uint8_t lut[256];
+    fmri_label_tables(V, L, vals, lut);
+    for (int64_t v = blockIdx.x * (int64_t)256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) {
+        const int k = lut[lab[v]];
+        out[v] = k ? (W)((W)1 << (8 * (k - 1))) : (W)0;
+    }
+}
+__global__ void __launch_bounds__(256) k_labels_expand_flat(const uint8_t* __restrict__ lab, int64_t n, int L, uint8_t* __restrict__ out,
+                                                            int64_t words, FmriLabelValues V) {
+    __shared__ __attribute__((aligned(4))) uint8_t vals[FMRI_MAX_LABELS];
+    __shared__ uint8_t lut[256];
+    fmri_label_tables(V, L, vals, lut);
+    const int64_t tid = blockIdx.x * (int64_t)256 + threadIdx.x, step = (int64_t)gridDim.x * 256, total = n * L;
+    for (int64_t t = tid; t < words; t += step) {
+        int64_t v = (t * 8) / L;
+        int l = (int)(t * 8 - v * L);
+        int k = lut[lab[v]];
+        unsigned long long w = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            w |= (unsigned long long)(k == l + 1) << (8 * j);
+            if (++l == L) {
+                l = 0;
+                ++v;
+                if (j < 7) k = lut[lab[v]];           // (v < n: byte t * 8 + j + 1 exists, the word lies below n * L)
+            }
+        }
+        reinterpret_cast<unsigned long long*>(out)[t] = w;
+    }
+    for (int64_t j = words * 8 + tid; j < total; j += step) {
+        const int64_t v = j / L;
+        out[j] = lut[lab[v]] == (int)(j - v * L) + 1;
+    }
+}
+extern "C" int fmri_labels_expand_u8(const uint8_t* lab, int64_t n, const uint8_t* values, int L, uint8_t* out, fmri_stream_t stream) {
+    FmriLabelValues V;
+    if (!lab || !out || n <= 0 || fmri_label_values(values, L, &V) != FMRI_OK) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    const bool row = (L == 1 || L == 2 || L == 4 || L == 8) && (reinterpret_cast<uintptr_t>(out) % L) == 0;
+    if (row) {
+        const int grid = grid_for(n, 256, 4096);
+        if (L == 1) k_labels_expand_row<uint8_t><<<grid, 256, 0, s>>>(lab, n, L, out, V);
+        else if (L == 2) k_labels_expand_row<uint16_t><<<grid, 256, 0, s>>>(lab, n, L, reinterpret_cast<uint16_t*>(out), V);
+        else if (L == 4) k_labels_expand_row<uint32_t><<<grid, 256, 0, s>>>(lab, n, L, reinterpret_cast<uint32_t*>(out), V);
+        else k_labels_expand_row<unsigned long long><<<grid, 256, 0, s>>>(lab, n, L, reinterpret_cast<unsigned long long*>(out), V);
+    } else {
+        const int64_t words = (reinterpret_cast<uintptr_t>(out) & 7u) == 0 ? n * L / 8 : 0;
+        k_labels_expand_flat<<<grid_for(words ? words : n * L, 256, 4096), 256, 0, s>>>(lab, n, L, out, words, V);
+    }
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }

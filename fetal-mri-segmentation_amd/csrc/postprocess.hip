@@ -1130,6 +1130,55 @@ __global__ __launch_bounds__(EV_THREADS) void k_seg_counts(const uint8_t* __rest
     }
 }
 
+// out[l] = {|T == v_l|, |P == v_l|, |both|} for all labels in one pass.  The bytes go through a 256-entry value -> index table in LDS; a wave
+// counts by vote, not by lane: the lanes whose (truth index, prediction index) pair equals the first unsettled lane's are counted with one
+// ballot and their number is added to the workgroup's LDS counters by that lane - label regions are contiguous, so a wave holds a few
+// distinct pairs and most waves none (all background: one ballot).  The workgroup's counters then go out as 64-bit integer atomics.
+// words = n / 4 when both pointers are 4-byte aligned (four voxels per load), else 0; the remaining voxels go one per thread.
+__device__ __forceinline__ void label_vote(int it, int ip, unsigned* __restrict__ cnt) {
+    const int key = it * (FMRI_MAX_LABELS + 1) + ip;
+    unsigned long long todo = __ballot(key != 0);
+    const int lane = threadIdx.x & 63;
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int k = __shfl(key, leader);
+        const unsigned long long same = __ballot(key == k) & todo;
+        if (lane == leader) {
+            const unsigned c = (unsigned)__popcll(same);
+            if (it) atomicAdd(&cnt[3 * (it - 1)], c);
+            if (ip) atomicAdd(&cnt[3 * (ip - 1) + 1], c);
+            if (it && it == ip) atomicAdd(&cnt[3 * (it - 1) + 2], c);
+        }
+        todo &= ~same;
+    }
+}
+__global__ __launch_bounds__(EV_THREADS) void k_label_counts(const uint8_t* __restrict__ truth, const uint8_t* __restrict__ pred, int64_t n,
+                                                             int64_t words, int L, unsigned long long* __restrict__ out, FmriLabelValues V) {
+    __shared__ __attribute__((aligned(4))) uint8_t vals[FMRI_MAX_LABELS];
+    __shared__ uint8_t lut[256];
+    __shared__ unsigned cnt[3 * FMRI_MAX_LABELS];
+    if (threadIdx.x < 3 * FMRI_MAX_LABELS) cnt[threadIdx.x] = 0;
+    fmri_label_tables(V, L, vals, lut);
+    // every lane of a wave makes the same number of trips (the votes need the whole wave): the loops run on the wave's first index
+    const int lane = threadIdx.x & 63;
+    const int64_t wave0 = (int64_t)blockIdx.x * EV_THREADS + (threadIdx.x - lane), step = (int64_t)gridDim.x * EV_THREADS;
+    const uint32_t* const t4 = reinterpret_cast<const uint32_t*>(truth);
+    const uint32_t* const p4 = reinterpret_cast<const uint32_t*>(pred);
+    for (int64_t w0 = wave0; w0 < words; w0 += step) {
+        const int64_t w = w0 + lane;
+        const uint32_t a = w < words ? t4[w] : 0u, b = w < words ? p4[w] : 0u;
+        if (__ballot((a | b) != 0) == 0) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) label_vote(lut[(a >> (8 * j)) & 255u], lut[(b >> (8 * j)) & 255u], cnt);
+    }
+    for (int64_t v0 = words * 4 + wave0; v0 < n; v0 += step) {
+        const int64_t v = v0 + lane;
+        label_vote(v < n ? lut[truth[v]] : 0, v < n ? lut[pred[v]] : 0, cnt);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * L && cnt[threadIdx.x]) atomicAdd(&out[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+}
+
 // blockIdx.y selects the volume (one or two in a launch).  CONN = scipy's connectivity: the neighbours with 1 .. CONN nonzero offsets.
 template <int CONN>
 __global__ __launch_bounds__(EV_THREADS) void k_surface(const uint8_t* __restrict__ m0, const uint8_t* __restrict__ m1, uint8_t* __restrict__ i0,
@@ -1282,6 +1331,20 @@ extern "C" int fmri_seg_counts_u8(const uint8_t* a, const uint8_t* b, int64_t n,
     const int64_t words = aligned ? n / 8 : 0;
     k_seg_counts<<<grid_for(aligned ? words : n, EV_THREADS, EV_GRID), EV_THREADS, 0, s>>>(a, b, n, words,
                                                                                                   reinterpret_cast<unsigned long long*>(out3));
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_label_counts_u8(const uint8_t* truth, const uint8_t* pred, int64_t n, const uint8_t* values, int L, int64_t* out,
+                                    fmri_stream_t stream) {
+    FmriLabelValues V;
+    if (!truth || !pred || !out || n <= 0 || fmri_label_values(values, L, &V) != FMRI_OK) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    if (hipMemsetAsync(out, 0, (size_t)3 * L * sizeof(int64_t), s) != hipSuccess) return FMRI_E_LAUNCH;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(truth) | reinterpret_cast<uintptr_t>(pred)) & 3u) == 0;
+    const int64_t words = aligned ? n / 4 : 0;
+    k_label_counts<<<grid_for(aligned ? words + 3 : n, EV_THREADS, EV_GRID), EV_THREADS, 0, s>>>(truth, pred, n, words, L,
+                                                                                                   reinterpret_cast<unsigned long long*>(out), V);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }

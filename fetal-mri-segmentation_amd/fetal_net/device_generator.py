@@ -407,6 +407,11 @@ def device_data_generator(data_file, index_list, batch_size=1, n_labels=1, label
     drop_easy_patches read one scalar back per patch (they decide on the host whether the patch is kept), everything else is
     enqueue-only.
 
+    n_labels > 1 (categorical=False, no masks): y holds n_labels binary channels, channel l = (label map == labels[l]), labels = 1 .. n_labels
+    by default (reference generator.py:404-419) - 3-D (N, n_labels, X, Y, truth_size), 2-D (N, X, Y, n_labels) with truth_size == 1.  skip_blank
+    and drop_easy_patches still decide on the raw label map: a patch that only holds values outside `labels` is kept and expands to zeros.
+    n_labels == 1 yields the raw label map and never reads `labels`.
+
     distance_masks (None | True | spacing per axis): for a data file without masks, make the distance masks of the mask-weighted loss on
     the device when the volumes are uploaded (DeviceDataFile) and yield ([x, masks], y); a DeviceDataFile handed in was built with its own.
 
@@ -424,6 +429,33 @@ def device_data_generator(data_file, index_list, batch_size=1, n_labels=1, label
     anything else in the process that draws from them (a validation generator on the main thread, for one) interleaves with the
     producer by timing, and the batches of both stop being reproducible - seeded reproducibility holds for prefetch=0 only.
     `Model.fit_generator` has its own producer thread and copy stream: leave prefetch at 0 there."""
+    n_labels = int(n_labels)
+    if n_labels > 1:
+        # several labels: the label patch is expanded into n_labels binary channels (get_multi_class_labels) by one launch per batch, behind
+        # everything that samples, warps and keeps / drops patches on the raw label map
+        if categorical:
+            raise ValueError("n_labels > 1 with categorical=True: to_categorical(y, 2) is binary (pass categorical=False)")
+        if distance_masks is not None or getattr(data_file, "mask", None) is not None or \
+                (not isinstance(data_file, DeviceDataFile) and hasattr(data_file.root, "mask") and data_file.root.mask is not None
+                 and len(data_file.root.mask)):
+            raise ValueError("n_labels > 1 with distance masks: the cross-entropy weight is per voxel, multi-label masks are not supported")
+        labels = tuple(range(1, n_labels + 1)) if labels is None else tuple(labels)
+        if len(labels) != n_labels:
+            raise ValueError("labels %r: %d values for n_labels = %d" % (labels, len(labels), n_labels))
+        if not is3d and truth_size != 1:
+            raise ValueError("n_labels > 1 on a 2-D model needs truth_size == 1 (got %r)" % (truth_size,))
+        from fmri_hip.ops import label_values
+        label_values(labels)
+    return _generate(data_file, index_list, batch_size, n_labels, labels, augment, patch_shape, shuffle_index_list, skip_blank, truth_index,
+                     truth_size, truth_downsample, categorical, prev_truth_index, prev_truth_size, drop_easy_patches, is3d, samples_pad, strict,
+                     noise_seed, device, prefetch, batched, distance_masks)
+
+
+def _generate(data_file, index_list, batch_size, n_labels, labels, augment, patch_shape, shuffle_index_list, skip_blank, truth_index,
+              truth_size, truth_downsample, categorical, prev_truth_index, prev_truth_size, drop_easy_patches, is3d, samples_pad, strict,
+              noise_seed, device, prefetch, batched, distance_masks):
+    """the generator behind device_data_generator, which has checked the label arguments (a generator function's body only runs at the
+    first next(): the checks belong to the call)"""
     import torch
     if truth_downsample is not None and truth_downsample > 1:
         raise NotImplementedError("truth_downsample is not part of the device generator")
@@ -481,6 +513,11 @@ def device_data_generator(data_file, index_list, batch_size=1, n_labels=1, label
                             t[filled + dst].copy_(t[filled + src])
             filled += len(keep)
         yy = y
+        if n_labels > 1:
+            # (N, X, Y, T) label bytes -> (N, X, Y, T, L) binary channels, channels last: 2-D (T = 1) yields (N, X, Y, L); 3-D yields the
+            # permuted VIEW (N, L, X, Y, T) of that buffer, which Model._to_device_y's permute(0, 2, 3, 4, 1).contiguous() takes back for free
+            ye = sampler.ops.labels_expand_u8(y, labels)
+            return (x.unsqueeze(1), ye.permute(0, 4, 1, 2, 3), None) if is3d else (x, ye.squeeze(3), None)
         if categorical:
             # keras.utils.to_categorical(y, 2) (reference generator.py:390-391): a trailing axis of size 1 is dropped before the one-hot
             # axis is appended - (N,X,Y,1) -> (N,X,Y,2), (N,X,Y,T>1) -> (N,X,Y,T,2) - float32
@@ -542,3 +579,26 @@ def device_data_generator(data_file, index_list, batch_size=1, n_labels=1, label
     finally:                                           # generator closed or collected: stop the producer, let it leave its put()
         stop.set()
         worker.join(timeout=10.0)
+
+
+def get_multi_class_labels(data, n_labels, labels=None):
+    """reference fetal_net/generator.py:404-419: data (n, 1, ...) label map -> (n, n_labels, ...) int8, channel l = (data == labels[l]), labels =
+    1 .. n_labels by default.  A numpy array gives a numpy array; a CUDA uint8 tensor goes through fmri_labels_expand_u8 and gives a CUDA int8
+    tensor (a permuted view of the channels-last buffer the kernel writes)."""
+    if data.shape[1] != 1:
+        raise ValueError("get_multi_class_labels: a label map (n, 1, ...) is needed (got %s)" % (tuple(data.shape),))
+    values = list(range(1, n_labels + 1)) if labels is None else list(labels)
+    if len(values) != n_labels:
+        raise ValueError("labels %r: %d values for n_labels = %d" % (labels, len(values), n_labels))
+    if isinstance(data, np.ndarray):
+        y = np.zeros((data.shape[0], n_labels) + tuple(data.shape[2:]), np.int8)
+        for l, v in enumerate(values):
+            y[:, l][data[:, 0] == v] = 1
+        return y
+    import torch
+    from fmri_hip import ops
+    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype == torch.uint8):
+        raise TypeError("get_multi_class_labels: a numpy array or a CUDA uint8 tensor")
+    out = ops.labels_expand_u8(data[:, 0].contiguous(), values)               # (n, ..., L)
+    nd = out.dim()
+    return out.view(torch.int8).permute(0, nd - 1, *range(1, nd - 1))

@@ -11,6 +11,7 @@ import csv
 import io
 import json
 import os
+import re
 import threading
 import time
 from collections import OrderedDict
@@ -540,6 +541,23 @@ class Model(object):
     def metrics_names(self):
         return ['loss'] + [m if isinstance(m, str) else getattr(m, '__name__', str(m)) for m in self.metrics]
 
+    def _label_metrics(self):
+        """the label indices of the compiled label_<i>_dice_coef metrics (metrics.get_label_dice_coefficient_function)"""
+        out = []
+        for name in self.metrics_names[1:]:
+            m = re.match(r"label_(\d+)_dice_coef$", name)
+            if m:
+                out.append(int(m.group(1)))
+        return out
+
+    def _set_label_metrics(self, eng):
+        idx = self._label_metrics()
+        n = int(eng.plan.n_labels) if idx else 0
+        if idx and max(idx) >= n:
+            raise ValueError("metric label_%d_dice_coef on a model with %d labels" % (max(idx), n))
+        if n != getattr(eng, "label_metrics", 0):
+            eng.set_label_metrics(n)
+
     def count_params(self):
         return int(sum(l.config.get("params", 0) for l in self.layers))
 
@@ -593,6 +611,7 @@ class Model(object):
             if dist_ctx is not None:
                 dist_ctx.broadcast_params(self._engine)
         self._engine.set_batch(batch)
+        self._set_label_metrics(self._engine)
         if self.loss is not None:
             try:
                 self._engine.loss_kind, self._engine.loss_param = self._loss_kind()
@@ -670,6 +689,13 @@ class Model(object):
         m = UNetEngine.metrics_from_sums(sums, 1.0, kind, param)
         out = OrderedDict(loss=m["loss"])
         for name in self.metrics_names[1:]:
+            lm = re.match(r"label_(\d+)_dice_coef$", name)
+            if lm:
+                # (2 I + 1) / (Sy + Sp + 1) of the label's own sums (metrics.py label_wise_dice_coefficient), behind the 16 metric sums
+                at = 16 + 3 * int(lm.group(1))
+                i, sy, sp = (float(v) for v in sums[at:at + 3])
+                out[name] = (2.0 * i + 1.0) / (sy + sp + 1.0)
+                continue
             key = {"dice_coef": "dice_coefficient"}.get(name, name)
             out[name] = m[key]
         return out
@@ -686,7 +712,7 @@ class Model(object):
         return torch.exp(-t.float() / self.loss.dist_sigma).reshape(-1).contiguous()
 
     # -- steps: enqueue now, read the metric sums later --------------------------------------------------------------------------
-    LOG_RING = 8          # pinned fp64[16] buffers for the metric sums in flight (the training thread runs at most this many steps ahead)
+    LOG_RING = 8          # pinned fp64 buffers (16 metric sums + room for 3 * 32 label-wise sums) for the metric sums in flight (the training thread runs at most this many steps ahead)
 
     def _stage_inline(self, x, y):
         """(x, y) of a direct train_on_batch / test_on_batch call -> _Staged on the calling thread's stream"""
@@ -709,15 +735,18 @@ class Model(object):
             sums = eng.loss_forward(staged.y, staged.weight)
         ring = self.__dict__.get("_log_ring")
         if ring is None:
-            ring = self.__dict__["_log_ring"] = dict(k=0, slots=[[torch.empty(16, dtype=torch.float64).pin_memory(), torch.cuda.Event(), None]
+            ring = self.__dict__["_log_ring"] = dict(k=0, slots=[[torch.empty(16 + 96, dtype=torch.float64).pin_memory(), torch.cuda.Event(), None]
                                                                  for _ in range(self.LOG_RING)])
         slot = ring["slots"][ring["k"] % self.LOG_RING]
         ring["k"] += 1
         if slot[2] is not None:
             slot[2].values()                                         # the buffer's previous owner reads it before it is overwritten
-        slot[0].copy_(sums, non_blocking=True)
+        if getattr(eng, "label_metrics", 0):
+            sums = eng.log_sums()                                    # the label-wise sums ride behind the 16, in the same copy
+        buf = slot[0][:sums.numel()]
+        buf.copy_(sums, non_blocking=True)
         slot[1].record(torch.cuda.current_stream())
-        slot[2] = _PendingLogs(self, slot[0], slot[1], staged.n)
+        slot[2] = _PendingLogs(self, buf, slot[1], staged.n)
         return slot[2]
 
     def train_on_batch(self, x, y, **kw):

@@ -59,6 +59,14 @@ def get_label_dice_coefficient_function(label_index):
     return f
 
 
+def label_wise_metrics(n_labels, include_label_wise_dice_coefficients):
+    """the metrics reference unet3d/unet.py:75-80 (commented out there) adds: one label-wise Dice per label when the flag is set and the
+    model has several labels, else none"""
+    if include_label_wise_dice_coefficients and n_labels > 1:
+        return [get_label_dice_coefficient_function(i) for i in range(n_labels)]
+    return []
+
+
 def weighted_cross_entropy_loss(y_true, y_pred, weight_mask=None):
     yt = _f(y_true)
     yp = np.clip(_f(y_pred), 1e-7, 1 - 1e-7)

@@ -43,6 +43,7 @@ class NormNetModel(Model):
             if getattr(self, "_pending_opt", None) is not None:
                 self._apply_optimizer_state(self._pending_opt)
         self._engine.set_batch(batch)
+        self._set_label_metrics(self._engine)
         if self.loss is not None:
             try:
                 self._engine.loss_kind, self._engine.loss_param = self._loss_kind()

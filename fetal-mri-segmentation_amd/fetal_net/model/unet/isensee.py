@@ -9,7 +9,7 @@ alone and the deeper heads - although the reference creates them, which advances
 Every block is Conv2D -> keras-contrib InstanceNormalization(axis=1) -> LeakyReLU.
 """
 from ...engine_model import Adam, Model
-from ...metrics import dice_coefficient, dice_coefficient_loss, vod_coefficient
+from ...metrics import dice_coefficient, dice_coefficient_loss, label_wise_metrics, vod_coefficient
 from ..graph import Graph
 
 
@@ -72,6 +72,9 @@ def isensee2017_model(input_shape=(128, 128, 5), n_base_filters=16, depth=5, dro
                           loss_function=loss_function, activation_name=activation_name, summation=summation)
     if "compute_dtype" in kargs:
         builder_kwargs["compute_dtype"] = kargs["compute_dtype"]
+    label_metrics = label_wise_metrics(n_labels, kargs.get("include_label_wise_dice_coefficients", False))
+    if label_metrics:
+        builder_kwargs["include_label_wise_dice_coefficients"] = True
     model = Model(_reachable(g.layers), None, "isensee2017_model", builder_kwargs, "channels_last_2d", name="isensee2017_2d_Model")
     model._graph_engine = True
     model._created_layers = list(g.layers)       # incl. the heads Keras would drop: what the reference builder CREATED (name counters)
@@ -80,5 +83,6 @@ def isensee2017_model(input_shape=(128, 128, 5), n_base_filters=16, depth=5, dro
     metrics = ['binary_accuracy', vod_coefficient]
     if loss_function != dice_coefficient_loss:
         metrics += [dice_coefficient]
+    metrics += label_metrics
     model.compile(optimizer=optimizer(lr=initial_learning_rate), loss=loss_function, metrics=metrics)
     return model

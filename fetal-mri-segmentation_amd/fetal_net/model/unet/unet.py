@@ -2,7 +2,7 @@
 unet_model_3d with channels-LAST input (X, Y, C) wrapped in Permute layers, optional SpatialDropout2D.  pool_size (2, 2) without dropout
 runs on the hand-scheduled engine; other pool sizes (per-axis factors 1..4) and dropout_rate > 0 on the layer-graph engine (UpSampling2D only)."""
 from ...engine_model import Adam, Model
-from ...metrics import dice_coefficient, dice_coefficient_loss, vod_coefficient
+from ...metrics import dice_coefficient, dice_coefficient_loss, label_wise_metrics, vod_coefficient
 from ..graph import Graph
 from ..unet3d.unet import check_pool_divides, pool_route
 
@@ -50,6 +50,9 @@ def unet_model_2d(input_shape, pool_size=(2, 2), n_labels=1, initial_learning_ra
                           dropout_rate=dropout_rate)
     if "compute_dtype" in kargs:
         builder_kwargs["compute_dtype"] = kargs["compute_dtype"]
+    label_metrics = label_wise_metrics(n_labels, include_label_wise_dice_coefficients)
+    if label_metrics:
+        builder_kwargs["include_label_wise_dice_coefficients"] = True
     plan_args = dict(in_channels=input_shape[-1], spatial=input_shape[:2], depth=depth, n_base_filters=n_base_filters,
                      n_labels=n_labels, ndim=2, norm="batch" if batch_normalization else None, deconvolution=bool(deconvolution))
     model = Model(g.layers, plan_args, "unet_model_2d", builder_kwargs, "channels_last_2d")
@@ -65,5 +68,6 @@ def unet_model_2d(input_shape, pool_size=(2, 2), n_labels=1, initial_learning_ra
     metrics = ['binary_accuracy', vod_coefficient]
     if loss_function != dice_coefficient_loss:
         metrics += [dice_coefficient]
+    metrics += label_metrics
     model.compile(optimizer=Adam(lr=initial_learning_rate), loss=loss_function, metrics=metrics)
     return model

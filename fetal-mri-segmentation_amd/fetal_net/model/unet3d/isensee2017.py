@@ -8,7 +8,7 @@ Conv3D -> keras-contrib InstanceNormalization(axis=1) -> LeakyReLU.  activation_
 output: the network that `norm_net_model` trains in front of a frozen segmenter (reference fetal_net/model/norm/NormNet.py:14-16).
 """
 from ...engine_model import Adam, Model
-from ...metrics import dice_coefficient, dice_coefficient_loss, vod_coefficient
+from ...metrics import dice_coefficient, dice_coefficient_loss, label_wise_metrics, vod_coefficient
 from ..graph import Graph
 
 
@@ -57,6 +57,9 @@ def isensee2017_model_3d(input_shape=(1, 128, 128, 128), n_base_filters=16, dept
                           loss_function=loss_function, activation_name=activation_name)
     if "compute_dtype" in kargs:
         builder_kwargs["compute_dtype"] = kargs["compute_dtype"]
+    label_metrics = label_wise_metrics(n_labels, kargs.get("include_label_wise_dice_coefficients", False))
+    if label_metrics:
+        builder_kwargs["include_label_wise_dice_coefficients"] = True
     if mask_shape is not None:
         builder_kwargs["mask_shape"] = tuple(int(v) for v in mask_shape)
     model = Model(g.layers, None, "isensee2017_model_3d", builder_kwargs, "channels_first_3d", name="isensee2017_3d_Model")
@@ -76,5 +79,6 @@ def isensee2017_model_3d(input_shape=(1, 128, 128, 128), n_base_filters=16, dept
     metrics = ['binary_accuracy', vod_coefficient]
     if loss_function != dice_coefficient_loss:
         metrics += [dice_coefficient]
+    metrics += label_metrics
     model.compile(optimizer=optimizer(lr=initial_learning_rate), loss=loss_function, metrics=metrics)
     return model

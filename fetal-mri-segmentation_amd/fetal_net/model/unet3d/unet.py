@@ -9,7 +9,7 @@ per-axis factors 1..4 - (2, 2, 1) for anisotropic volumes - on the layer-graph e
 ['binary_accuracy', vod_coefficient] (+ dice_coefficient when the loss is not the Dice loss).
 """
 from ...engine_model import Adam, Model
-from ...metrics import dice_coefficient, dice_coefficient_loss, vod_coefficient
+from ...metrics import dice_coefficient, dice_coefficient_loss, label_wise_metrics, vod_coefficient
 from ..graph import Graph
 
 
@@ -99,6 +99,9 @@ def unet_model_3d(input_shape, pool_size=(2, 2, 2), n_labels=1, initial_learning
                           batch_normalization=batch_normalization, activation_name=activation_name, loss_function=loss_function)
     if "compute_dtype" in kargs:
         builder_kwargs["compute_dtype"] = kargs["compute_dtype"]
+    label_metrics = label_wise_metrics(n_labels, include_label_wise_dice_coefficients)
+    if label_metrics:
+        builder_kwargs["include_label_wise_dice_coefficients"] = True
     plan_args = dict(in_channels=input_shape[0], spatial=input_shape[1:], depth=depth, n_base_filters=n_base_filters,
                      n_labels=n_labels, ndim=3, norm="batch" if batch_normalization else None, deconvolution=bool(deconvolution))
     model = Model(g.layers, plan_args, "unet_model_3d", builder_kwargs, "channels_first_3d")
@@ -109,6 +112,7 @@ def unet_model_3d(input_shape, pool_size=(2, 2, 2), n_labels=1, initial_learning
     metrics = ['binary_accuracy', vod_coefficient]
     if loss_function != dice_coefficient_loss:
         metrics += [dice_coefficient]
+    metrics += label_metrics
     model.compile(optimizer=Adam(lr=initial_learning_rate), loss=loss_function, metrics=metrics)
     return model
 

@@ -52,9 +52,18 @@ def _half_pads(delta):
     return [(int(np.ceil(d / 2)), int(np.floor(d / 2))) for d in delta]
 
 
+def _is3d(model):
+    """the reference counts the output axes longer than 1 (prediction.py:120-121), which takes a 2-D model with several labels - output
+    (N, X, Y, L) - for a 3-D one: a model that names its layout (this package's, or a foreign object with `_input_layout`) is asked"""
+    layout = getattr(model, "_input_layout", None)
+    if layout in ("channels_first_3d", "channels_last_2d"):
+        return layout == "channels_first_3d"
+    return int(np.sum(np.array(model.output_shape[1:]) > 1)) > 2
+
+
 def _geometry(model, data, patch_shape, overlap_factor):
     out_shape = model.output_shape
-    is3d = int(np.sum(np.array(out_shape[1:]) > 1)) > 2
+    is3d = _is3d(model)
     prediction_shape = tuple(out_shape[-3:]) if is3d else tuple(out_shape[-3:-1]) + (1,)
     min_overlap = np.subtract(patch_shape, prediction_shape)
     max_overlap = np.subtract(patch_shape, (1, 1, 1))
@@ -84,6 +93,34 @@ def _unpad(arr, pad_for_fit):
 def patch_wise_prediction(model, data, patch_shape, overlap_factor=0, batch_size=5, permute=False, truth_data=None,
                           prev_truth_index=None, prev_truth_size=None):
     """data (1,X,Y,Z) -> (X,Y,Z,C) float64 mean of all tiles covering each voxel."""
+    return _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size, None)
+
+
+def patch_wise_label_map(model, data, patch_shape, overlap_factor=0, batch_size=5, threshold=0.5, labels=None, permute=False,
+                         truth_data=None, prev_truth_index=None, prev_truth_size=None):
+    """data (1,X,Y,Z) -> (X,Y,Z) uint8 label map: get_prediction_labels of patch_wise_prediction's mean, taken on the device.  The tile
+    loop is patch_wise_prediction's - same captured graphs, same slab pipeline - with fmri_tile_finalize_labels in place of
+    fmri_tile_finalize, so one byte per voxel comes down instead of 8 * C.  Wherever patch_wise_prediction leaves the device path
+    (permute, a foreign model object) the label map is get_prediction_labels of its result."""
+    n_labels = int(model.output_shape[1] if _is3d(model) else model.output_shape[-1])
+    values = _label_values(n_labels, labels)
+    out = _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size,
+                      (float(threshold), values))
+    if out.dtype != np.uint8:                                # the host path's float64 means (X, Y, Z, C)
+        out = np.asarray(prediction_to_image(np.moveaxis(out, -1, 0)[np.newaxis], label_map=True, threshold=threshold,
+                                             labels=values)).astype(np.uint8)
+    return out
+
+
+def _label_values(n_labels, labels):
+    values = list(range(1, n_labels + 1)) if labels is None else [int(v) for v in labels]
+    if len(values) != n_labels:
+        raise ValueError("labels %r: %d values for %d output channels" % (labels, len(values), n_labels))
+    return values
+
+
+def _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size, label_map):
+    """patch_wise_prediction (label_map None) / patch_wise_label_map ((threshold, values): the device path then returns the uint8 map)"""
     is3d, pad0, pad_for_fit, data_0, indices, data_shape = _geometry(model, data, patch_shape, overlap_factor)
     layout2d = getattr(model, "_input_layout", "") == "channels_last_2d"
     # previous-slice truth on the device: 2-D models only (a 3-D model's truth channels are concatenated along z, reference prediction.py:100-110)
@@ -96,10 +133,10 @@ def patch_wise_prediction(model, data, patch_shape, overlap_factor=0, batch_size
             truth_0 = np.pad(truth_0, pad_for_fit, 'constant', constant_values=0)
         out, count_ok = _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d, truth_0=truth_0,
                                             aux_dz=int(prev_truth_index) if truth_0 is not None else 0,
-                                            aux_nz=int(prev_truth_size) if truth_0 is not None else 0)
+                                            aux_nz=int(prev_truth_size) if truth_0 is not None else 0, label_map=label_map)
         assert count_ok, 'Found zeros in count'
         out = _unpad(out, pad_for_fit)
-        assert np.array_equal(out.shape[:-1], data[0].shape), 'prediction shape wrong'
+        assert np.array_equal(out.shape[:3], data[0].shape), 'prediction shape wrong'
         return out
 
     if truth_data is not None:
@@ -128,13 +165,16 @@ def patch_wise_prediction(model, data, patch_shape, overlap_factor=0, batch_size
     return predicted_output / predicted_count
 
 
-def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d=True, truth_0=None, aux_dz=0, aux_nz=0):
+def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d=True, truth_0=None, aux_dz=0, aux_nz=0,
+                        label_map=None):
     """Upload once, then per tile batch: gather -> network -> float64 overlap-add, all on the device.  The static buffers
     (volume, accumulators, tile batch, index list) and one captured hipGraph per distinct batch size are cached on the
     model and re-used for every following volume of the same padded shape.  2-D models: a tile (px, py, slices) IS the
     channels-last input of the network (the slice stack is the channel axis) and its output is one slice (px, py, 1).
     truth_0 (2-D models): the padded truth volume (data_0's extent); every tile then carries aux_nz more channels, its truth slices from
-    aux_dz slices past the tile's corner (reference batch_iterator, prediction.py:98-114)."""
+    aux_dz slices past the tile's corner (reference batch_iterator, prediction.py:98-114).
+    label_map (threshold, values): finished slabs become label bytes on the device (fmri_tile_finalize_labels) and the uint8 map
+    (X, Y, Z) is what comes down and is returned; None: the float64 means (X, Y, Z, C)."""
     import torch
     from fmri_hip import ops
     patch = tuple(int(p) for p in patch_shape)
@@ -222,8 +262,12 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
     st["acc"].zero_()
     st["cnt"].zero_()
     idx_all = torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).cuda()
-    out_dev = torch.empty_like(st["acc"])
-    out_host = torch.empty(ashape, dtype=torch.float64, pin_memory=True)
+    if label_map is None:
+        out_dev = torch.empty_like(st["acc"])
+        out_host = torch.empty(ashape, dtype=torch.float64, pin_memory=True)
+    else:
+        out_dev = torch.empty(ashape[:3], dtype=torch.uint8, device="cuda")
+        out_host = torch.empty(ashape[:3], dtype=torch.uint8, pin_memory=True)
     bad = torch.zeros(1, dtype=torch.int32, device="cuda")
     pin_np, src = st["pin_in"].numpy(), np.asarray(data_0)
     pin_aux, src_aux = (st["pin_aux"].numpy(), np.asarray(truth_0)) if aux_nz else (None, None)
@@ -253,7 +297,10 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
             pb["body"]()
         final = ashape[0] if hi >= n else min(ashape[0], min(starts_x[hi:]))
         if final > done_to:
-            ops.tile_finalize(st["acc"][done_to:final], st["cnt"][done_to:final], out_dev[done_to:final], bad)
+            if label_map is None:
+                ops.tile_finalize(st["acc"][done_to:final], st["cnt"][done_to:final], out_dev[done_to:final], bad)
+            else:
+                ops.tile_finalize_labels(st["acc"][done_to:final], st["cnt"][done_to:final], out_dev[done_to:final], bad, *label_map)
             down.wait_stream(main)
             with torch.cuda.stream(down):
                 out_host[done_to:final].copy_(out_dev[done_to:final], non_blocking=True)
@@ -261,6 +308,46 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
     down.synchronize()
     main.synchronize()
     return out_host.numpy(), int(bad.item()) == 0
+
+
+def get_prediction_labels(prediction, threshold=0.5, labels=None):
+    """prediction (n_samples, L, X, Y, Z) -> a list of uint8 label maps (X, Y, Z), one per sample: argmax over the label axis plus 1 (ties go
+    to the lowest index), 0 where the maximum lies below `threshold`, then mapped through `labels` (value k becomes labels[k - 1]).
+    Reference prediction.py:214-227.  Departure: the reference's line 218 takes argmax(..., axis=1) of a sample that has already lost its
+    batch axis and never adds 1, so its `labels[value - 1]` mapping and its docstring describe what is implemented here, not what it runs."""
+    prediction = np.asarray(prediction)
+    n_labels = prediction.shape[1]
+    values = np.asarray([0] + _label_values(n_labels, labels), dtype=np.uint8)
+    out = []
+    for sample in prediction:
+        label_data = np.argmax(sample, axis=0) + 1
+        label_data[np.max(sample, axis=0) < threshold] = 0
+        out.append(values[label_data])
+    return out
+
+
+def multi_class_prediction(prediction):
+    """one array per label channel of a prediction (1, L, X, Y, Z) (reference prediction.py:268-274, which wraps them in Nifti1Image; this
+    package writes NIfTI through utils.nifti)"""
+    prediction = np.asarray(prediction)
+    return [prediction[0, i] for i in range(prediction.shape[1])]
+
+
+def prediction_to_image(prediction, label_map=False, threshold=0.5, labels=None):
+    """reference prediction.py:243-265, returning arrays: one channel -> its volume, as a label map labels[0] (default 1) where it is
+    > threshold; several channels -> the label map of get_prediction_labels, or the list of multi_class_prediction.  Note the two rules
+    differ at equality: one channel needs > threshold, several keep a maximum equal to the threshold (only < threshold is background)."""
+    prediction = np.asarray(prediction)
+    if prediction.shape[1] == 1:
+        data = prediction[0, 0]
+        if label_map:
+            label_map_data = np.zeros(prediction[0, 0].shape, np.int8)
+            label_map_data[data > threshold] = labels[0] if labels else 1
+            data = label_map_data
+        return data
+    if label_map:
+        return get_prediction_labels(prediction, threshold=threshold, labels=labels)[0]
+    return multi_class_prediction(prediction)
 
 
 def predict(model, data, permute=False):
@@ -383,9 +470,12 @@ def predict_augment(data, model, overlap_factor, patch_shape, num_augments=32):
 
 
 def run_validation_case(data_index, output_dir, model, data_file, training_modalities, patch_shape, overlap_factor=0,
-                        permute=False, prev_truth_index=None, prev_truth_size=None, use_augmentations=False):
+                        permute=False, prev_truth_index=None, prev_truth_size=None, use_augmentations=False, *, output_label_map=False,
+                        threshold=0.5, labels=None):
     """Predict one case of an opened data file (any object with `.root.data[i]` / `.root.truth[i]`) and write
-    data_<modality>.nii.gz, truth.nii.gz, prediction.nii.gz under output_dir (reference prediction.py:277-330)."""
+    data_<modality>.nii.gz, truth.nii.gz, prediction.nii.gz under output_dir (reference prediction.py:277-330).
+    output_label_map (reference docstring :284-288): also write prediction_labels.nii.gz, the uint8 label map of the prediction
+    (prediction_to_image's rules with `threshold` and `labels`)."""
     from .utils.nifti import save_nifti
     if not os.path.exists(output_dir):
         os.makedirs(output_dir)
@@ -396,12 +486,24 @@ def run_validation_case(data_index, output_dir, model, data_file, training_modal
     save_nifti(np.asarray(data_file.root.truth[data_index]), os.path.join(output_dir, "truth.nii.gz"))
     if tuple(patch_shape) == tuple(test_data.shape[-3:]):
         prediction = predict(model, test_data[:, np.newaxis] if test_data.ndim == 4 else test_data, permute=permute)
+        mode = "whole"
     elif use_augmentations:
+        mode = "augment"
         prediction = predict_augment(data=test_data, model=model, overlap_factor=overlap_factor, patch_shape=patch_shape)
     else:
         prediction = patch_wise_prediction(model=model, data=test_data, overlap_factor=overlap_factor, patch_shape=patch_shape,
                                            truth_data=test_truth_data, prev_truth_index=prev_truth_index,
                                            prev_truth_size=prev_truth_size)[np.newaxis]
+        mode = "patches"
+    if output_label_map:
+        if mode == "whole":                                   # (1, L, X, Y, Z) as the model gives it
+            channels_first = prediction
+        elif mode == "augment":                               # the stack of single-channel variants: their mean
+            channels_first = np.mean(prediction, axis=0)[np.newaxis, np.newaxis]
+        else:                                                 # (1, X, Y, Z, C)
+            channels_first = np.moveaxis(prediction, -1, 1)
+        label_data = np.asarray(prediction_to_image(channels_first, label_map=True, threshold=threshold, labels=labels)).astype(np.uint8)
+        save_nifti(label_data, os.path.join(output_dir, "prediction_labels.nii.gz"))
     prediction = prediction.squeeze()
     filename = os.path.join(output_dir, "prediction.nii.gz")
     save_nifti(prediction, filename)

@@ -47,6 +47,7 @@ SIGNATURES = {
     "fmri_sigmoid_loss_bwd": [p, p, p, p, i64, i32, f32, f32, f32, p],
     "fmri_weighted_dice_fwd": [p, p, p, p, i32, i64, i32, f32, p],
     "fmri_weighted_dice_bwd": [p, p, p, p, p, i32, i64, i32, f32, f32, p],
+    "fmri_label_sums": [p, p, i64, i32, p, p],
     "fmri_maxpool3d_2x_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_maxpool3d_2x_bwd": [p, p, p, i32, i32, p, i32, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_upsample_nearest2x_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
@@ -92,6 +93,7 @@ SIGNATURES = {
     "fmri_correlate1d_asym_f64": [p, p, i32, i32, i32, i32, p, i32, p],
     "fmri_grad_magnitude_combine_f64": [p, p, p, p, i64, p],
     "fmri_seg_counts_u8": [p, p, i64, p, p],
+    "fmri_label_counts_u8": [p, p, i64, p, i32, p, p],
     "fmri_surface_u8": [p, p, p, p, i32, i32, i32, i32, p, p],
     "fmri_masked_stats_workspace_bytes": [],
     "fmri_masked_stats_f64": [p, p, i64, p, p, p],
@@ -109,6 +111,8 @@ SIGNATURES = {
     "fmri_tile_gather_stack": [p, p, i32, i32, i32, p, i32, i32, i32, i32, i32, i32, p, i32, p],
     "fmri_tile_scatter_accumulate": [p, p, i32, i32, i32, i32, i32, p, p, i32, i32, i32, p],
     "fmri_tile_finalize": [p, p, p, p, i64, i32, p],
+    "fmri_labels_expand_u8": [p, i64, p, i32, p, p],
+    "fmri_tile_finalize_labels": [p, p, p, p, i64, i32, C.c_double, p, p],
     "fmri_cast": [p, i32, p, i32, i64, p],
     "fmri_conv3d_upcat_ok": [i32, i32, i32, i32, i32, i32, i32],
     "fmri_conv3d_upcat_fwd_bias27": [p, i32, p, i32, p, p, p, p, i32, i32, i32, i32, i32, i32, f32, i32, p],

@@ -55,6 +55,13 @@ class ChainEngine(object):
     logits = property(lambda self: self.seg.logits)
     probs = property(lambda self: self.seg.probs)
     _dummy_y = property(lambda self: self.seg._dummy_y)
+    label_metrics = property(lambda self: self.seg.label_metrics)
+
+    def set_label_metrics(self, n):
+        self.seg.set_label_metrics(n)
+
+    def log_sums(self):
+        return self.seg.log_sums()
 
     def keras_to_flat(self, W):
         return self.norm.keras_to_flat(W)

@@ -92,7 +92,11 @@ class EngineBase(object):
         self._wg_stream = torch.cuda.Stream(device=self.dev) if (training and self.dev.type == "cuda" and self.sw["WGRAD_STREAM"]) else None
         # ONE tensor for the engine's lifetime: captured hipGraphs of other batch sizes keep its address (re-creating it per buffer
         # set left them writing into freed memory, which the allocator then handed to the tile index list of the next volume)
-        self.sums = torch.zeros(16, dtype=torch.float64, device=self.dev)
+        # Behind the 16 metric sums, in the same tensor: the 3 * L label-wise sums (ops.label_sums) of a model that carries label-wise Dice
+        # metrics (label_metrics = L, set by the model; 0: no launch, nothing read back) - one pinned read-back takes both (log_sums)
+        self._sums_all = torch.zeros(16 + 3 * ops.MAX_LABELS, dtype=torch.float64, device=self.dev)
+        self.sums = self._sums_all[:16]
+        self.label_metrics = 0
 
     def _alloc_params(self):
         """P in the engine's layout (n_flat fp32 values) and, when training, G, M and V of the same size"""
@@ -144,6 +148,8 @@ class EngineBase(object):
         """y_true uint8 [nvox*L] device.  probs + the 8 metric sums (accumulated into zeroed self.sums)."""
         self.sums.zero_()
         ops.sigmoid_dice_fwd(self.logits, y_true, self.probs, self.sums, weight=weight)
+        if self.label_metrics:
+            ops.label_sums(self.probs.reshape(-1), y_true, self.label_metrics, self._sums_all[16:])
         if self.loss_kind == ops.LOSS_WEIGHTED_DICE:
             ns, nl = self._wdice_groups()
             if getattr(self, "_gsums", None) is None or self._gsums.numel() < 3 * ns * nl:
@@ -152,6 +158,20 @@ class EngineBase(object):
         if self.dist is not None and self.dist.world > 1 and self.dist.global_dice:
             self.dist.all_reduce_sums(self.sums)
         return self.sums
+
+    def log_sums(self):
+        """what a step's read-back copies: the 16 metric sums, with the [L][3] label-wise sums behind them when label_metrics is set"""
+        return self._sums_all[:16 + 3 * self.label_metrics] if self.label_metrics else self.sums
+
+    def set_label_metrics(self, n):
+        """n = the model's label count when it carries label_<i>_dice_coef metrics, else 0"""
+        n = int(n)
+        if n and n != self.plan.n_labels:
+            raise ValueError("label-wise metrics for %d labels on an engine with %d" % (n, self.plan.n_labels))
+        if n and self.dist is not None and self.dist.world > 1:
+            raise NotImplementedError("label-wise Dice metrics (include_label_wise_dice_coefficients) are not all-reduced: build the model "
+                                      "without them for data-parallel training")
+        self.label_metrics = n
 
     def _wdice_groups(self):
         """(groups along the batch axis, labels per group) of weighted_dice_coefficient's axis=(-3,-2,-1) (reference metrics.py:39): the 3-D

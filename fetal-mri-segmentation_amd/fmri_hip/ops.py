@@ -295,6 +295,53 @@ def tile_finalize(acc, cnt, out, bad):
     check(lib().fmri_tile_finalize(_p(acc), _p(cnt), _p(out), _p(bad), cnt.numel(), Cc, _s()), "fmri_tile_finalize")
 
 
+MAX_LABELS = 32
+
+
+def label_values(values):
+    """the label values of the multi-label kernels as the host byte array they read at enqueue: 1 to 32 distinct integers in 1..255"""
+    import ctypes
+    vals = [int(v) for v in values]
+    if not 1 <= len(vals) <= MAX_LABELS or any(v != w or not 1 <= v <= 255 for v, w in zip(vals, values)) or len(set(vals)) != len(vals):
+        raise ValueError("labels: 1 to %d distinct integers in 1..255 (got %r)" % (MAX_LABELS, list(values)))
+    return (ctypes.c_uint8 * len(vals))(*vals)
+
+
+def labels_expand_u8(lab, values, out=None):
+    """out (*lab.shape, L) uint8, channels last = (lab == values[l]); a byte that is no label - background included - gives a zero row.
+    One launch whatever lab's shape (a whole batch of label patches)."""
+    vals = label_values(values)
+    if out is None:
+        out = torch.empty(tuple(lab.shape) + (len(vals),), dtype=torch.uint8, device=lab.device)
+    _need_cuda(lab, out)
+    if lab.dtype != torch.uint8 or out.dtype != torch.uint8 or out.numel() != lab.numel() * len(vals):
+        raise ValueError("labels_expand_u8: uint8 label map and a uint8 output of L times its size")
+    check(lib().fmri_labels_expand_u8(_p(lab), lab.numel(), vals, len(vals), _p(out), _s()), "fmri_labels_expand_u8")
+    return out
+
+
+def tile_finalize_labels(acc, cnt, out, bad, threshold, values):
+    """out uint8 like cnt: the label map of acc / cnt (tile_finalize's division) - C == 1: values[0] where the mean > threshold; C > 1:
+    values[first argmax], 0 where the maximum < threshold"""
+    _need_cuda(acc, cnt, out, bad)
+    vals = label_values(values)
+    Cc = acc.shape[-1]
+    if len(vals) != Cc or out.dtype != torch.uint8 or out.numel() != cnt.numel():
+        raise ValueError("tile_finalize_labels: %d label values for %d channels, uint8 output of cnt's size" % (len(vals), Cc))
+    check(lib().fmri_tile_finalize_labels(_p(acc), _p(cnt), _p(out), _p(bad), cnt.numel(), Cc, float(threshold), vals, _s()),
+          "fmri_tile_finalize_labels")
+
+
+def label_sums(probs, y_true, n_labels, lsums):
+    """lsums float64 [3 * L] (overwritten) = per label {sum y*p, sum y, sum p} of probs fp32 / y_true uint8 [nvox * L], label = index % L"""
+    _need_cuda(probs, y_true, lsums)
+    n = probs.numel()
+    if probs.dtype != torch.float32 or y_true.dtype != torch.uint8 or y_true.numel() != n or n % n_labels or lsums.dtype != torch.float64 \
+            or lsums.numel() < 3 * n_labels:
+        raise ValueError("label_sums: fp32 probs and uint8 targets of nvox * L elements, 3 * L float64 sums")
+    check(lib().fmri_label_sums(_p(probs), _p(y_true), n // n_labels, n_labels, _p(lsums), _s()), "fmri_label_sums")
+
+
 def cast(src, dst):
     _need_cuda(src, dst)
     check(lib().fmri_cast(_p(src), dt(src), _p(dst), dt(dst), src.numel(), _s()), "fmri_cast")
@@ -1175,6 +1222,16 @@ def seg_counts_u8(a, b):
         out = torch.empty(3, dtype=torch.int64, device=a.device)
         check(lib().fmri_seg_counts_u8(_p(a), _p(b), a.numel(), _p(out), _s()), "fmri_seg_counts_u8")
     return tuple(int(v) for v in out.tolist())
+
+
+def label_counts_u8(truth, pred, values):
+    """[(|T == v|, |P == v|, |both|) for v in values] as Python ints of two uint8 device label maps: exact, one pass for all labels"""
+    _masks_u8(truth, pred)
+    vals = label_values(values)
+    with torch.cuda.device(truth.device):
+        out = torch.empty((len(vals), 3), dtype=torch.int64, device=truth.device)
+        check(lib().fmri_label_counts_u8(_p(truth), _p(pred), truth.numel(), vals, len(vals), _p(out), _s()), "fmri_label_counts_u8")
+    return [tuple(int(v) for v in row) for row in out.tolist()]
 
 
 def _surface(a, b, connectivity, counts):

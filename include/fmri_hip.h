@@ -240,6 +240,12 @@ int fmri_sigmoid_dice_fwd_weighted(const float* logits, const uint8_t* y_true, c
 int fmri_sigmoid_loss_bwd_weighted(const float* probs, const uint8_t* y_true, const float* weight, const double* sums, float* dlogits,
                                    int64_t n, int kind, float param, float smooth, float grad_scale, fmri_stream_t stream);
 
+/* ---- label-wise Dice (reference metrics.py:52-59; the metrics unet.py:75-80 would add): lsums [L][3] doubles (device, OVERWRITTEN) =
+ * {sum y*p, sum y, sum p} of label l over all nvox voxels of the batch, probs / y_true indexed [v * L + l] like the logits; 1 <= L <= 32.
+ * label_l_dice_coef = (2 lsums[l][0] + 1) / (lsums[l][1] + lsums[l][2] + 1).  Under fmri_set_deterministic the workgroups' sums meet as
+ * 2^-20 fixed-point integers (as the sums of fmri_sigmoid_dice_fwd): two calls agree bit for bit. */
+int fmri_label_sums(const float* probs, const uint8_t* y_true, int64_t nvox, int L, double* lsums, fmri_stream_t stream);
+
 /* ---- MaxPooling3D(2,2,2) — reference unet.py:51.  D,H,W are the INPUT dims (even). */
 int fmri_maxpool3d_2x_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int dtype, int planar,
                           fmri_stream_t stream);
@@ -409,6 +415,16 @@ int fmri_tile_scatter_accumulate(const float* pred, const int32_t* idx, int B, i
 /* out (double) [n][C] = acc / cnt ; *bad (int32, accumulated) counts voxels with cnt == 0 (reference asserts none) */
 int fmri_tile_finalize(const double* acc, const int32_t* cnt, double* out, int32_t* bad, int64_t nvox, int C,
                        fmri_stream_t stream);
+
+/* ---- several labels (reference generator.py:404-419 get_multi_class_labels, prediction.py:214-274).  `values`: L label values, uint8,
+ * HOST memory (read at enqueue), 1 <= L <= 32, every value in 1..255 and no value twice - anything else is FMRI_E_SHAPE.
+ * fmri_labels_expand_u8: out [n][L] (channels last) = (lab[v] == values[l]); a byte that is no label - background included - gives a zero row.
+ * fmri_tile_finalize_labels: out[v] (uint8) from q_c = acc[v][c] / cnt[v] in float64 (fmri_tile_finalize's division).  C == 1: values[0]
+ *   where q_0 > threshold, else 0; C > 1: values[k] with k the first index of the maximum q_c (np.argmax), 0 where max q < threshold.
+ *   cnt[v] == 0: out[v] = 0 and *bad (accumulated) counts it. */
+int fmri_labels_expand_u8(const uint8_t* lab, int64_t n, const uint8_t* values, int L, uint8_t* out, fmri_stream_t stream);
+int fmri_tile_finalize_labels(const double* acc, const int32_t* cnt, uint8_t* out, int32_t* bad, int64_t nvox, int C, double threshold,
+                              const uint8_t* values, fmri_stream_t stream);
 
 /* ---- device-side patch sampler + intensity augmentation.  Replaces, per training patch, the host chain
  * reference fetal_net/generator.py:246-328 (add_data / extract_patch) -> augment.py:222-377 (augment_data) ->
@@ -603,7 +619,11 @@ int fmri_grad_magnitude_combine_f64(const double* d0, const double* d1, const do
  *   max is exact; the sum is added in an order fixed by n (per-workgroup partials in `workspace`,
  *   fmri_masked_stats_workspace_bytes() bytes on the device, then one workgroup over the partials): two calls agree bit for bit.
  * fmri_masked_compact_f64: the same selection copied densely to out[*cursor], out[*cursor + 1], ... in unspecified order; *cursor
- *   (device, set by the caller) ends advanced by the number selected.  Slots at or past `capacity` are not written. */
+ *   (device, set by the caller) ends advanced by the number selected.  Slots at or past `capacity` are not written.
+ * fmri_label_counts_u8: out [L][3] (device int64, overwritten) = {|T == values[l]|, |P == values[l]|, |both|}, exact, one pass over the two
+ *   volumes for all labels; `values` as for fmri_labels_expand_u8 (host, 1 <= L <= 32, distinct, nonzero). */
+int fmri_label_counts_u8(const uint8_t* truth, const uint8_t* pred, int64_t n, const uint8_t* values, int L, int64_t* out,
+                         fmri_stream_t stream);
 int fmri_seg_counts_u8(const uint8_t* a, const uint8_t* b, int64_t n, int64_t* out3, fmri_stream_t stream);
 int fmri_surface_u8(const uint8_t* mask, uint8_t* inv_border, const uint8_t* mask2, uint8_t* inv_border2, int X, int Y, int Z,
                     int connectivity, int64_t* count, fmri_stream_t stream);
