@@ -26,19 +26,22 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {          // scipy mod
 // NEAREST = scipy mode 'nearest' (a a a a | a b c d | d d d d), what skimage.filters.gaussian passes; else 'reflect'.
 // ANTI = NI_Correlate1D's antisymmetric branch (weights with w[r + j] == -w[r - j]: the order-1 Gaussian of gaussian_gradient_magnitude):
 // the pairs are subtracted, x[l + jj] - x[l - jj], instead of added.
-template <typename T, bool NEAREST, bool ANTI = false>
+// CL = a channels-last volume [X][Y][Z / L][L] (Z counts the elements of a row, L per voxel): axes 0 and 1 see rows of Z elements as
+// before, axis 2 runs over the Z / L voxels of a row with an element stride of L.
+template <typename T, bool NEAREST, bool ANTI = false, bool CL = false>
 __global__ void k_correlate1d_sym(const T* __restrict__ src, T* __restrict__ dst, int X, int Y, int Z, int axis,
-                                  const double* __restrict__ w, int radius) {
+                                  const double* __restrict__ w, int radius, int L) {
 #pragma clang fp contract(off)      // separately rounded multiply and add: scipy's C loop is compiled without fused operations
     const int64_t total = (int64_t)X * Y * Z;
-    const int n = axis == 0 ? X : (axis == 1 ? Y : Z);
-    const int64_t stride = axis == 0 ? (int64_t)Y * Z : (axis == 1 ? Z : 1);
+    const int es = CL ? L : 1;
+    const int n = axis == 0 ? X : (axis == 1 ? Y : Z / es);
+    const int64_t stride = axis == 0 ? (int64_t)Y * Z : (axis == 1 ? Z : es);
     auto at = [&](int i) { return NEAREST ? min(max(i, 0), n - 1) : reflect_idx(i, n); };
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int z = (int)(t % Z);
         const int64_t q = t / Z;
         const int y = (int)(q % Y), x = (int)(q / Y);
-        const int l = axis == 0 ? x : (axis == 1 ? y : z);
+        const int l = axis == 0 ? x : (axis == 1 ? y : z / es);
         const int64_t base = t - (int64_t)l * stride;
         double acc = (double)src[t] * w[radius];
         for (int jj = -radius; jj < 0; ++jj) {
@@ -151,7 +154,7 @@ __global__ void k_cc_select(const int32_t* __restrict__ lab, const unsigned long
 extern "C" int fmri_correlate1d_f64(const double* src, double* dst, int X, int Y, int Z, int axis, const double* weights, int radius,
                                     fmri_stream_t stream) {
     if (!src || !dst || !weights || src == dst || X <= 0 || Y <= 0 || Z <= 0 || axis < 0 || axis > 2 || radius < 0) return FMRI_E_SHAPE;
-    k_correlate1d_sym<double, false><<<grid_for((int64_t)X * Y * Z, 256, 8192), 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z, axis, weights, radius);
+    k_correlate1d_sym<double, false><<<grid_for((int64_t)X * Y * Z, 256, 8192), 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z, axis, weights, radius, 1);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
@@ -159,7 +162,7 @@ extern "C" int fmri_correlate1d_asym_f64(const double* src, double* dst, int X, 
                                          fmri_stream_t stream) {
     if (!src || !dst || !weights || src == dst || X <= 0 || Y <= 0 || Z <= 0 || axis < 0 || axis > 2 || radius < 0) return FMRI_E_SHAPE;
     k_correlate1d_sym<double, false, true><<<grid_for((int64_t)X * Y * Z, 256, 8192), 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z, axis, weights,
-                                                                                                                  radius);
+                                                                                                                  radius, 1);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
@@ -168,8 +171,8 @@ extern "C" int fmri_correlate1d_f32(const float* src, float* dst, int X, int Y, 
     if (!src || !dst || !weights || src == dst || X <= 0 || Y <= 0 || Z <= 0 || axis < 0 || axis > 2 || radius < 0 || (mode != 0 && mode != 1))
         return FMRI_E_SHAPE;
     const int grid = grid_for((int64_t)X * Y * Z, 256, 8192);
-    if (mode == 1) k_correlate1d_sym<float, true><<<grid, 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z, axis, weights, radius);
-    else k_correlate1d_sym<float, false><<<grid, 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z, axis, weights, radius);
+    if (mode == 1) k_correlate1d_sym<float, true><<<grid, 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z, axis, weights, radius, 1);
+    else k_correlate1d_sym<float, false><<<grid, 256, 0, as_stream(stream)>>>(src, dst, X, Y, Z, axis, weights, radius, 1);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
@@ -221,6 +224,289 @@ extern "C" int fmri_largest_component_step(const uint8_t* mask, int32_t* labels,
         k_cc_best<<<grid, 256, 0, st>>>(counts, n, best);
         k_cc_select<<<grid, 256, 0, st>>>(labels, best, out, n);
     }
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The same clean-up for L <= 32 label channels in one pass (fetal_net.postprocess.postprocess_label_map).  The probabilities come
+// channels last, [X][Y][Z][L] fp64, as the tile loop leaves them.  After smoothing and "> threshold" the L masks of a voxel are the L low
+// bits of one uint32 word, and every later stage works on words:
+//   smoothing    k_correlate1d_sym<.., CL>: axes 0 and 1 see rows of Z * L elements, axis 2 an element stride of L - per channel the sums
+//                of the single-label kernel, bit for bit
+//   threshold    a workgroup reads the 256 * L doubles of 256 voxels with coalesced loads and ORs the bits together in LDS
+//   fill holes   reached' = reached | (OR of the six neighbours' reached words & ~mask), started from ~mask on the volume's border: the
+//                flood of all channels' backgrounds at once, word-wide.  As in k_flood_sweep the front runs on along the contiguous z row.
+//                Several threads may add bits to one word in the same sweep, so every update is an atomicOr.  `valid` (the L low bits)
+//                keeps the unused bits from ever counting as background.
+//   components   int32 labels [L][n], channel-major: label 1 + voxel index inside its channel, scipy's numbering order per channel.
+//                One thread per voxel walks the set bits of its word (k_cc_sweep's min-label propagation with root chasing per bit), one
+//                launch per sweep and one `changed` flag for all channels; a converged channel finds nothing to lower and stays as it is.
+//                Labels are written and read only where the channel's bit is set - a neighbour's bit is looked up in its word - so
+//                nothing of the L * n array is initialised or read for background, and counts / best are zeroed and read only at the
+//                roots (label == own index + 1).  The count adds the lanes of a wave that share a destination as one atomic.
+//   combine      a voxel reads its word and, only for the set bits, the smoothed values: values[first argmax] or 0, one byte out
+// Scratch of the whole chain at n voxels: 2 * L * n doubles (the smoothed volume and the other buffer of the passes), two uint32 [n]
+// (mask / result words and `reached`), int32 [L * n] labels, int32 [L * (n + 1)] counts, uint64 [L] best.
+namespace {
+
+__global__ __launch_bounds__(256) void k_threshold_bits(const double* __restrict__ src, uint32_t* __restrict__ words, int64_t n, int L,
+                                                        double thr) {
+    __shared__ uint32_t w[256];
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += (int64_t)gridDim.x * 256) {
+        w[threadIdx.x] = 0;
+        __syncthreads();
+        const int cnt = (int)min((int64_t)256, n - base) * L;
+        const double* const p = src + base * L;
+        for (int e = threadIdx.x; e < cnt; e += 256)
+            if (p[e] > thr) atomicOr(&w[e / L], 1u << (e % L));
+        __syncthreads();
+        if (base + threadIdx.x < n) words[base + threadIdx.x] = w[threadIdx.x];
+    }
+}
+
+__global__ void k_flood_bits_init(const uint32_t* __restrict__ mask, uint32_t* __restrict__ reached, int X, int Y, int Z, uint32_t valid) {
+    const int64_t total = (int64_t)X * Y * Z;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int z = (int)(t % Z);
+        const int64_t q = t / Z;
+        const int y = (int)(q % Y), x = (int)(q / Y);
+        const bool border = x == 0 || y == 0 || z == 0 || x == X - 1 || y == Y - 1 || z == Z - 1;
+        reached[t] = border ? ~mask[t] & valid : 0u;
+    }
+}
+__global__ void k_flood_bits_sweep(const uint32_t* __restrict__ mask, uint32_t* reached, int X, int Y, int Z, uint32_t valid,
+                                   int* __restrict__ changed) {
+    const int64_t total = (int64_t)X * Y * Z;
+    bool any = false;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t cand = ~mask[t] & valid & ~reached[t];                 // background bits not reached yet
+        if (!cand) continue;
+        const int z = (int)(t % Z);
+        const int64_t q = t / Z;
+        const int y = (int)(q % Y), x = (int)(q / Y);
+        const int64_t sx = (int64_t)Y * Z;
+        uint32_t nb = 0;
+        if (x > 0) nb |= reached[t - sx];
+        if (x < X - 1) nb |= reached[t + sx];
+        if (y > 0) nb |= reached[t - Z];
+        if (y < Y - 1) nb |= reached[t + Z];
+        if (z > 0) nb |= reached[t - 1];
+        if (z < Z - 1) nb |= reached[t + 1];
+        const uint32_t add = nb & cand;
+        if (!add) continue;
+        atomicOr(&reached[t], add);
+        any = true;
+        uint32_t f = add;                                                     // the bits still running along +z, then -z
+        for (int k = z + 1; k < Z; ++k) {
+            f &= ~mask[t - z + k] & ~reached[t - z + k];
+            if (!f) break;
+            atomicOr(&reached[t - z + k], f);
+        }
+        f = add;
+        for (int k = z - 1; k >= 0; --k) {
+            f &= ~mask[t - z + k] & ~reached[t - z + k];
+            if (!f) break;
+            atomicOr(&reached[t - z + k], f);
+        }
+    }
+    if (any) *changed = 1;
+}
+__global__ void k_fill_bits_from_reached(const uint32_t* __restrict__ reached, uint32_t* __restrict__ out, int64_t n, uint32_t valid) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = ~reached[i] & valid;
+}
+
+__global__ void k_ccb_init(const uint32_t* __restrict__ words, int32_t* __restrict__ lab, int64_t n, uint32_t valid) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+        for (uint32_t m = words[t] & valid; m; m &= m - 1) lab[(int64_t)(__ffs(m) - 1) * n + t] = (int32_t)(t + 1);
+}
+__global__ void k_ccb_sweep(const uint32_t* __restrict__ words, int32_t* lab, int X, int Y, int Z, uint32_t valid, int* __restrict__ changed) {
+    const int64_t total = (int64_t)X * Y * Z;
+    bool any = false;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t w = words[t] & valid;
+        if (!w) continue;
+        const int z = (int)(t % Z);
+        const int64_t q = t / Z;
+        const int y = (int)(q % Y), x = (int)(q / Y);
+        const int64_t sx = (int64_t)Y * Z;
+        const uint32_t w0 = x > 0 ? words[t - sx] : 0u, w1 = x < X - 1 ? words[t + sx] : 0u, w2 = y > 0 ? words[t - Z] : 0u,
+                       w3 = y < Y - 1 ? words[t + Z] : 0u, w4 = z > 0 ? words[t - 1] : 0u, w5 = z < Z - 1 ? words[t + 1] : 0u;
+        for (uint32_t todo = w & (w0 | w1 | w2 | w3 | w4 | w5); todo; todo &= todo - 1) {      // channels in which the voxel has a neighbour
+            const uint32_t bit = todo & (0u - todo);
+            int32_t* const lb = lab + (int64_t)(__ffs(todo) - 1) * total;
+            const int32_t mine = lb[t];
+            int32_t m = mine;
+            auto look = [&](uint32_t wn, int64_t o) {
+                if (wn & bit) {
+                    const int32_t v = lb[o];
+                    if (v < m) m = v;
+                }
+            };
+            look(w0, t - sx);
+            look(w1, t + sx);
+            look(w2, t - Z);
+            look(w3, t + Z);
+            look(w4, t - 1);
+            look(w5, t + 1);
+            // k_cc_sweep's chase; a label is always 1 + the index of a voxel of the same component, the range test only keeps a caller's
+            // mismatched words / labels inside the array
+            for (int hop = 0; hop < 8 && (uint32_t)(m - 1) < (uint32_t)total; ++hop) {
+                const int32_t up = lb[m - 1];
+                if (up >= m) break;
+                m = up;
+            }
+            if (m < mine && (uint32_t)(mine - 1) < (uint32_t)total && m > 0) {
+                atomicMin(&lb[t], m);
+                atomicMin(&lb[mine - 1], m);
+                any = true;
+            }
+        }
+    }
+    if (any) *changed = 1;
+}
+// roots only: counts[l][root label] = 0 and best[l] = 0 ahead of the count
+__global__ void k_ccb_zero(const uint32_t* __restrict__ words, const int32_t* __restrict__ lab, int32_t* __restrict__ counts,
+                           unsigned long long* __restrict__ best, int64_t n, int L, uint32_t valid) {
+    if (blockIdx.x == 0 && threadIdx.x < L) best[threadIdx.x] = 0ull;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+        for (uint32_t m = words[t] & valid; m; m &= m - 1) {
+            const int l = __ffs(m) - 1;
+            if (lab[(int64_t)l * n + t] == (int32_t)(t + 1)) counts[(int64_t)l * (n + 1) + t + 1] = 0;
+        }
+}
+// consecutive z of one component are the common case: the lanes of the wave that share the first active lane's destination add once
+__global__ void k_ccb_count(const uint32_t* __restrict__ words, const int32_t* __restrict__ lab, int32_t* __restrict__ counts, int64_t n,
+                            uint32_t valid) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+        for (uint32_t m = words[t] & valid; m; m &= m - 1) {
+            const int l = __ffs(m) - 1;
+            const int32_t v = lab[(int64_t)l * n + t];
+            if ((uint32_t)(v - 1) >= (uint32_t)n) continue;
+            const int l0 = __builtin_amdgcn_readfirstlane(l);
+            const int32_t v0 = __builtin_amdgcn_readfirstlane(v);
+            const bool with_first = l == l0 && v == v0;
+            const unsigned long long same = __ballot(with_first);
+            if (!with_first) atomicAdd(&counts[(int64_t)l * (n + 1) + v], 1);
+            else if (lane == __ffsll((long long)same) - 1) atomicAdd(&counts[(int64_t)l * (n + 1) + v], (int32_t)__popcll(same));
+        }
+}
+// k_cc_best's key per channel: (count << 32) | ~label - largest count, first in scan order among equals
+__global__ void k_ccb_best(const uint32_t* __restrict__ words, const int32_t* __restrict__ lab, const int32_t* __restrict__ counts,
+                           unsigned long long* __restrict__ best, int64_t n, uint32_t valid) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+        for (uint32_t m = words[t] & valid; m; m &= m - 1) {
+            const int l = __ffs(m) - 1;
+            if (lab[(int64_t)l * n + t] != (int32_t)(t + 1)) continue;
+            const int32_t c = counts[(int64_t)l * (n + 1) + t + 1];
+            if (c > 0) atomicMax(&best[l], ((unsigned long long)(unsigned)c << 32) | (unsigned long long)(0xffffffffu - (unsigned)(t + 1)));
+        }
+}
+__global__ __launch_bounds__(256) void k_ccb_select(const uint32_t* __restrict__ words, const int32_t* __restrict__ lab,
+                                                    const unsigned long long* __restrict__ best, uint32_t* __restrict__ out, int64_t n, int L,
+                                                    uint32_t valid) {
+    __shared__ int32_t want[FMRI_MAX_LABELS];
+    if (threadIdx.x < FMRI_MAX_LABELS) {
+        const unsigned long long b = threadIdx.x < L ? best[threadIdx.x] : 0ull;
+        want[threadIdx.x] = b ? (int32_t)(0xffffffffu - (unsigned)(b & 0xffffffffull)) : -1;
+    }
+    __syncthreads();
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t keep = 0;
+        for (uint32_t m = words[t] & valid; m; m &= m - 1) {
+            const int l = __ffs(m) - 1;
+            if (lab[(int64_t)l * n + t] == want[l]) keep |= 1u << l;
+        }
+        out[t] = keep;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_label_map_bits(const uint32_t* __restrict__ words, const double* __restrict__ smoothed,
+                                                        uint8_t* __restrict__ out, int64_t n, int L, uint32_t valid, FmriLabelValues V) {
+    __shared__ __attribute__((aligned(4))) uint8_t vals[FMRI_MAX_LABELS];
+    fmri_label_tables(V, L, vals, nullptr);
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const double* const row = smoothed + t * L;
+        double top = 0.0;
+        int k = -1;
+        for (uint32_t m = words[t] & valid; m; m &= m - 1) {                  // ascending channels, strict ">": ties stay with the lowest
+            const int l = __ffs(m) - 1;
+            const double v = row[l];
+            if (k < 0 || v > top) { top = v; k = l; }
+        }
+        out[t] = k < 0 ? (uint8_t)0 : vals[k];
+    }
+}
+
+inline uint32_t low_bits(int L) { return L >= 32 ? 0xffffffffu : (1u << L) - 1u; }
+
+}  // namespace
+
+extern "C" int fmri_correlate1d_cl_f64(const double* src, double* dst, int X, int Y, int Z, int L, int axis, const double* weights, int radius,
+                                       fmri_stream_t stream) {
+    if (!src || !dst || !weights || src == dst || X <= 0 || Y <= 0 || Z <= 0 || L < 1 || L > FMRI_MAX_LABELS || axis < 0 || axis > 2 ||
+        radius < 0 || (int64_t)Z * L > 0x7fffffff)
+        return FMRI_E_SHAPE;
+    k_correlate1d_sym<double, false, false, true><<<grid_for((int64_t)X * Y * Z * L, 256, 8192), 256, 0, as_stream(stream)>>>(
+        src, dst, X, Y, Z * L, axis, weights, radius, L);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+extern "C" int fmri_threshold_bits_f64(const double* src, uint32_t* words, int64_t n, int L, double threshold, fmri_stream_t stream) {
+    if (!src || !words || n <= 0 || L < 1 || L > FMRI_MAX_LABELS) return FMRI_E_SHAPE;
+    k_threshold_bits<<<grid_for(n, 256, 8192), 256, 0, as_stream(stream)>>>(src, words, n, L, threshold);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+// fmri_fill_holes_step on words: bit l of a word is channel l's mask, bits L..31 of the input are ignored and come out zero
+extern "C" int fmri_fill_holes_bits_step(const uint32_t* mask, uint32_t* reached, uint32_t* out, int X, int Y, int Z, int L, int phase,
+                                         int sweeps, int* changed, fmri_stream_t stream) {
+    if (!mask || !reached || X <= 0 || Y <= 0 || Z <= 0 || L < 1 || L > FMRI_MAX_LABELS) return FMRI_E_SHAPE;
+    const int64_t n = (int64_t)X * Y * Z;
+    const uint32_t valid = low_bits(L);
+    hipStream_t st = as_stream(stream);
+    const int grid = grid_for(n, 256, 8192);
+    if (phase == 0) k_flood_bits_init<<<grid, 256, 0, st>>>(mask, reached, X, Y, Z, valid);
+    else if (phase == 1) {
+        if (!changed) return FMRI_E_SHAPE;
+        for (int i = 0; i < sweeps; ++i) k_flood_bits_sweep<<<grid, 256, 0, st>>>(mask, reached, X, Y, Z, valid, changed);
+    } else {
+        if (!out) return FMRI_E_SHAPE;
+        k_fill_bits_from_reached<<<grid, 256, 0, st>>>(reached, out, n, valid);
+    }
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+// fmri_largest_component_step on words; `words` is the same array in all three phases (it says where `labels` holds a label)
+extern "C" int fmri_largest_components_bits_step(const uint32_t* words, int32_t* labels, int32_t* counts, unsigned long long* best,
+                                                 uint32_t* out, int X, int Y, int Z, int L, int phase, int sweeps, int* changed,
+                                                 fmri_stream_t stream) {
+    if (!words || !labels || X <= 0 || Y <= 0 || Z <= 0 || L < 1 || L > FMRI_MAX_LABELS) return FMRI_E_SHAPE;
+    const int64_t n = (int64_t)X * Y * Z;
+    if (n >= 0x7fffffff) return FMRI_E_SHAPE;
+    const uint32_t valid = low_bits(L);
+    hipStream_t st = as_stream(stream);
+    const int grid = grid_for(n, 256, 8192);
+    if (phase == 0) k_ccb_init<<<grid, 256, 0, st>>>(words, labels, n, valid);
+    else if (phase == 1) {
+        if (!changed) return FMRI_E_SHAPE;
+        for (int i = 0; i < sweeps; ++i) k_ccb_sweep<<<grid, 256, 0, st>>>(words, labels, X, Y, Z, valid, changed);
+    } else {
+        if (!counts || !best || !out || out == words) return FMRI_E_SHAPE;
+        k_ccb_zero<<<grid, 256, 0, st>>>(words, labels, counts, best, n, L, valid);
+        k_ccb_count<<<grid, 256, 0, st>>>(words, labels, counts, n, valid);
+        k_ccb_best<<<grid, 256, 0, st>>>(words, labels, counts, best, n, valid);
+        k_ccb_select<<<grid, 256, 0, st>>>(words, labels, best, out, n, L, valid);
+    }
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+extern "C" int fmri_label_map_bits(const uint32_t* words, const double* smoothed, uint8_t* out, int64_t n, int L, const uint8_t* values,
+                                   fmri_stream_t stream) {
+    FmriLabelValues V;
+    if (!words || !smoothed || !out || n <= 0 || fmri_label_values(values, L, &V) != FMRI_OK) return FMRI_E_SHAPE;
+    k_label_map_bits<<<grid_for(n, 256, 8192), 256, 0, as_stream(stream)>>>(words, smoothed, out, n, L, low_bits(L), V);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }

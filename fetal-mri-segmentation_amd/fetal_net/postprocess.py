@@ -4,7 +4,13 @@ smoothing, threshold, hole filling, largest connected component.
 Two implementations of the same definition: scipy.ndimage on the host (what the reference runs), and - when a GPU and the HIP library are
 there and the input is a float64 3-D volume, i.e. the output of `patch_wise_prediction` - the device kernels of csrc/postprocess.hip
 (`fmri_correlate1d_f64`, `fmri_threshold_f64`, `fmri_fill_holes_step`, `fmri_largest_component_step`): the gaussian sums in scipy's own
-order in fp64, so the two produce the same mask voxel for voxel (tests/test_gpu_postprocess.py).  `device=` forces one or the other."""
+order in fp64, so the two produce the same mask voxel for voxel (tests/test_gpu_postprocess.py).  `device=` forces one or the other.
+
+Several labels: `postprocess_label_map` cleans every channel of a channels-last prediction (X, Y, Z, L) by the same four steps and
+merges the cleaned masks into one uint8 label map.  Its host form is the definition (scipy per channel, numpy for the merge); its device
+form packs the L masks of a voxel into one uint32 word and runs hole filling and the component search on all channels at once
+(`fmri_correlate1d_cl_f64`, `fmri_threshold_bits_f64`, `fmri_fill_holes_bits_step`, `fmri_largest_components_bits_step`,
+`fmri_label_map_bits`) and returns the same bytes (tests/test_gpu_postprocess_labels.py)."""
 import numpy as np
 from scipy import ndimage
 
@@ -18,8 +24,8 @@ def get_main_connected_component(data):
     return components == 1 + int(np.argmax(voxels_per_component))
 
 
-def _device_ok(pred):
-    if not (isinstance(pred, np.ndarray) and pred.ndim == 3 and pred.dtype == np.float64):
+def _device_ok(pred, ndims=(3,)):
+    if not (isinstance(pred, np.ndarray) and pred.ndim in ndims and pred.dtype == np.float64):
         return False
     try:
         import torch
@@ -59,3 +65,73 @@ def _postprocess_on_device(pred, gaussian_std, threshold, fill_holes, connected_
     if connected_component:
         mask = ops.largest_component_u8(mask)
     return mask.cpu().numpy().astype(bool)
+
+
+MAX_LABELS = 32          # fmri_hip.ops.MAX_LABELS: the channels of a voxel are the bits of one word
+
+
+def _label_bytes(n_labels, labels):
+    """fmri_hip.ops.label_values' rule without the device package: n_labels distinct integers in 1..255, default 1..n_labels"""
+    given = list(range(1, n_labels + 1)) if labels is None else list(labels)
+    try:
+        values = [int(v) for v in given]
+    except (TypeError, ValueError):
+        values = None
+    if values is None or len(values) != n_labels or any(v != g or not 1 <= v <= 255 for v, g in zip(values, given)) \
+            or len(set(values)) != len(values):
+        raise ValueError("labels %r: %d distinct integers in 1..255, one per label channel" % (labels, n_labels))
+    return values
+
+
+def postprocess_label_map(prediction, gaussian_std=1, threshold=0.5, fill_holes=True, connected_component=True, labels=None, device=None):
+    """uint8 label map (X, Y, Z) of a float64 prediction (X, Y, Z, L), channels last as `patch_wise_prediction` returns it ((X, Y, Z)
+    means L = 1), 1 <= L <= 32.  With S_l = gaussian_filter(prediction[..., l], gaussian_std) and M_l = postprocess_prediction(
+    prediction[..., l], gaussian_std, threshold, fill_holes, connected_component): a voxel in no M_l gets 0, any other voxel gets
+    labels[l*], l* = the argmax of S_l over the channels whose M_l holds the voxel, ties to the lowest channel.  `labels`: L distinct
+    values in 1..255 (default 1..L), anything else is a ValueError.
+
+    - A voxel that only hole filling put into M_l has S_l <= threshold and still competes with its S_l.
+    - The test is "> threshold" per channel, as in postprocess_prediction; get_prediction_labels keeps a maximum EQUAL to the threshold,
+      so the two differ at equality.
+    - For L = 1 the result is labels[0] * postprocess_prediction(...).
+    NaN input is not specified.
+
+    device=None: the device path when a GPU and the library are there and the input is a float64 array of 3 or 4 dimensions, else the
+    host path; True / False force one.  A float64 CUDA tensor in gives a uint8 CUDA tensor out, with no round trip."""
+    is_tensor = not isinstance(prediction, np.ndarray) and hasattr(prediction, "is_cuda")
+    if not is_tensor:
+        prediction = np.asarray(prediction)
+    if prediction.ndim not in (3, 4):
+        raise ValueError("prediction: (X, Y, Z, L) or (X, Y, Z), got shape %r" % (tuple(prediction.shape),))
+    n_labels = 1 if prediction.ndim == 3 else int(prediction.shape[3])
+    if not 1 <= n_labels <= MAX_LABELS:
+        raise ValueError("prediction: 1 to %d label channels, got %d" % (MAX_LABELS, n_labels))
+    values = _label_bytes(n_labels, labels)
+    if device is None:
+        device = bool(prediction.is_cuda) if is_tensor else _device_ok(prediction, (3, 4))
+    if device:
+        return _label_map_on_device(prediction, n_labels, gaussian_std, threshold, fill_holes, connected_component, values, is_tensor)
+    if is_tensor:
+        prediction = prediction.cpu().numpy()
+    pred4 = prediction.reshape(prediction.shape[:3] + (n_labels,))
+    smoothed = np.stack([ndimage.gaussian_filter(pred4[..., l], gaussian_std) for l in range(n_labels)])
+    masks = np.stack([postprocess_prediction(pred4[..., l], gaussian_std, threshold, fill_holes, connected_component, device=False)
+                      for l in range(n_labels)])
+    index = np.argmax(np.where(masks, smoothed, -np.inf), axis=0) + 1          # np.argmax: the first of equal maxima
+    index[~masks.any(axis=0)] = 0
+    return np.asarray([0] + values, dtype=np.uint8)[index]
+
+
+def _label_map_on_device(pred, n_labels, gaussian_std, threshold, fill_holes, connected_component, values, keep_on_device):
+    import torch
+    from fmri_hip import ops
+    vol = pred if isinstance(pred, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float64)).cuda()
+    vol = vol.contiguous().reshape(tuple(vol.shape[:3]) + (n_labels,))
+    smoothed = ops.gaussian_filter_channels_f64(vol, gaussian_std)
+    words = ops.threshold_bits_f64(smoothed, threshold)
+    if fill_holes:
+        words = ops.binary_fill_holes_bits(words, n_labels)
+    if connected_component:
+        words = ops.largest_components_bits(words, n_labels)
+    out = ops.label_map_from_bits(words, smoothed, values)
+    return out if keep_on_device else out.cpu().numpy()

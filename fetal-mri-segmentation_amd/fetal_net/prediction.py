@@ -471,11 +471,13 @@ def predict_augment(data, model, overlap_factor, patch_shape, num_augments=32):
 
 def run_validation_case(data_index, output_dir, model, data_file, training_modalities, patch_shape, overlap_factor=0,
                         permute=False, prev_truth_index=None, prev_truth_size=None, use_augmentations=False, *, output_label_map=False,
-                        threshold=0.5, labels=None):
+                        threshold=0.5, labels=None, postprocess_labels=None):
     """Predict one case of an opened data file (any object with `.root.data[i]` / `.root.truth[i]`) and write
     data_<modality>.nii.gz, truth.nii.gz, prediction.nii.gz under output_dir (reference prediction.py:277-330).
     output_label_map (reference docstring :284-288): also write prediction_labels.nii.gz, the uint8 label map of the prediction
-    (prediction_to_image's rules with `threshold` and `labels`)."""
+    (prediction_to_image's rules with `threshold` and `labels`).
+    postprocess_labels: None, or a dict of `fetal_net.postprocess.postprocess_label_map` options (may be empty; `threshold` and `labels`
+    above are its defaults): together with output_label_map, prediction_labels.nii.gz is then the cleaned label map of the prediction."""
     from .utils.nifti import save_nifti
     if not os.path.exists(output_dir):
         os.makedirs(output_dir)
@@ -502,7 +504,14 @@ def run_validation_case(data_index, output_dir, model, data_file, training_modal
             channels_first = np.mean(prediction, axis=0)[np.newaxis, np.newaxis]
         else:                                                 # (1, X, Y, Z, C)
             channels_first = np.moveaxis(prediction, -1, 1)
-        label_data = np.asarray(prediction_to_image(channels_first, label_map=True, threshold=threshold, labels=labels)).astype(np.uint8)
+        if postprocess_labels is not None:
+            from .postprocess import postprocess_label_map
+            options = dict(dict(threshold=threshold, labels=labels), **postprocess_labels)
+            label_data = postprocess_label_map(np.ascontiguousarray(np.moveaxis(np.asarray(channels_first, dtype=np.float64)[0], 0, -1)),
+                                               **options)
+        else:
+            label_data = np.asarray(prediction_to_image(channels_first, label_map=True, threshold=threshold,
+                                                        labels=labels)).astype(np.uint8)
         save_nifti(label_data, os.path.join(output_dir, "prediction_labels.nii.gz"))
     prediction = prediction.squeeze()
     filename = os.path.join(output_dir, "prediction.nii.gz")
@@ -512,9 +521,10 @@ def run_validation_case(data_index, output_dir, model, data_file, training_modal
 
 def run_validation_cases(validation_keys_file, model_file, training_modalities, hdf5_file, patch_shape, output_dir=".",
                          overlap_factor=0, permute=False, prev_truth_index=None, prev_truth_size=None, use_augmentations=False,
-                         data_file=None, model=None):
+                         data_file=None, model=None, *, output_label_map=False, threshold=0.5, labels=None, postprocess_labels=None):
     """reference prediction.py:333-351.  `hdf5_file` is opened with `fetal_net.data.open_data_file` (plain-layout files through libhdf5,
-    PyTables files through PyTables when installed); callers may instead pass an already opened duck-typed `data_file` (and a `model`)."""
+    PyTables files through PyTables when installed); callers may instead pass an already opened duck-typed `data_file` (and a `model`).
+    The keyword-only arguments are run_validation_case's and go to every case."""
     import glob
     import pickle
     from .training import load_old_model
@@ -537,7 +547,8 @@ def run_validation_cases(validation_keys_file, model_file, training_modalities, 
         return [run_validation_case(data_index=i, output_dir=case_dir(i), model=model, data_file=data_file,
                                     training_modalities=training_modalities, overlap_factor=overlap_factor, permute=permute,
                                     patch_shape=patch_shape, prev_truth_index=prev_truth_index, prev_truth_size=prev_truth_size,
-                                    use_augmentations=use_augmentations) for i in validation_indices]
+                                    use_augmentations=use_augmentations, output_label_map=output_label_map, threshold=threshold,
+                                    labels=labels, postprocess_labels=postprocess_labels) for i in validation_indices]
     finally:
         if own:
             data_file.close()

@@ -78,6 +78,11 @@ SIGNATURES = {
     "fmri_threshold_f64": [p, p, i64, C.c_double, p],
     "fmri_fill_holes_step": [p, p, p, i32, i32, i32, i32, i32, p, p],
     "fmri_largest_component_step": [p, p, p, p, p, i32, i32, i32, i32, i32, p, p],
+    "fmri_correlate1d_cl_f64": [p, p, i32, i32, i32, i32, i32, p, i32, p],
+    "fmri_threshold_bits_f64": [p, p, i64, i32, C.c_double, p],
+    "fmri_fill_holes_bits_step": [p, p, p, i32, i32, i32, i32, i32, i32, p, p],
+    "fmri_largest_components_bits_step": [p, p, p, p, p, i32, i32, i32, i32, i32, i32, p, p],
+    "fmri_label_map_bits": [p, p, p, i64, i32, p, p],
     "fmri_edt_lds_max_line": [],
     "fmri_edt_u8": [p, p, p, i32, i32, i32, C.c_double, C.c_double, C.c_double, p],
     "fmri_edt_two_class_u8": [p, p, p, i32, i32, i32, C.c_double, C.c_double, C.c_double, p],

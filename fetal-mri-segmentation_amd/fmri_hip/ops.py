@@ -864,6 +864,100 @@ def largest_component_u8(mask):
     return out
 
 
+# ---- the same steps for L <= MAX_LABELS channels at once: the masks of a voxel are the L low bits of one uint32 word (bit l = channel l)
+def _words(words, n_labels):
+    _need_cuda(words)
+    if words.dtype != torch.uint32 or words.dim() != 3 or not 1 <= int(n_labels) <= MAX_LABELS:
+        raise ValueError("mask words: a uint32 volume [X,Y,Z] of 1 to %d channel bits" % MAX_LABELS)
+    return tuple(words.shape) + (int(n_labels),)
+
+
+def gaussian_filter_channels_f64(vol4, sigma, truncate=4.0):
+    """scipy.ndimage.gaussian_filter(vol4[..., l], sigma) for every channel of a channels-last float64 device volume [X,Y,Z,L]: the
+    passes of gaussian_filter_f64 (sigma per spatial axis, an axis whose sigma is ~0 skipped) without splitting the channels apart -
+    bit-identical to the host result per channel"""
+    import numpy as np
+    _need_cuda(vol4)
+    if vol4.dtype != torch.float64 or vol4.dim() != 4 or not 1 <= vol4.shape[3] <= MAX_LABELS:
+        raise ValueError("gaussian_filter_channels_f64: a float64 volume [X,Y,Z,L] with 1 to %d channels" % MAX_LABELS)
+    X, Y, Z, L = vol4.shape
+    sig = [float(sigma)] * 3 if np.isscalar(sigma) else [float(v) for v in sigma]
+    if len(sig) != 3:
+        raise ValueError("gaussian_filter_channels_f64: one sigma, or one per spatial axis")
+    a, b = vol4, None
+    for axis, sd in enumerate(sig):
+        if sd <= 1e-15:
+            continue
+        radius = int(truncate * sd + 0.5)
+        x = np.arange(-radius, radius + 1)
+        phi = np.exp(-0.5 / (sd * sd) * x ** 2)
+        with torch.cuda.device(vol4.device):
+            w = torch.from_numpy(phi / phi.sum()).to(vol4.device)
+            b = torch.empty_like(vol4) if b is None or b is vol4 else b        # two buffers ping-pong; the input is never written
+            check(lib().fmri_correlate1d_cl_f64(_p(a), _p(b), X, Y, Z, L, axis, _p(w), radius, _s()), "fmri_correlate1d_cl_f64")
+        a, b = b, a
+    return a if a is not vol4 else vol4.clone()
+
+
+def threshold_bits_f64(smoothed, thr):
+    """words uint32 [X,Y,Z] of a channels-last float64 device volume [X,Y,Z,L]: bit l = smoothed[..., l] > thr"""
+    _need_cuda(smoothed)
+    if smoothed.dtype != torch.float64 or smoothed.dim() != 4 or not 1 <= smoothed.shape[3] <= MAX_LABELS:
+        raise ValueError("threshold_bits_f64: a float64 volume [X,Y,Z,L] with 1 to %d channels" % MAX_LABELS)
+    words = torch.empty(smoothed.shape[:3], dtype=torch.uint32, device=smoothed.device)
+    with torch.cuda.device(smoothed.device):
+        check(lib().fmri_threshold_bits_f64(_p(smoothed), _p(words), words.numel(), smoothed.shape[3], float(thr), _s()),
+              "fmri_threshold_bits_f64")
+    return words
+
+
+def binary_fill_holes_bits(words, n_labels):
+    """scipy.ndimage.binary_fill_holes of every channel of the mask words at once; bits n_labels..31 come out zero"""
+    X, Y, Z, nl = _words(words, n_labels)
+    reached, out = torch.empty_like(words), torch.empty_like(words)
+    L = lib()
+    with torch.cuda.device(words.device):
+        check(L.fmri_fill_holes_bits_step(_p(words), _p(reached), 0, X, Y, Z, nl, 0, 0, 0, _s()), "fmri_fill_holes_bits_step")
+        _until_stable(lambda k, ch: check(L.fmri_fill_holes_bits_step(_p(words), _p(reached), 0, X, Y, Z, nl, 1, k, _p(ch), _s()),
+                                          "fmri_fill_holes_bits_step"), words.device)
+        check(L.fmri_fill_holes_bits_step(_p(words), _p(reached), _p(out), X, Y, Z, nl, 2, 0, 0, _s()), "fmri_fill_holes_bits_step")
+    return out
+
+
+def largest_components_bits(words, n_labels):
+    """every channel of the mask words reduced to its largest 6-connected component (largest_component_u8 per channel: ties to the
+    component scipy numbers first, an empty channel stays empty); all channels share the sweeps and the convergence flag"""
+    X, Y, Z, nl = _words(words, n_labels)
+    n = words.numel()
+    labels = torch.empty(nl * n, dtype=torch.int32, device=words.device)
+    counts = torch.empty(nl * (n + 1), dtype=torch.int32, device=words.device)
+    best = torch.empty(nl, dtype=torch.int64, device=words.device)
+    out = torch.empty_like(words)
+    L = lib()
+    with torch.cuda.device(words.device):
+        check(L.fmri_largest_components_bits_step(_p(words), _p(labels), 0, 0, 0, X, Y, Z, nl, 0, 0, 0, _s()),
+              "fmri_largest_components_bits_step")
+        _until_stable(lambda k, ch: check(L.fmri_largest_components_bits_step(_p(words), _p(labels), 0, 0, 0, X, Y, Z, nl, 1, k, _p(ch), _s()),
+                                          "fmri_largest_components_bits_step"), words.device, sweeps=8)
+        check(L.fmri_largest_components_bits_step(_p(words), _p(labels), _p(counts), _p(best), _p(out), X, Y, Z, nl, 2, 0, 0, _s()),
+              "fmri_largest_components_bits_step")
+    return out
+
+
+def label_map_from_bits(words, smoothed, values):
+    """uint8 [X,Y,Z]: values[l] of the first channel l among the set bits of a voxel's word with the largest smoothed value, 0 where no
+    bit is set.  smoothed: float64 [X,Y,Z,L], values: L label values (label_values' rule)"""
+    vals = label_values(values)
+    X, Y, Z, nl = _words(words, len(vals))
+    _need_cuda(smoothed)
+    if smoothed.dtype != torch.float64 or tuple(smoothed.shape) != (X, Y, Z, nl) or smoothed.device != words.device:
+        raise ValueError("label_map_from_bits: a float64 volume [X,Y,Z,%d] next to the words, %d label values" % (nl, nl))
+    out = torch.empty(words.shape, dtype=torch.uint8, device=words.device)
+    with torch.cuda.device(words.device):
+        check(lib().fmri_label_map_bits(_p(words), _p(smoothed), _p(out), words.numel(), nl, vals, _s()), "fmri_label_map_bits")
+    return out
+
+
 def _edt_sampling(sampling):
     import numpy as np
     if sampling is None:

@@ -539,6 +539,31 @@ int fmri_fill_holes_step(const uint8_t* mask, uint8_t* reached, uint8_t* out, in
 int fmri_largest_component_step(const uint8_t* mask, int32_t* labels, int32_t* counts, unsigned long long* best, uint8_t* out, int X, int Y,
                                 int Z, int phase, int sweeps, int* changed, fmri_stream_t stream);
 
+/* ---- the same clean-up for L label channels at once (1 <= L <= 32; fetal_net.postprocess.postprocess_label_map).  Probabilities are
+ * channels last, [X][Y][Z][L] fp64; the L masks of a voxel are the L low bits of one uint32 word (bit l = channel l).  Bits L..31 of an
+ * input word are ignored and every output word has them zero.
+ * fmri_correlate1d_cl_f64: fmri_correlate1d_f64 on every channel of a channels-last volume (axis 0, 1, 2 = x, y, z); per channel the
+ *   same sums, so three calls reproduce scipy.ndimage.gaussian_filter of each channel bit for bit.  src != dst, Z * L < 2^31.
+ * fmri_threshold_bits_f64: words[v] bit l = src[v * L + l] > threshold.
+ * fmri_fill_holes_bits_step: fmri_fill_holes_step's phases on words (scipy.ndimage.binary_fill_holes of every channel): phase 0
+ *   reached := ~mask on the volume's border, phase 1 `sweeps` sweeps (*changed as above), phase 2 out := ~reached.  reached: uint32 [X*Y*Z].
+ * fmri_largest_components_bits_step: fmri_largest_component_step's phases, every channel keeping its own largest 6-connected component
+ *   (ties: the component whose first voxel comes first in C order).  One launch per sweep and one *changed for all channels; a channel
+ *   that has converged is left as it is while others still run.  `words` is the same array in all phases and out != words.  labels:
+ *   int32 [L][X*Y*Z] (written and read only where the channel's bit is set), counts: int32 [L][X*Y*Z + 1], best: uint64 [L] - all
+ *   scratch, initialised here where it is read.  X*Y*Z < 2^31 - 1.
+ * fmri_label_map_bits: out[v] (uint8) = values[l*], l* the first channel among the set bits of words[v] with the largest
+ *   smoothed[v * L + l]; 0 when no bit is set.  `values` as for fmri_tile_finalize_labels (L distinct bytes in 1..255, HOST memory). */
+int fmri_correlate1d_cl_f64(const double* src, double* dst, int X, int Y, int Z, int L, int axis, const double* weights, int radius,
+                            fmri_stream_t stream);
+int fmri_threshold_bits_f64(const double* src, uint32_t* words, int64_t n, int L, double threshold, fmri_stream_t stream);
+int fmri_fill_holes_bits_step(const uint32_t* mask, uint32_t* reached, uint32_t* out, int X, int Y, int Z, int L, int phase, int sweeps,
+                              int* changed, fmri_stream_t stream);
+int fmri_largest_components_bits_step(const uint32_t* words, int32_t* labels, int32_t* counts, unsigned long long* best, uint32_t* out, int X,
+                                      int Y, int Z, int L, int phase, int sweeps, int* changed, fmri_stream_t stream);
+int fmri_label_map_bits(const uint32_t* words, const double* smoothed, uint8_t* out, int64_t n, int L, const uint8_t* values,
+                        fmri_stream_t stream);
+
 /* ---- exact Euclidean distance transform of a label volume [X][Y][Z] (uint8, z contiguous) with per-axis voxel spacing, fp64: the distance
  * masks of the mask-weighted loss (reference fetal_net/utils/create_distance_masks.py: scipy.ndimage.distance_transform_edt(mask,
  * sampling) + distance_transform_edt(1 - mask, sampling)).  Separable min-plus passes on squared distances along z, y, x with separately
