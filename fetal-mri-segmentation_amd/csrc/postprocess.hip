@@ -2,7 +2,9 @@
 //   scipy.ndimage.gaussian_filter -> "> threshold" -> binary_fill_holes -> largest connected component (scipy.ndimage.label).
 // The production flow of the reference (prod/predict_nifti2.py:77-95) runs this once per stage on a whole 160x256x256-class volume; with
 // the sliding-window result already in HBM it costs four small HBM-bound passes and two label-propagation loops instead of a download
-// plus ~1 s of single-threaded scipy.  All kernels are byte / index movers: one thread per voxel, z (contiguous) fastest.
+// plus ~1 s of single-threaded scipy.  All kernels are word / index movers: one thread per voxel, z (contiguous) fastest.  There is one
+// chain for any number of label channels, L <= 32: the masks of a voxel are the low bits of one uint32 word (the block after the
+// correlate entry points); a single probability volume is that chain at L = 1.
 //
 // Exactness: the 1-D correlation sums in scipy's own order (centre tap first, then the symmetric pairs from the outermost inwards,
 // ni_filters.c NI_Correlate1D symmetric branch) in fp64 with host-computed weights, so the smoothed volume - and therefore the
@@ -52,103 +54,6 @@ __global__ void k_correlate1d_sym(const T* __restrict__ src, T* __restrict__ dst
     }
 }
 
-__global__ void k_threshold(const double* __restrict__ src, uint8_t* __restrict__ dst, int64_t n, double thr) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i] > thr ? 1 : 0;
-}
-
-// ---- binary_fill_holes = NOT (background reachable from outside the volume, 6-connectivity)
-__global__ void k_flood_init(const uint8_t* __restrict__ mask, uint8_t* __restrict__ reached, int X, int Y, int Z) {
-    const int64_t total = (int64_t)X * Y * Z;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int z = (int)(t % Z);
-        const int64_t q = t / Z;
-        const int y = (int)(q % Y), x = (int)(q / Y);
-        const bool border = x == 0 || y == 0 || z == 0 || x == X - 1 || y == Y - 1 || z == Z - 1;
-        reached[t] = (!mask[t] && border) ? 1 : 0;
-    }
-}
-// one sweep: every unreached background voxel with a reached 6-neighbour becomes reached; then the front runs on along +z / -z inside
-// the thread's own row as far as it can (rows are contiguous: the long axis costs one sweep instead of Z)
-__global__ void k_flood_sweep(const uint8_t* __restrict__ mask, uint8_t* __restrict__ reached, int X, int Y, int Z, int* __restrict__ changed) {
-    const int64_t total = (int64_t)X * Y * Z;
-    bool any = false;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        if (mask[t] || reached[t]) continue;
-        const int z = (int)(t % Z);
-        const int64_t q = t / Z;
-        const int y = (int)(q % Y), x = (int)(q / Y);
-        const int64_t sx = (int64_t)Y * Z;
-        const bool hit = (x > 0 && reached[t - sx]) || (x < X - 1 && reached[t + sx]) || (y > 0 && reached[t - Z]) || (y < Y - 1 && reached[t + Z]) ||
-                         (z > 0 && reached[t - 1]) || (z < Z - 1 && reached[t + 1]);
-        if (!hit) continue;
-        reached[t] = 1;
-        any = true;
-        for (int k = z + 1; k < Z && !mask[t - z + k] && !reached[t - z + k]; ++k) reached[t - z + k] = 1;
-        for (int k = z - 1; k >= 0 && !mask[t - z + k] && !reached[t - z + k]; --k) reached[t - z + k] = 1;
-    }
-    if (any) *changed = 1;
-}
-__global__ void k_fill_from_reached(const uint8_t* __restrict__ reached, uint8_t* __restrict__ out, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = reached[i] ? 0 : 1;
-}
-
-// ---- connected components (6-connectivity) by min-label propagation with root chasing: label = 1 + linear index of the component's
-// first voxel once converged - the order scipy.ndimage.label numbers the components in
-__global__ void k_cc_init(const uint8_t* __restrict__ mask, int32_t* __restrict__ lab, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) lab[i] = mask[i] ? (int32_t)(i + 1) : 0;
-}
-__global__ void k_cc_sweep(int32_t* __restrict__ lab, int X, int Y, int Z, int* __restrict__ changed) {
-    const int64_t total = (int64_t)X * Y * Z;
-    bool any = false;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t mine = lab[t];
-        if (!mine) continue;
-        const int z = (int)(t % Z);
-        const int64_t q = t / Z;
-        const int y = (int)(q % Y), x = (int)(q / Y);
-        const int64_t sx = (int64_t)Y * Z;
-        int32_t m = mine;
-        auto look = [&](int64_t o) { const int32_t v = lab[o]; if (v && v < m) m = v; };
-        if (x > 0) look(t - sx);
-        if (x < X - 1) look(t + sx);
-        if (y > 0) look(t - Z);
-        if (y < Y - 1) look(t + Z);
-        if (z > 0) look(t - 1);
-        if (z < Z - 1) look(t + 1);
-        // chase the chain of representatives: the label of voxel (m - 1) is never larger than m and belongs to the same component
-        for (int hop = 0; hop < 8; ++hop) {
-            const int32_t up = lab[m - 1];
-            if (up == m) break;
-            m = up;
-        }
-        if (m < mine) {
-            atomicMin(&lab[t], m);
-            atomicMin(&lab[mine - 1], m);          // hand the better label to the old representative too (union by smaller index)
-            any = true;
-        }
-    }
-    if (any) *changed = 1;
-}
-__global__ void k_cc_count(const int32_t* __restrict__ lab, int32_t* __restrict__ counts, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        if (lab[i]) atomicAdd(&counts[lab[i]], 1);
-}
-// best = (largest count, smallest label among equals), packed as (count << 32) | (0xffffffff - label) so that one 64-bit max does both
-__global__ void k_cc_best(const int32_t* __restrict__ counts, int64_t n, unsigned long long* __restrict__ best) {
-    unsigned long long mine = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1; i <= n; i += (int64_t)gridDim.x * blockDim.x)
-        if (counts[i] > 0) {
-            const unsigned long long key = ((unsigned long long)(unsigned)counts[i] << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
-            if (key > mine) mine = key;
-        }
-    if (mine) atomicMax(best, mine);
-}
-__global__ void k_cc_select(const int32_t* __restrict__ lab, const unsigned long long* __restrict__ best, uint8_t* __restrict__ out, int64_t n) {
-    const unsigned long long b = *best;
-    const int32_t want = b ? (int32_t)(0xffffffffu - (unsigned)(b & 0xffffffffull)) : -1;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = lab[i] == want ? 1 : 0;
-}
-
 }  // namespace
 
 extern "C" int fmri_correlate1d_f64(const double* src, double* dst, int X, int Y, int Z, int axis, const double* weights, int radius,
@@ -176,75 +81,29 @@ extern "C" int fmri_correlate1d_f32(const float* src, float* dst, int X, int Y, 
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
-extern "C" int fmri_threshold_f64(const double* src, uint8_t* dst, int64_t n, double threshold, fmri_stream_t stream) {
-    if (!src || !dst || n <= 0) return FMRI_E_SHAPE;
-    k_threshold<<<grid_for(n, 256, 8192), 256, 0, as_stream(stream)>>>(src, dst, n, threshold);
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
-}
-// phase 0: reached := background voxels on the volume's border; phase 1: `sweeps` propagation sweeps (sets *changed when a sweep still
-// grew the region - the caller repeats until it stays 0); phase 2: out := NOT reached (the filled mask)
-extern "C" int fmri_fill_holes_step(const uint8_t* mask, uint8_t* reached, uint8_t* out, int X, int Y, int Z, int phase, int sweeps, int* changed,
-                                    fmri_stream_t stream) {
-    if (!mask || !reached || X <= 0 || Y <= 0 || Z <= 0) return FMRI_E_SHAPE;
-    const int64_t n = (int64_t)X * Y * Z;
-    hipStream_t st = as_stream(stream);
-    const int grid = grid_for(n, 256, 8192);
-    if (phase == 0) k_flood_init<<<grid, 256, 0, st>>>(mask, reached, X, Y, Z);
-    else if (phase == 1) {
-        if (!changed) return FMRI_E_SHAPE;
-        for (int i = 0; i < sweeps; ++i) k_flood_sweep<<<grid, 256, 0, st>>>(mask, reached, X, Y, Z, changed);
-    } else {
-        if (!out) return FMRI_E_SHAPE;
-        k_fill_from_reached<<<grid, 256, 0, st>>>(reached, out, n);
-    }
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
-}
-// phase 0: labels := 1 + linear index on the foreground; phase 1: `sweeps` propagation sweeps (*changed as above); phase 2: out := the
-// largest component (counts: int32 [n + 1] scratch, best: uint64 scratch - both zeroed here)
-extern "C" int fmri_largest_component_step(const uint8_t* mask, int32_t* labels, int32_t* counts, unsigned long long* best, uint8_t* out, int X,
-                                           int Y, int Z, int phase, int sweeps, int* changed, fmri_stream_t stream) {
-    if (!labels || X <= 0 || Y <= 0 || Z <= 0) return FMRI_E_SHAPE;
-    const int64_t n = (int64_t)X * Y * Z;
-    if (n >= 0x7fffffff) return FMRI_E_SHAPE;
-    hipStream_t st = as_stream(stream);
-    const int grid = grid_for(n, 256, 8192);
-    if (phase == 0) {
-        if (!mask) return FMRI_E_SHAPE;
-        k_cc_init<<<grid, 256, 0, st>>>(mask, labels, n);
-    } else if (phase == 1) {
-        if (!changed) return FMRI_E_SHAPE;
-        for (int i = 0; i < sweeps; ++i) k_cc_sweep<<<grid, 256, 0, st>>>(labels, X, Y, Z, changed);
-    } else {
-        if (!counts || !best || !out) return FMRI_E_SHAPE;
-        if (hipMemsetAsync(counts, 0, (size_t)(n + 1) * sizeof(int32_t), st) != hipSuccess) return FMRI_E_LAUNCH;
-        if (hipMemsetAsync(best, 0, sizeof(unsigned long long), st) != hipSuccess) return FMRI_E_LAUNCH;
-        k_cc_count<<<grid, 256, 0, st>>>(labels, counts, n);
-        k_cc_best<<<grid, 256, 0, st>>>(counts, n, best);
-        k_cc_select<<<grid, 256, 0, st>>>(labels, best, out, n);
-    }
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-// The same clean-up for L <= 32 label channels in one pass (fetal_net.postprocess.postprocess_label_map).  The probabilities come
-// channels last, [X][Y][Z][L] fp64, as the tile loop leaves them.  After smoothing and "> threshold" the L masks of a voxel are the L low
-// bits of one uint32 word, and every later stage works on words:
+// The clean-up for L <= 32 label channels in one pass (fetal_net.postprocess: postprocess_label_map, and postprocess_prediction at
+// L = 1).  The probabilities come channels last, [X][Y][Z][L] fp64, as the tile loop leaves them.  After smoothing and "> threshold" the
+// L masks of a voxel are the L low bits of one uint32 word, and every later stage works on words:
 //   smoothing    k_correlate1d_sym<.., CL>: axes 0 and 1 see rows of Z * L elements, axis 2 an element stride of L - per channel the sums
-//                of the single-label kernel, bit for bit
+//                of the plain [X][Y][Z] instantiation, bit for bit
 //   threshold    a workgroup reads the 256 * L doubles of 256 voxels with coalesced loads and ORs the bits together in LDS
-//   fill holes   reached' = reached | (OR of the six neighbours' reached words & ~mask), started from ~mask on the volume's border: the
-//                flood of all channels' backgrounds at once, word-wide.  As in k_flood_sweep the front runs on along the contiguous z row.
-//                Several threads may add bits to one word in the same sweep, so every update is an atomicOr.  `valid` (the L low bits)
-//                keeps the unused bits from ever counting as background.
-//   components   int32 labels [L][n], channel-major: label 1 + voxel index inside its channel, scipy's numbering order per channel.
-//                One thread per voxel walks the set bits of its word (k_cc_sweep's min-label propagation with root chasing per bit), one
-//                launch per sweep and one `changed` flag for all channels; a converged channel finds nothing to lower and stays as it is.
-//                Labels are written and read only where the channel's bit is set - a neighbour's bit is looked up in its word - so
-//                nothing of the L * n array is initialised or read for background, and counts / best are zeroed and read only at the
-//                roots (label == own index + 1).  The count adds the lanes of a wave that share a destination as one atomic.
+//   fill holes   binary_fill_holes = NOT (background reachable from outside the volume, 6-connectivity), as a flood of all channels'
+//                backgrounds at once, word-wide: reached' = reached | (OR of the six neighbours' reached words & ~mask), started from
+//                ~mask on the volume's border.  A voxel that takes new bits then carries them on along +z / -z inside its own row as far
+//                as they go (rows are contiguous: the long axis costs one sweep instead of Z).  Several threads may add bits to one word
+//                in the same sweep, so every update is an atomicOr.  `valid` (the L low bits) keeps the unused bits from ever counting
+//                as background.
+//   components   6-connected components by min-label propagation with root chasing.  int32 labels [L][n], channel-major: a voxel starts
+//                with 1 + its index inside the channel and takes the smallest label among its neighbours of the same channel, so a
+//                converged component carries 1 + the index of its first voxel - the order scipy.ndimage.label numbers the components
+//                in.  One thread per voxel walks the set bits of its word, one launch per sweep and one `changed` flag for all
+//                channels; a converged channel finds nothing to lower and stays as it is.  Labels are written and read only where the
+//                channel's bit is set - a neighbour's bit is looked up in its word - so nothing of the L * n array is initialised or
+//                read for background, and counts / best are zeroed and read only at the roots (label == own index + 1).  The count adds
+//                the lanes of a wave that share a destination as one atomic; the largest component of a channel is one 64-bit max
+//                over the keys (count << 32) | ~label of its roots: largest count, smallest label among equals.
 //   combine      a voxel reads its word and, only for the set bits, the smoothed values: values[first argmax] or 0, one byte out
 // Scratch of the whole chain at n voxels: 2 * L * n doubles (the smoothed volume and the other buffer of the passes), two uint32 [n]
 // (mask / result words and `reached`), int32 [L * n] labels, int32 [L * (n + 1)] counts, uint64 [L] best.
@@ -265,6 +124,7 @@ __global__ __launch_bounds__(256) void k_threshold_bits(const double* __restrict
     }
 }
 
+// reached := the background bits of the words on the volume's border
 __global__ void k_flood_bits_init(const uint32_t* __restrict__ mask, uint32_t* __restrict__ reached, int X, int Y, int Z, uint32_t valid) {
     const int64_t total = (int64_t)X * Y * Z;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
@@ -275,6 +135,7 @@ __global__ void k_flood_bits_init(const uint32_t* __restrict__ mask, uint32_t* _
         reached[t] = border ? ~mask[t] & valid : 0u;
     }
 }
+// one sweep: every background bit not reached yet with a reached 6-neighbour becomes reached; then the front runs on along the z row
 __global__ void k_flood_bits_sweep(const uint32_t* __restrict__ mask, uint32_t* reached, int X, int Y, int Z, uint32_t valid,
                                    int* __restrict__ changed) {
     const int64_t total = (int64_t)X * Y * Z;
@@ -349,8 +210,9 @@ __global__ void k_ccb_sweep(const uint32_t* __restrict__ words, int32_t* lab, in
             look(w3, t + Z);
             look(w4, t - 1);
             look(w5, t + 1);
-            // k_cc_sweep's chase; a label is always 1 + the index of a voxel of the same component, the range test only keeps a caller's
-            // mismatched words / labels inside the array
+            // chase the chain of representatives: the label of voxel (m - 1) is never larger than m and belongs to the same component.
+            // A label is always 1 + the index of a voxel of the same component, the range test only keeps a caller's mismatched
+            // words / labels inside the array
             for (int hop = 0; hop < 8 && (uint32_t)(m - 1) < (uint32_t)total; ++hop) {
                 const int32_t up = lb[m - 1];
                 if (up >= m) break;
@@ -358,7 +220,7 @@ __global__ void k_ccb_sweep(const uint32_t* __restrict__ words, int32_t* lab, in
             }
             if (m < mine && (uint32_t)(mine - 1) < (uint32_t)total && m > 0) {
                 atomicMin(&lb[t], m);
-                atomicMin(&lb[mine - 1], m);
+                atomicMin(&lb[mine - 1], m);          // hand the better label to the old representative too (union by smaller index)
                 any = true;
             }
         }
@@ -392,7 +254,8 @@ __global__ void k_ccb_count(const uint32_t* __restrict__ words, const int32_t* _
             else if (lane == __ffsll((long long)same) - 1) atomicAdd(&counts[(int64_t)l * (n + 1) + v], (int32_t)__popcll(same));
         }
 }
-// k_cc_best's key per channel: (count << 32) | ~label - largest count, first in scan order among equals
+// best[l] = (largest count, smallest label among equals) over channel l's roots, packed as (count << 32) | (0xffffffff - label) so that
+// one 64-bit max does both
 __global__ void k_ccb_best(const uint32_t* __restrict__ words, const int32_t* __restrict__ lab, const int32_t* __restrict__ counts,
                            unsigned long long* __restrict__ best, int64_t n, uint32_t valid) {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
@@ -459,7 +322,9 @@ extern "C" int fmri_threshold_bits_f64(const double* src, uint32_t* words, int64
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
-// fmri_fill_holes_step on words: bit l of a word is channel l's mask, bits L..31 of the input are ignored and come out zero
+// bit l of a word is channel l's mask, bits L..31 of the input are ignored and come out zero.  phase 0: reached := background bits on the
+// volume's border; phase 1: `sweeps` propagation sweeps (sets *changed when a sweep still grew the region - the caller repeats until it
+// stays 0); phase 2: out := NOT reached (the filled masks)
 extern "C" int fmri_fill_holes_bits_step(const uint32_t* mask, uint32_t* reached, uint32_t* out, int X, int Y, int Z, int L, int phase,
                                          int sweeps, int* changed, fmri_stream_t stream) {
     if (!mask || !reached || X <= 0 || Y <= 0 || Z <= 0 || L < 1 || L > FMRI_MAX_LABELS) return FMRI_E_SHAPE;
@@ -478,7 +343,9 @@ extern "C" int fmri_fill_holes_bits_step(const uint32_t* mask, uint32_t* reached
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
-// fmri_largest_component_step on words; `words` is the same array in all three phases (it says where `labels` holds a label)
+// phase 0: labels := 1 + voxel index where a channel's bit is set; phase 1: `sweeps` propagation sweeps (*changed as above); phase 2:
+// out := every channel's largest component (counts: int32 [L][n + 1] scratch, best: uint64 [L] scratch - zeroed here where they are
+// read).  `words` is the same array in all three phases (it says where `labels` holds a label)
 extern "C" int fmri_largest_components_bits_step(const uint32_t* words, int32_t* labels, int32_t* counts, unsigned long long* best,
                                                  uint32_t* out, int X, int Y, int Z, int L, int phase, int sweeps, int* changed,
                                                  fmri_stream_t stream) {

@@ -1,16 +1,16 @@
 """Binary clean-up of a probability volume (same entry points and defaults as reference fetal_net/postprocess.py:7-19): gaussian
 smoothing, threshold, hole filling, largest connected component.
 
-Two implementations of the same definition: scipy.ndimage on the host (what the reference runs), and - when a GPU and the HIP library are
-there and the input is a float64 3-D volume, i.e. the output of `patch_wise_prediction` - the device kernels of csrc/postprocess.hip
-(`fmri_correlate1d_f64`, `fmri_threshold_f64`, `fmri_fill_holes_step`, `fmri_largest_component_step`): the gaussian sums in scipy's own
-order in fp64, so the two produce the same mask voxel for voxel (tests/test_gpu_postprocess.py).  `device=` forces one or the other.
+`postprocess_prediction` cleans one volume into a boolean mask.  `postprocess_label_map` cleans every channel of a channels-last
+prediction (X, Y, Z, L) by the same four steps and merges the cleaned masks into one uint8 label map.
 
-Several labels: `postprocess_label_map` cleans every channel of a channels-last prediction (X, Y, Z, L) by the same four steps and
-merges the cleaned masks into one uint8 label map.  Its host form is the definition (scipy per channel, numpy for the merge); its device
-form packs the L masks of a voxel into one uint32 word and runs hole filling and the component search on all channels at once
-(`fmri_correlate1d_cl_f64`, `fmri_threshold_bits_f64`, `fmri_fill_holes_bits_step`, `fmri_largest_components_bits_step`,
-`fmri_label_map_bits`) and returns the same bytes (tests/test_gpu_postprocess_labels.py)."""
+The host form of both is the definition: scipy.ndimage per channel (what the reference runs), numpy for the merge.  When a GPU and the
+HIP library are there and the input is float64, i.e. the output of `patch_wise_prediction`, both run the one device implementation of
+csrc/postprocess.hip instead: the L masks of a voxel are the low bits of one uint32 word, and hole filling and the component search
+work on all channels at once (`fmri_correlate1d_cl_f64`, `fmri_threshold_bits_f64`, `fmri_fill_holes_bits_step`,
+`fmri_largest_components_bits_step`, `fmri_label_map_bits`); a single volume is that chain at L = 1.  The gaussian sums in scipy's own
+order in fp64, the rest is integer work, so host and device produce the same mask voxel for voxel and the same label bytes
+(tests/test_gpu_postprocess.py, tests/test_gpu_postprocess_labels.py).  `device=` forces one or the other."""
 import numpy as np
 from scipy import ndimage
 
@@ -43,7 +43,7 @@ def postprocess_prediction(pred, gaussian_std=1, threshold=0.5, fill_holes=True,
     if device is None:
         device = _device_ok(pred)
     if device:
-        return _postprocess_on_device(pred, gaussian_std, threshold, fill_holes, connected_component)
+        return _label_map_on_device(pred, 1, gaussian_std, threshold, fill_holes, connected_component, [1], False) != 0
     mask = ndimage.gaussian_filter(pred, gaussian_std) > threshold
     steps = []
     if fill_holes:
@@ -53,18 +53,6 @@ def postprocess_prediction(pred, gaussian_std=1, threshold=0.5, fill_holes=True,
     for step in steps:
         mask = step(mask)
     return mask
-
-
-def _postprocess_on_device(pred, gaussian_std, threshold, fill_holes, connected_component):
-    import torch
-    from fmri_hip import ops
-    vol = pred if isinstance(pred, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float64)).cuda()
-    mask = ops.threshold_f64(ops.gaussian_filter_f64(vol, gaussian_std), threshold)
-    if fill_holes:
-        mask = ops.binary_fill_holes_u8(mask)
-    if connected_component:
-        mask = ops.largest_component_u8(mask)
-    return mask.cpu().numpy().astype(bool)
 
 
 MAX_LABELS = 32          # fmri_hip.ops.MAX_LABELS: the channels of a voxel are the bits of one word

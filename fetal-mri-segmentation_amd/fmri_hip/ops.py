@@ -785,6 +785,24 @@ def border_class_sums(dy, out27):
 
 
 # ---------------------------------------------------------------------------------------------------- post-processing (fetal_net.postprocess)
+def _gaussian_passes(vol, sig, truncate, launch):
+    """the separable passes of scipy.ndimage.gaussian_filter (order 0) over the axes of `sig`: an axis whose sigma is ~0 is skipped as
+    scipy skips it, any other gets scipy's normalised weights of radius int(truncate * sd + 0.5) on the device and one
+    `launch(src, dst, axis, weights, radius)`.  Two buffers ping-pong and `vol` is never written; returns the last destination, or `vol`
+    itself when every axis was skipped"""
+    a, b = vol, None
+    with torch.cuda.device(vol.device):                       # a volume on a non-current GPU: its device's stream, its device's weights
+        for axis, sd in enumerate(sig):
+            if sd <= 1e-15:
+                continue
+            radius = int(truncate * sd + 0.5)
+            w = torch.from_numpy(gaussian_kernel1d(sd, 0, radius)).to(vol.device)
+            b = torch.empty_like(vol) if b is None or b is vol else b
+            launch(a, b, axis, w, radius)
+            a, b = b, a
+    return a
+
+
 def gaussian_filter_f64(vol, sigma, truncate=4.0):
     """scipy.ndimage.gaussian_filter(vol, sigma) (order 0, mode 'reflect') of a float64 device volume [X,Y,Z]: three separable passes with
     scipy's own weights and summation order - bit-identical to the host result"""
@@ -793,27 +811,9 @@ def gaussian_filter_f64(vol, sigma, truncate=4.0):
     assert vol.dtype == torch.float64 and vol.dim() == 3
     X, Y, Z = vol.shape
     sig = [float(sigma)] * 3 if np.isscalar(sigma) else [float(v) for v in sigma]
-    a, b = vol, None
-    for axis, sd in enumerate(sig):
-        if sd <= 1e-15:                                       # scipy skips an axis whose sigma is ~0
-            continue
-        radius = int(truncate * sd + 0.5)
-        x = np.arange(-radius, radius + 1)
-        phi = np.exp(-0.5 / (sd * sd) * x ** 2)               # scipy.ndimage._filters._gaussian_kernel1d, order 0
-        with torch.cuda.device(vol.device):                   # a volume on a non-current GPU: its device's stream, its device's weights
-            w = torch.from_numpy(phi / phi.sum()).to(vol.device)
-            b = torch.empty_like(vol)
-            check(lib().fmri_correlate1d_f64(_p(a), _p(b), X, Y, Z, axis, _p(w), radius, _s()), "fmri_correlate1d_f64")
-        a = b
-    return a if a is not vol else vol.clone()
-
-
-def threshold_f64(vol, thr):
-    _need_cuda(vol)
-    out = torch.empty(vol.shape, dtype=torch.uint8, device=vol.device)
-    with torch.cuda.device(vol.device):
-        check(lib().fmri_threshold_f64(_p(vol), _p(out), vol.numel(), float(thr), _s()), "fmri_threshold_f64")
-    return out
+    out = _gaussian_passes(vol, sig, truncate, lambda a, b, axis, w, radius: check(
+        lib().fmri_correlate1d_f64(_p(a), _p(b), X, Y, Z, axis, _p(w), radius, _s()), "fmri_correlate1d_f64"))
+    return out if out is not vol else vol.clone()
 
 
 def _until_stable(step, device, sweeps=16, limit=100000):
@@ -830,41 +830,8 @@ def _until_stable(step, device, sweeps=16, limit=100000):
     raise RuntimeError("label propagation did not converge")
 
 
-def binary_fill_holes_u8(mask):
-    """scipy.ndimage.binary_fill_holes (default 6-connectivity) of a uint8 0/1 device volume"""
-    _need_cuda(mask)
-    assert mask.dtype == torch.uint8 and mask.dim() == 3
-    X, Y, Z = mask.shape
-    reached, out = torch.empty_like(mask), torch.empty_like(mask)
-    L = lib()
-    with torch.cuda.device(mask.device):
-        check(L.fmri_fill_holes_step(_p(mask), _p(reached), 0, X, Y, Z, 0, 0, 0, _s()), "fmri_fill_holes_step")
-        _until_stable(lambda n, ch: check(L.fmri_fill_holes_step(_p(mask), _p(reached), 0, X, Y, Z, 1, n, _p(ch), _s()), "fmri_fill_holes_step"),
-                      mask.device)
-        check(L.fmri_fill_holes_step(_p(mask), _p(reached), _p(out), X, Y, Z, 2, 0, 0, _s()), "fmri_fill_holes_step")
-    return out
-
-
-def largest_component_u8(mask):
-    """mask of the largest 6-connected component (scipy.ndimage.label + argmax of the sizes; all zero when there is no foreground)"""
-    _need_cuda(mask)
-    assert mask.dtype == torch.uint8 and mask.dim() == 3
-    X, Y, Z = mask.shape
-    n = mask.numel()
-    labels = torch.empty(n, dtype=torch.int32, device=mask.device)
-    counts = torch.empty(n + 1, dtype=torch.int32, device=mask.device)
-    best = torch.empty(1, dtype=torch.int64, device=mask.device)
-    out = torch.empty_like(mask)
-    L = lib()
-    with torch.cuda.device(mask.device):
-        check(L.fmri_largest_component_step(_p(mask), _p(labels), 0, 0, 0, X, Y, Z, 0, 0, 0, _s()), "fmri_largest_component_step")
-        _until_stable(lambda k, ch: check(L.fmri_largest_component_step(0, _p(labels), 0, 0, 0, X, Y, Z, 1, k, _p(ch), _s()),
-                                          "fmri_largest_component_step"), mask.device, sweeps=8)
-        check(L.fmri_largest_component_step(0, _p(labels), _p(counts), _p(best), _p(out), X, Y, Z, 2, 0, 0, _s()), "fmri_largest_component_step")
-    return out
-
-
-# ---- the same steps for L <= MAX_LABELS channels at once: the masks of a voxel are the L low bits of one uint32 word (bit l = channel l)
+# ---- threshold, hole filling and the largest component for L <= MAX_LABELS channels at once: the masks of a voxel are the L low bits of
+# one uint32 word (bit l = channel l); a single mask is L = 1
 def _words(words, n_labels):
     _need_cuda(words)
     if words.dtype != torch.uint32 or words.dim() != 3 or not 1 <= int(n_labels) <= MAX_LABELS:
@@ -884,19 +851,9 @@ def gaussian_filter_channels_f64(vol4, sigma, truncate=4.0):
     sig = [float(sigma)] * 3 if np.isscalar(sigma) else [float(v) for v in sigma]
     if len(sig) != 3:
         raise ValueError("gaussian_filter_channels_f64: one sigma, or one per spatial axis")
-    a, b = vol4, None
-    for axis, sd in enumerate(sig):
-        if sd <= 1e-15:
-            continue
-        radius = int(truncate * sd + 0.5)
-        x = np.arange(-radius, radius + 1)
-        phi = np.exp(-0.5 / (sd * sd) * x ** 2)
-        with torch.cuda.device(vol4.device):
-            w = torch.from_numpy(phi / phi.sum()).to(vol4.device)
-            b = torch.empty_like(vol4) if b is None or b is vol4 else b        # two buffers ping-pong; the input is never written
-            check(lib().fmri_correlate1d_cl_f64(_p(a), _p(b), X, Y, Z, L, axis, _p(w), radius, _s()), "fmri_correlate1d_cl_f64")
-        a, b = b, a
-    return a if a is not vol4 else vol4.clone()
+    out = _gaussian_passes(vol4, sig, truncate, lambda a, b, axis, w, radius: check(
+        lib().fmri_correlate1d_cl_f64(_p(a), _p(b), X, Y, Z, L, axis, _p(w), radius, _s()), "fmri_correlate1d_cl_f64"))
+    return out if out is not vol4 else vol4.clone()
 
 
 def threshold_bits_f64(smoothed, thr):
@@ -912,7 +869,8 @@ def threshold_bits_f64(smoothed, thr):
 
 
 def binary_fill_holes_bits(words, n_labels):
-    """scipy.ndimage.binary_fill_holes of every channel of the mask words at once; bits n_labels..31 come out zero"""
+    """scipy.ndimage.binary_fill_holes (default 6-connectivity) of every channel of the mask words at once; bits n_labels..31 come out
+    zero"""
     X, Y, Z, nl = _words(words, n_labels)
     reached, out = torch.empty_like(words), torch.empty_like(words)
     L = lib()
@@ -925,8 +883,9 @@ def binary_fill_holes_bits(words, n_labels):
 
 
 def largest_components_bits(words, n_labels):
-    """every channel of the mask words reduced to its largest 6-connected component (largest_component_u8 per channel: ties to the
-    component scipy numbers first, an empty channel stays empty); all channels share the sweeps and the convergence flag"""
+    """every channel of the mask words reduced to its largest 6-connected component (scipy.ndimage.label + argmax of the sizes per
+    channel: ties to the component scipy numbers first, an empty channel stays empty); all channels share the sweeps and the convergence
+    flag; bits n_labels..31 come out zero"""
     X, Y, Z, nl = _words(words, n_labels)
     n = words.numel()
     labels = torch.empty(nl * n, dtype=torch.int32, device=words.device)
@@ -1537,18 +1496,8 @@ def gaussian_filter_f32(patch, sigma, truncate=4.0, mode="nearest"):
     else:                                                 # one sigma per axis (0: the axis is left alone)
         sig = [float(v) for v in sigma]
         assert len(sig) == 3
-    a = patch
-    for axis, sd in enumerate(sig):
-        if sd <= 1e-15:
-            continue
-        radius = int(truncate * sd + 0.5)
-        x = np.arange(-radius, radius + 1)
-        phi = np.exp(-0.5 / (sd * sd) * x ** 2)
-        w = torch.from_numpy(phi / phi.sum()).to(patch.device)
-        b = torch.empty_like(patch)
-        check(lib().fmri_correlate1d_f32(_p(a), _p(b), X, Y, Z, axis, _p(w), radius, 1 if mode == "nearest" else 0, _s()), "fmri_correlate1d_f32")
-        a = b
-    return a
+    return _gaussian_passes(patch, sig, truncate, lambda a, b, axis, w, radius: check(
+        lib().fmri_correlate1d_f32(_p(a), _p(b), X, Y, Z, axis, _p(w), radius, 1 if mode == "nearest" else 0, _s()), "fmri_correlate1d_f32"))
 
 
 def elastic_ksize(sigma):

@@ -523,35 +523,29 @@ int fmri_correlate1d_f32(const float* src, float* dst, int X, int Y, int Z, int 
 /* ---- plumbing: dtype casts used around the boundary (fp32 <-> bf16), n elements */
 int fmri_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, fmri_stream_t stream);
 
-/* ---- post-processing of a predicted probability volume [X][Y][Z] (reference fetal_net/postprocess.py:7-19, used by
+/* ---- post-processing of a predicted probability volume (reference fetal_net/postprocess.py:7-19, used by
  * prod/predict_nifti2.py:77-95): scipy.ndimage.gaussian_filter -> "> threshold" -> binary_fill_holes -> largest connected component.
- * fmri_correlate1d_f64: one axis of the separable gaussian, mode 'reflect', weights [2*radius+1] fp64 on the device (the caller computes
- *   them as scipy does); sums in scipy's order, so three calls (axis 0, 1, 2) reproduce gaussian_filter bit for bit.  src != dst.
- * fmri_fill_holes_step / fmri_largest_component_step: phase 0 = initialise, phase 1 = `sweeps` propagation sweeps (6-connectivity;
- *   *changed, a device int the caller zeroes, is set while the region still grows: repeat phase 1 until it stays 0), phase 2 = write the
- *   result mask (uint8 0/1).  Largest component: ties go to the component whose first voxel comes first in C order (scipy's numbering);
- *   counts = int32 [X*Y*Z + 1] scratch, best = 8-byte scratch. */
+ * fmri_correlate1d_f64: one axis of the separable gaussian on a volume [X][Y][Z], mode 'reflect', weights [2*radius+1] fp64 on the device
+ *   (the caller computes them as scipy does); sums in scipy's order, so three calls (axis 0, 1, 2) reproduce gaussian_filter bit for bit.
+ *   src != dst. */
 int fmri_correlate1d_f64(const double* src, double* dst, int X, int Y, int Z, int axis, const double* weights, int radius,
                          fmri_stream_t stream);
-int fmri_threshold_f64(const double* src, uint8_t* dst, int64_t n, double threshold, fmri_stream_t stream);
-int fmri_fill_holes_step(const uint8_t* mask, uint8_t* reached, uint8_t* out, int X, int Y, int Z, int phase, int sweeps, int* changed,
-                         fmri_stream_t stream);
-int fmri_largest_component_step(const uint8_t* mask, int32_t* labels, int32_t* counts, unsigned long long* best, uint8_t* out, int X, int Y,
-                                int Z, int phase, int sweeps, int* changed, fmri_stream_t stream);
 
-/* ---- the same clean-up for L label channels at once (1 <= L <= 32; fetal_net.postprocess.postprocess_label_map).  Probabilities are
- * channels last, [X][Y][Z][L] fp64; the L masks of a voxel are the L low bits of one uint32 word (bit l = channel l).  Bits L..31 of an
- * input word are ignored and every output word has them zero.
+/* ---- the clean-up itself, for L label channels at once (1 <= L <= 32; fetal_net.postprocess: postprocess_label_map, and
+ * postprocess_prediction at L = 1).  Probabilities are channels last, [X][Y][Z][L] fp64; the L masks of a voxel are the L low bits of one
+ * uint32 word (bit l = channel l).  Bits L..31 of an input word are ignored and every output word has them zero.
  * fmri_correlate1d_cl_f64: fmri_correlate1d_f64 on every channel of a channels-last volume (axis 0, 1, 2 = x, y, z); per channel the
  *   same sums, so three calls reproduce scipy.ndimage.gaussian_filter of each channel bit for bit.  src != dst, Z * L < 2^31.
  * fmri_threshold_bits_f64: words[v] bit l = src[v * L + l] > threshold.
- * fmri_fill_holes_bits_step: fmri_fill_holes_step's phases on words (scipy.ndimage.binary_fill_holes of every channel): phase 0
- *   reached := ~mask on the volume's border, phase 1 `sweeps` sweeps (*changed as above), phase 2 out := ~reached.  reached: uint32 [X*Y*Z].
- * fmri_largest_components_bits_step: fmri_largest_component_step's phases, every channel keeping its own largest 6-connected component
- *   (ties: the component whose first voxel comes first in C order).  One launch per sweep and one *changed for all channels; a channel
- *   that has converged is left as it is while others still run.  `words` is the same array in all phases and out != words.  labels:
- *   int32 [L][X*Y*Z] (written and read only where the channel's bit is set), counts: int32 [L][X*Y*Z + 1], best: uint64 [L] - all
- *   scratch, initialised here where it is read.  X*Y*Z < 2^31 - 1.
+ * fmri_fill_holes_bits_step: scipy.ndimage.binary_fill_holes of every channel (6-connectivity): phase 0 reached := ~mask on the volume's
+ *   border, phase 1 `sweeps` propagation sweeps (*changed, a device int the caller zeroes, is set while the region still grows: repeat
+ *   phase 1 until it stays 0), phase 2 out := ~reached.  reached: uint32 [X*Y*Z].
+ * fmri_largest_components_bits_step: every channel keeps its own largest 6-connected component (ties: the component whose first voxel
+ *   comes first in C order, scipy's numbering).  phase 0 = initialise the labels, phase 1 = `sweeps` propagation sweeps (*changed as
+ *   above), phase 2 = write the result words.  One launch per sweep and one *changed for all channels; a channel that has converged is
+ *   left as it is while others still run.  `words` is the same array in all phases and out != words.  labels: int32 [L][X*Y*Z] (written
+ *   and read only where the channel's bit is set), counts: int32 [L][X*Y*Z + 1], best: uint64 [L] - all scratch, initialised here where
+ *   it is read.  X*Y*Z < 2^31 - 1.
  * fmri_label_map_bits: out[v] (uint8) = values[l*], l* the first channel among the set bits of words[v] with the largest
  *   smoothed[v * L + l]; 0 when no bit is set.  `values` as for fmri_tile_finalize_labels (L distinct bytes in 1..255, HOST memory). */
 int fmri_correlate1d_cl_f64(const double* src, double* dst, int X, int Y, int Z, int L, int axis, const double* weights, int radius,

@@ -26,20 +26,30 @@ def test_gaussian_filter_bit_exact(shape):
         assert np.array_equal(got, ref), (shape, sigma, float(np.abs(got - ref).max()))
 
 
+def _fill_holes(mask):
+    """ops.binary_fill_holes_bits at one label on a 0/1 uint8 volume: packed with numpy, bit 0 unpacked, bits 1..31 must be zero"""
+    from fmri_hip import ops
+    words = ops.binary_fill_holes_bits(torch.from_numpy(mask.astype(np.uint32)).cuda(), 1).cpu().numpy()
+    assert not (words >> 1).any()
+    return (words & 1).astype(bool)
+
+
+def _largest_component(mask):
+    from fmri_hip import ops
+    words = ops.largest_components_bits(torch.from_numpy(mask.astype(np.uint32)).cuda(), 1).cpu().numpy()
+    assert not (words >> 1).any()
+    return (words & 1).astype(bool)
+
+
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
 def test_fill_holes_and_largest_component_equal_scipy(seed):
-    from fmri_hip import ops
     from fetal_net.postprocess import get_main_connected_component
     m = _blobs((48, 56, 40), seed)
-    md = torch.from_numpy(m).cuda()
-    filled = ops.binary_fill_holes_u8(md).cpu().numpy().astype(bool)
-    assert np.array_equal(filled, ndimage.binary_fill_holes(m))
-    big = ops.largest_component_u8(md).cpu().numpy().astype(bool)
-    assert np.array_equal(big, get_main_connected_component(m))
+    assert np.array_equal(_fill_holes(m), ndimage.binary_fill_holes(m))
+    assert np.array_equal(_largest_component(m), get_main_connected_component(m))
 
 
 def test_edge_cases():
-    from fmri_hip import ops
     from fetal_net.postprocess import get_main_connected_component
     shape = (20, 24, 28)
     m = np.zeros(shape, np.uint8)
@@ -49,19 +59,18 @@ def test_edge_cases():
     m[4:16, 10:12, 0:8] = 1                       # an arm to the border
     m[10, 11, 0:12] = 0                           # a tunnel from the border into the hole: not a hole any more
     for vol in (m, np.zeros(shape, np.uint8), np.ones(shape, np.uint8)):
-        d = torch.from_numpy(vol).cuda()
-        assert np.array_equal(ops.binary_fill_holes_u8(d).cpu().numpy().astype(bool), ndimage.binary_fill_holes(vol))
-        assert np.array_equal(ops.largest_component_u8(d).cpu().numpy().astype(bool), get_main_connected_component(vol))
+        assert np.array_equal(_fill_holes(vol), ndimage.binary_fill_holes(vol))
+        assert np.array_equal(_largest_component(vol), get_main_connected_component(vol))
     t = np.zeros(shape, np.uint8)                 # three components of 8 voxels each: scipy's argmax takes the first in scan order
     t[10:12, 10:12, 20:22] = 1
     t[2:4, 2:4, 2:4] = 1
     t[15:17, 3:5, 7:9] = 1
-    got = ops.largest_component_u8(torch.from_numpy(t).cuda()).cpu().numpy().astype(bool)
+    got = _largest_component(t)
     assert np.array_equal(got, get_main_connected_component(t)) and got[2, 2, 2] and got.sum() == 8
     s = np.zeros((9, 40, 40), np.uint8)           # a long snake: many propagation steps
     s[4, 2:38:4, 2:38] = 1
     s[4, 2:38, 2] = 1
-    assert np.array_equal(ops.largest_component_u8(torch.from_numpy(s).cuda()).cpu().numpy().astype(bool), get_main_connected_component(s))
+    assert np.array_equal(_largest_component(s), get_main_connected_component(s))
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(gaussian_std=0.5), dict(fill_holes=False), dict(connected_component=False, threshold=0.4)])
@@ -77,3 +86,20 @@ def test_postprocess_prediction_device_equals_host(kw):
     assert dev.dtype == bool and dev.shape == host.shape
     assert np.array_equal(dev, host)
     assert np.array_equal(postprocess_prediction(p, **kw), host)          # the default picks the device path here and agrees
+
+
+def test_single_volume_is_the_label_chain_at_one_label():
+    """one channel of the smallest field of tests/test_gpu_postprocess_labels.py (its CASES[0]: 17x33x9, 5 channels, seed 0): the mask of
+    postprocess_prediction is where postprocess_label_map puts its one label, and both device forms equal the host"""
+    from fetal_net.postprocess import postprocess_label_map, postprocess_prediction
+    rs = np.random.RandomState(0)
+    field = np.stack([ndimage.gaussian_filter(rs.rand(17, 33, 9), 2.0) for _ in range(5)], axis=-1)
+    field = (field - field.min()) / (field.max() - field.min())
+    p = np.ascontiguousarray(field[..., 0])
+    thr = float(np.quantile(ndimage.gaussian_filter(p, 1), 0.6))
+    host = postprocess_prediction(p, threshold=thr, device=False)
+    dev = postprocess_prediction(p, threshold=thr, device=True)
+    assert dev.dtype == bool and dev.shape == p.shape and host.any() and not host.all()
+    assert np.array_equal(dev, postprocess_label_map(p, threshold=thr, labels=[7], device=True) == 7)
+    assert np.array_equal(dev, host)
+    assert np.array_equal(postprocess_label_map(p, threshold=thr, labels=[7], device=False) == 7, host)

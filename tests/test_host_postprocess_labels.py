@@ -147,3 +147,15 @@ def test_run_validation_case_writes_the_cleaned_map_when_asked(tmp_path):
     out = str(tmp_path / "off")                                                           # without output_label_map the keyword does nothing
     run_validation_case(0, out, _Stub(), DataFile, ["volume"], patch_shape=(8, 8, 8), postprocess_labels={})
     assert not os.path.exists(os.path.join(out, "prediction_labels.nii.gz"))
+
+
+@pytest.mark.parametrize("sigma", [0.5, 1, 2.0, 2.3])
+def test_order0_gaussian_weights_are_the_same_doubles_reversed(sigma):
+    """the device gaussians take their weights from ops.gaussian_kernel1d(sd, 0, radius), which reverses the kernel as scipy's
+    gaussian_filter1d does: the order-0 kernel is symmetric, so that is bit for bit the unreversed phi / phi.sum()"""
+    from fmri_hip import ops
+    radius = int(4.0 * sigma + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    w = ops.gaussian_kernel1d(float(sigma), 0, radius)
+    assert w.dtype == np.float64 and w.tobytes() == (phi / phi.sum()).tobytes() and w.tobytes() == w[::-1].tobytes()

@@ -6,12 +6,10 @@ Volume 160x256x256 (BASELINE configs[4]) with L = 1, 4, 32 channels of smooth ra
 
   new_host    postprocess_label_map(array, device=True): upload, all labels in one pass, one byte per voxel back
   new_device  the same from a float64 CUDA tensor to a uint8 CUDA tensor (no transfer)
-  loop_api    what a user had before: postprocess_prediction(pred[..., l], device=True) per label, the smoothed channel from
+  loop_api    the loop over the labels: postprocess_prediction(pred[..., l], device=True) per label, the smoothed channel from
               ops.gaussian_filter_f64 (the merge needs it and postprocess_prediction does not return it), then the definition's
               argmax / masking with numpy on the host
-  loop_ops    the same loop written against the single-label ops directly: one upload and one smoothing per label, the mask and the
-              smoothed channel downloaded, the same host merge - the cheapest form of the loop the single-label kernels allow
-  single      L = 1 only: postprocess_prediction(device=True), the single-label path the new one must not lose to
+  single      L = 1 only: postprocess_prediction(device=True), the same word kernels at one label with the mask brought to the host
   stages      device-event time of each stage of new_device
 
 usage: bench_postprocess_labels.py [--labels 1,4,32] [--reps 5] [--shape 160,256,256] [--out FILE]"""
@@ -76,22 +74,13 @@ def run(shape, n_labels, reps):
         mk = np.stack([postprocess_prediction(np.ascontiguousarray(pred[..., l]), threshold=thr, device=True) for l in range(n_labels)])
         return _merge(sm, mk, values)
 
-    def loop_ops():
-        sm, mk = [], []
-        for l in range(n_labels):
-            s = ops.gaussian_filter_f64(torch.from_numpy(np.ascontiguousarray(pred[..., l])).cuda(), 1)
-            m = ops.largest_component_u8(ops.binary_fill_holes_u8(ops.threshold_f64(s, thr)))
-            sm.append(s.cpu().numpy())
-            mk.append(m.cpu().numpy().astype(bool))
-        return _merge(np.stack(sm), np.stack(mk), values)
-
     arms = {"new_host": lambda: postprocess_label_map(pred, threshold=thr, device=True),
             "new_device": lambda: postprocess_label_map(dev_in, threshold=thr),
-            "loop_api": loop_api, "loop_ops": loop_ops}
+            "loop_api": loop_api}
     if n_labels == 1:
         arms["single"] = lambda: postprocess_prediction(pred[..., 0], threshold=thr, device=True)
     results = {k: f() for k, f in arms.items()}                         # warm-up of every arm, and the results to compare
-    same = bool(np.array_equal(results["new_host"], results["loop_api"]) and np.array_equal(results["loop_ops"], results["loop_api"])
+    same = bool(np.array_equal(results["new_host"], results["loop_api"])
                 and np.array_equal(results["new_device"].cpu().numpy(), results["loop_api"]))
     if n_labels == 1:
         same = same and bool(np.array_equal(results["single"], results["new_host"] != 0))
@@ -125,7 +114,6 @@ def run(shape, n_labels, reps):
     out.update({k: _stats(v) for k, v in times.items()})
     out["stages_ms_median"] = {k: float(np.median([s[k] for s in st])) for k in st[0]}
     out["speedup_new_host_over_loop_api"] = out["loop_api"]["ms_median"] / out["new_host"]["ms_median"]
-    out["speedup_new_host_over_loop_ops"] = out["loop_ops"]["ms_median"] / out["new_host"]["ms_median"]
     return out
 
 
