@@ -1156,6 +1156,150 @@ __global__ __launch_bounds__(256) void k_grad_combine(const double* d0, const do
     }
 }
 
+// ---- moments of a volume: what numpy's ndarray.mean() / ndarray.std() compute (sum / n; a SECOND pass for sqrt(sum((x - mean)^2) / n)),
+// with min, max and the NaN count of k_minmax64 taken in the first pass.  Two launches per pass: k_moments_partials leaves one partial
+// per workgroup in the workspace, k_moments_finish (one workgroup) combines them in index order.  Every sum is a pair {s, c} in
+// Neumaier's form (s the running sum, c the rounding errors it dropped; the value is s + c) from the lane's own loop up to the last
+// combine, so the result is within a few ulp of the exact sum whatever n is; where every partial sum is exactly representable (integer
+// volumes) c stays 0 and the sum is exact.  Order: a lane adds the element pairs 2p, 2p + 1 for p = its index, + lanes, + 2 * lanes ...;
+// lanes combine in a fixed tree (wave by shuffles, the four waves through LDS, the workgroups in k_moments_finish).  The grid is a
+// function of n alone and the pair a lane reads does not depend on how it is loaded (one 16-byte load, or two 8-byte loads for a src that
+// is not 16-byte aligned), so the same values give the same bits on every run, device and alignment.
+constexpr int MOM_THREADS = 256, MOM_WAVES = MOM_THREADS / 64, MOM_GRID = 2048, MOM_PAIRS = 8;     // pairs per lane before the grid saturates
+struct MomPartial {
+    double s, c;
+    unsigned long long lo, hi, nans;
+};
+struct MomSum {
+    double s, c;
+};
+__device__ __forceinline__ void mom_add(MomSum& a, double x) {
+#pragma clang fp contract(off)
+    const double t = a.s + x;
+    a.c += fabs(a.s) >= fabs(x) ? (a.s - t) + x : (x - t) + a.s;
+    a.s = t;
+}
+__device__ __forceinline__ void mom_merge(MomSum& a, double bs, double bc) {
+#pragma clang fp contract(off)
+    const double c = a.c + bc;
+    a.c = 0.0;
+    mom_add(a, bs);
+    a.c += c;
+}
+
+template <bool VEC, int PASS>       // PASS 0: sum, min / max keys, NaN count of x;  PASS 1: sum of (x - *mean)^2
+__global__ __launch_bounds__(MOM_THREADS) void k_moments_partials(const double* __restrict__ x, int64_t n, const double* __restrict__ mean,
+                                                                 MomPartial* __restrict__ partial) {
+#pragma clang fp contract(off)
+    __shared__ MomPartial part[MOM_WAVES];
+    const double m = PASS ? *mean : 0.0;
+    MomSum acc{0.0, 0.0};
+    unsigned long long lo = ~0ull, hi = 0ull, nans = 0;
+    auto take = [&](double v) {
+        if (PASS) {
+            const double d = v - m;
+            mom_add(acc, d * d);
+        } else {
+            mom_add(acc, v);
+            if (v != v) {
+                ++nans;
+            } else {
+                const unsigned long long k = f64_key(v);
+                lo = k < lo ? k : lo;
+                hi = k > hi ? k : hi;
+            }
+        }
+    };
+    const int64_t pairs = n >> 1, step = (int64_t)gridDim.x * MOM_THREADS;
+    for (int64_t p = (int64_t)blockIdx.x * MOM_THREADS + threadIdx.x; p < pairs; p += step) {
+        double a, b;
+        if (VEC) {
+            const double2 v = *reinterpret_cast<const double2*>(x + 2 * p);
+            a = v.x;
+            b = v.y;
+        } else {
+            a = x[2 * p];
+            b = x[2 * p + 1];
+        }
+        take(a);
+        take(b);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) take(x[n - 1]);       // the odd last element
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {                                        // lane 0 ends with the wave's tree
+        const double bs = __shfl_down(acc.s, o), bc = __shfl_down(acc.c, o);
+        mom_merge(acc, bs, bc);
+        if (!PASS) {
+            const unsigned long long l2 = __shfl_down(lo, o), h2 = __shfl_down(hi, o);
+            lo = l2 < lo ? l2 : lo;
+            hi = h2 > hi ? h2 : hi;
+            nans += __shfl_down(nans, o);
+        }
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = MomPartial{acc.s, acc.c, lo, hi, nans};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        MomPartial r = part[0];
+        MomSum t{r.s, r.c};
+        for (int w = 1; w < MOM_WAVES; ++w) {
+            mom_merge(t, part[w].s, part[w].c);
+            r.lo = part[w].lo < r.lo ? part[w].lo : r.lo;
+            r.hi = part[w].hi > r.hi ? part[w].hi : r.hi;
+            r.nans += part[w].nans;
+        }
+        r.s = t.s;
+        r.c = t.c;
+        partial[blockIdx.x] = r;
+    }
+}
+
+// one workgroup: thread i combines partials i, i + 256, ... in that order, then a fixed tree over the 256 threads.  PASS 0 writes
+// out5[0] = mean, [2] = min, [3] = max, [4] = sum and *nan_count; PASS 1 writes out5[1] = std.
+template <int PASS>
+__global__ __launch_bounds__(MOM_THREADS) void k_moments_finish(const MomPartial* __restrict__ partial, int parts, int64_t n, double* __restrict__ out5,
+                                                               long long* __restrict__ nan_count) {
+#pragma clang fp contract(off)
+    __shared__ MomPartial sh[MOM_THREADS];
+    MomSum acc{0.0, 0.0};
+    unsigned long long lo = ~0ull, hi = 0ull, nans = 0;
+    for (int i = threadIdx.x; i < parts; i += MOM_THREADS) {
+        const MomPartial p = partial[i];
+        mom_merge(acc, p.s, p.c);
+        lo = p.lo < lo ? p.lo : lo;
+        hi = p.hi > hi ? p.hi : hi;
+        nans += p.nans;
+    }
+    sh[threadIdx.x] = MomPartial{acc.s, acc.c, lo, hi, nans};
+    __syncthreads();
+    for (int o = MOM_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            MomPartial a = sh[threadIdx.x];
+            const MomPartial b = sh[threadIdx.x + o];
+            MomSum t{a.s, a.c};
+            mom_merge(t, b.s, b.c);
+            a.s = t.s;
+            a.c = t.c;
+            a.lo = b.lo < a.lo ? b.lo : a.lo;
+            a.hi = b.hi > a.hi ? b.hi : a.hi;
+            a.nans += b.nans;
+            sh[threadIdx.x] = a;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double total = sh[0].s + sh[0].c;
+        if (PASS) {
+            out5[1] = sqrt(total / (double)n);
+        } else {
+            out5[0] = total / (double)n;
+            out5[2] = key_f64(sh[0].lo);               // no value that is not a NaN: the initial keys decode to NaNs, as in k_minmax64_decode
+            out5[3] = key_f64(sh[0].hi);
+            out5[4] = total;
+            *nan_count = (long long)sh[0].nans;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int64_t fmri_order_stats_workspace_bytes(void) { return (int64_t)sizeof(SelState); }
@@ -1186,6 +1330,28 @@ extern "C" int fmri_minmax_f64(const double* src, int64_t n, double* out2, int64
     k_minmax64_init<<<1, 1, 0, s>>>(mm, nc);
     k_minmax64<<<grid_for(n, 256, 2048), 256, 0, s>>>(src, n, mm, nc);
     k_minmax64_decode<<<1, 1, 0, s>>>(mm);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int64_t fmri_moments_workspace_bytes(void) { return (int64_t)(MOM_GRID * sizeof(MomPartial)); }
+
+extern "C" int fmri_moments_f64(const double* src, int64_t n, double* out5, int64_t* nan_count, void* workspace, fmri_stream_t stream) {
+    if (!src || !out5 || !nan_count || !workspace || n <= 0 || (reinterpret_cast<uintptr_t>(src) & 7u)) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    MomPartial* const partial = static_cast<MomPartial*>(workspace);
+    long long* const nc = reinterpret_cast<long long*>(nan_count);
+    const int parts = grid_for(ceil_div64(n >> 1, MOM_PAIRS), MOM_THREADS, MOM_GRID);       // a function of n alone
+    if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
+        k_moments_partials<true, 0><<<parts, MOM_THREADS, 0, s>>>(src, n, nullptr, partial);
+        k_moments_finish<0><<<1, MOM_THREADS, 0, s>>>(partial, parts, n, out5, nc);
+        k_moments_partials<true, 1><<<parts, MOM_THREADS, 0, s>>>(src, n, out5, partial);
+    } else {
+        k_moments_partials<false, 0><<<parts, MOM_THREADS, 0, s>>>(src, n, nullptr, partial);
+        k_moments_finish<0><<<1, MOM_THREADS, 0, s>>>(partial, parts, n, out5, nc);
+        k_moments_partials<false, 1><<<parts, MOM_THREADS, 0, s>>>(src, n, out5, partial);
+    }
+    k_moments_finish<1><<<1, MOM_THREADS, 0, s>>>(partial, parts, n, out5, nc);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }

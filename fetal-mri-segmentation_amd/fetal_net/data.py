@@ -14,7 +14,9 @@ plus `/subject_ids`, and everything downstream only uses `data_file.root.<name>[
     written by `write_plain_data_file` here or by `tools/convert_data_file.py`, which runs where PyTables exists and rewrites a
     reference data file sample by sample (PyTables itself writes the plain arrays, so the converter needs nothing of this package).
 
-Also here: the train / validation / test split pickles and `norm_params.json` exactly as the reference writes them.
+Also here: the train / validation / test split pickles and `norm_params.json` exactly as the reference writes them, and
+`write_data_to_file` (reference data.py:20-74): NIfTI scans -> zoom, filter, normalisation (on the device, or with scipy / numpy) -> a
+plain-layout data file.
 """
 import json
 import os
@@ -201,21 +203,161 @@ def write_plain_data_file(out_file, data, truth, mask=None, subject_ids=None):
     if len(truth) != n or (mask is not None and len(mask) not in (0, n)) or (subject_ids is not None and len(subject_ids) != n):
         raise ValueError("data, truth, mask and subject_ids must have one entry per subject")
     tmp = out_file + ".tmp"
-    with hdf5.File(tmp, "w") as f:
-        f.attrs[PLAIN_MARK] = np.int32(1)
-        f.attrs["n_samples"] = np.int32(n)
-        for name, seq in (("data", data), ("truth", truth), ("mask", mask if mask else None)):
-            if seq is None:
-                continue
-            g = f.create_group(name)
-            for i, a in enumerate(seq):
-                g.create_dataset("s%d" % i, data=np.ascontiguousarray(a)).close()
-            g.close()
-        if subject_ids is not None:
-            ids = np.asarray([s if isinstance(s, bytes) else str(s).encode("utf8") for s in subject_ids], dtype="S")
-            f.create_dataset("subject_ids", data=ids).close()
-    os.replace(tmp, out_file)
+    try:
+        with hdf5.File(tmp, "w") as f:
+            f.attrs[PLAIN_MARK] = np.int32(1)
+            f.attrs["n_samples"] = np.int32(n)
+            for name, seq in (("data", data), ("truth", truth), ("mask", mask if mask else None)):
+                if seq is None:
+                    continue
+                g = f.create_group(name)
+                for i, a in enumerate(seq):
+                    g.create_dataset("s%d" % i, data=np.ascontiguousarray(a)).close()
+                g.close()
+            if subject_ids is not None:
+                ids = np.asarray([s if isinstance(s, bytes) else str(s).encode("utf8") for s in subject_ids], dtype="S")
+                f.create_dataset("subject_ids", data=ids).close()
+        os.replace(tmp, out_file)
+    except BaseException:
+        if os.path.exists(tmp):                              # a write that fails midway leaves nothing behind
+            os.remove(tmp)
+        raise
     return out_file
+
+
+# ------------------------------------------------------------------------------------------------ building a data file from scans
+NORMALIZATIONS = ("all", "each")
+
+
+def _resolve_preproc(preproc):
+    """-> (callable or None, whether it is one of fetal_net.preprocess' filters, which take device tensors)"""
+    from . import preprocess
+    if preproc is None:
+        return None, False
+    if isinstance(preproc, str):
+        if preproc not in preprocess.__all__:
+            raise ValueError("preproc %r is not one of %s of fetal_net.preprocess" % (preproc, preprocess.__all__))
+        return getattr(preprocess, preproc), True
+    if not callable(preproc):
+        raise TypeError("preproc must be a callable or one of %s of fetal_net.preprocess (got %r)" % (preprocess.__all__, preproc))
+    return preproc, getattr(preprocess, getattr(preproc, "__name__", ""), None) is preproc
+
+
+def _device_available():
+    from .postprocess import _device_ok
+    return _device_ok(np.zeros((1, 1, 1)))
+
+
+def write_data_to_file(training_data_files, out_file, truth_dtype=np.uint8, subject_ids=None, normalize='all', scale=None, preproc=None,
+                       *, device=None, device_budget=None):
+    """reference data.py:42-74: read every subject's files - a tuple (volume, truth) or (volume, truth, mask) of NIfTI paths, read with
+    `fetal_net.utils.nifti.load_nifti` -, zoom volume (order 3) and truth (order 0) by `scale`, apply `preproc` (a callable, or the name
+    of a filter of `fetal_net.preprocess`) to the zoomed volume, store data float64 / truth `truth_dtype` / mask float64, normalise the
+    volumes (`normalize`: 'all' | 'each' as in `fetal_net.normalize`; anything that is not a string: not at all) and write `out_file`.
+    Returns (out_file, (mean, std)); (None, None) unless normalize == 'all'.
+
+    The file is the plain layout (`write_plain_data_file`; `open_data_file` reads it, no PyTables needed), written to a temporary name
+    and moved into place at the end: a build that fails leaves no file behind.
+
+    device (keyword only; None = the device form when a GPU and the HIP library are there, True / False force one): where the
+    per-volume arithmetic runs.  The default holds for every setting: a cohort of 160x256x256 volumes builds 1.2x (no zoom, no filter) to
+    4.4x (zoom) quicker per subject on the device, file reading and writing included (profiles/r10_dataset_build.log).  The device form uploads a subject once, zooms with `fmri_hip.ops.zoom_f64` (labels as float64 and
+    back, exact for integers), runs a named `preproc` on the device tensor (a caller's own callable gets a numpy array in between) and
+    takes the volume's mean and standard deviation with `ops.moments_f64` while it is resident.  'each' normalises there and downloads.
+    'all' needs the last subject's statistics before the first volume can be normalised: volumes stay on the device while they fit in
+    `device_budget` bytes (default: half of the device memory that is free when the call starts), are normalised there at the end and
+    downloaded once; beyond the budget they are downloaded un-normalised and normalised with numpy - the same subtract and divide by the
+    same two doubles, so the same bits (device_budget=0 takes that route for every volume).
+    device=False is the host form: scipy and numpy throughout, the reference's arithmetic.
+    Host and device form agree exactly in truth, masks and un-zoomed data, to 1e-12 * max(1, max|value|) in spline-zoomed data (the
+    bound of `zoom_f64`), and in mean / std to the rounding of the sums (`fetal_net.normalize`).
+
+    Departures from the reference:
+      * the volume is taken as float64 from the start.  The reference zooms and filters in the file's stored type, so a float32 file
+        gives float32-rounded intermediate results there and an integer file rounded integers; for float64 files the two agree.
+      * a subject tuple with fewer than 2 or more than 3 files raises ValueError (the reference silently takes file 2 as the truth and
+        ignores the rest);
+      * `scale` together with mask files raises ValueError (the reference leaves the mask on the unscaled grid, where it fits nothing);
+      * a string other than 'all' / 'each' for `normalize` raises ValueError (the reference: KeyError after the volumes were written)."""
+    from .normalize import combine_statistics, normalize_data_storage, normalize_data_storage_each
+    from .utils.nifti import load_nifti
+    if isinstance(normalize, str) and normalize not in NORMALIZATIONS:
+        raise ValueError("normalize must be one of %r, or not a string for no normalisation (got %r)" % (NORMALIZATIONS, normalize))
+    mode = normalize if isinstance(normalize, str) else None
+    pre, pre_named = _resolve_preproc(preproc)
+    files = [tuple(s) for s in training_data_files]
+    for s in files:
+        if not 2 <= len(s) <= 3:
+            raise ValueError("a subject is (volume, truth) or (volume, truth, mask): got %d files %r" % (len(s), s))
+        if scale is not None and len(s) == 3:
+            raise ValueError("scale with mask files: the masks would stay on the unscaled grid")
+    if subject_ids and len(subject_ids) != len(files):
+        raise ValueError("%d subject ids for %d subjects" % (len(subject_ids), len(files)))
+    if device is None:
+        device = _device_available()
+    data, truth, mask = [], [], []
+    mean = std = None
+    if not device:
+        from scipy import ndimage
+        for s in files:
+            vol = np.asarray(load_nifti(s[0]), dtype=np.float64)
+            lab = np.asarray(load_nifti(s[1]))
+            if scale is not None:
+                vol = ndimage.zoom(vol, scale)
+                lab = ndimage.zoom(lab, scale, order=0)
+            if pre is not None:
+                vol = pre(vol, device=False) if pre_named else pre(vol)
+            data.append(np.asarray(vol).astype(np.float64))
+            truth.append(np.asarray(lab, dtype=truth_dtype))
+            if len(s) == 3:
+                mask.append(np.asarray(load_nifti(s[2])).astype(np.float64))
+        if mode == "all":
+            _, mean, std = normalize_data_storage(data, device=False)
+        elif mode == "each":
+            normalize_data_storage_each(data, device=False)
+    else:
+        import torch
+        from fmri_hip import ops
+        if device_budget is None:
+            device_budget = torch.cuda.mem_get_info()[0] // 2
+        resident, held, moments = {}, 0, []
+        for k, s in enumerate(files):
+            vol = np.asarray(load_nifti(s[0]))
+            if vol.ndim != 3 or vol.size == 0:
+                raise ValueError("%s: the device form builds from non-empty volumes [X,Y,Z] (got shape %r)" % (s[0], vol.shape))
+            t = torch.from_numpy(np.ascontiguousarray(vol, dtype=np.float64)).cuda()
+            lab = np.asarray(load_nifti(s[1]))
+            if scale is not None:
+                t = ops.zoom_f64(t, scale, order=3)
+                lab_t = torch.from_numpy(np.ascontiguousarray(lab, dtype=np.float64)).cuda()
+                lab = ops.zoom_f64(lab_t, scale, order=0).cpu().numpy()
+            if pre is not None and pre_named:
+                t = pre(t)
+            elif pre is not None:
+                t = torch.from_numpy(np.ascontiguousarray(np.asarray(pre(t.cpu().numpy())), dtype=np.float64)).cuda()
+            truth.append(np.asarray(lab).astype(truth_dtype))
+            if len(s) == 3:
+                mask.append(np.asarray(load_nifti(s[2])).astype(np.float64))
+            if mode is not None:
+                moments.append(ops.moments_f64(t)[:2])
+            if mode == "each":
+                t = ops.normalize_f64(t, *moments[-1])
+            nbytes = t.numel() * 8
+            if mode == "all" and held + nbytes <= device_budget:
+                resident[k] = t
+                held += nbytes
+                data.append(None)
+            else:
+                data.append(t.cpu().numpy())
+        if mode == "all":
+            mean, std = combine_statistics([m[0] for m in moments], [m[1] for m in moments])
+            for k in range(len(files)):
+                if k in resident:
+                    data[k] = ops.normalize_f64(resident.pop(k), float(mean), float(std)).cpu().numpy()
+                else:
+                    data[k] = (data[k] - mean) / std
+    write_plain_data_file(out_file, data, truth, mask or None, list(subject_ids) if subject_ids else None)
+    return out_file, (mean, std)
 
 
 # ------------------------------------------------------------------------------------------------ split lists, normalisation record

@@ -90,6 +90,8 @@ SIGNATURES = {
     "fmri_order_stats_workspace_bytes": [],
     "fmri_order_stats_f64": [p, i64, p, i32, p, p, p, p],
     "fmri_minmax_f64": [p, i64, p, p, p],
+    "fmri_moments_workspace_bytes": [],
+    "fmri_moments_f64": [p, i64, p, p, p, p],
     "fmri_intensity_map_f64": [p, p, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, p],
     "fmri_laplace_f64": [p, p, i32, i32, i32, p],
     "fmri_correlate1d_asym_f64": [p, p, i32, i32, i32, i32, p, i32, p],

@@ -1151,6 +1151,33 @@ def minmax_f64(vol):
     return (float("nan"), float("nan")) if int(nan.item()) else (lo, hi)
 
 
+def moments_f64(vol):
+    """(vol.mean(), vol.std(), vol.min(), vol.max()) of a float64 device tensor as Python floats, numpy's definitions (population std
+    from a second pass around the mean); one call of fmri_moments_f64, one read-back.  The sums are compensated and added in an order
+    fixed by the size: within a few ulp of the exact values, mean identical to numpy's where the partial sums are exact (integer
+    volumes), same bits on every run.  A NaN in vol gives NaN for all four, as numpy does.  Infinities are not covered (they make the
+    compensated sums NaN where numpy's mean is an infinity).  `vol` must be dense; a view may start anywhere in its storage."""
+    host = moments_f64_enqueue(vol).cpu()
+    if int(host[5:].view(torch.int64).item()):
+        return (float("nan"),) * 4
+    mean, std, lo, hi = host[:4].tolist()
+    return mean, std, lo, hi
+
+
+def moments_f64_enqueue(vol):
+    """the launches of moments_f64 on the current stream, nothing read back -> a device tensor of 6 float64: {mean, std, min, max, sum} as
+    fmri_moments_f64 leaves them (min / max over the values that are not NaN) and, in the last 8 bytes, the int64 number of NaNs"""
+    _need_cuda(vol)
+    if vol.dtype != torch.float64 or vol.numel() == 0 or not vol.is_contiguous():
+        raise ValueError("a non-empty contiguous float64 tensor is needed (got %s %s)" % (vol.dtype, tuple(vol.shape)))
+    L = lib()
+    with torch.cuda.device(vol.device):
+        ws = torch.empty(L.fmri_moments_workspace_bytes(), dtype=torch.uint8, device=vol.device)
+        out = torch.empty(6, dtype=torch.float64, device=vol.device)
+        check(L.fmri_moments_f64(_p(vol), vol.numel(), _p(out), out.data_ptr() + 40, _p(ws), _s()), "fmri_moments_f64")
+    return out
+
+
 def intensity_map_f64(vol, kind, p0, p1, p2=0.0, p3=0.0, out=None):
     """out = map(vol) element by element (csrc/postprocess.hip: MAP_WINDOW, MAP_MINMAX, MAP_ZSCORE); out=None: a new tensor, out=vol: in
     place"""

@@ -603,6 +603,13 @@ int fmri_median_stack_f64(const double* stack, int K, int64_t n, double* out, fm
  *   passes are separate launches on `stream`, nothing is read back.  n >= 2^31, K > 8 or a rank outside [0, n): FMRI_E_SHAPE.
  *   Environment switch FMRI_SELECT_BITS = 11 (default) | 8: the digit width (6 or 8 passes), read at every call.
  * fmri_minmax_f64: out2 (device) = {min, max} of the values that are not NaN, *nan_count (device) = the number of NaNs.
+ * fmri_moments_f64: out5 (device) = {mean, std, min, max, sum} of src[0..n) with numpy's definitions: mean = sum / n, std =
+ *   sqrt(sum((x - mean)^2) / n) from a second pass around the first pass's mean (ndarray.std); min, max and *nan_count as
+ *   fmri_minmax_f64 gives them, from the first pass.  Both sums are compensated (Neumaier) in every lane and at every combine, and
+ *   are added in an order fixed by n: within a few ulp of the exact sums, exact where every partial sum is representable (integer
+ *   volumes), and the same bits on every run, device and alignment of src (8 bytes is enough; 16 gets vector loads).  The mean stays on
+ *   the device between the passes: four launches on `stream`, nothing read back.  workspace: fmri_moments_workspace_bytes() bytes on the
+ *   device, any contents.  An infinity among the values gives NaN sums.
  * fmri_intensity_map_f64: dst[i] = map(src[i]); src == dst is allowed.
  *   FMRI_MAP_WINDOW  (min(max(x, p0), p1) - p0) * p2 + p3      p0, p1 = window, p2 = scale, p3 = out_min; np.clip's NaN rules
  *   FMRI_MAP_MINMAX  -1 + (2 * (x - p0)) / (p1 - p0)           p0, p1 = min, max
@@ -619,6 +626,8 @@ int64_t fmri_order_stats_workspace_bytes(void);
 int fmri_order_stats_f64(const double* src, int64_t n, const int64_t* ranks_host, int K, double* out, int64_t* nan_count, void* workspace,
                          fmri_stream_t stream);
 int fmri_minmax_f64(const double* src, int64_t n, double* out2, int64_t* nan_count, fmri_stream_t stream);
+int64_t fmri_moments_workspace_bytes(void);
+int fmri_moments_f64(const double* src, int64_t n, double* out5, int64_t* nan_count, void* workspace, fmri_stream_t stream);
 int fmri_intensity_map_f64(const double* src, double* dst, int64_t n, int kind, double p0, double p1, double p2, double p3,
                            fmri_stream_t stream);
 int fmri_laplace_f64(const double* src, double* dst, int X, int Y, int Z, fmri_stream_t stream);
