@@ -54,6 +54,26 @@ __device__ __forceinline__ void fmri_grad_add(const FmriDetCfg& c, float* p, flo
         atomicAdd(p, v);
 }
 
+// ---- a float64 sum in Neumaier's form: s the running sum, c the rounding errors it dropped; the value is s + c.  mom_add takes one
+// term, mom_merge another pair.  Used from a lane's own loop up to the last combine by the ordered reductions (fmri_moments_f64 in
+// postprocess.hip, fmri_grad_sumsq in pointwise.hip), whose results are then within a few ulp of the exact sum whatever n is.
+struct MomSum {
+    double s, c;
+};
+__device__ __forceinline__ void mom_add(MomSum& a, double x) {
+#pragma clang fp contract(off)
+    const double t = a.s + x;
+    a.c += fabs(a.s) >= fabs(x) ? (a.s - t) + x : (x - t) + a.s;
+    a.s = t;
+}
+__device__ __forceinline__ void mom_merge(MomSum& a, double bs, double bc) {
+#pragma clang fp contract(off)
+    const double c = a.c + bc;
+    a.c = 0.0;
+    mom_add(a, bs);
+    a.c += c;
+}
+
 #define FMRI_LAUNCH_CHECK()                                   \
     do {                                                      \
         if (hipGetLastError() != hipSuccess) return FMRI_E_LAUNCH; \

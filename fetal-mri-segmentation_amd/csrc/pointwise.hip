@@ -1034,6 +1034,263 @@ extern "C" int fmri_adam_step(float* p, const float* g, float* m, float* v, int6
     return FMRI_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ Keras SGD / RMSprop / AMSGrad, clipping
+// Keras 2.2.4 keras/optimizers.py as published (restated from the published source: no Keras was at hand to run against, so these
+// formulas are parity-unpinned; tests/optimizer_restatement.py is the float64 form the kernels are tested against).
+//
+// The gradient every update sees (Optimizer.get_gradients, clip_norm): g = grad_scale * G[i]; with a norm (fmri_grad_sumsq's out[1],
+// read from device memory) and clipnorm > 0 and norm >= clipnorm: g = g * clipnorm / norm; with clipvalue > 0: g clamped to +-clipvalue.
+// A zero norm is below every clipnorm: nothing is clipped, nothing divided.
+template <bool CLIP>
+struct OptGrad {
+    float gs, clipnorm, norm, clipvalue;
+    bool by_norm;
+    __device__ __forceinline__ OptGrad(float gs_, const double* gnorm, float clipnorm_, float clipvalue_)
+        : gs(gs_), clipnorm(clipnorm_), norm(0.f), clipvalue(clipvalue_), by_norm(false) {
+        if (CLIP && gnorm != nullptr && clipnorm > 0.f) {
+            norm = (float)*gnorm;
+            by_norm = norm >= clipnorm;
+        }
+    }
+    __device__ __forceinline__ float operator()(float g) const {
+        float gr = g * gs;
+        if (CLIP) {
+            if (by_norm) gr = gr * clipnorm / norm;
+            if (clipvalue > 0.f) gr = fminf(fmaxf(gr, -clipvalue), clipvalue);
+        }
+        return gr;
+    }
+    // the same gradient in float64 (for an increment that cancels, see k_sgd)
+    __device__ __forceinline__ double f64(float g) const {
+        double gr = (double)g * (double)gs;
+        if (CLIP) {
+            if (by_norm) gr = gr * (double)clipnorm / (double)norm;
+            if (clipvalue > 0.f) gr = fmin(fmax(gr, -(double)clipvalue), (double)clipvalue);
+        }
+        return gr;
+    }
+};
+
+// SGD: v = momentum * m - lr * g; m <- v; p <- p + v, or with Nesterov p <- p + momentum * v - lr * g.  The Nesterov increment is a
+// difference of two terms that cancel wherever momentum and gradient oppose each other: it is formed in float64 from the stored v and
+// rounded once, so the parameter's error stays relative to the increment itself (the kernel is HBM-bound, the fp64 work is free).
+template <bool CLIP, bool NESTEROV>
+__global__ void k_sgd(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, int64_t n, float lr, float mom, float gs,
+                      const double* __restrict__ gnorm, float clipnorm, float clipvalue) {
+    const OptGrad<CLIP> grad(gs, gnorm, clipnorm, clipvalue);
+    auto step = [&](float& pk, float gk, float& mk) {
+        const float v = mom * mk - lr * grad(gk);
+        mk = v;
+        if (NESTEROV) pk = (float)((double)pk + ((double)mom * (double)v - (double)lr * grad.f64(gk)));
+        else pk += v;
+    };
+    const int64_t n4 = n >> 2;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        float4 pp = ((float4*)p)[i], gg = ((const float4*)g)[i], mm = ((float4*)m)[i];
+        float* pa = (float*)&pp; float* ga = (float*)&gg; float* ma = (float*)&mm;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) step(pa[k], ga[k], ma[k]);
+        ((float4*)p)[i] = pp; ((float4*)m)[i] = mm;
+    }
+    for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        step(p[i], g[i], m[i]);
+}
+
+// RMSprop: a <- rho * a + (1 - rho) * g^2; p <- p - lr * g / (sqrt(a) + eps)
+template <bool CLIP>
+__global__ void k_rmsprop(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ a, int64_t n, float lr, float rho, float eps,
+                          float gs, const double* __restrict__ gnorm, float clipnorm, float clipvalue) {
+    const OptGrad<CLIP> grad(gs, gnorm, clipnorm, clipvalue);
+    auto step = [&](float& pk, float gk, float& ak) {
+        const float gr = grad(gk);
+        ak = rho * ak + (1.f - rho) * gr * gr;
+        pk -= lr * gr / (sqrtf(ak) + eps);
+    };
+    const int64_t n4 = n >> 2;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        float4 pp = ((float4*)p)[i], gg = ((const float4*)g)[i], aa = ((float4*)a)[i];
+        float* pa = (float*)&pp; float* ga = (float*)&gg; float* sa = (float*)&aa;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) step(pa[k], ga[k], sa[k]);
+        ((float4*)p)[i] = pp; ((float4*)a)[i] = aa;
+    }
+    for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        step(p[i], g[i], a[i]);
+}
+
+// Adam as k_adam (the <false, false> instantiation is its arithmetic, expression for expression), with AMSGrad:
+// vhat <- max(vhat, v), and sqrt(vhat) in the denominator
+template <bool CLIP, bool AMS>
+__global__ void k_adam_ex(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                          float* __restrict__ vhat, int64_t n, float lr_t, float b1, float b2, float eps, float gs,
+                          const double* __restrict__ gnorm, float clipnorm, float clipvalue) {
+    const OptGrad<CLIP> grad(gs, gnorm, clipnorm, clipvalue);
+    const int64_t n4 = n >> 2;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        float4 pp = ((float4*)p)[i], gg = ((const float4*)g)[i], mm = ((float4*)m)[i], vv = ((float4*)v)[i], hh;
+        if (AMS) hh = ((float4*)vhat)[i];
+        float* pa = (float*)&pp; float* ga = (float*)&gg; float* ma = (float*)&mm; float* va = (float*)&vv; float* ha = (float*)&hh;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float gr = grad(ga[k]);
+            ma[k] = b1 * ma[k] + (1.f - b1) * gr;
+            va[k] = b2 * va[k] + (1.f - b2) * gr * gr;
+            if (AMS) {
+                ha[k] = fmaxf(ha[k], va[k]);
+                pa[k] -= lr_t * ma[k] / (sqrtf(ha[k]) + eps);
+            } else {
+                pa[k] -= lr_t * ma[k] / (sqrtf(va[k]) + eps);
+            }
+        }
+        ((float4*)p)[i] = pp; ((float4*)m)[i] = mm; ((float4*)v)[i] = vv;
+        if (AMS) ((float4*)vhat)[i] = hh;
+    }
+    for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float gr = grad(g[i]);
+        float mi = b1 * m[i] + (1.f - b1) * gr, vi = b2 * v[i] + (1.f - b2) * gr * gr;
+        m[i] = mi; v[i] = vi;
+        if (AMS) {
+            const float hi = fmaxf(vhat[i], vi);
+            vhat[i] = hi;
+            p[i] -= lr_t * mi / (sqrtf(hi) + eps);
+        } else {
+            p[i] -= lr_t * mi / (sqrtf(vi) + eps);
+        }
+    }
+}
+
+// n and alignment rules of fmri_adam_step; the clipping instantiation only where something clips
+#define OPT_REFUSE(n, bits)                                  \
+    do {                                                     \
+        if ((n) <= 0) return FMRI_E_SHAPE;                   \
+        if ((bits) & 15) return FMRI_E_ALIGN;                \
+    } while (0)
+static inline bool opt_clips(const double*& gnorm, float clipnorm, float clipvalue) {
+    if (!(clipnorm > 0.f)) gnorm = nullptr;          // no clipnorm: the norm is not read
+    return gnorm != nullptr || clipvalue > 0.f;
+}
+
+extern "C" int fmri_sgd_step(float* p, const float* g, float* m, int64_t n, float lr, float momentum, int nesterov, float grad_scale,
+                             const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream) {
+    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m));
+    const bool clip = opt_clips(gnorm, clipnorm, clipvalue);
+    if (((uintptr_t)gnorm) & 7) return FMRI_E_ALIGN;
+    const int grid = grid_for(n / 4 + 1, 256, 2048);
+    hipStream_t s = as_stream(stream);
+#define SGD(C, N) k_sgd<C, N><<<grid, 256, 0, s>>>(p, g, m, n, lr, momentum, grad_scale, gnorm, clipnorm, clipvalue)
+    if (clip) { if (nesterov) SGD(true, true); else SGD(true, false); }
+    else { if (nesterov) SGD(false, true); else SGD(false, false); }
+#undef SGD
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_rmsprop_step(float* p, const float* g, float* a, int64_t n, float lr, float rho, float eps, float grad_scale,
+                                 const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream) {
+    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)a));
+    const bool clip = opt_clips(gnorm, clipnorm, clipvalue);
+    if (((uintptr_t)gnorm) & 7) return FMRI_E_ALIGN;
+    const int grid = grid_for(n / 4 + 1, 256, 2048);
+    hipStream_t s = as_stream(stream);
+    if (clip) k_rmsprop<true><<<grid, 256, 0, s>>>(p, g, a, n, lr, rho, eps, grad_scale, gnorm, clipnorm, clipvalue);
+    else k_rmsprop<false><<<grid, 256, 0, s>>>(p, g, a, n, lr, rho, eps, grad_scale, gnorm, clipnorm, clipvalue);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_adam_step_ex(float* p, const float* g, float* m, float* v, float* vhat, int64_t n, float lr_t, float beta1, float beta2,
+                                 float eps, float grad_scale, const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream) {
+    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)vhat));
+    const bool clip = opt_clips(gnorm, clipnorm, clipvalue);
+    if (((uintptr_t)gnorm) & 7) return FMRI_E_ALIGN;
+    const int grid = grid_for(n / 4 + 1, 256, 2048);
+    hipStream_t s = as_stream(stream);
+#define ADAM(C, A) k_adam_ex<C, A><<<grid, 256, 0, s>>>(p, g, m, v, vhat, n, lr_t, beta1, beta2, eps, grad_scale, gnorm, clipnorm, clipvalue)
+    if (clip) { if (vhat) ADAM(true, true); else ADAM(true, false); }
+    else { if (vhat) ADAM(false, true); else ADAM(false, false); }
+#undef ADAM
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+// ---- sum of squares of the scaled gradient, for clipnorm: out[0] = sum (float(grad_scale * g_i))^2 in float64, out[1] = sqrt(out[0]).
+// Built like fmri_moments_f64 (postprocess.hip): a lane adds the squares of the quads q, q + lanes, q + 2 * lanes ... of its index in
+// Neumaier's form, lanes combine in a fixed tree (wave by shuffles, the four waves through LDS), k_grad_sumsq_finish (one workgroup) adds
+// the workgroups' partials in index order.  The grid is a function of n alone and nothing is added atomically: the same values give the
+// same bits on every run and stream, which is what FMRI_DETERMINISTIC=1 asks for - there is no second route.  A float32 squared is exact
+// in float64 (48 significant bits; the exponent range of float squares lies inside that of float64).
+constexpr int GSQ_THREADS = 256, GSQ_WAVES = GSQ_THREADS / 64, GSQ_GRID = 2048, GSQ_QUADS = 8;     // quads per lane before the grid saturates
+
+__global__ __launch_bounds__(GSQ_THREADS) void k_grad_sumsq_partials(const float* __restrict__ g, int64_t n, float gs,
+                                                                    MomSum* __restrict__ partial) {
+#pragma clang fp contract(off)
+    __shared__ MomSum part[GSQ_WAVES];
+    MomSum acc{0.0, 0.0};
+    auto take = [&](float v) {
+        const float x = gs * v;
+        const double d = (double)x;
+        mom_add(acc, d * d);
+    };
+    const int64_t quads = n >> 2, step = (int64_t)gridDim.x * GSQ_THREADS;
+    for (int64_t q = (int64_t)blockIdx.x * GSQ_THREADS + threadIdx.x; q < quads; q += step) {
+        const float4 v = ((const float4*)g)[q];
+        take(v.x);
+        take(v.y);
+        take(v.z);
+        take(v.w);
+    }
+    if (blockIdx.x == 0 && (int64_t)threadIdx.x < (n & 3)) take(g[(quads << 2) + threadIdx.x]);       // the last n % 4 elements
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {                                        // lane 0 ends with the wave's tree
+        const double bs = __shfl_down(acc.s, o), bc = __shfl_down(acc.c, o);
+        mom_merge(acc, bs, bc);
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        MomSum t = part[0];
+        for (int w = 1; w < GSQ_WAVES; ++w) mom_merge(t, part[w].s, part[w].c);
+        partial[blockIdx.x] = t;
+    }
+}
+
+// one workgroup: thread i combines partials i, i + 256, ... in that order, then a fixed tree over the 256 threads
+__global__ __launch_bounds__(GSQ_THREADS) void k_grad_sumsq_finish(const MomSum* __restrict__ partial, int parts, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ MomSum sh[GSQ_THREADS];
+    MomSum acc{0.0, 0.0};
+    for (int i = threadIdx.x; i < parts; i += GSQ_THREADS) mom_merge(acc, partial[i].s, partial[i].c);
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = GSQ_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            MomSum t = sh[threadIdx.x];
+            mom_merge(t, sh[threadIdx.x + o].s, sh[threadIdx.x + o].c);
+            sh[threadIdx.x] = t;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double total = sh[0].s + sh[0].c;
+        out[0] = total;
+        out[1] = sqrt(total);
+    }
+}
+
+extern "C" int64_t fmri_grad_sumsq_workspace_bytes(void) { return (int64_t)(GSQ_GRID * sizeof(MomSum)); }
+
+extern "C" int fmri_grad_sumsq(const float* g, int64_t n, float grad_scale, void* workspace, double* out, fmri_stream_t stream) {
+    if (!g || !workspace || !out || n <= 0) return FMRI_E_SHAPE;
+    if ((((uintptr_t)g) & 15) || ((((uintptr_t)workspace) | ((uintptr_t)out)) & 7)) return FMRI_E_ALIGN;
+    hipStream_t s = as_stream(stream);
+    MomSum* const partial = static_cast<MomSum*>(workspace);
+    const int parts = grid_for(ceil_div64(n >> 2, GSQ_QUADS), GSQ_THREADS, GSQ_GRID);       // a function of n alone
+    k_grad_sumsq_partials<<<parts, GSQ_THREADS, 0, s>>>(g, n, grad_scale, partial);
+    k_grad_sumsq_finish<<<1, GSQ_THREADS, 0, s>>>(partial, parts, out);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ weight packing
 // fp32 master [27][Cout][Cin] -> compute-dtype copies: forward layout and the tap-flipped transposed dgrad layout.
 template <typename T>

@@ -1170,22 +1170,7 @@ struct MomPartial {
     double s, c;
     unsigned long long lo, hi, nans;
 };
-struct MomSum {
-    double s, c;
-};
-__device__ __forceinline__ void mom_add(MomSum& a, double x) {
-#pragma clang fp contract(off)
-    const double t = a.s + x;
-    a.c += fabs(a.s) >= fabs(x) ? (a.s - t) + x : (x - t) + a.s;
-    a.s = t;
-}
-__device__ __forceinline__ void mom_merge(MomSum& a, double bs, double bc) {
-#pragma clang fp contract(off)
-    const double c = a.c + bc;
-    a.c = 0.0;
-    mom_add(a, bs);
-    a.c += c;
-}
+// (MomSum, mom_add and mom_merge - the compensated pair and its two steps - are in common.h: fmri_grad_sumsq sums the same way)
 
 template <bool VEC, int PASS>       // PASS 0: sum, min / max keys, NaN count of x;  PASS 1: sum of (x - *mean)^2
 __global__ __launch_bounds__(MOM_THREADS) void k_moments_partials(const double* __restrict__ x, int64_t n, const double* __restrict__ mean,

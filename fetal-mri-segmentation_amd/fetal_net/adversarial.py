@@ -160,12 +160,28 @@ def input2gan(real_patches, real_segs, d_out_shape, semi_patches=None):
     return [real_patches, semi_patches], [real_segs, valid]
 
 
+def _adam_only(optimizer, where):
+    """the adversarial loops step plain Adam (their one per-model hyper-parameter is beta_1): any other optimizer - or an Adam option
+    those steps would drop silently - is refused by name"""
+    from .optimizers import Optimizer
+    if not isinstance(optimizer, Optimizer):
+        return                                # an object of any other type: its lr, with Adam's defaults
+    extras = [k for k in ("amsgrad", "decay", "clipnorm", "clipvalue") if getattr(optimizer, k, None)]
+    if not isinstance(optimizer, Adam) or extras:
+        raise NotImplementedError("%s trains with plain Adam: %s%s is not stepped there" % (
+            where, type(optimizer).__name__, "(%s)" % ", ".join(extras) if extras else ""))
+
+
 # ----------------------------------------------------------------------------------------------------------------- discriminator model
 class DiscriminatorModel(Model):
     """Keras-Model duck type of `discriminator_image_3d`: train_on_batch / test_on_batch / evaluate / predict with float targets,
     loss = mean binary cross-entropy, metric 'mae' (Keras reports it as mean_absolute_error)."""
 
     _graph_engine = True
+
+    def compile(self, optimizer=None, loss=None, metrics=None, **kw):
+        _adam_only(optimizer, "DiscriminatorModel")
+        Model.compile(self, optimizer=optimizer, loss=loss, metrics=metrics, **kw)
 
     @property
     def metrics_names(self):
@@ -270,6 +286,8 @@ class CombinedModel(object):
             raise NotImplementedError("a mask-weighted generator loss inside the combined model")
         if gen_model._input_layout != "channels_first_3d":
             raise NotImplementedError("the adversarial loop is 3-D (the reference's 2-D discriminator cannot be built)")
+        _adam_only(gen_model.optimizer, "CombinedModel (the generator)")
+        _adam_only(dis_model.optimizer, "CombinedModel (the discriminator)")
         self.gen, self.dis, self.ratio, self.mode = gen_model, dis_model, float(gd_loss_ratio), mode
         self.optimizer = Adam(lr if lr is not None else gen_model.optimizer.lr)
         self._d_in = {}

@@ -21,6 +21,7 @@ from queue import Full, Queue
 import numpy as np
 
 from . import metrics as M
+from .optimizers import Adam, Optimizer          # (Adam: the name the builders import from here)
 
 
 # ----------------------------------------------------------------------------------------------------------------- layers
@@ -34,16 +35,6 @@ class Layer(object):
 
     def __repr__(self):
         return "<%s %s %s>" % (self.class_name, self.name, self.output_shape)
-
-
-class Adam(object):
-    """Optimizer token with the Keras attribute the callbacks touch (`lr`)."""
-
-    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
-        self.lr, self.beta_1, self.beta_2, self.epsilon = float(lr), beta_1, beta_2, epsilon
-
-    def get_config(self):
-        return dict(lr=self.lr, beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.epsilon)
 
 
 # ----------------------------------------------------------------------------------------------------------------- callbacks
@@ -606,10 +597,12 @@ class Model(object):
             if self._pending_weights is not None:
                 self._engine.load_keras_weights(self._pending_weights)
                 self._pending_weights = None
+            self._sync_optimizer(self._engine)
             if getattr(self, "_pending_opt", None) is not None:
                 self._apply_optimizer_state(self._pending_opt)
             if dist_ctx is not None:
                 dist_ctx.broadcast_params(self._engine)
+        self._sync_optimizer(self._engine)
         self._engine.set_batch(batch)
         self._set_label_metrics(self._engine)
         if self.loss is not None:
@@ -910,36 +903,77 @@ class Model(object):
         else:
             self._pending_weights = OrderedDict((k, np.asarray(v)) for k, v in W.items())
 
-    def get_optimizer_state(self):
-        """(m, v, iterations) with m / v as {'<layer>/<key>': ndarray in Keras layout}, or None before the first training step"""
+    # the optimizer's slots by class, in Keras' `optimizer.weights` order: (slot name, the engine buffer that holds it)
+    _OPT_SLOTS = {"Adam": (("m", "M"), ("v", "V"), ("vhat", "Vhat")), "SGD": (("moments", "M"),), "RMSprop": (("accumulators", "V"),)}
+
+    def _optimizer_class(self):
+        """the class name a checkpoint records: an object that is none of this package's optimizers is stepped as Adam"""
+        return type(self.optimizer).__name__ if isinstance(self.optimizer, Optimizer) else "Adam"
+
+    def _sync_optimizer(self, eng):
+        """hand the compiled optimizer's hyper-parameters to the engine (again after a compile() or a changed attribute); an object
+        of any other type gives its `lr` per step and runs with Adam's defaults"""
+        spec = self.optimizer.engine_spec() if isinstance(self.optimizer, Optimizer) else None
+        if getattr(eng, "_model_spec", ()) != spec:
+            eng.set_optimizer(spec)
+            eng._model_spec = spec
+
+    def get_optimizer_slots(self):
+        """the optimizer state of any class: dict(class_name, iterations, slots) with slots = {slot name: {'<layer>/<key>': ndarray in
+        Keras layout}} - Adam: m, v (and vhat with amsgrad), SGD: moments, RMSprop: accumulators - or None before the first step"""
         eng = self._engine
-        if eng is None or not eng.training or eng.t == 0:
-            return getattr(self, "_pending_opt", None)
-        m = eng.flat_to_keras(eng.M.detach().cpu().numpy(), moving=False)
-        v = eng.flat_to_keras(eng.V.detach().cpu().numpy(), moving=False)
-        return m, v, int(eng.t)
+        if eng is None or not eng.training or (eng.t == 0 and not self.__dict__.get("_opt_restored")):
+            return _as_slots(getattr(self, "_pending_opt", None))
+        cls = self._optimizer_class()
+        slots = OrderedDict()
+        for name, buf in self._OPT_SLOTS[cls]:
+            t = getattr(eng, buf)
+            if t is not None and (name != "vhat" or self.optimizer.amsgrad):
+                slots[name] = eng.flat_to_keras(t.detach().cpu().numpy(), moving=False)
+        return dict(class_name=cls, iterations=int(eng.t), slots=slots)
+
+    def get_optimizer_state(self):
+        """(m, v, iterations) of an Adam with m / v as {'<layer>/<key>': ndarray in Keras layout}, or None before the first training
+        step.  (get_optimizer_slots is the form for every class, and the one that carries AMSGrad's vhat.)"""
+        state = self.get_optimizer_slots()
+        if state is None:
+            return None
+        if state["class_name"] != "Adam":
+            raise TypeError("get_optimizer_state() is Adam's (m, v, iterations); this model trains with %s: use get_optimizer_slots()"
+                            % state["class_name"])
+        return state["slots"]["m"], state["slots"]["v"], state["iterations"]
 
     def _apply_optimizer_state(self, state):
+        """state: get_optimizer_slots' dict, or Adam's (m, v, iterations)"""
         eng = self._engine
         if eng is None or not eng.training:
             self._pending_opt = state
             return
         import torch
-        m, v, t = state
+        state = _as_slots(state)
+        cls = self._optimizer_class()
+        if state["class_name"] != cls:
+            raise ValueError("the saved optimizer state is %s's, the model is compiled with %s" % (state["class_name"], cls))
+        self._sync_optimizer(eng)
         Wz = eng.flat_to_keras(np.zeros(eng.n_flat, np.float32), moving=False)       # zeros for anything the state does not name
-        eng.M.copy_(torch.from_numpy(eng.keras_to_flat(dict(Wz, **m))))
-        eng.V.copy_(torch.from_numpy(eng.keras_to_flat(dict(Wz, **v))))
-        eng.t = int(t)
+        for name, buf in self._OPT_SLOTS[cls]:
+            if name in state["slots"] and getattr(eng, buf) is not None:
+                getattr(eng, buf).copy_(torch.from_numpy(eng.keras_to_flat(dict(Wz, **state["slots"][name]))))
+        eng.t = int(state["iterations"])
         self._pending_opt = None
+        self._opt_restored = True
 
     def save_weights(self, path):
         self.save(path, include_optimizer=False, weights_only=True)
 
     def _checkpoint_meta(self):
-        return dict(format="fmri-npz-1", builder=self._builder, builder_kwargs=_jsonable(self._builder_kwargs),
+        meta = dict(format="fmri-npz-1", builder=self._builder, builder_kwargs=_jsonable(self._builder_kwargs),
                     optimizer=self.optimizer.get_config() if self.optimizer else None,
                     loss=getattr(self.loss, "__name__", None),
                     metrics=[m if isinstance(m, str) else getattr(m, "__name__", str(m)) for m in self.metrics])
+        if self.optimizer is not None and self._optimizer_class() != "Adam":
+            meta["optimizer_class"] = self._optimizer_class()         # (no key: Adam, as every earlier checkpoint)
+        return meta
 
     def save(self, path, include_optimizer=True, weights_only=False):
         """Full-model checkpoint in the reference's container: a Keras 2.2 HDF5 file (reference training.py:31-32 via ModelCheckpoint;
@@ -957,13 +991,13 @@ class Model(object):
         W = self.get_weights_dict()
         arrays = {"w/" + k: v for k, v in W.items()}
         meta = self._checkpoint_meta()
-        state = self.get_optimizer_state() if include_optimizer else None
+        state = self.get_optimizer_slots() if include_optimizer else None
         if state is not None:
-            for k, a in state[0].items():
-                arrays["opt_m/" + k] = a
-            for k, a in state[1].items():
-                arrays["opt_v/" + k] = a
-            meta["opt_t"] = state[2]
+            for slot, arrs in state["slots"].items():
+                for k, a in arrs.items():
+                    arrays["opt_%s/%s" % (slot, k)] = a
+            # (RMSprop: Keras 2.2.4 leaves `iterations` out of RMSprop.weights - the count resumes at 0 from either container)
+            meta["opt_t"] = 0 if state["class_name"] == "RMSprop" else state["iterations"]
         arrays["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
         with open(tmp, "wb") as f:
             np.savez(f, **arrays)
@@ -986,13 +1020,33 @@ class Model(object):
             z = np.load(path, allow_pickle=False)
             self.set_weights_dict(OrderedDict((k[2:], z[k]) for k in z.files if k.startswith("w/")))
             state = None
-            if any(k.startswith("opt_m/") for k in z.files):
-                t = int(json.loads(bytes(z["meta"]).decode()).get("opt_t", 0))
-                state = (OrderedDict((k[6:], z[k]) for k in z.files if k.startswith("opt_m/")),
-                         OrderedDict((k[6:], z[k]) for k in z.files if k.startswith("opt_v/")), t)
+            meta = json.loads(bytes(z["meta"]).decode())
+            cls = meta.get("optimizer_class", "Adam")
+            slots = OrderedDict()
+            for slot, _ in self._OPT_SLOTS.get(cls, ()):
+                pre = "opt_%s/" % slot
+                if any(k.startswith(pre) for k in z.files):
+                    slots[slot] = OrderedDict((k[len(pre):], z[k]) for k in z.files if k.startswith(pre))
+            if slots:
+                state = dict(class_name=cls, iterations=int(meta.get("opt_t", 0)), slots=slots)
+                if cls == "Adam" and "vhat" not in slots:              # plain Adam: (m, v, iterations), as keras_h5.read_optimizer gives it
+                    state = (slots["m"], slots["v"], state["iterations"])
+        if state is not None and _as_slots(state)["class_name"] != self._optimizer_class():
+            import warnings
+            warnings.warn("optimizer state of %s not restored (it is %s's, the model is compiled with %s): the optimizer starts fresh"
+                          % (path, _as_slots(state)["class_name"], self._optimizer_class()))
+            state = None
         if state is not None:
             self._apply_optimizer_state(state)
         return self
+
+
+def _as_slots(state):
+    """Adam's (m, v, iterations) in the form of Model.get_optimizer_slots (which passes through, as None does)"""
+    if state is None or isinstance(state, dict):
+        return state
+    m, v, t = state
+    return dict(class_name="Adam", iterations=int(t), slots=OrderedDict((("m", m), ("v", v))))
 
 
 def read_checkpoint_meta(path):
@@ -1007,7 +1061,8 @@ def read_checkpoint_meta(path):
             raise ValueError("%s is a weights-only HDF5 file (no model_config): build the model and call load_weights" % path)
         name, kwargs = keras_h5.infer_builder(mc, tc)
         opt = tc["optimizer_config"]["config"] if tc else None
-        return dict(format="keras-h5", builder=name, builder_kwargs=kwargs, optimizer=opt)
+        return dict(format="keras-h5", builder=name, builder_kwargs=kwargs, optimizer=opt,
+                    optimizer_class=tc["optimizer_config"]["class_name"] if tc else "Adam")
     z = np.load(path, allow_pickle=False)
     return json.loads(bytes(z["meta"]).decode())
 

@@ -9,7 +9,8 @@ LAYOUT of keras/engine/saving.py (Keras 2.2.x - the version the reference's API 
   /model_weights         attrs: layer_names [S], backend, keras_version
      /<layer>            attrs: weight_names [S]  e.g. conv3d_1/kernel:0, conv3d_1/bias:0
         /<layer>/kernel:0   dataset (k1,k2,k3,Cin,Cout) float32      (Conv3DTranspose: (k1,k2,k3,Cout,Cin))
-  /optimizer_weights     attrs: weight_names [S]; datasets: Adam iterations (int64 scalar), then m per trainable weight, then v
+  /optimizer_weights     attrs: weight_names [S]; datasets: `optimizer.weights` by position - Adam: iterations (int64 scalar), then m per
+                         trainable weight, then v, then vhat; SGD: iterations, then the moments; RMSprop: the accumulators alone
 A weights-only file (`save_weights`) is the /model_weights group placed at the root.
 
 Writing: the files are meant to open in Keras 2.2 (`load_model(..., custom_objects=...)`, `load_weights`) - the layer configs below
@@ -152,12 +153,22 @@ def _fn_name(f):
     return f if isinstance(f, str) else getattr(f, "__name__", str(f))
 
 
+def optimizer_config(model):
+    """Keras' {"class_name", "config"} of the compiled optimizer: the full config of this package's Adam / SGD / RMSprop (clipnorm and
+    clipvalue only when set, as Keras writes them); any other object is recorded as the Adam it is stepped as"""
+    from .optimizers import Optimizer
+    opt = model.optimizer
+    if isinstance(opt, Optimizer):
+        return {"class_name": type(opt).__name__, "config": opt.keras_config()}
+    opt = opt.get_config() if opt is not None else {}
+    return {"class_name": "Adam",
+            "config": {"lr": float(np.float32(opt.get("lr", 0.001))), "beta_1": float(np.float32(opt.get("beta_1", 0.9))),
+                       "beta_2": float(np.float32(opt.get("beta_2", 0.999))), "decay": 0.0,
+                       "epsilon": float(opt.get("epsilon", 1e-7)), "amsgrad": False}}
+
+
 def training_config(model):
-    opt = model.optimizer.get_config() if model.optimizer is not None else {}
-    return {"optimizer_config": {"class_name": "Adam",
-                                 "config": {"lr": float(np.float32(opt.get("lr", 0.001))), "beta_1": float(np.float32(opt.get("beta_1", 0.9))),
-                                            "beta_2": float(np.float32(opt.get("beta_2", 0.999))), "decay": 0.0,
-                                            "epsilon": float(opt.get("epsilon", 1e-7)), "amsgrad": False}},
+    return {"optimizer_config": optimizer_config(model),
             "loss": _fn_name(model.loss), "metrics": [_fn_name(m) for m in model.metrics], "sample_weight_mode": None, "loss_weights": None}
 
 
@@ -224,9 +235,9 @@ def save_model(model, path, include_optimizer=True, weights_only=False, extra_me
         g.close()
         if model.optimizer is not None and model.loss is not None:
             f.attrs["training_config"] = json.dumps(training_config(model)).encode("utf8")
-        state = model.get_optimizer_state() if include_optimizer else None
+        state = model.get_optimizer_slots() if include_optimizer else None
         if state is not None:
-            m, v, t = state
+            cls, t, slots = state["class_name"], state["iterations"], state["slots"]
             og = f.create_group("optimizer_weights")
             keys = trainable_keys(model)
             # Keras 2.2.x Adam.weights = [iterations] + ms + vs + vhats (keras/optimizers.py Adam.get_updates): the slots are anonymous
@@ -236,15 +247,22 @@ def save_model(model, path, include_optimizer=True, weights_only=False, extra_me
             # them BY POSITION (optimizer.set_weights), so the count - 1 + 3n - is what has to be right for a file written here to
             # resume there; the names only have to be unique.  (No Keras exists in this image: the golden file this layout is tested
             # against, tests/golden/keras_like_golden.h5, is generated by this repository's own restatement of Keras' saving sequence.)
+            # SGD.weights = [iterations] + moments; RMSprop.weights = accumulators - Keras 2.2.4 leaves `iterations` out of it, so a
+            # resumed RMSprop counts from 0 again (it matters to `decay` only).
             n = len(keys)
-            var = lambda i: "training/Adam/Variable%s:0" % ("" if i == 0 else "_%d" % i)
-            names = ["Adam/iterations:0"] + [var(i) for i in range(3 * n)]
+            groups = [slots[name] for name in slots]
+            if cls == "Adam" and "vhat" not in slots:
+                groups.append(dict((k, np.zeros((1,), np.float32)) for k in keys))
+            var = lambda i: "training/%s/Variable%s:0" % (cls, "" if i == 0 else "_%d" % i)
+            names = ([] if cls == "RMSprop" else ["%s/iterations:0" % cls]) + [var(i) for i in range(len(groups) * n)]
             _set_list_attr(og, "weight_names", [n_.encode() for n_ in names])
-            og.create_dataset(names[0], data=np.int64(t)).close()
+            at = 0
+            if cls != "RMSprop":
+                og.create_dataset(names[0], data=np.int64(t)).close()
+                at = 1
             for i, k in enumerate(keys):
-                og.create_dataset(names[1 + i], data=np.asarray(m[k], np.float32)).close()
-                og.create_dataset(names[1 + n + i], data=np.asarray(v[k], np.float32)).close()
-                og.create_dataset(names[1 + 2 * n + i], data=np.zeros((1,), np.float32)).close()
+                for gi, grp in enumerate(groups):
+                    og.create_dataset(names[at + gi * n + i], data=np.asarray(grp[k], np.float32)).close()
             og.close()
 
 
@@ -292,7 +310,10 @@ def map_weights(model, file_layers):
 
 
 def read_optimizer(path, model):
-    """-> (m dict, v dict, iterations) keyed like trainable_keys(model), or None when the file has no optimizer state"""
+    """-> the state of the optimizer class named in the file's training_config (Adam where there is none), or None when the file has no
+    optimizer state.  A plain Adam gives (m dict, v dict, iterations) keyed like trainable_keys(model), as ever; SGD, RMSprop and an Adam
+    with parameter-shaped vhats give dict(class_name, iterations, slots) as Model.get_optimizer_slots does.  ValueError: a class this
+    package does not step, or a slot count / shape that is not that class's."""
     with hdf5.File(path) as f:
         if "optimizer_weights" not in f:
             return None
@@ -300,27 +321,41 @@ def read_optimizer(path, model):
         names = _get_list_attr(og, "weight_names")
         arrays = [np.asarray(og[n][()]) for n in names]
         og.close()
+    tc = read_configs(path)[1]
+    cls = tc["optimizer_config"]["class_name"] if tc else "Adam"
     keys = trainable_keys(model)
     n = len(keys)
     short = [nm.rsplit("/", 1)[-1].split(":")[0] for nm in names]
-    if all(("m_" + k) in short and ("v_" + k) in short for k in keys):
+    if cls == "Adam" and all(("m_" + k) in short and ("v_" + k) in short for k in keys):
         # files of this package's first format: slots named after their parameter
         at = dict(zip(short, arrays))
         it = [a for nm, a in zip(short, arrays) if nm == "iterations"]
         return (OrderedDict((k, at["m_" + k]) for k in keys), OrderedDict((k, at["v_" + k]) for k in keys), int(it[0]) if it else 0)
-    # Keras layout, by position: [iterations] + ms + vs (+ one shape-(1,) vhat placeholder per parameter when amsgrad=False, or
-    # parameter-shaped vhats when amsgrad=True - ignored either way: this engine's Adam has no amsgrad)
-    if len(arrays) not in (1 + 2 * n, 1 + 3 * n):
-        raise ValueError("optimizer_weights holds %d arrays, expected 1 + 2 x %d or 1 + 3 x %d (Keras Adam)" % (len(arrays), n, n))
-    t = int(np.asarray(arrays[0]).reshape(-1)[0])
-    m = OrderedDict(zip(keys, arrays[1:1 + n]))
-    v = OrderedDict(zip(keys, arrays[1 + n:1 + 2 * n]))
+    # Keras layouts, by position.  Adam: [iterations] + ms + vs (+ vhats: parameter-shaped with amsgrad=True, one shape-(1,) placeholder
+    # per parameter without - those are dropped); SGD: [iterations] + moments; RMSprop: the accumulators alone
+    layouts = {"Adam": (1, ("m", "v", "vhat"), (1 + 2 * n, 1 + 3 * n)), "SGD": (1, ("moments",), (1 + n,)),
+               "RMSprop": (0, ("accumulators",), (n,))}
+    if cls not in layouts:
+        raise ValueError("optimizer_weights of a %s optimizer: this package steps %s" % (cls, ", ".join(sorted(layouts))))
+    lead, slot_names, counts = layouts[cls]
+    if len(arrays) not in counts:
+        raise ValueError("optimizer_weights holds %d arrays, expected %s for %d trainable weights (Keras %s)"
+                         % (len(arrays), " or ".join(str(c) for c in counts), n, cls))
+    t = int(np.asarray(arrays[0]).reshape(-1)[0]) if lead else 0
     shapes = weight_shapes(model)
-    for k in keys:
-        for slot, a in (("m", m[k]), ("v", v[k])):
+    slots = OrderedDict()
+    for si, slot in enumerate(slot_names):
+        part = arrays[lead + si * n:lead + (si + 1) * n]
+        placeholders = slot == "vhat" and all(tuple(a.shape) == (1,) for a in part) and any(tuple(shapes[k]) != (1,) for k in keys)
+        if len(part) < n or placeholders:
+            continue
+        for k, a in zip(keys, part):
             if tuple(a.shape) != tuple(shapes[k]):
                 raise ValueError("optimizer slot %s of %s has shape %s, the parameter has %s" % (slot, k, tuple(a.shape), tuple(shapes[k])))
-    return m, v, t
+        slots[slot] = OrderedDict(zip(keys, part))
+    if cls == "Adam" and "vhat" not in slots:
+        return slots["m"], slots["v"], t
+    return dict(class_name=cls, iterations=t, slots=slots)
 
 
 def read_configs(path):

@@ -40,8 +40,10 @@ class NormNetModel(Model):
             if self._pending_weights is not None:
                 self._engine.load_keras_weights(self._pending_weights)
                 self._pending_weights = None
+            self._sync_optimizer(self._engine)
             if getattr(self, "_pending_opt", None) is not None:
                 self._apply_optimizer_state(self._pending_opt)
+        self._sync_optimizer(self._engine)
         self._engine.set_batch(batch)
         self._set_label_metrics(self._engine)
         if self.loss is not None:

@@ -53,6 +53,25 @@ def _model_from_config(config):
         mask_shape=config["input_shape"] if config["weight_mask"] is not None else None))
 
 
+def _restore_optimizer(model, meta):
+    """the optimizer a checkpoint names, rebuilt from its config in front of load_weights (which then holds the saved slots pending for
+    it).  A Keras optimizer this package does not step leaves the builder's fresh Adam, at the saved lr, behind a warning."""
+    from . import optimizers
+    config = meta.get("optimizer")
+    if not config:
+        return
+    name = meta.get("optimizer_class", "Adam")
+    try:
+        opt = optimizers.deserialize({"class_name": name, "config": config})
+    except ValueError:
+        import warnings
+        warnings.warn("the checkpoint was trained with %s, which this package does not step: training continues with a fresh Adam"
+                      % name, UserWarning)
+        model.optimizer.lr = float(config["lr"])
+        return
+    model.optimizer = opt
+
+
 def load_old_model(model_file, verbose=True, config=None) -> Model:
     """Re-open a checkpoint: Keras-2.2 HDF5 files (the reference's ModelCheckpoint output, or `Model.save` of this package) are rebuilt
     from their `model_config`; when the header cannot be used and the run's `config` is given, the model is rebuilt from the config and
@@ -63,9 +82,8 @@ def load_old_model(model_file, verbose=True, config=None) -> Model:
     try:
         meta = read_checkpoint_meta(model_file)
         model = _builder_call(meta["builder"], meta["builder_kwargs"])
+        _restore_optimizer(model, meta)
         model.load_weights(model_file)
-        if meta.get("optimizer"):
-            model.optimizer.lr = float(meta["optimizer"]["lr"])
         return model
     except (ValueError, KeyError, OSError) as error:
         print(error)

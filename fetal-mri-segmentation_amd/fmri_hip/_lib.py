@@ -107,6 +107,11 @@ SIGNATURES = {
     "fmri_slice_channels": [p, i32, i32, p, i32, i64, i32, i32, p],
     "fmri_channel_scale": [p, p, p, i32, i64, i32, i32, p],
     "fmri_adam_step": [p, p, p, p, i64, f32, f32, f32, f32, f32, p],
+    "fmri_grad_sumsq_workspace_bytes": [],
+    "fmri_grad_sumsq": [p, i64, f32, p, p, p],
+    "fmri_sgd_step": [p, p, p, i64, f32, f32, i32, f32, p, f32, f32, p],
+    "fmri_rmsprop_step": [p, p, p, i64, f32, f32, f32, f32, p, f32, f32, p],
+    "fmri_adam_step_ex": [p, p, p, p, p, i64, f32, f32, f32, f32, f32, p, f32, f32, p],
     "fmri_set_deterministic": [p, p, i64],
     "fmri_deterministic_finish": [p, p, i64, p],
     "fmri_set_deterministic_scratch": [p, i64],

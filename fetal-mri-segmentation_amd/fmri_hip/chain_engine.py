@@ -3,7 +3,7 @@
     x -> norm net (LayerGraphEngine with a linear output) -> logits, fp32 -> cast to the segmenter's dtype -> segmenter -> loss
 
 One training step: norm forward; cast; segmenter forward + loss; segmenter backward(params=False), which ends in dL/d(its input);
-that gradient is the `dprobs` of the norm net's backward(seg_loss=False); Adam on the norm net only.  Nothing of the segmenter moves: its
+that gradient is the `dprobs` of the norm net's backward(seg_loss=False); the optimizer steps the norm net only.  Nothing of the segmenter moves: its
 P, M, V, t and BatchNormalization moving statistics are bit-identical after any number of steps.
 
 Frozen-segmenter semantics (the precedent of fetal_net.adversarial.CombinedModel, and Keras 2.2 under learning phase 1 with
@@ -50,6 +50,8 @@ class ChainEngine(object):
     G = property(lambda self: self.norm.G)
     M = property(lambda self: self.norm.M)
     V = property(lambda self: self.norm.V)
+    Vhat = property(lambda self: self.norm.Vhat)
+    opt = property(lambda self: self.norm.opt)
     n_flat = property(lambda self: self.norm.n_flat)
     N = property(lambda self: self.norm.N)
     logits = property(lambda self: self.seg.logits)
@@ -80,6 +82,12 @@ class ChainEngine(object):
 
     def adam_step(self, lr, **kw):
         self.norm.adam_step(lr, **kw)
+
+    def set_optimizer(self, spec=None):
+        self.norm.set_optimizer(spec)
+
+    def optimizer_step(self, lr, **kw):
+        self.norm.optimizer_step(lr, **kw)
 
     @staticmethod
     def metrics_from_sums(s, smooth=1.0, loss_kind=0, loss_param=1.0):
@@ -123,5 +131,5 @@ class ChainEngine(object):
         self.forward(x)
         self.seg.loss_forward(y_true, weight)
         self.backward(y_true, grad_scale=(self.dist.grad_scale if self.dist is not None else 1.0), weight=weight)
-        self.norm.adam_step(lr)
+        self.norm.optimizer_step(lr)
         return self.seg.sums

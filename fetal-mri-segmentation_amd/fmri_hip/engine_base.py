@@ -1,10 +1,11 @@
 """What the two engines share: `UNetEngine` (engine.py, the hand-scheduled U-Net) and `LayerGraphEngine` (graph_engine.py, the layer-graph
 interpreter) differ in how they schedule a step, not in what surrounds the schedule.
 
-`EngineBase` holds that part: the flat fp32 parameter store (P, its gradient G and the Adam moments M / V, all in the engine's `layout`),
-the loss head (sigmoid + metric sums, the seg-loss gradient), Keras Adam, Keras weight export / import and the weight-gradient side
-stream.  An engine sets `layout` / `n_flat` and calls `_alloc_params`, keeps `logits` / `probs` / `dlogits` / `_dummy_y` of the current
-batch, and provides `forward`, `backward`, `refresh_weight_copies`, `keras_to_flat` and `flat_to_keras`.
+`EngineBase` holds that part: the flat fp32 parameter store (P, its gradient G and the optimizer slots M / V, all in the engine's `layout`),
+the loss head (sigmoid + metric sums, the seg-loss gradient), the Keras optimizers (Adam by default; SGD, RMSprop, AMSGrad and gradient
+clipping through set_optimizer: one launch per step for each), Keras weight export / import and the weight-gradient side stream.  An
+engine sets `layout` / `n_flat` and calls `_alloc_params`, keeps `logits` / `probs` / `dlogits` / `_dummy_y` of the current batch, and
+provides `forward`, `backward`, `refresh_weight_copies`, `keras_to_flat` and `flat_to_keras`.
 
 `read_switches` is the one place where the engines look at their FMRI_* environment switches: once, in `__init__`, into `self.sw`.  Buffers
 are sized and kernel routes planned from those values, so a switch that changes afterwards changes nothing (nor under a captured hipGraph).
@@ -70,6 +71,14 @@ def reserve_deterministic_scratch(nbytes, dev):
     ops.set_deterministic_scratch(_DET_SCRATCH[0])
 
 
+# The optimizer of EngineBase.optimizer_step: Keras 2.2.4's Adam / SGD / RMSprop with their argument names (keras/optimizers.py as
+# published; parity-unpinned, see include/fmri_hip.h).  The default is the plain Adam every builder compiles with.
+DEFAULT_OPTIMIZER = dict(kind="adam", beta_1=0.9, beta_2=0.999, epsilon=1e-7, decay=0.0, amsgrad=False,      # adam
+                         momentum=0.0, nesterov=False,                                                       # sgd
+                         rho=0.9,                                                                            # rmsprop (epsilon, decay: above)
+                         clipnorm=0.0, clipvalue=0.0)
+
+
 class EngineBase(object):
     def __init__(self, dtype, device, training, dist_ctx, frozen=False, **switches):
         """switches: the engine's own FMRI_* switches and their defaults (read_switches), next to FMRI_WGRAD_STREAM and FMRI_DETERMINISTIC
@@ -85,8 +94,11 @@ class EngineBase(object):
         # norm_net_model): it writes no parameter gradient anybody reads, so it takes no registration, but it runs the ordered routes.
         self.deterministic = bool(training and self.dev.type == "cuda" and self.sw["DETERMINISTIC"])
         self.frozen = bool(frozen)
-        self.t = 0                       # Adam step counter
+        self.t = 0                       # optimizer step counter (Keras' `iterations`)
         self.beta1 = 0.9                 # Adam's beta_1 when adam_step is given none (fetal_net.adversarial sets the optimizer's)
+        self.opt = dict(DEFAULT_OPTIMIZER)            # what optimizer_step runs (set_optimizer)
+        self.Vhat = None                              # AMSGrad's running maximum of V: allocated by set_optimizer when asked for
+        self._gnorm_work = self._gnorm = None         # clipnorm: workspace and {sum of squares, norm} of ops.grad_sumsq
         self.loss_kind, self.loss_param = 0, 1.0      # ops.LOSS_KINDS: 0 = dice_coefficient_loss
         # the weight gradients run on their own stream (FMRI_WGRAD_STREAM=0: on the main stream)
         self._wg_stream = torch.cuda.Stream(device=self.dev) if (training and self.dev.type == "cuda" and self.sw["WGRAD_STREAM"]) else None
@@ -228,14 +240,65 @@ class EngineBase(object):
         ops.adam_step(self.P, self.G, self.M, self.V, lr_t, beta1, beta2, eps, grad_scale)
         self.refresh_weight_copies()
 
+    def set_optimizer(self, spec=None):
+        """spec: the keys of DEFAULT_OPTIMIZER that differ from it (fetal_net.optimizers' objects give theirs; None = the default, plain
+        Adam).  SGD keeps its moments in M, RMSprop its accumulators in V, AMSGrad gets a third buffer Vhat; the sum-of-squares workspace
+        and its two float64 results exist only with clipnorm > 0.  A change of the optimizer kind starts the slots and the step count
+        afresh."""
+        spec = dict(spec or {})
+        unknown = sorted(set(spec) - set(DEFAULT_OPTIMIZER))
+        if unknown:
+            raise ValueError("optimizer spec: unknown key(s) %s" % ", ".join(unknown))
+        opt = dict(DEFAULT_OPTIMIZER, **spec)
+        if opt["kind"] not in ("adam", "sgd", "rmsprop"):
+            raise ValueError("optimizer kind %r (this engine steps adam, sgd and rmsprop)" % (opt["kind"],))
+        for k in ("clipnorm", "clipvalue"):                   # Keras: a clip argument that is not > 0 is off
+            opt[k] = float(opt[k]) if opt[k] is not None and float(opt[k]) > 0.0 else 0.0
+        if self.training and opt["kind"] != self.opt["kind"]:
+            self.M.zero_()
+            self.V.zero_()
+            self.t = 0
+        if opt["kind"] == "adam":
+            self.beta1 = float(opt["beta_1"])
+        if self.training and opt["kind"] == "adam" and opt["amsgrad"] and self.Vhat is None:
+            self.Vhat = torch.zeros_like(self.P)
+        if self.training and opt["clipnorm"] > 0.0 and self._gnorm is None:
+            self._gnorm_work, self._gnorm = ops.grad_sumsq_workspace(self.dev)
+        self.opt = opt
+
+    def optimizer_step(self, lr, grad_scale=1.0):
+        """one optimizer launch over the flat buffers, after backward() - which ends with the deterministic finish and the data-parallel
+        all-reduce, so the norm below is that of the reduced gradient on every rank.  Plain Adam (the default) is adam_step: the one
+        fmri_adam_step launch.  `decay` is Keras': step k (1-based) runs at lr / (1 + decay * (k - 1))."""
+        o = self.opt
+        if o["decay"] > 0.0:
+            lr = lr / (1.0 + o["decay"] * self.t)
+        clips = o["clipnorm"] > 0.0 or o["clipvalue"] > 0.0
+        if o["kind"] == "adam" and not o["amsgrad"] and not clips:
+            return self.adam_step(lr, beta2=o["beta_2"], eps=o["epsilon"], grad_scale=grad_scale)
+        gnorm = None
+        if o["clipnorm"] > 0.0:
+            gnorm = ops.grad_sumsq(self.G, grad_scale, self._gnorm_work, self._gnorm)
+        clip = dict(grad_scale=grad_scale, gnorm=gnorm, clipnorm=o["clipnorm"], clipvalue=o["clipvalue"])
+        self.t += 1
+        if o["kind"] == "sgd":
+            ops.sgd_step(self.P, self.G, self.M, lr, o["momentum"], o["nesterov"], **clip)
+        elif o["kind"] == "rmsprop":
+            ops.rmsprop_step(self.P, self.G, self.V, lr, o["rho"], o["epsilon"], **clip)
+        else:
+            lr_t = lr * math.sqrt(1.0 - o["beta_2"] ** self.t) / (1.0 - self.beta1 ** self.t)
+            ops.adam_step_ex(self.P, self.G, self.M, self.V, self.Vhat if o["amsgrad"] else None, lr_t, self.beta1, o["beta_2"], o["epsilon"],
+                             **clip)
+        self.refresh_weight_copies()
+
     def train_step(self, x, y_true, lr, weight=None):
-        """one full step: forward, Dice, backward, (all-reduce), Adam.  Returns the device tensor of metric sums."""
+        """one full step: forward, Dice, backward, (all-reduce), optimizer.  Returns the device tensor of metric sums."""
         self.forward(x)
         self.loss_forward(y_true, weight)
         # data parallel: with the global-batch Dice sums the ranks' gradients are summed (scale 1); with per-rank losses
         # (global_dice=False) the all-reduce sum is turned into the mean by scaling each rank's loss gradient by 1/world
         self.backward(y_true, grad_scale=(self.dist.grad_scale if self.dist is not None else 1.0), weight=weight)
-        self.adam_step(lr)
+        self.optimizer_step(lr)
         return self.sums
 
     @staticmethod

@@ -257,6 +257,44 @@ def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0
           "fmri_adam_step")
 
 
+def grad_sumsq_workspace(device):
+    """the partial-sum workspace of grad_sumsq and its two float64 results {sum of squares, norm}: allocated once by the caller"""
+    return (torch.empty(lib().fmri_grad_sumsq_workspace_bytes() // 8, dtype=torch.float64, device=device),
+            torch.zeros(2, dtype=torch.float64, device=device))
+
+
+def grad_sumsq(g, grad_scale, work, out):
+    """out[0] = sum (float(grad_scale * g_i))^2 in float64 (compensated, ordered: the same bits every run), out[1] = its square root"""
+    _need_cuda(g, work, out)
+    check(lib().fmri_grad_sumsq(_p(g), g.numel(), float(grad_scale), _p(work), _p(out), _s()), "fmri_grad_sumsq")
+    return out
+
+
+def _gnorm_ptr(gnorm):
+    """device pointer to the norm (out[1] of grad_sumsq) from the 2-element result tensor, or 0"""
+    return 0 if gnorm is None else gnorm.data_ptr() + 8
+
+
+def sgd_step(p, g, m, lr, momentum=0.0, nesterov=False, grad_scale=1.0, gnorm=None, clipnorm=0.0, clipvalue=0.0):
+    """Keras SGD on flat buffers; gnorm: the result tensor of grad_sumsq (clipnorm reads its norm on the device) or None"""
+    _need_cuda(p, g, m, gnorm)
+    check(lib().fmri_sgd_step(_p(p), _p(g), _p(m), p.numel(), float(lr), float(momentum), int(bool(nesterov)), float(grad_scale),
+                              _gnorm_ptr(gnorm), float(clipnorm), float(clipvalue), _s()), "fmri_sgd_step")
+
+
+def rmsprop_step(p, g, a, lr, rho=0.9, eps=1e-7, grad_scale=1.0, gnorm=None, clipnorm=0.0, clipvalue=0.0):
+    _need_cuda(p, g, a, gnorm)
+    check(lib().fmri_rmsprop_step(_p(p), _p(g), _p(a), p.numel(), float(lr), float(rho), float(eps), float(grad_scale),
+                                  _gnorm_ptr(gnorm), float(clipnorm), float(clipvalue), _s()), "fmri_rmsprop_step")
+
+
+def adam_step_ex(p, g, m, v, vhat, lr_t, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, gnorm=None, clipnorm=0.0, clipvalue=0.0):
+    """adam_step with AMSGrad (vhat: a tensor, or None for none) and clipping"""
+    _need_cuda(p, g, m, v, vhat, gnorm)
+    check(lib().fmri_adam_step_ex(_p(p), _p(g), _p(m), _p(v), _p(vhat), p.numel(), float(lr_t), float(beta1), float(beta2), float(eps),
+                                  float(grad_scale), _gnorm_ptr(gnorm), float(clipnorm), float(clipvalue), _s()), "fmri_adam_step_ex")
+
+
 def tile_gather(vol, idx, patch, tiles):
     _need_cuda(vol, idx, tiles)
     X, Y, Z = vol.shape

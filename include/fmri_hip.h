@@ -398,6 +398,34 @@ int64_t fmri_norm_det_workspace_bytes(int N, int64_t V, int C, int per_instance)
 int fmri_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
                    float eps, float grad_scale, fmri_stream_t stream);
 
+/* ---- Keras 2.2.4 SGD / RMSprop / Adam with AMSGrad, and gradient clipping (keras/optimizers.py as published; restated without a Keras to
+ * run against: parity-unpinned).  One launch over the flat buffers each; n <= 0: FMRI_E_SHAPE, a buffer that is not 16-byte aligned (gnorm:
+ * 8-byte): FMRI_E_ALIGN - nothing is launched then.  Plain Adam stays on fmri_adam_step.
+ * The gradient every update sees (Optimizer.get_gradients, clip_norm), in fp32, left to right:
+ *     g = grad_scale * G[i]
+ *     gnorm != NULL and clipnorm > 0 and norm >= clipnorm:   g = g * clipnorm / norm       norm = (float)*gnorm, read on the device
+ *     clipvalue > 0:                                         g = min(max(g, -clipvalue), clipvalue)
+ *   gnorm points at out[1] of fmri_grad_sumsq, enqueued in front on the same stream; a zero norm clips nothing and divides nothing.
+ * fmri_sgd_step      v = momentum * m - lr * g;  m <- v;  p <- p + v, or with nesterov != 0  p <- p + momentum * v - lr * g (that
+ *                    increment is formed in float64 and rounded once: its two terms cancel where momentum and gradient oppose)
+ * fmri_rmsprop_step  a <- rho * a + (1 - rho) * g^2;  p <- p - lr * g / (sqrt(a) + eps)
+ * fmri_adam_step_ex  fmri_adam_step's update; vhat != NULL (AMSGrad): vhat <- max(vhat, v), p <- p - lr_t * m / (sqrt(vhat) + eps).
+ *                    With vhat, gnorm NULL and clipvalue 0 it gives fmri_adam_step's bits.
+ * lr (lr_t for Adam) carries Keras' `decay` and Adam's bias correction, both computed by the host.
+ * fmri_grad_sumsq: out[0] (device, float64) = sum over i of (float(grad_scale * g[i]))^2, out[1] = sqrt(out[0]).  The squares are exact
+ *   in float64; they are added in Neumaier's compensated form in an order fixed by n (two launches, no atomics, as fmri_moments_f64): a
+ *   few ulp from the exact sum, and the same bits on every run and stream - also what FMRI_DETERMINISTIC=1 uses.  workspace:
+ *   fmri_grad_sumsq_workspace_bytes() bytes on the device, 8-byte aligned, any contents.  NULL pointer or n <= 0: FMRI_E_SHAPE; g not
+ *   16-byte or out / workspace not 8-byte aligned: FMRI_E_ALIGN. */
+int64_t fmri_grad_sumsq_workspace_bytes(void);
+int fmri_grad_sumsq(const float* g, int64_t n, float grad_scale, void* workspace, double* out, fmri_stream_t stream);
+int fmri_sgd_step(float* p, const float* g, float* m, int64_t n, float lr, float momentum, int nesterov, float grad_scale,
+                  const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream);
+int fmri_rmsprop_step(float* p, const float* g, float* a, int64_t n, float lr, float rho, float eps, float grad_scale,
+                      const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream);
+int fmri_adam_step_ex(float* p, const float* g, float* m, float* v, float* vhat, int64_t n, float lr_t, float beta1, float beta2,
+                      float eps, float grad_scale, const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream);
+
 /* ---- sliding-window overlap-add — reference prediction.py:98-114 (batch_iterator/get_patch_from_3d_data), :188-193, :210.
  * vol fp32 [X][Y][Z] (already padded by the host as prediction.py:138-146); idx int32 [B][3] device; tiles out (dtype)
  * [B][px][py][pz] (C = 1, NDHWC == NCDHW). */
