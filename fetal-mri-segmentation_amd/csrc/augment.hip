@@ -26,6 +26,36 @@ struct AffineB {                        // per patch of a launch: the volume, it
     float cval[AFF_MAXB];
     Affine34 A[AFF_MAXB];
 };
+// (cx, cy, cz) = A . (pi, pj, pk, 1), the products fused in a WRITTEN-OUT order: left to the compiler's contraction, two kernels that share the
+// expression a0 pi + a1 pj + a2 pk + a3 can fuse different products and round the last bit of a coordinate differently.  The order is the
+// one k_affine_sample has always compiled to (its results do not move), and k_affine_sample_slices shares it bit for bit.
+__device__ __forceinline__ void affine_point(const Affine34& A, double pi, double pj, double pk, double& cx, double& cy, double& cz) {
+    cx = fma(A.a[2], pk, fma(A.a[1], pj, A.a[0] * pi)) + A.a[3];
+    cy = fma(A.a[6], pk, fma(A.a[4], pi, A.a[5] * pj)) + A.a[7];
+    cz = fma(A.a[10], pk, fma(A.a[8], pi, A.a[9] * pj)) + A.a[11];
+}
+// one source point (cx, cy, cz) of vol [X][Y][Z]
+template <typename TI>
+__device__ __forceinline__ float sample_at(const TI* __restrict__ vol, int X, int Y, int Z, double cx, double cy, double cz, int order, float cval) {
+    float v = cval;
+    if (cx >= 0.0 && cx <= (double)(X - 1) && cy >= 0.0 && cy <= (double)(Y - 1) && cz >= 0.0 && cz <= (double)(Z - 1)) {
+        if (order == 0) {
+            const int ix = (int)floor(cx + 0.5), iy = (int)floor(cy + 0.5), iz = (int)floor(cz + 0.5);
+            v = ld_any<TI>(vol, ((int64_t)ix * Y + iy) * Z + iz);
+        } else {
+            const int ix = (int)floor(cx), iy = (int)floor(cy), iz = (int)floor(cz);
+            const double fx = cx - ix, fy = cy - iy, fz = cz - iz;
+            const int jx = min(ix + 1, X - 1), jy = min(iy + 1, Y - 1), jz = min(iz + 1, Z - 1);
+            auto at = [&](int a, int b, int c) { return (double)ld_any<TI>(vol, ((int64_t)a * Y + b) * Z + c); };
+            const double c00 = at(ix, iy, iz) * (1 - fz) + at(ix, iy, jz) * fz;
+            const double c01 = at(ix, jy, iz) * (1 - fz) + at(ix, jy, jz) * fz;
+            const double c10 = at(jx, iy, iz) * (1 - fz) + at(jx, iy, jz) * fz;
+            const double c11 = at(jx, jy, iz) * (1 - fz) + at(jx, jy, jz) * fz;
+            v = (float)((c00 * (1 - fy) + c01 * fy) * (1 - fx) + (c10 * (1 - fy) + c11 * fy) * fx);
+        }
+    }
+    return v;
+}
 template <typename TI, typename TO>
 __global__ void k_affine_sample(AffineB P, int nx, int ny, int nz, int order, TO* __restrict__ out, int ld, int64_t out_stride) {
     const int pb = blockIdx.y;
@@ -40,27 +70,43 @@ __global__ void k_affine_sample(AffineB P, int nx, int ny, int nz, int order, TO
         const int64_t q = t / nz;
         const int j = (int)(q % ny), i = (int)(q / ny);
         const double pi = x0 + i, pj = y0 + j, pk = z0 + k;
-        const double cx = A.a[0] * pi + A.a[1] * pj + A.a[2] * pk + A.a[3];
-        const double cy = A.a[4] * pi + A.a[5] * pj + A.a[6] * pk + A.a[7];
-        const double cz = A.a[8] * pi + A.a[9] * pj + A.a[10] * pk + A.a[11];
-        float v = cval;
-        if (cx >= 0.0 && cx <= (double)(X - 1) && cy >= 0.0 && cy <= (double)(Y - 1) && cz >= 0.0 && cz <= (double)(Z - 1)) {
-            if (order == 0) {
-                const int ix = (int)floor(cx + 0.5), iy = (int)floor(cy + 0.5), iz = (int)floor(cz + 0.5);
-                v = ld_any<TI>(vol, ((int64_t)ix * Y + iy) * Z + iz);
-            } else {
-                const int ix = (int)floor(cx), iy = (int)floor(cy), iz = (int)floor(cz);
-                const double fx = cx - ix, fy = cy - iy, fz = cz - iz;
-                const int jx = min(ix + 1, X - 1), jy = min(iy + 1, Y - 1), jz = min(iz + 1, Z - 1);
-                auto at = [&](int a, int b, int c) { return (double)ld_any<TI>(vol, ((int64_t)a * Y + b) * Z + c); };
-                const double c00 = at(ix, iy, iz) * (1 - fz) + at(ix, iy, jz) * fz;
-                const double c01 = at(ix, jy, iz) * (1 - fz) + at(ix, jy, jz) * fz;
-                const double c10 = at(jx, iy, iz) * (1 - fz) + at(jx, iy, jz) * fz;
-                const double c11 = at(jx, jy, iz) * (1 - fz) + at(jx, jy, jz) * fz;
-                v = (float)((c00 * (1 - fy) + c01 * fy) * (1 - fx) + (c10 * (1 - fy) + c11 * fy) * fx);
-            }
+        double cx, cy, cz;
+        affine_point(A, pi, pj, pk, cx, cy, cz);
+        st_any<TO>(out, q * ld + k, sample_at<TI>(vol, X, Y, Z, cx, cy, cz, order, cval));
+    }
+}
+
+// Inter-slice motion of a fetal stack (not in the reference): k_affine_sample with one in-plane rigid map PER OUTPUT SLICE, folded into the
+// gather - the moved slices are read from the volume once, with one interpolation.  tab: device fp64 [patches][nzt][6]; output slice k of
+// patch pb takes row r = k + z_off as (i', j') = (m0 i + m1 j + m2, m3 i + m4 j + m5) in PATCH coordinates, and the source point is
+// A . (corner + (i', j', k), 1).  A row outside [0, nzt) is the identity: z_off places the label / previous-truth slices (a sub-range of the
+// image's slices) under the image slice they belong to.  An identity row gives k_affine_sample's coordinates bit for bit (1 * i + 0 * j + 0).
+template <typename TI, typename TO>
+__global__ void k_affine_sample_slices(AffineB P, const double* __restrict__ tab, int nzt, int z_off, int nx, int ny, int nz, int order,
+                                       TO* __restrict__ out, int ld, int64_t out_stride) {
+    const int pb = blockIdx.y;
+    const TI* __restrict__ vol = static_cast<const TI*>(P.vol[pb]);
+    const int X = P.X[pb], Y = P.Y[pb], Z = P.Z[pb], x0 = P.x0[pb], y0 = P.y0[pb], z0 = P.z0[pb];
+    const float cval = P.cval[pb];
+    const Affine34& A = P.A[pb];
+    out += pb * out_stride;
+    tab += (int64_t)pb * nzt * 6;
+    const int64_t total = (int64_t)nx * ny * nz;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int k = (int)(t % nz);
+        const int64_t q = t / nz;
+        const int j = (int)(q % ny), i = (int)(q / ny);
+        const int r = k + z_off;
+        double ip = i, jp = j;
+        if (r >= 0 && r < nzt) {
+            const double* __restrict__ m = tab + 6 * r;
+            ip = m[0] * i + m[1] * j + m[2];
+            jp = m[3] * i + m[4] * j + m[5];
         }
-        st_any<TO>(out, q * ld + k, v);
+        const double pi = x0 + ip, pj = y0 + jp, pk = z0 + k;
+        double cx, cy, cz;
+        affine_point(A, pi, pj, pk, cx, cy, cz);
+        st_any<TO>(out, q * ld + k, sample_at<TI>(vol, X, Y, Z, cx, cy, cz, order, cval));
     }
 }
 
@@ -427,6 +473,81 @@ __global__ void __launch_bounds__(AUG_THREADS) k_rescale_ws(T* __restrict__ x, i
         }
     }
     __syncthreads();
+    emit_minmax(mn, mx, ws, stats);
+}
+
+// The acquisition effects of a fetal stack (not in the reference) on a dense patch [X][Y][Z], one launch, per voxel in this order:
+//   gamma        v = ((v - lo) / (hi - lo)) ^ g * (hi - lo) + lo on the patch's own range {lo, hi} = stats (hi == lo: left alone); g == 0 skips
+//   bias field   v = (v - vmin) * exp(P(x, y, z)) + vmin, P = sum of coef[t] x^a y^b z^c over a + b + c <= order in lexicographic (a, b, c)
+//                order, x, y, z in [-1, 1] across the patch (an axis of length 1 sits at 0); order == 0 skips
+//   slice gain   v = (v - vmin) * gain[k] + vmin for slice k; a null pointer skips
+// Gains are relative to vmin, the volume's minimum: the data are z-scored, the background is a NEGATIVE constant, and a coil or a spin
+// history scales signal, not background.  A patch that skips all three is not written; the others leave their new range in stats.
+constexpr int MRI_MAXT = 20;           // monomials of a cubic in three variables
+struct MriB {
+    float gamma[AUG_MAXB], vmin[AUG_MAXB];
+    int order[AUG_MAXB];
+    const float* gain[AUG_MAXB];
+    float coef[AUG_MAXB][MRI_MAXT];
+};
+template <typename T>
+__global__ void __launch_bounds__(AUG_THREADS) k_mri_intensity_ws(T* __restrict__ x, int X, int Y, int Z, int64_t stride, float* __restrict__ stats,
+                                                                  int* __restrict__ ws, MriB P) {
+    const int b = blockIdx.y;
+    const float g = P.gamma[b], vmin = P.vmin[b];
+    const int order = P.order[b];
+    const float* __restrict__ gain = P.gain[b];
+    if (g == 0.f && order == 0 && !gain) return;
+    x += b * stride;
+    ws += b * AUG_WS_INTS;
+    stats += b * 2;
+    const float lo = stats[0], span = stats[1] - stats[0];
+    const bool curve = g != 0.f && span > 0.f;
+    const float sx = X > 1 ? 2.f / (X - 1) : 0.f, sy = Y > 1 ? 2.f / (Y - 1) : 0.f, sz = Z > 1 ? 2.f / (Z - 1) : 0.f;
+    const float ox = X > 1 ? -1.f : 0.f, oy = Y > 1 ? -1.f : 0.f, oz = Z > 1 ? -1.f : 0.f;
+    const unsigned n = (unsigned)X * Y * Z;                    // < 2^31 (checked by the caller): 32-bit index arithmetic
+    float mn = INFINITY, mx = -INFINITY;
+    constexpr unsigned CH = 4 * AUG_THREADS;                   // four loads in flight per thread, as k_rescale_ws
+    for (unsigned c = blockIdx.x; (uint64_t)c * CH < n; c += gridDim.x) {
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint64_t t = (uint64_t)c * CH + k * AUG_THREADS + threadIdx.x;
+            v[k] = t < n ? to_f<T>(x[t]) : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint64_t t64 = (uint64_t)c * CH + k * AUG_THREADS + threadIdx.x;
+            if (t64 >= n) continue;
+            const unsigned t = (unsigned)t64, q = t / (unsigned)Z;
+            const int kz = (int)(t - q * (unsigned)Z), j = (int)(q % (unsigned)Y), i = (int)(q / (unsigned)Y);
+            float w = v[k];
+            if (curve) w = powf(fmaxf((w - lo) / span, 0.f), g) * span + lo;
+            if (order > 0) {
+                const float fx = i * sx + ox, fy = j * sy + oy, fz = kz * sz + oz;
+                float p = 0.f, xa = 1.f;
+                int term = 0;
+                for (int a = 0; a <= order; ++a, xa *= fx) {
+                    float yb = xa;
+                    for (int bb = 0; bb <= order - a; ++bb, yb *= fy) {
+                        float zc = yb;
+                        for (int cc = 0; cc <= order - a - bb; ++cc, zc *= fz) p = fmaf(P.coef[b][term++], zc, p);
+                    }
+                }
+                w = (w - vmin) * expf(p) + vmin;
+            }
+            if (gain) {
+                const float gk = gain[kz];
+                if (gk != 1.f) w = (w - vmin) * gk + vmin;     // a slice that was not chosen keeps its bits
+            }
+            const T o = from_f<T>(w);
+            x[t] = o;
+            const float r = to_f<T>(o);
+            mn = fminf(mn, r);
+            mx = fmaxf(mx, r);
+        }
+    }
+    __syncthreads();                                           // every thread has read stats before the last workgroup rewrites it
     emit_minmax(mn, mx, ws, stats);
 }
 
@@ -807,6 +928,58 @@ extern "C" int fmri_affine_sample_batch(int B, const void* const* vols, const in
     return FMRI_OK;
 }
 
+static int affine_sample_slices_launch(const AffineB& P, int B, const double* tab, int nzt, int z_off, int vol_dtype, int nx, int ny, int nz, int order,
+                                       void* out, int out_dtype, int out_ld, int64_t out_stride, hipStream_t st) {
+    const dim3 grid(grid_for((int64_t)nx * ny * nz), B);
+#define FMRI_AS(TI, TO) k_affine_sample_slices<TI, TO><<<grid, 256, 0, st>>>(P, tab, nzt, z_off, nx, ny, nz, order, (TO*)out, out_ld, out_stride)
+    if (vol_dtype == FMRI_F32 && out_dtype == FMRI_F32) FMRI_AS(float, float);
+    else if (vol_dtype == FMRI_F32 && out_dtype == FMRI_BF16) FMRI_AS(float, bf16_t);
+    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_U8) FMRI_AS(uint8_t, uint8_t);
+    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_F32) FMRI_AS(uint8_t, float);
+    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_BF16) FMRI_AS(uint8_t, bf16_t);
+    else return FMRI_E_DTYPE;
+#undef FMRI_AS
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+extern "C" int fmri_affine_sample_slices(const void* vol, int vol_dtype, int X, int Y, int Z, const double* affine, const double* table, int nz_table,
+                                         int z_off, int x0, int y0, int z0, int nx, int ny, int nz, int order, float cval, void* out, int out_dtype,
+                                         int out_ld, fmri_stream_t stream) {
+    if (X < 1 || Y < 1 || Z < 1 || nx < 1 || ny < 1 || nz < 1 || out_ld < nz || (order != 0 && order != 1) || !affine || !table || nz_table < 1)
+        return FMRI_E_SHAPE;
+    AffineB P;
+    P.vol[0] = vol;
+    P.X[0] = X; P.Y[0] = Y; P.Z[0] = Z; P.x0[0] = x0; P.y0[0] = y0; P.z0[0] = z0;
+    P.cval[0] = cval;
+    for (int i = 0; i < 12; ++i) P.A[0].a[i] = affine[i];
+    return affine_sample_slices_launch(P, 1, table, nz_table, z_off, vol_dtype, nx, ny, nz, order, out, out_dtype, out_ld, 0, as_stream(stream));
+}
+extern "C" int fmri_affine_sample_slices_batch(int B, const void* const* vols, const int* dims, const double* affines, const double* table, int nz_table,
+                                               int z_off, const int* corners, const float* cvals, int vol_dtype, int nx, int ny, int nz, int order,
+                                               void* out, int out_dtype, int out_ld, int64_t out_stride, fmri_stream_t stream) {
+    if (B < 1 || !vols || !dims || !affines || !table || nz_table < 1 || !corners || !cvals || nx < 1 || ny < 1 || nz < 1 || out_ld < nz ||
+        (order != 0 && order != 1))
+        return FMRI_E_SHAPE;
+    const int esz = out_dtype == FMRI_F32 ? 4 : (out_dtype == FMRI_BF16 ? 2 : 1);
+    for (int b0 = 0; b0 < B; b0 += AFF_MAXB) {
+        const int nb = B - b0 < AFF_MAXB ? B - b0 : AFF_MAXB;
+        AffineB P;
+        for (int b = 0; b < nb; ++b) {
+            const int g = b0 + b;
+            if (!vols[g] || dims[3 * g] < 1 || dims[3 * g + 1] < 1 || dims[3 * g + 2] < 1) return FMRI_E_SHAPE;
+            P.vol[b] = vols[g];
+            P.X[b] = dims[3 * g]; P.Y[b] = dims[3 * g + 1]; P.Z[b] = dims[3 * g + 2];
+            P.x0[b] = corners[3 * g]; P.y0[b] = corners[3 * g + 1]; P.z0[b] = corners[3 * g + 2];
+            P.cval[b] = cvals[g];
+            for (int i = 0; i < 12; ++i) P.A[b].a[i] = affines[12 * g + i];
+        }
+        const int rc = affine_sample_slices_launch(P, nb, table + (int64_t)b0 * nz_table * 6, nz_table, z_off, vol_dtype, nx, ny, nz, order,
+                                                   (char*)out + (int64_t)b0 * out_stride * esz, out_dtype, out_ld, out_stride, as_stream(stream));
+        if (rc != FMRI_OK) return rc;
+    }
+    return FMRI_OK;
+}
+
 extern "C" int fmri_minmax(const void* x, int64_t n, int dtype, float* out2, fmri_stream_t stream) {
     if (n < 1) return FMRI_E_SHAPE;
     hipStream_t st = as_stream(stream);
@@ -890,6 +1063,35 @@ extern "C" int fmri_rescale_intensity_ws_batch(void* x, int64_t n, int64_t strid
             k_rescale_ws<float><<<grid, AUG_THREADS, 0, st>>>(patch_ptr((float*)x, stride, b0), n, stride, stats + 2 * b0, ws + b0 * AUG_WS_INTS, P);
         else
             k_rescale_ws<bf16_t><<<grid, AUG_THREADS, 0, st>>>(patch_ptr((bf16_t*)x, stride, b0), n, stride, stats + 2 * b0, ws + b0 * AUG_WS_INTS, P);
+    }
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_mri_intensity_ws_batch(void* x, int X, int Y, int Z, int64_t stride, int B, int dtype, float* stats, int* ws, const float* params,
+                                           const float* const* gains, fmri_stream_t stream) {
+    if (X < 1 || Y < 1 || Z < 1 || (int64_t)X * Y * Z > 0x7fffffff || B < 1 || !x || !stats || !ws || !params) return FMRI_E_SHAPE;
+    if (dtype != FMRI_F32 && dtype != FMRI_BF16) return FMRI_E_DTYPE;
+    hipStream_t st = as_stream(stream);
+    const int64_t n = (int64_t)X * Y * Z;
+    FMRI_FOR_CHUNKS(B) {
+        MriB P;
+        for (int b = 0; b < AUG_MAXB; ++b) {
+            const float* q = params + FMRI_MRI_PARAMS * (b0 + (b < nb ? b : 0));
+            const int terms = b < nb ? (int)q[2] : 0;
+            if (terms != 0 && terms != 4 && terms != 10 && terms != 20) return FMRI_E_SHAPE;
+            if (!(q[0] >= 0.f)) return FMRI_E_SHAPE;
+            P.gamma[b] = b < nb ? q[0] : 0.f;
+            P.vmin[b] = q[1];
+            P.order[b] = terms == 20 ? 3 : (terms == 10 ? 2 : (terms == 4 ? 1 : 0));
+            P.gain[b] = (b < nb && gains) ? gains[b0 + b] : nullptr;
+            for (int t = 0; t < MRI_MAXT; ++t) P.coef[b][t] = t < terms ? q[3 + t] : 0.f;
+        }
+        const dim3 grid(grid_for(n, AUG_THREADS, AUG_BLOCKS), nb);
+        if (dtype == FMRI_F32)
+            k_mri_intensity_ws<float><<<grid, AUG_THREADS, 0, st>>>(patch_ptr((float*)x, stride, b0), X, Y, Z, stride, stats + 2 * b0, ws + b0 * AUG_WS_INTS, P);
+        else
+            k_mri_intensity_ws<bf16_t><<<grid, AUG_THREADS, 0, st>>>(patch_ptr((bf16_t*)x, stride, b0), X, Y, Z, stride, stats + 2 * b0, ws + b0 * AUG_WS_INTS, P);
     }
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;

@@ -31,13 +31,21 @@ The noise fields (normal, uniform and Poisson draws) are made inside the kernels
 on the host (every draw of the reference, in its order) and then LAUNCHED together, one launch per step of the chain (`_Sampler.plan` /
 `launch_batch`, previous-slice truth channels included); configurations the batch kernels do not cover (piecewise affine, the Gaussian
 filter, drop_easy_patches' interleaved draws) go patch by patch (`launch_one`) - same draws, same batches (tests/test_gpu_augment.py).
+
+Departures from the reference: four optional `augment` keys it does not have, the acquisition effects of a fetal stack of 2-D slices -
+slice_motion, gamma, bias_field, slice_intensity (fetal_net/augment.py: draw_mri_parameters and the float64 host forms).  There is no
+reference ordering to keep for them: their draws come from a generator of their own (seeded from `noise_seed`; numpy's global state, python's
+`random` and the imgaug state above are not advanced, so every other draw of a configuration stays what it was), slice motion rides inside
+the affine gather (one in-plane rigid map per slice, labels / mask / previous-slice truth under the image slice they belong to: no second
+resampling), and gamma, bias field and slice gain are ONE launch behind contrast / intensity_multiplication and before the filter and the
+noises - acquisition before noise.  A configuration without these keys draws nothing and launches nothing new.
 """
 import random
 import warnings
 
 import numpy as np
 
-from .augment import distort_image, draw_augment_parameters
+from .augment import MRI_KEYS, distort_image, draw_augment_parameters, draw_mri_parameters
 
 _UNSUPPORTED = ()                          # every augmenter of reference augment.py:222-377 is applied
 
@@ -158,6 +166,9 @@ class _Sampler(object):
         # imgaug keeps its own random state (the reference's numpy / python streams are not advanced by its draws): the grid sizes of the coarse
         # dropout come from a private host generator, everything per voxel from the device generator
         self.host_rng = np.random.RandomState(noise_seed)
+        # the fetal keys (slice_motion, gamma, bias_field, slice_intensity) draw from a third state: adding them moves no other draw
+        self.mri_rng = np.random.RandomState((int(noise_seed) ^ 0x4D5249) & 0xFFFFFFFF)
+        self.mri = augment is not None and any(augment.get(k) is not None for k in MRI_KEYS)
         if augment is not None:
             bad = [k for k in _UNSUPPORTED if augment.get(k) is not None]
             if bad:
@@ -179,7 +190,7 @@ class _Sampler(object):
         data, truth = ddf.data[index], ddf.truth[index]
         corner = [np.random.randint(low=0, high=h) for h in np.array(truth.shape) - np.array(ps)]
         q = {"index": index, "corner": corner, "corners": None, "elastic_seq": 0, "elastic_rng": True, "shot_seq": 0, "speckle_seq": 0,
-             "gaussian_seq": 0, "dropout_seq": 0, "grid": (1, 1)}
+             "gaussian_seq": 0, "dropout_seq": 0, "grid": (1, 1), "mri": None}
         if self.augment is not None:
             p = draw_augment_parameters(self.augment, 3, ddf.min[index], ddf.max[index])
             geo = dict(flip_axis=p["flip_axis"], scale_factor=p["scale_factor"], rotate_factor=p["rotate_factor"], translate_factor=p["translate_factor"])
@@ -206,6 +217,9 @@ class _Sampler(object):
             q["elastic_seq"] = self._next_seq() if q["elastic_rng"] else -1
         q["need_intensity"] = bool(p["contrast"] is not None or p["intensity_multiplication"] != 1 or p["apply_speckle_noise"] or p["apply_gaussian_noise"]
                                    or p["apply_gaussian_filter"] or p["apply_poisson_noise"] or p["coarse_dropout"])
+        if self.mri:
+            q["mri"] = draw_mri_parameters(self.augment, ps, self.mri_rng)
+            q["need_intensity"] = q["need_intensity"] or self._mri_intensity(q)
         if p["apply_poisson_noise"]:
             q["shot_seq"] = self._next_seq()
         if p["apply_speckle_noise"]:
@@ -217,6 +231,43 @@ class _Sampler(object):
             q["grid"] = _coarse_grid((ps[0], ps[1]), self.augment["coarse_dropout"]["size_percent"], self.host_rng)
             q["dropout_seq"] = self._next_seq()
         return q
+
+    @staticmethod
+    def _mri_intensity(q):
+        r = q["mri"]
+        return r is not None and (r["gamma"] != 0 or r["bias_coef"] is not None or r["slice_gain"] is not None)
+
+    def _upload(self, a):
+        """a small host array -> device on the current stream, through pinned memory: enqueue-only like the launches (a copy from pageable
+        memory would make the host wait for the stream)"""
+        return self.torch.from_numpy(a).pin_memory().to(self.ddf.device, non_blocking=True)
+
+    def _slice_tables(self, plans):
+        """the slice-motion tables of `plans` as ONE device tensor (B, slices, 6) float64 (identity rows for a patch that drew none), uploaded
+        on the current stream; None when no patch drew slice motion - the plain gathers are called then"""
+        if not any(q["mri"] is not None and q["mri"]["slice_table"] is not None for q in plans):
+            return None
+        tab = np.tile(np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0]), (len(plans), self.patch_shape[2], 1))
+        for b, q in enumerate(plans):
+            if q["mri"] is not None and q["mri"]["slice_table"] is not None:
+                tab[b] = q["mri"]["slice_table"]
+        return self._upload(tab)
+
+    def _mri_intensity_launch(self, plans, x, stats, ws):
+        """gamma, bias field and slice gain of `plans` on the dense image slices x (B, X, Y, slices): one launch, one upload for the gains"""
+        mri = [q["mri"] if self._mri_intensity(q) else None for q in plans]
+        if not any(r is not None for r in mri):
+            return
+        gains = None
+        if any(r is not None and r["slice_gain"] is not None for r in mri):
+            g = np.ones((len(plans), self.patch_shape[2]), dtype=np.float32)
+            for b, r in enumerate(mri):
+                if r is not None and r["slice_gain"] is not None:
+                    g[b] = r["slice_gain"]
+            gains = self._upload(g)
+        self.ops.mri_intensity_ws_batch(x, stats, ws, [0.0 if r is None else r["gamma"] for r in mri], [None if r is None else r["bias_coef"] for r in mri],
+                                        [gains[b] if r is not None and r["slice_gain"] is not None else None for b, r in enumerate(mri)],
+                                        [self.ddf.min[q["index"]] for q in plans])
 
     def sample_into(self, index, x_slot, y_slot, m_slot=None):
         """one patch: x_slot: float32 view (X, Y, n_chan) of the batch tensor; y_slot: uint8 view (X, Y, truth_size); m_slot: float32 view
@@ -258,11 +309,20 @@ class _Sampler(object):
             d = ops.elastic_fields_rng_batch((ps[0], ps[1]), [q["p"]["elastic_transform_scale"] if q["elastic_seq"] else 0.0 for q in plans],
                                              self.augment["elastic_transform"]["sigma"], self.seed, [q["elastic_seq"] for q in plans], device=x.device)
         corners_t = [(q["corner"][0], q["corner"][1], q["corner"][2] + self.truth_index) for q in plans]
+        table = self._slice_tables(plans)
+
+        def gather(vols, affines, corners, size, out, order, cvals, z_off, out_ld=None):
+            # some patch drew slice motion: the gather that moves output slice k by table row k + z_off (z_off: where `out` sits among the
+            # image slices); else the plain gather, called as ever
+            if table is None:
+                return ops.affine_sample_batch(vols, affines, corners, size, out, order, cvals, out_ld=out_ld)
+            return ops.affine_sample_slices_batch(vols, affines, corners, size, out, order, cvals, table, z_off, out_ld=out_ld)
+
         # image: trilinear, outside = the volume's minimum; labels: nearest, outside = 0 (identity affine = the plain crop)
         xt = target(xd, ps, torch.float32)
-        ops.affine_sample_batch([ddf.data[i] for i in idx], [q["A"] for q in plans], [q["corner"] for q in plans], ps, xt, 1, [ddf.min[i] for i in idx])
+        gather([ddf.data[i] for i in idx], [q["A"] for q in plans], [q["corner"] for q in plans], ps, xt, 1, [ddf.min[i] for i in idx], 0)
         yt = target(y, tshape, torch.uint8)
-        ops.affine_sample_batch([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_t, tshape, yt, 0, [0.0] * B)
+        gather([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_t, tshape, yt, 0, [0.0] * B, self.truth_index)
         if warped:
             ops.elastic_warp_batch(xt, d, 1, xd)
             ops.elastic_warp_batch(yt, d, 0, y)
@@ -270,7 +330,7 @@ class _Sampler(object):
             # augmented: outside the mask = 0 (interpolate_affine_range, cval 0); plain crop: edge values
             src = [ddf.mask[q["index"]] if q["p"] is not None else ddf.mask_for_crops(q["index"]) for q in plans]
             mt = target(m, tshape, torch.float32)
-            ops.affine_sample_batch(src, [q["Am"] for q in plans], corners_t, tshape, mt, 0, [0.0] * B)
+            gather(src, [q["Am"] for q in plans], corners_t, tshape, mt, 0, [0.0] * B, self.truth_index)
             if warped:
                 ops.elastic_warp_batch(mt, d, 0, m)
         if prev:
@@ -278,8 +338,8 @@ class _Sampler(object):
             corners_p = [(q["corner"][0], q["corner"][1], q["corner"][2] + self.prev_truth_index) for q in plans]
             xp = x[..., ps[2]:]
             pt = torch.empty((B,) + pshape, device=x.device, dtype=torch.float32) if warped else xp
-            ops.affine_sample_batch([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_p, pshape, pt, 0, [0.0] * B,
-                                    out_ld=None if warped else self.n_chan)
+            gather([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_p, pshape, pt, 0, [0.0] * B, self.prev_truth_index,
+                   out_ld=None if warped else self.n_chan)
             if warped:
                 ops.elastic_warp_batch(pt, d, 0, xp)
         if any(q["p"] is not None and q["need_intensity"] for q in plans):
@@ -303,6 +363,7 @@ class _Sampler(object):
                 params.append((2 if p["contrast"] is not None else 1, lo, hi, p["intensity_multiplication"]))
         if any(r[0] for r in params):
             ops.rescale_intensity_ws_batch(x, stats, ws, params)
+        self._mri_intensity_launch(plans, x, stats, ws)                  # acquisition effects: behind the reference's contrast, before its noises
         # order of reference augment.py:354-367: (gaussian filter,) shot (poisson) noise, speckle, gaussian noise; coarse dropout last
         if any(q["shot_seq"] for q in plans):
             ops.shot_noise_rng_batch(x, stats, ws, self.seed, [q["shot_seq"] for q in plans])
@@ -344,19 +405,26 @@ class _Sampler(object):
             if elastic is not None:
                 ops.elastic_warp(tmp, elastic[0], elastic[1], order, slot)
 
+        table = self._slice_tables([q])
+
+        def gather(vol, affine, start, size, out, order, cval, z_off, out_ld=None):
+            if table is None:
+                return ops.affine_sample(vol, affine, start, size, out, order=order, cval=cval, out_ld=out_ld)
+            return ops.affine_sample_slices(vol, affine, start, size, out, table[0], z_off, order=order, cval=cval, out_ld=out_ld)
+
         tshape = (ps[0], ps[1], self.truth_size)
         # image: trilinear, outside = the volume's minimum; labels: nearest, outside = 0 (identity affine = the plain crop)
         xt = target(x_slot[..., :ps[2]], ps, self.torch.float32)
-        ops.affine_sample(data, A, corner, ps, xt, order=1, cval=ddf.min[index], out_ld=self.n_chan if not warped else ps[2])
+        gather(data, A, corner, ps, xt, 1, ddf.min[index], 0, out_ld=self.n_chan if not warped else ps[2])
         settle(xt, x_slot[..., :ps[2]], 1)
         yt = target(y_slot, tshape, self.torch.uint8)
-        ops.affine_sample(truth, At, (corner[0], corner[1], zt), tshape, yt, order=0, cval=0.0, out_ld=self.truth_size)
+        gather(truth, At, (corner[0], corner[1], zt), tshape, yt, 0, 0.0, self.truth_index, out_ld=self.truth_size)
         settle(yt, y_slot, 0)
         if m_slot is not None:
             # augmented: outside the mask = 0 (interpolate_affine_range, cval 0); plain crop: edge values
             src = ddf.mask[index] if p is not None else ddf.mask_for_crops(index)
             mt = target(m_slot, tshape, self.torch.float32)
-            ops.affine_sample(src, Am, (corner[0], corner[1], zt), tshape, mt, order=0, cval=0.0, out_ld=self.truth_size)
+            gather(src, Am, (corner[0], corner[1], zt), tshape, mt, 0, 0.0, self.truth_index, out_ld=self.truth_size)
             settle(mt, m_slot, 0)
         img = x_slot if self.n_chan == ps[2] else None
         if p is not None:
@@ -371,6 +439,7 @@ class _Sampler(object):
                 if p["contrast"] is not None or p["intensity_multiplication"] != 1:
                     lo, hi = p["contrast"] if p["contrast"] is not None else (0.0, 0.0)
                     ops.rescale_intensity_ws(img, stats, ws, p["contrast"] is not None, lo, hi, p["intensity_multiplication"])
+                self._mri_intensity_launch([q], img.unsqueeze(0), stats, ws)      # acquisition effects: behind contrast, before the filter and the noises
                 # order of reference augment.py:354-367: gaussian filter, shot (poisson) noise, speckle, gaussian noise
                 if p["apply_gaussian_filter"]:
                     smooth = ops.gaussian_filter_f32(img, p["gaussian_sigma"])
@@ -390,7 +459,7 @@ class _Sampler(object):
         if self.prev_truth_index is not None:
             zp = corner[2] + self.prev_truth_index
             prev = self.torch.empty((ps[0], ps[1], self.prev_truth_size), device=x_slot.device, dtype=self.torch.float32)
-            ops.affine_sample(truth, At, (corner[0], corner[1], zp), (ps[0], ps[1], self.prev_truth_size), prev, order=0, cval=0.0)
+            gather(truth, At, (corner[0], corner[1], zp), (ps[0], ps[1], self.prev_truth_size), prev, 0, 0.0, self.prev_truth_index)
             if corners is not None:
                 prev = ops.piecewise_affine(prev, corners, 0, self.torch.empty_like(prev))
             if elastic is not None:

@@ -150,6 +150,9 @@ SIGNATURES = {
     "fmri_affine_sample_batch": [i32, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, i32, i64, p],
     "fmri_minmax_ws_batch": [p, i64, i64, i32, i32, p, p, p],
     "fmri_rescale_intensity_ws_batch": [p, i64, i64, i32, i32, p, p, p, p],
+    "fmri_affine_sample_slices": [p, i32, i32, i32, i32, p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, p, i32, i32, p],
+    "fmri_affine_sample_slices_batch": [i32, p, p, p, p, i32, i32, p, p, i32, i32, i32, i32, i32, p, i32, i32, i64, p],
+    "fmri_mri_intensity_ws_batch": [p, i32, i32, i32, i64, i32, i32, p, p, p, p, p],
     "fmri_noise_rng_batch": [p, i64, i64, i32, i32, p, p, i32, f32, u64, p, p],
     "fmri_shot_noise_rng_batch": [p, i64, i64, i32, i32, p, p, u64, p, p],
     "fmri_elastic_fields_rng_batch": [p, i32, i32, i32, p, p, u64, p, i32, p],

@@ -1790,6 +1790,96 @@ def affine_sample_batch(vols, affines, corners, size, out, order, cvals, out_ld=
     return out
 
 
+def _slice_table(table, B):
+    """device fp64 (B, nz_table, 6) -> nz_table"""
+    if not (table.is_cuda and table.dtype == torch.float64 and table.is_contiguous() and table.dim() == 3 and table.shape[0] == B
+            and table.shape[1] >= 1 and table.shape[2] == 6):
+        raise RuntimeError("slice table: a contiguous device float64 tensor (patches, rows, 6)")
+    return int(table.shape[1])
+
+
+def affine_sample_slices_batch(vols, affines, corners, size, out, order, cvals, table, z_off=0, out_ld=None):
+    """affine_sample_batch with inter-slice motion: output slice k of patch b is displaced in-plane by row k + z_off of table[b] (device float64
+    (B, nz_table, 6): (i', j') = (m0 i + m1 j + m2, m3 i + m4 j + m5) in patch coordinates; a row outside the table is the identity) before the
+    affine - fmri_affine_sample_slices_batch.  z_off: where the first output slice sits among the image slices the table was drawn for."""
+    import ctypes
+    import numpy as np
+    B = len(vols)
+    nx, ny, nz = (int(v) for v in size)
+    if out_ld is None:
+        assert out.is_cuda and tuple(out.shape) == (B, nx, ny, nz) and out[0].is_contiguous()
+        out_ld = nz
+    else:
+        out_ld = int(out_ld)
+        assert out.is_cuda and tuple(out.shape) == (B, nx, ny, nz) and out_ld >= nz
+        assert out.stride(3) == 1 and out.stride(2) == out_ld and out.stride(1) == ny * out_ld, "rows of out_ld elements, channels contiguous"
+    for v in vols:
+        if not v.is_cuda or not v.is_contiguous() or v.dtype != vols[0].dtype or v.dim() != 3:
+            raise RuntimeError("fmri_hip ops need contiguous device volumes of one dtype")
+    nzt = _slice_table(table, B)
+    ptrs = (ctypes.c_void_p * B)(*[v.data_ptr() for v in vols])
+    dims = np.ascontiguousarray([v.shape for v in vols], dtype=np.int32)
+    A = np.ascontiguousarray(np.asarray(affines, dtype=np.float64)[:, :3, :4])
+    cr = np.ascontiguousarray(corners, dtype=np.int32)
+    cv = np.ascontiguousarray(cvals, dtype=np.float32)
+    assert A.shape == (B, 3, 4) and cr.shape == (B, 3) and cv.shape == (B,)
+    check(lib().fmri_affine_sample_slices_batch(B, ctypes.cast(ptrs, ctypes.c_void_p), dims.ctypes.data, A.ctypes.data, _p(table), nzt, int(z_off),
+                                                cr.ctypes.data, cv.ctypes.data, _dt_any(vols[0]), nx, ny, nz, int(order), _p(out), _dt_any(out), out_ld,
+                                                int(out.stride(0)), _s()), "fmri_affine_sample_slices_batch")
+    return out
+
+
+def affine_sample_slices(vol, affine, start, size, out, table, z_off=0, order=1, cval=0.0, out_ld=None):
+    """affine_sample with inter-slice motion (affine_sample_slices_batch for one patch): table is a device float64 (nz_table, 6)"""
+    import ctypes
+    import numpy as np
+    if not vol.is_cuda or not out.is_cuda or not vol.is_contiguous():
+        raise RuntimeError("fmri_hip ops need device tensors (no CPU path)")
+    nzt = _slice_table(table.unsqueeze(0), 1)
+    X, Y, Z = vol.shape
+    a = np.ascontiguousarray(np.asarray(affine, dtype=np.float64)[:3, :4]).reshape(12)
+    arr = (ctypes.c_double * 12)(*a.tolist())
+    nx, ny, nz = (int(v) for v in size)
+    check(lib().fmri_affine_sample_slices(_p(vol), _dt_any(vol), X, Y, Z, ctypes.cast(arr, ctypes.c_void_p), _p(table), nzt, int(z_off), int(start[0]),
+                                          int(start[1]), int(start[2]), nx, ny, nz, int(order), float(cval), _p(out), _dt_any(out),
+                                          int(out_ld if out_ld is not None else nz), _s()), "fmri_affine_sample_slices")
+    return out
+
+
+MRI_PARAMS, MRI_TERMS = 23, (0, 4, 10, 20)        # FMRI_MRI_PARAMS; monomials of order 0 (no field) .. 3
+
+
+def mri_intensity_ws_batch(xb, stats, ws, gammas, coefs, gains, vmins):
+    """gamma, bias field and slice gain in place on the dense patches xb (B, X, Y, Z), one launch (fmri_mri_intensity_ws_batch).  Per patch:
+    gammas[b] (0 = skip), coefs[b] (None, or the 4 / 10 / 20 coefficients of the order 1 / 2 / 3 field), gains[b] (None, or a device float32
+    tensor of Z slice gains), vmins[b] (the volume's minimum, which the gains leave in place).  stats[b] = range of xb[b] before the call, updated
+    for every patch that is written; a patch that skips all three is not touched."""
+    import ctypes
+    import numpy as np
+    _need_cuda(stats, ws)
+    assert xb.dim() == 4
+    B, n, stride = _batch_geometry(xb)
+    X, Y, Z = (int(v) for v in xb.shape[1:])
+    assert len(gammas) == B and len(coefs) == B and len(gains) == B and len(vmins) == B
+    a = np.zeros((B, MRI_PARAMS), dtype=np.float32)
+    ptrs = (ctypes.c_void_p * B)()
+    for b in range(B):
+        a[b, 0], a[b, 1] = gammas[b], vmins[b]
+        if coefs[b] is not None:
+            c = np.asarray(coefs[b], dtype=np.float32).reshape(-1)
+            assert c.size in MRI_TERMS[1:], "bias field: 4, 10 or 20 coefficients"
+            a[b, 2] = c.size
+            a[b, 3:3 + c.size] = c
+        g = gains[b]
+        if g is not None:
+            if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.numel() == Z):
+                raise RuntimeError("slice gains: a contiguous device float32 tensor, one gain per slice")
+            ptrs[b] = g.data_ptr()
+    check(lib().fmri_mri_intensity_ws_batch(_p(xb), X, Y, Z, stride, B, dt(xb), _p(stats), _p(ws), a.ctypes.data, ctypes.cast(ptrs, ctypes.c_void_p),
+                                            _s()), "fmri_mri_intensity_ws_batch")
+    return xb
+
+
 def elastic_fields_rng_batch(shape2d, alphas, sigma, seed, seqs, device="cuda"):
     """-> d (B, 2, X, Y) fp32: d[b, 0] = shift along axis 0, d[b, 1] along axis 1 (ops.elastic_fields' (d0, d1)), the noise drawn in the kernel
     (fmri_elastic_fields_rng_batch: one launch); seqs[b] == 0 -> zero fields.  Kernel widths above ELASTIC_RNG_KMAX (sigma >= 12) are not
@@ -1829,6 +1919,11 @@ def minmax_ws(x, stats, ws):
 
 def rescale_intensity_ws(x, stats, ws, contrast, lo=0.0, hi=0.0, mult=1.0):
     rescale_intensity_ws_batch(x.unsqueeze(0), stats, ws, [[2 if contrast else 1, lo, hi, mult]])
+    return x
+
+
+def mri_intensity_ws(x, stats, ws, gamma=0.0, coef=None, gains=None, vmin=0.0):
+    mri_intensity_ws_batch(x.unsqueeze(0), stats, ws, [gamma], [coef], [gains], [vmin])
     return x
 
 

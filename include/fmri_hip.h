@@ -521,6 +521,29 @@ int fmri_minmax_ws_batch(const void* x, int64_t n, int64_t stride, int B, int dt
  * mult only, 2 contrast to [lo, hi] then multiply.  Updates stats[b]. */
 int fmri_rescale_intensity_ws_batch(void* x, int64_t n, int64_t stride, int B, int dtype, float* stats, int* ws, const float* params,
                                     fmri_stream_t stream);
+/* ---- acquisition effects of a fetal stack of 2-D slices (not in the reference; fetal_net/augment.py holds the float64 host forms).
+ * fmri_affine_sample with one in-plane rigid map per OUTPUT SLICE (inter-slice motion), folded into the gather.  table: DEVICE doubles
+ * [nz_table][6] ([B][nz_table][6] for the batch).  Output slice k takes row r = k + z_off: (i', j') = (m0 i + m1 j + m2, m3 i + m4 j + m5)
+ * in patch coordinates, and the source point is affine . (corner + (i', j', k), 1); a row index outside [0, nz_table) is the identity.
+ * z_off places a sub-range of slices (labels, mask, previous-slice truth) under the image slices they belong to.  Everything else as
+ * fmri_affine_sample / fmri_affine_sample_batch; a table of identity rows {1, 0, 0, 0, 1, 0} gives their output bit for bit. */
+int fmri_affine_sample_slices(const void* vol, int vol_dtype, int X, int Y, int Z, const double* affine, const double* table, int nz_table, int z_off,
+                              int x0, int y0, int z0, int nx, int ny, int nz, int order, float cval, void* out, int out_dtype, int out_ld,
+                              fmri_stream_t stream);
+int fmri_affine_sample_slices_batch(int B, const void* const* vols, const int* dims, const double* affines, const double* table, int nz_table, int z_off,
+                                    const int* corners, const float* cvals, int vol_dtype, int nx, int ny, int nz, int order, void* out, int out_dtype,
+                                    int out_ld, int64_t out_stride, fmri_stream_t stream);
+/* gamma, bias field and slice gain on the dense patches [X][Y][Z] of a batch, one launch.  params: HOST floats [B][FMRI_MRI_PARAMS] =
+ * {gamma, vmin, terms, coef[20]}; gains: HOST array of B device pointers (Z floats each), or NULL.  Per voxel, in this order:
+ *   gamma (0 = skip)        v = ((v - lo) / (hi - lo)) ^ gamma * (hi - lo) + lo, {lo, hi} = stats[b]; a constant patch is left alone
+ *   bias (terms 0 = skip)   v = (v - vmin) * exp(P(x, y, z)) + vmin; P = sum coef[t] x^a y^b z^c over a + b + c <= order, (a, b, c)
+ *                           lexicographic, terms = 4 | 10 | 20 for order 1 | 2 | 3; x, y, z in [-1, 1] across the patch, 0 on an axis of length 1
+ *   gain (NULL = skip)      v = (v - vmin) * gains[b][k] + vmin on slice k; a gain of exactly 1 leaves the slice's bits
+ * vmin is the volume's minimum (the background of z-scored data): gains scale signal, not background.  A patch that skips all three is
+ * not written; the others leave stats[b] = min / max of the new values and ws[b] re-armed. */
+#define FMRI_MRI_PARAMS 23
+int fmri_mri_intensity_ws_batch(void* x, int X, int Y, int Z, int64_t stride, int B, int dtype, float* stats, int* ws, const float* params,
+                                const float* const* gains, fmri_stream_t stream);
 /* fmri_noise_augment with N(0,1) draws by Box-Muller; kind 0 gaussian, 1 speckle (reference augment.py:99-110). In place; updates stats[b]. */
 int fmri_noise_rng_batch(void* x, int64_t n, int64_t stride, int B, int dtype, float* stats, int* ws, int kind, float sigma, uint64_t seed,
                          const uint32_t* seqs, fmri_stream_t stream);
