@@ -1,6 +1,7 @@
 // HBM-bound kernels of the U-Net step: pooling, up-sampling, final 1x1x1 conv, sigmoid+Dice, Adam, weight packing,
 // sliding-window tile gather / overlap-add, casts.  All channels-last, vectorised where the channel count allows.
 #include <cstdlib>
+#include <type_traits>
 #include "common.h"
 
 FMRI_DET_TU(pointwise)
@@ -45,209 +46,45 @@ __device__ __forceinline__ void decode_vox(int64_t v, int Do, int Ho, int Wo, in
     n = (int)(v / Do);
 }
 
-// ------------------------------------------------------------------------------------------------ max-pool 2x2x2
-// One thread per (pooled voxel, channel group of VEC).  Reference: MaxPooling3D(pool_size) at unet3d/unet.py:51.
-template <typename T, int VEC>
-__global__ void k_maxpool_fwd(const T* __restrict__ x, T* __restrict__ y, int N, int D, int H, int W, int C, int pd) {
-    const int Do = D >> pd, Ho = H >> 1, Wo = W >> 1, CG = C / VEC;      // pd = 0: planar (2-D slices), window 1x2x2
-    const int64_t total = (int64_t)N * Do * Ho * Wo * CG;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        int cg = (int)(i % CG), n, d_o, ho, wo;
-        decode_vox(i / CG, Do, Ho, Wo, n, d_o, ho, wo);
-        float m[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) m[k] = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (t >= (4 << pd)) break;
-            int dd = (d_o << pd) + (t >> 2), hh = 2 * ho + ((t >> 1) & 1), ww = 2 * wo + (t & 1);
-            float xv[VEC];
-            ldv<T, VEC>(x + ((((int64_t)n * D + dd) * H + hh) * W + ww) * C + cg * VEC, xv);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) m[k] = fmaxf(m[k], xv[k]);
-        }
-        stv<T, VEC>(y + ((((int64_t)n * Do + d_o) * Ho + ho) * Wo + wo) * C + cg * VEC, m);
-    }
-}
-
-// backward: one thread per (pooled voxel, channel group): recompute the window max, route dy to the FIRST max in
-// (d,h,w) scan order, add the skip gradient, apply the producer's ReLU mask, write all 8 children.
-template <typename T, int VEC>
-__global__ void __launch_bounds__(256) k_maxpool_bwd(const T* __restrict__ x, const T* __restrict__ dy, const T* __restrict__ add, int add_ld,
-                              int add_off, T* __restrict__ dx, int N, int D, int H, int W, int C, int relu_mask, int pd) {
-    const int Do = D >> pd, Ho = H >> 1, Wo = W >> 1, CG = C / VEC;
-    const int64_t total = (int64_t)N * Do * Ho * Wo * CG;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        int cg = (int)(i % CG), n, d_o, ho, wo;
-        decode_vox(i / CG, Do, Ho, Wo, n, d_o, ho, wo);
-        float xv[8][VEC], m[VEC], g[VEC];
-        int64_t off[8];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) m[k] = -INFINITY;
-        const int nt = 4 << pd;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (t >= nt) break;
-            int dd = (d_o << pd) + (t >> 2), hh = 2 * ho + ((t >> 1) & 1), ww = 2 * wo + (t & 1);
-            off[t] = (((int64_t)n * D + dd) * H + hh) * W + ww;
-            ldv<T, VEC>(x + off[t] * C + cg * VEC, xv[t]);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) m[k] = fmaxf(m[k], xv[t][k]);
-        }
-        ldv<T, VEC>(dy + ((((int64_t)n * Do + d_o) * Ho + ho) * Wo + wo) * C + cg * VEC, g);
-        bool taken[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) taken[k] = false;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (t >= nt) break;
-            float r[VEC], a[VEC];
-            if (add) ldv<T, VEC>(add + off[t] * add_ld + add_off + cg * VEC, a);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                float rr = 0.f;
-                if (!taken[k] && xv[t][k] == m[k]) { rr = g[k]; taken[k] = true; }
-                if (add) rr += a[k];
-                if (relu_mask && !(xv[t][k] > 0.f)) rr = 0.f;
-                r[k] = rr;
-            }
-            stv<T, VEC>(dx + off[t] * C + cg * VEC, r);
-        }
-    }
-}
-
-extern "C" int fmri_maxpool3d_2x_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int dtype, int planar,
-                                     fmri_stream_t stream) {
-    const int pd = planar ? 0 : 1;
-    if (N <= 0 || C <= 0 || D < 1 || (H & 1) || (W & 1) || (pd && (D & 1))) return FMRI_E_SHAPE;
-    int vec = pick_vec(C);
-    int grid = grid_for((int64_t)N * (D >> pd) * (H / 2) * (W / 2) * (C / vec));
-    hipStream_t s = as_stream(stream);
-    if (dtype == FMRI_F32) LAUNCH_TV(k_maxpool_fwd, float, vec, grid, 256, s, (const float*)x, (float*)y, N, D, H, W, C, pd);
-    else if (dtype == FMRI_BF16) LAUNCH_TV(k_maxpool_fwd, bf16_t, vec, grid, 256, s, (const bf16_t*)x, (bf16_t*)y, N, D, H, W, C, pd);
-    else return FMRI_E_DTYPE;
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
-}
-
-extern "C" int fmri_maxpool3d_2x_bwd(const void* x, const void* dy, const void* add, int add_ld, int add_off, void* dx,
-                                     int N, int D, int H, int W, int C, int relu_mask, int dtype, int planar, fmri_stream_t stream) {
-    const int pd = planar ? 0 : 1;
-    if (N <= 0 || C <= 0 || D < 1 || (H & 1) || (W & 1) || (pd && (D & 1))) return FMRI_E_SHAPE;
-    int vec = pick_vec(C);
-    if (add) { while (vec > 1 && ((add_ld % vec) || (add_off % vec))) vec >>= 1; }
-    int grid = grid_for((int64_t)N * (D >> pd) * (H / 2) * (W / 2) * (C / vec));
-    hipStream_t s = as_stream(stream);
-    if (dtype == FMRI_F32)
-        LAUNCH_TV(k_maxpool_bwd, float, vec, grid, 256, s, (const float*)x, (const float*)dy, (const float*)add, add_ld,
-                  add_off, (float*)dx, N, D, H, W, C, relu_mask, pd);
-    else if (dtype == FMRI_BF16)
-        LAUNCH_TV(k_maxpool_bwd, bf16_t, vec, grid, 256, s, (const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)add, add_ld,
-                  add_off, (bf16_t*)dx, N, D, H, W, C, relu_mask, pd);
-    else return FMRI_E_DTYPE;
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ nearest up-sampling x2
-// Reference: UpSampling3D(size=pool_size) at unet3d/unet.py:138.  D,H,W = low-resolution dims.
-template <typename T, int VEC>
-__global__ void k_upsample_fwd(const T* __restrict__ x, T* __restrict__ y, int y_ld, int y_off, int N, int D, int H, int W,
-                               int C, int pd) {
-    const int CG = C / VEC;
-    const int64_t total = (int64_t)N * D * H * W * CG;
-    const int D2 = D << pd, H2 = 2 * H, W2 = 2 * W;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        int cg = (int)(i % CG), n, d, h, w;
-        decode_vox(i / CG, D, H, W, n, d, h, w);
-        float v[VEC];
-        ldv<T, VEC>(x + (i / CG) * C + cg * VEC, v);
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (t >= (4 << pd)) break;
-            int64_t o = (((int64_t)n * D2 + (d << pd) + (t >> 2)) * H2 + 2 * h + ((t >> 1) & 1)) * W2 + 2 * w + (t & 1);
-            stv<T, VEC>(y + o * y_ld + y_off + cg * VEC, v);
-        }
-    }
-}
-template <typename T, int VEC>
-__global__ void k_upsample_bwd(const T* __restrict__ dy, int dy_ld, int dy_off, const T* __restrict__ xmask,
-                               T* __restrict__ dx, int N, int D, int H, int W, int C, int pd) {
-    const int CG = C / VEC;
-    const int64_t total = (int64_t)N * D * H * W * CG;
-    const int D2 = D << pd, H2 = 2 * H, W2 = 2 * W;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        int cg = (int)(i % CG), n, d, h, w;
-        decode_vox(i / CG, D, H, W, n, d, h, w);
-        float acc[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (t >= (4 << pd)) break;
-            int64_t o = (((int64_t)n * D2 + (d << pd) + (t >> 2)) * H2 + 2 * h + ((t >> 1) & 1)) * W2 + 2 * w + (t & 1);
-            float g[VEC];
-            ldv<T, VEC>(dy + o * dy_ld + dy_off + cg * VEC, g);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) acc[k] += g[k];
-        }
-        if (xmask) {
-            float m[VEC];
-            ldv<T, VEC>(xmask + (i / CG) * C + cg * VEC, m);
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) if (!(m[k] > 0.f)) acc[k] = 0.f;
-        }
-        stv<T, VEC>(dx + (i / CG) * C + cg * VEC, acc);
-    }
-}
-
-extern "C" int fmri_upsample_nearest2x_fwd(const void* x, void* y, int y_ld, int y_off, int N, int D, int H, int W, int C,
-                                           int dtype, int planar, fmri_stream_t stream) {
-    const int pd = planar ? 0 : 1;
-    if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || y_ld < y_off + C) return FMRI_E_SHAPE;
-    int vec = pick_vec(C);
-    while (vec > 1 && ((y_ld % vec) || (y_off % vec))) vec >>= 1;
-    int grid = grid_for((int64_t)N * D * H * W * (C / vec));
-    hipStream_t s = as_stream(stream);
-    if (dtype == FMRI_F32) LAUNCH_TV(k_upsample_fwd, float, vec, grid, 256, s, (const float*)x, (float*)y, y_ld, y_off, N, D, H, W, C, pd);
-    else if (dtype == FMRI_BF16) LAUNCH_TV(k_upsample_fwd, bf16_t, vec, grid, 256, s, (const bf16_t*)x, (bf16_t*)y, y_ld, y_off, N, D, H, W, C, pd);
-    else return FMRI_E_DTYPE;
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
-}
-extern "C" int fmri_upsample_nearest2x_bwd(const void* dy, int dy_ld, int dy_off, const void* xmask, void* dx, int N, int D,
-                                           int H, int W, int C, int dtype, int planar, fmri_stream_t stream) {
-    const int pd = planar ? 0 : 1;
-    if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || dy_ld < dy_off + C) return FMRI_E_SHAPE;
-    int vec = pick_vec(C);
-    while (vec > 1 && ((dy_ld % vec) || (dy_off % vec))) vec >>= 1;
-    int grid = grid_for((int64_t)N * D * H * W * (C / vec));
-    hipStream_t s = as_stream(stream);
-    if (dtype == FMRI_F32)
-        LAUNCH_TV(k_upsample_bwd, float, vec, grid, 256, s, (const float*)dy, dy_ld, dy_off, (const float*)xmask, (float*)dx, N, D, H, W, C, pd);
-    else if (dtype == FMRI_BF16)
-        LAUNCH_TV(k_upsample_bwd, bf16_t, vec, grid, 256, s, (const bf16_t*)dy, dy_ld, dy_off, (const bf16_t*)xmask, (bf16_t*)dx, N, D, H, W, C, pd);
-    else return FMRI_E_DTYPE;
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ max-pool / nearest up-sampling, per-axis factors
-// MaxPooling3D(pool_size) / UpSampling3D(size) of the reference's builders with a window other than 2x2x2 - (2, 2, 1) for the anisotropic
-// fetal volumes - or, planar, MaxPooling2D / UpSampling2D as (1, ph, pw).  Factors 1..4 per axis, stride = window: every fine voxel belongs
-// to exactly one window, so one thread (one channel vector) owns a window and writes all of its children - no atomics.  Same arithmetic
-// as the 2x kernels above, in the same (d, h, w) scan order; the windows are walked by run-time loops, nothing window-sized is kept in
-// registers (a 4x4x4 window is 64 voxels): the backward max-pool reads x twice - find the maximum, then route.
+// ------------------------------------------------------------------------------------------------ max-pool / nearest up-sampling
+// MaxPooling3D(pool_size) / UpSampling3D(size) of the reference's builders (unet3d/unet.py:51, :138) with per-axis factors 1..4, stride =
+// window: 2x2x2, (2, 2, 1) for the anisotropic fetal volumes or, planar, MaxPooling2D / UpSampling2D as (1, ph, pw).  Every fine voxel
+// belongs to exactly one window, so one thread (one channel vector of VEC) owns a window and writes all of its children - no atomics.
+// The window PD x PH x PW is a template argument: 2x2x2 and 1x2x2 (the training step's) are walked by fully unrolled loops, PD = 0 takes
+// the window from PoolDims and walks it by run-time loops.  Every instantiation visits a window in (d, h, w) scan order: one
+// first-maximum rule, one fp32 summation order.
 struct PoolDims {
     int D, H, W;          // coarse dims
     int pd, ph, pw;
 };
+template <int PD, int PH, int PW>
+__device__ __forceinline__ PoolDims with_window(PoolDims p) {
+    if (PD > 0) { p.pd = PD; p.ph = PH; p.pw = PW; }
+    return p;
+}
 __device__ __forceinline__ int64_t fine_vox(const PoolDims& p, int n, int d, int h, int w, int a, int b, int c) {
     return (((int64_t)n * (p.D * p.pd) + d * p.pd + a) * (p.H * p.ph) + h * p.ph + b) * (p.W * p.pw) + w * p.pw + c;
 }
+// f(a, b, c) for every voxel of the window, in (d, h, w) scan order
+template <int PD, int PH, int PW, typename F>
+__device__ __forceinline__ void for_window(const PoolDims& p, F f) {
+    if constexpr (PD > 0) {
+#pragma unroll
+        for (int a = 0; a < PD; ++a)
+#pragma unroll
+            for (int b = 0; b < PH; ++b)
+#pragma unroll
+                for (int c = 0; c < PW; ++c) f(a, b, c);
+    } else {
+        for (int a = 0; a < p.pd; ++a)
+            for (int b = 0; b < p.ph; ++b)
+                for (int c = 0; c < p.pw; ++c) f(a, b, c);
+    }
+}
 
-template <typename T, int VEC>
-__global__ void __launch_bounds__(256) k_maxpool_p_fwd(const T* __restrict__ x, T* __restrict__ y, int N, int C, PoolDims p) {
+template <typename T, int VEC, int PD, int PH, int PW>
+__global__ void __launch_bounds__(256) k_maxpool_fwd(const T* __restrict__ x, T* __restrict__ y, int N, int C, PoolDims pr) {
+    const PoolDims p = with_window<PD, PH, PW>(pr);
     const int CG = C / VEC;
     const int64_t total = (int64_t)N * p.D * p.H * p.W * CG;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -256,21 +93,25 @@ __global__ void __launch_bounds__(256) k_maxpool_p_fwd(const T* __restrict__ x, 
         float m[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) m[k] = -INFINITY;
-        for (int a = 0; a < p.pd; ++a)
-            for (int b = 0; b < p.ph; ++b)
-                for (int c = 0; c < p.pw; ++c) {
-                    float xv[VEC];
-                    ldv<T, VEC>(x + fine_vox(p, n, d, h, w, a, b, c) * C + cg * VEC, xv);
+        for_window<PD, PH, PW>(p, [&](int a, int b, int c) {
+            float xv[VEC];
+            ldv<T, VEC>(x + fine_vox(p, n, d, h, w, a, b, c) * C + cg * VEC, xv);
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) m[k] = fmaxf(m[k], xv[k]);
-                }
+            for (int k = 0; k < VEC; ++k) m[k] = fmaxf(m[k], xv[k]);
+        });
         stv<T, VEC>(y + (i / CG) * C + cg * VEC, m);
     }
 }
 
-template <typename T, int VEC>
-__global__ void __launch_bounds__(256) k_maxpool_p_bwd(const T* __restrict__ x, const T* __restrict__ dy, const T* __restrict__ add, int add_ld,
-                                                       int add_off, T* __restrict__ dx, int N, int C, int relu_mask, PoolDims p) {
+// backward: the window's maximum, then dy to the FIRST maximum in scan order, + the skip gradient, the producer's ReLU mask, every child
+// written.  A fixed window of at most 8 voxels keeps its values and offsets in registers and reads x once; any other window is too large
+// for that (4x4x4 is 64 voxels) and reads x twice - find the maximum, then route.
+template <typename T, int VEC, int PD, int PH, int PW>
+__global__ void __launch_bounds__(256) k_maxpool_bwd(const T* __restrict__ x, const T* __restrict__ dy, const T* __restrict__ add, int add_ld,
+                                                     int add_off, T* __restrict__ dx, int N, int C, int relu_mask, PoolDims pr) {
+    constexpr int NT = PD * PH * PW;
+    constexpr bool IN_REGS = NT >= 1 && NT <= 8;
+    const PoolDims p = with_window<PD, PH, PW>(pr);
     const int CG = C / VEC;
     const int64_t total = (int64_t)N * p.D * p.H * p.W * CG;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -280,37 +121,61 @@ __global__ void __launch_bounds__(256) k_maxpool_p_bwd(const T* __restrict__ x, 
         bool taken[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { m[k] = -INFINITY; taken[k] = false; }
-        for (int a = 0; a < p.pd; ++a)                       // pass 1: the window's maximum
-            for (int b = 0; b < p.ph; ++b)
-                for (int c = 0; c < p.pw; ++c) {
-                    float xv[VEC];
-                    ldv<T, VEC>(x + fine_vox(p, n, d, h, w, a, b, c) * C + cg * VEC, xv);
+        // the gradient of fine voxel v (its values xv).  A macro, not a lambda: a closure that captures `taken` moves those flags from
+        // wave masks into vector registers in the run-time instantiation, which then is no longer the code that was measured
+#define ROUTE(v, xv)                                                                           \
+    do {                                                                                       \
+        float r[VEC], s[VEC];                                                                  \
+        if (add) ldv<T, VEC>(add + (v) * add_ld + add_off + cg * VEC, s);                      \
+        _Pragma("unroll") for (int k = 0; k < VEC; ++k) {                                      \
+            float rr = 0.f;                                                                    \
+            if (!taken[k] && (xv)[k] == m[k]) { rr = g[k]; taken[k] = true; }                  \
+            if (add) rr += s[k];                                                               \
+            if (relu_mask && !((xv)[k] > 0.f)) rr = 0.f;                                       \
+            r[k] = rr;                                                                         \
+        }                                                                                      \
+        stv<T, VEC>(dx + (v) * C + cg * VEC, r);                                               \
+    } while (0)
+        if constexpr (IN_REGS) {
+            float xw[NT][VEC];
+            int64_t vw[NT];
+            for_window<PD, PH, PW>(p, [&](int a, int b, int c) {
+                const int t = (a * PH + b) * PW + c;
+                vw[t] = fine_vox(p, n, d, h, w, a, b, c);
+                ldv<T, VEC>(x + vw[t] * C + cg * VEC, xw[t]);
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) m[k] = fmaxf(m[k], xv[k]);
-                }
-        ldv<T, VEC>(dy + (i / CG) * C + cg * VEC, g);
-        for (int a = 0; a < p.pd; ++a)                       // pass 2: dy to the first maximum in scan order, + skip gradient, ReLU mask
-            for (int b = 0; b < p.ph; ++b)
-                for (int c = 0; c < p.pw; ++c) {
-                    const int64_t v = fine_vox(p, n, d, h, w, a, b, c);
-                    float xv[VEC], r[VEC], s[VEC];
-                    ldv<T, VEC>(x + v * C + cg * VEC, xv);
-                    if (add) ldv<T, VEC>(add + v * add_ld + add_off + cg * VEC, s);
+                for (int k = 0; k < VEC; ++k) m[k] = fmaxf(m[k], xw[t][k]);
+            });
+            ldv<T, VEC>(dy + (i / CG) * C + cg * VEC, g);
+            for_window<PD, PH, PW>(p, [&](int a, int b, int c) {
+                const int t = (a * PH + b) * PW + c;
+                ROUTE(vw[t], xw[t]);
+            });
+        } else {
+            for_window<PD, PH, PW>(p, [&](int a, int b, int c) {
+                float xv[VEC];
+                ldv<T, VEC>(x + fine_vox(p, n, d, h, w, a, b, c) * C + cg * VEC, xv);
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) {
-                        float rr = 0.f;
-                        if (!taken[k] && xv[k] == m[k]) { rr = g[k]; taken[k] = true; }
-                        if (add) rr += s[k];
-                        if (relu_mask && !(xv[k] > 0.f)) rr = 0.f;
-                        r[k] = rr;
+                for (int k = 0; k < VEC; ++k) m[k] = fmaxf(m[k], xv[k]);
+            });
+            ldv<T, VEC>(dy + (i / CG) * C + cg * VEC, g);
+            for (int a = 0; a < p.pd; ++a)                       // (plain loops: `taken` in no closure, see ROUTE)
+                for (int b = 0; b < p.ph; ++b)
+                    for (int c = 0; c < p.pw; ++c) {
+                        const int64_t v = fine_vox(p, n, d, h, w, a, b, c);
+                        float xv[VEC];
+                        ldv<T, VEC>(x + v * C + cg * VEC, xv);
+                        ROUTE(v, xv);
                     }
-                    stv<T, VEC>(dx + v * C + cg * VEC, r);
-                }
+        }
+#undef ROUTE
     }
 }
 
-template <typename T, int VEC>
-__global__ void __launch_bounds__(256) k_upsample_p_fwd(const T* __restrict__ x, T* __restrict__ y, int y_ld, int y_off, int N, int C, PoolDims p) {
+// D, H, W of PoolDims = the low-resolution dims; y / dy: channel slice [off, off + C) of a tensor with ld channels
+template <typename T, int VEC, int PD, int PH, int PW>
+__global__ void __launch_bounds__(256) k_upsample_fwd(const T* __restrict__ x, T* __restrict__ y, int y_ld, int y_off, int N, int C, PoolDims pr) {
+    const PoolDims p = with_window<PD, PH, PW>(pr);
     const int CG = C / VEC;
     const int64_t total = (int64_t)N * p.D * p.H * p.W * CG;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -318,15 +183,14 @@ __global__ void __launch_bounds__(256) k_upsample_p_fwd(const T* __restrict__ x,
         decode_vox(i / CG, p.D, p.H, p.W, n, d, h, w);
         float v[VEC];
         ldv<T, VEC>(x + (i / CG) * C + cg * VEC, v);
-        for (int a = 0; a < p.pd; ++a)
-            for (int b = 0; b < p.ph; ++b)
-                for (int c = 0; c < p.pw; ++c) stv<T, VEC>(y + fine_vox(p, n, d, h, w, a, b, c) * y_ld + y_off + cg * VEC, v);
+        for_window<PD, PH, PW>(p, [&](int a, int b, int c) { stv<T, VEC>(y + fine_vox(p, n, d, h, w, a, b, c) * y_ld + y_off + cg * VEC, v); });
     }
 }
 
-template <typename T, int VEC>
-__global__ void __launch_bounds__(256) k_upsample_p_bwd(const T* __restrict__ dy, int dy_ld, int dy_off, const T* __restrict__ xmask,
-                                                        T* __restrict__ dx, int N, int C, PoolDims p) {
+template <typename T, int VEC, int PD, int PH, int PW>
+__global__ void __launch_bounds__(256) k_upsample_bwd(const T* __restrict__ dy, int dy_ld, int dy_off, const T* __restrict__ xmask,
+                                                      T* __restrict__ dx, int N, int C, PoolDims pr) {
+    const PoolDims p = with_window<PD, PH, PW>(pr);
     const int CG = C / VEC;
     const int64_t total = (int64_t)N * p.D * p.H * p.W * CG;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -335,14 +199,12 @@ __global__ void __launch_bounds__(256) k_upsample_p_bwd(const T* __restrict__ dy
         float acc[VEC];
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-        for (int a = 0; a < p.pd; ++a)
-            for (int b = 0; b < p.ph; ++b)
-                for (int c = 0; c < p.pw; ++c) {
-                    float g[VEC];
-                    ldv<T, VEC>(dy + fine_vox(p, n, d, h, w, a, b, c) * dy_ld + dy_off + cg * VEC, g);
+        for_window<PD, PH, PW>(p, [&](int a, int b, int c) {
+            float g[VEC];
+            ldv<T, VEC>(dy + fine_vox(p, n, d, h, w, a, b, c) * dy_ld + dy_off + cg * VEC, g);
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) acc[k] += g[k];
-                }
+            for (int k = 0; k < VEC; ++k) acc[k] += g[k];
+        });
         if (xmask) {
             float m[VEC];
             ldv<T, VEC>(xmask + (i / CG) * C + cg * VEC, m);
@@ -359,18 +221,44 @@ static inline bool pool_factors_ok(int pd, int ph, int pw) {
     return pd * ph * pw > 1;
 }
 
+// dtype x vector width x window -> one instantiation: launch(T{}, VEC, PD, PH, PW), the last four as integral constants.  The fixed
+// windows are 2x2x2 and 1x2x2; every other window is PD = 0.
+template <int V> using IntC = std::integral_constant<int, V>;
+template <typename F>
+static int pool_dispatch(int dtype, int vec, const PoolDims& p, F launch) {
+    auto by_window = [&](auto t, auto v) {
+        if (p.pd == 2 && p.ph == 2 && p.pw == 2) launch(t, v, IntC<2>{}, IntC<2>{}, IntC<2>{});
+        else if (p.pd == 1 && p.ph == 2 && p.pw == 2) launch(t, v, IntC<1>{}, IntC<2>{}, IntC<2>{});
+        else launch(t, v, IntC<0>{}, IntC<0>{}, IntC<0>{});
+    };
+    auto by_vec = [&](auto t) {
+        switch (vec) {
+            case 8: by_window(t, IntC<8>{}); break;
+            case 4: by_window(t, IntC<4>{}); break;
+            case 2: by_window(t, IntC<2>{}); break;
+            default: by_window(t, IntC<1>{}); break;
+        }
+    };
+    if (dtype == FMRI_F32) by_vec(float{});
+    else if (dtype == FMRI_BF16) by_vec(bf16_t{});
+    else return FMRI_E_DTYPE;
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+// the `launch` of pool_dispatch for kernel KERN; its arguments cast the tensors with (T*) / (const T*)
+#define POOL_LAUNCH(KERN, grid, s, ...)                                                                                              \
+    [&](auto t, auto v, auto a, auto b, auto c) {                                                                                    \
+        using T = decltype(t);                                                                                                       \
+        KERN<T, decltype(v)::value, decltype(a)::value, decltype(b)::value, decltype(c)::value><<<grid, 256, 0, s>>>(__VA_ARGS__);   \
+    }
+
 extern "C" int fmri_maxpool3d_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int pd, int ph, int pw, int dtype,
                                   fmri_stream_t stream) {
     if (N <= 0 || C <= 0 || D < 1 || H < 1 || W < 1 || !pool_factors_ok(pd, ph, pw) || D % pd || H % ph || W % pw) return FMRI_E_SHAPE;
     const PoolDims p = {D / pd, H / ph, W / pw, pd, ph, pw};
     int vec = pick_vec(C);
     int grid = grid_for((int64_t)N * p.D * p.H * p.W * (C / vec));
-    hipStream_t s = as_stream(stream);
-    if (dtype == FMRI_F32) LAUNCH_TV(k_maxpool_p_fwd, float, vec, grid, 256, s, (const float*)x, (float*)y, N, C, p);
-    else if (dtype == FMRI_BF16) LAUNCH_TV(k_maxpool_p_fwd, bf16_t, vec, grid, 256, s, (const bf16_t*)x, (bf16_t*)y, N, C, p);
-    else return FMRI_E_DTYPE;
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
+    return pool_dispatch(dtype, vec, p, POOL_LAUNCH(k_maxpool_fwd, grid, as_stream(stream), (const T*)x, (T*)y, N, C, p));
 }
 
 extern "C" int fmri_maxpool3d_bwd(const void* x, const void* dy, const void* add, int add_ld, int add_off, void* dx, int N, int D, int H,
@@ -381,16 +269,8 @@ extern "C" int fmri_maxpool3d_bwd(const void* x, const void* dy, const void* add
     int vec = pick_vec(C);
     if (add) { while (vec > 1 && ((add_ld % vec) || (add_off % vec))) vec >>= 1; }
     int grid = grid_for((int64_t)N * p.D * p.H * p.W * (C / vec));
-    hipStream_t s = as_stream(stream);
-    if (dtype == FMRI_F32)
-        LAUNCH_TV(k_maxpool_p_bwd, float, vec, grid, 256, s, (const float*)x, (const float*)dy, (const float*)add, add_ld, add_off,
-                  (float*)dx, N, C, relu_mask, p);
-    else if (dtype == FMRI_BF16)
-        LAUNCH_TV(k_maxpool_p_bwd, bf16_t, vec, grid, 256, s, (const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)add, add_ld, add_off,
-                  (bf16_t*)dx, N, C, relu_mask, p);
-    else return FMRI_E_DTYPE;
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
+    return pool_dispatch(dtype, vec, p, POOL_LAUNCH(k_maxpool_bwd, grid, as_stream(stream), (const T*)x, (const T*)dy, (const T*)add, add_ld,
+                                                    add_off, (T*)dx, N, C, relu_mask, p));
 }
 
 extern "C" int fmri_upsample_nearest_fwd(const void* x, void* y, int y_ld, int y_off, int N, int D, int H, int W, int C, int pd, int ph,
@@ -400,12 +280,7 @@ extern "C" int fmri_upsample_nearest_fwd(const void* x, void* y, int y_ld, int y
     int vec = pick_vec(C);
     while (vec > 1 && ((y_ld % vec) || (y_off % vec))) vec >>= 1;
     int grid = grid_for((int64_t)N * D * H * W * (C / vec));
-    hipStream_t s = as_stream(stream);
-    if (dtype == FMRI_F32) LAUNCH_TV(k_upsample_p_fwd, float, vec, grid, 256, s, (const float*)x, (float*)y, y_ld, y_off, N, C, p);
-    else if (dtype == FMRI_BF16) LAUNCH_TV(k_upsample_p_fwd, bf16_t, vec, grid, 256, s, (const bf16_t*)x, (bf16_t*)y, y_ld, y_off, N, C, p);
-    else return FMRI_E_DTYPE;
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
+    return pool_dispatch(dtype, vec, p, POOL_LAUNCH(k_upsample_fwd, grid, as_stream(stream), (const T*)x, (T*)y, y_ld, y_off, N, C, p));
 }
 
 extern "C" int fmri_upsample_nearest_bwd(const void* dy, int dy_ld, int dy_off, const void* xmask, void* dx, int N, int D, int H, int W,
@@ -415,14 +290,8 @@ extern "C" int fmri_upsample_nearest_bwd(const void* dy, int dy_ld, int dy_off, 
     int vec = pick_vec(C);
     while (vec > 1 && ((dy_ld % vec) || (dy_off % vec))) vec >>= 1;
     int grid = grid_for((int64_t)N * D * H * W * (C / vec));
-    hipStream_t s = as_stream(stream);
-    if (dtype == FMRI_F32)
-        LAUNCH_TV(k_upsample_p_bwd, float, vec, grid, 256, s, (const float*)dy, dy_ld, dy_off, (const float*)xmask, (float*)dx, N, C, p);
-    else if (dtype == FMRI_BF16)
-        LAUNCH_TV(k_upsample_p_bwd, bf16_t, vec, grid, 256, s, (const bf16_t*)dy, dy_ld, dy_off, (const bf16_t*)xmask, (bf16_t*)dx, N, C, p);
-    else return FMRI_E_DTYPE;
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
+    return pool_dispatch(dtype, vec, p, POOL_LAUNCH(k_upsample_bwd, grid, as_stream(stream), (const T*)dy, dy_ld, dy_off, (const T*)xmask,
+                                                    (T*)dx, N, C, p));
 }
 
 // ------------------------------------------------------------------------------------------------ final 1x1x1 conv
@@ -830,12 +699,26 @@ __global__ void k_sigmoid_loss_bwd(const float* __restrict__ probs, const uint8_
         dl[i] = grad_scale * g;
     }
 }
+// the two passes of the sigmoid losses, weight NULL or a per-voxel weight on the cross-entropy term; the entry points check their arguments
+static int sigmoid_dice_fwd_launch(const float* logits, const uint8_t* y, const float* weight, float* probs, double* sums, int64_t n,
+                                   fmri_stream_t stream) {
+    const bool v4 = n % 4 == 0 && !((((uintptr_t)logits) | ((uintptr_t)probs) | ((uintptr_t)weight)) & 15) && !(((uintptr_t)y) & 3);
+    if (v4) k_sigmoid_dice_fwd<4><<<grid_for(n / 4, 256, 512), 256, 0, as_stream(stream)>>>(logits, y, weight, probs, sums, n);
+    else k_sigmoid_dice_fwd<1><<<grid_for(n, 256, 512), 256, 0, as_stream(stream)>>>(logits, y, weight, probs, sums, n);
+    if (h_det_on) k_isums_finish<<<1, 64, 0, as_stream(stream)>>>(sums);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+static int sigmoid_loss_bwd_launch(const float* probs, const uint8_t* y, const float* weight, const double* sums, float* dlogits, int64_t n,
+                                   int kind, float param, float smooth, float grad_scale, fmri_stream_t stream) {
+    k_sigmoid_loss_bwd<<<grid_for(n, 256, 2048), 256, 0, as_stream(stream)>>>(probs, y, weight, sums, dlogits, n, kind, param, smooth, grad_scale);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
 extern "C" int fmri_sigmoid_loss_bwd(const float* probs, const uint8_t* y_true, const double* sums, float* dlogits, int64_t n, int kind,
                                      float param, float smooth, float grad_scale, fmri_stream_t stream) {
     if (n <= 0 || kind < 0 || kind > 5) return FMRI_E_SHAPE;
-    k_sigmoid_loss_bwd<<<grid_for(n, 256, 2048), 256, 0, as_stream(stream)>>>(probs, y_true, nullptr, sums, dlogits, n, kind, param, smooth, grad_scale);
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
+    return sigmoid_loss_bwd_launch(probs, y_true, nullptr, sums, dlogits, n, kind, param, smooth, grad_scale, stream);
 }
 // ---- weighted_dice_coefficient_loss (reference metrics.py:39-55): Dice per (sample, label) over the voxel axes, smooth 1e-5, MEAN over the
 // (sample, label) groups - the only loss whose values the reference's own tests pin (test/test_metrics.py:10-38).
@@ -916,35 +799,19 @@ extern "C" int fmri_weighted_dice_bwd(const float* probs, const uint8_t* y_true,
 extern "C" int fmri_sigmoid_dice_fwd_weighted(const float* logits, const uint8_t* y_true, const float* weight, float* probs, double* sums,
                                               int64_t n, fmri_stream_t stream) {
     if (n <= 0 || !weight) return FMRI_E_SHAPE;
-    {
-        const bool v4 = n % 4 == 0 && !((((uintptr_t)logits) | ((uintptr_t)probs) | ((uintptr_t)weight)) & 15) && !(((uintptr_t)y_true) & 3);
-        if (v4) k_sigmoid_dice_fwd<4><<<grid_for(n / 4, 256, 512), 256, 0, as_stream(stream)>>>(logits, y_true, weight, probs, sums, n);
-        else k_sigmoid_dice_fwd<1><<<grid_for(n, 256, 512), 256, 0, as_stream(stream)>>>(logits, y_true, weight, probs, sums, n);
-    }
-    if (h_det_on) k_isums_finish<<<1, 64, 0, as_stream(stream)>>>(sums);
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
+    return sigmoid_dice_fwd_launch(logits, y_true, weight, probs, sums, n, stream);
 }
 extern "C" int fmri_sigmoid_loss_bwd_weighted(const float* probs, const uint8_t* y_true, const float* weight, const double* sums,
                                               float* dlogits, int64_t n, int kind, float param, float smooth, float grad_scale,
                                               fmri_stream_t stream) {
     if (n <= 0 || !weight || (kind != 1 && kind != 2)) return FMRI_E_SHAPE;
-    k_sigmoid_loss_bwd<<<grid_for(n, 256, 2048), 256, 0, as_stream(stream)>>>(probs, y_true, weight, sums, dlogits, n, kind, param, smooth, grad_scale);
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
+    return sigmoid_loss_bwd_launch(probs, y_true, weight, sums, dlogits, n, kind, param, smooth, grad_scale, stream);
 }
 
 extern "C" int fmri_sigmoid_dice_fwd(const float* logits, const uint8_t* y_true, float* probs, double* sums, int64_t n,
                                      fmri_stream_t stream) {
     if (n <= 0) return FMRI_E_SHAPE;
-    {
-        const bool v4 = n % 4 == 0 && !((((uintptr_t)logits) | ((uintptr_t)probs)) & 15) && !(((uintptr_t)y_true) & 3);
-        if (v4) k_sigmoid_dice_fwd<4><<<grid_for(n / 4, 256, 512), 256, 0, as_stream(stream)>>>(logits, y_true, nullptr, probs, sums, n);
-        else k_sigmoid_dice_fwd<1><<<grid_for(n, 256, 512), 256, 0, as_stream(stream)>>>(logits, y_true, nullptr, probs, sums, n);
-    }
-    if (h_det_on) k_isums_finish<<<1, 64, 0, as_stream(stream)>>>(sums);
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
+    return sigmoid_dice_fwd_launch(logits, y_true, nullptr, probs, sums, n, stream);
 }
 extern "C" int fmri_sigmoid_dice_bwd(const float* probs, const uint8_t* y_true, const double* sums, float* dlogits, int64_t n,
                                      float smooth, float grad_scale, fmri_stream_t stream) {
@@ -1001,41 +868,9 @@ extern "C" int fmri_label_sums(const float* probs, const uint8_t* y_true, int64_
     return FMRI_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ Keras Adam
-// Reference: Adam(lr=initial_learning_rate) at unet3d/unet.py:85; Keras 2.2 update rule (epsilon outside the sqrt).
-__global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                       int64_t n, float lr_t, float b1, float b2, float eps, float gs) {
-    const int64_t n4 = n >> 2;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 pp = ((float4*)p)[i], gg = ((const float4*)g)[i], mm = ((float4*)m)[i], vv = ((float4*)v)[i];
-        float* pa = (float*)&pp; float* ga = (float*)&gg; float* ma = (float*)&mm; float* va = (float*)&vv;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float gr = ga[k] * gs;
-            ma[k] = b1 * ma[k] + (1.f - b1) * gr;
-            va[k] = b2 * va[k] + (1.f - b2) * gr * gr;
-            pa[k] -= lr_t * ma[k] / (sqrtf(va[k]) + eps);
-        }
-        ((float4*)p)[i] = pp; ((float4*)m)[i] = mm; ((float4*)v)[i] = vv;
-    }
-    for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float gr = g[i] * gs;
-        float mi = b1 * m[i] + (1.f - b1) * gr, vi = b2 * v[i] + (1.f - b2) * gr * gr;
-        m[i] = mi; v[i] = vi;
-        p[i] -= lr_t * mi / (sqrtf(vi) + eps);
-    }
-}
-extern "C" int fmri_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
-                              float eps, float grad_scale, fmri_stream_t stream) {
-    if (n <= 0) return FMRI_E_SHAPE;
-    if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return FMRI_E_ALIGN;
-    k_adam<<<grid_for(n / 4 + 1, 256, 2048), 256, 0, as_stream(stream)>>>(p, g, m, v, n, lr_t, beta1, beta2, eps, grad_scale);
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ Keras SGD / RMSprop / AMSGrad, clipping
-// Keras 2.2.4 keras/optimizers.py as published (restated from the published source: no Keras was at hand to run against, so these
+// ------------------------------------------------------------------------------------------------ Keras Adam / SGD / RMSprop / AMSGrad, clipping
+// Reference: Adam(lr=initial_learning_rate) at unet3d/unet.py:85; Keras 2.2 update rule (epsilon outside the sqrt).  The other optimizers
+// and the clipping: Keras 2.2.4 keras/optimizers.py as published (restated from the published source: no Keras was at hand to run against, so these
 // formulas are parity-unpinned; tests/optimizer_restatement.py is the float64 form the kernels are tested against).
 //
 // The gradient every update sees (Optimizer.get_gradients, clip_norm): g = grad_scale * G[i]; with a norm (fmri_grad_sumsq's out[1],
@@ -1118,12 +953,12 @@ __global__ void k_rmsprop(float* __restrict__ p, const float* __restrict__ g, fl
         step(p[i], g[i], a[i]);
 }
 
-// Adam as k_adam (the <false, false> instantiation is its arithmetic, expression for expression), with AMSGrad:
-// vhat <- max(vhat, v), and sqrt(vhat) in the denominator
+// Adam: m <- b1 * m + (1 - b1) * g; v <- b2 * v + (1 - b2) * g^2; p <- p - lr_t * m / (sqrt(v) + eps).  <false, false> is plain Adam
+// (fmri_adam_step: g = grad_scale * G[i], vhat and gnorm NULL); AMS: vhat <- max(vhat, v), and sqrt(vhat) in the denominator
 template <bool CLIP, bool AMS>
-__global__ void k_adam_ex(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                          float* __restrict__ vhat, int64_t n, float lr_t, float b1, float b2, float eps, float gs,
-                          const double* __restrict__ gnorm, float clipnorm, float clipvalue) {
+__global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                       float* __restrict__ vhat, int64_t n, float lr_t, float b1, float b2, float eps, float gs,
+                       const double* __restrict__ gnorm, float clipnorm, float clipvalue) {
     const OptGrad<CLIP> grad(gs, gnorm, clipnorm, clipvalue);
     const int64_t n4 = n >> 2;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
@@ -1159,7 +994,7 @@ __global__ void k_adam_ex(float* __restrict__ p, const float* __restrict__ g, fl
     }
 }
 
-// n and alignment rules of fmri_adam_step; the clipping instantiation only where something clips
+// n and alignment rules of the optimizer entries; the clipping instantiation only where something clips
 #define OPT_REFUSE(n, bits)                                  \
     do {                                                     \
         if ((n) <= 0) return FMRI_E_SHAPE;                   \
@@ -1198,6 +1033,15 @@ extern "C" int fmri_rmsprop_step(float* p, const float* g, float* a, int64_t n, 
     return FMRI_OK;
 }
 
+extern "C" int fmri_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
+                              float eps, float grad_scale, fmri_stream_t stream) {
+    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v));
+    k_adam<false, false><<<grid_for(n / 4 + 1, 256, 2048), 256, 0, as_stream(stream)>>>(p, g, m, v, nullptr, n, lr_t, beta1, beta2, eps,
+                                                                                        grad_scale, nullptr, 0.f, 0.f);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
 extern "C" int fmri_adam_step_ex(float* p, const float* g, float* m, float* v, float* vhat, int64_t n, float lr_t, float beta1, float beta2,
                                  float eps, float grad_scale, const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream) {
     OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)vhat));
@@ -1205,7 +1049,7 @@ extern "C" int fmri_adam_step_ex(float* p, const float* g, float* m, float* v, f
     if (((uintptr_t)gnorm) & 7) return FMRI_E_ALIGN;
     const int grid = grid_for(n / 4 + 1, 256, 2048);
     hipStream_t s = as_stream(stream);
-#define ADAM(C, A) k_adam_ex<C, A><<<grid, 256, 0, s>>>(p, g, m, v, vhat, n, lr_t, beta1, beta2, eps, grad_scale, gnorm, clipnorm, clipvalue)
+#define ADAM(C, A) k_adam<C, A><<<grid, 256, 0, s>>>(p, g, m, v, vhat, n, lr_t, beta1, beta2, eps, grad_scale, gnorm, clipnorm, clipvalue)
     if (clip) { if (vhat) ADAM(true, true); else ADAM(true, false); }
     else { if (vhat) ADAM(false, true); else ADAM(false, false); }
 #undef ADAM

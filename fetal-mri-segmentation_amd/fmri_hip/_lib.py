@@ -48,10 +48,6 @@ SIGNATURES = {
     "fmri_weighted_dice_fwd": [p, p, p, p, i32, i64, i32, f32, p],
     "fmri_weighted_dice_bwd": [p, p, p, p, p, i32, i64, i32, f32, f32, p],
     "fmri_label_sums": [p, p, i64, i32, p, p],
-    "fmri_maxpool3d_2x_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, p],
-    "fmri_maxpool3d_2x_bwd": [p, p, p, i32, i32, p, i32, i32, i32, i32, i32, i32, i32, i32, p],
-    "fmri_upsample_nearest2x_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
-    "fmri_upsample_nearest2x_bwd": [p, i32, i32, p, p, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_maxpool3d_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_maxpool3d_bwd": [p, p, p, i32, i32, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_upsample_nearest_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],

@@ -127,7 +127,7 @@ class LayerGraphEngine(EngineBase):
             return len(c) == 1 and (cls is None or self.by_name[c[0]].class_name in cls)
 
         def window(l, key):
-            """per-axis factors of a pooling / up-sampling layer; None = all 2s, the path of the 2x kernels (and of the fused up0)"""
+            """per-axis factors of a pooling / up-sampling layer; None = all 2s, the fixed-window kernels (and the fused up0)"""
             size = tuple(int(v) for v in (l.config.get(key) or (2,) * nd))
             if len(size) != nd or not all(1 <= v <= 4 for v in size) or all(v == 1 for v in size):
                 raise NotImplementedError("%s %s of layer %s: per-axis factors 1..4, not all 1" % (key, size, l.name))

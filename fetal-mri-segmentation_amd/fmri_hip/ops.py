@@ -184,7 +184,10 @@ def sigmoid_dice_bwd(probs, y_true, sums, dlogits, smooth=1.0, grad_scale=1.0):
 
 
 def _pool3(pool, planar):
-    """per-axis factors (pd, ph, pw) of a layer's pool_size / size; the 2-D layer of a planar tensor leaves the slice axis alone"""
+    """per-axis factors (pd, ph, pw) of a layer's pool_size / size; None: all 2s; the 2-D layer of a planar tensor leaves the slice axis
+    alone"""
+    if pool is None:
+        return (1, 2, 2) if planar else (2, 2, 2)
     pool = tuple(int(v) for v in pool)
     if len(pool) == 2:
         if not planar:
@@ -196,15 +199,12 @@ def _pool3(pool, planar):
 
 
 def maxpool_fwd(x, y, planar=False, pool=None):
-    """pool=None: the 2x2x2 (planar: 1x2x2) kernels; pool=(pd, ph, pw) or, planar, (ph, pw): per-axis factors 1..4"""
+    """pool=(pd, ph, pw) or, planar, (ph, pw): per-axis factors 1..4; None: 2x2x2 (planar: 1x2x2)"""
     _need_cuda(x, y)
     N, D, H, W, Cc = x.shape
-    if pool is not None:
-        pd, ph, pw = _pool3(pool, planar)
-        assert tuple(y.shape) == (N, D // pd, H // ph, W // pw, Cc), (tuple(x.shape), tuple(y.shape), pool)
-        check(lib().fmri_maxpool3d_fwd(_p(x), _p(y), N, D, H, W, Cc, pd, ph, pw, dt(x), _s()), "fmri_maxpool3d_fwd")
-        return y
-    check(lib().fmri_maxpool3d_2x_fwd(_p(x), _p(y), N, D, H, W, Cc, dt(x), int(planar), _s()), "fmri_maxpool3d_2x_fwd")
+    pd, ph, pw = _pool3(pool, planar)
+    assert tuple(y.shape) == (N, D // pd, H // ph, W // pw, Cc), (tuple(x.shape), tuple(y.shape), pool)
+    check(lib().fmri_maxpool3d_fwd(_p(x), _p(y), N, D, H, W, Cc, pd, ph, pw, dt(x), _s()), "fmri_maxpool3d_fwd")
     return y
 
 
@@ -212,42 +212,30 @@ def maxpool_bwd(x, dy, dx, add=None, add_off=0, relu_mask=True, planar=False, po
     _need_cuda(x, dy, dx, add)
     N, D, H, W, Cc = x.shape
     add_ld = 0 if add is None else add.shape[-1]
-    if pool is not None:
-        pd, ph, pw = _pool3(pool, planar)
-        assert tuple(dy.shape) == (N, D // pd, H // ph, W // pw, Cc) and dx.shape == x.shape, (tuple(x.shape), tuple(dy.shape), pool)
-        check(lib().fmri_maxpool3d_bwd(_p(x), _p(dy), _p(add), add_ld, add_off, _p(dx), N, D, H, W, Cc, pd, ph, pw, int(relu_mask), dt(x), _s()),
-              "fmri_maxpool3d_bwd")
-        return dx
-    check(lib().fmri_maxpool3d_2x_bwd(_p(x), _p(dy), _p(add), add_ld, add_off, _p(dx), N, D, H, W, Cc, int(relu_mask), dt(x), int(planar), _s()),
-          "fmri_maxpool3d_2x_bwd")
+    pd, ph, pw = _pool3(pool, planar)
+    assert tuple(dy.shape) == (N, D // pd, H // ph, W // pw, Cc) and dx.shape == x.shape, (tuple(x.shape), tuple(dy.shape), pool)
+    check(lib().fmri_maxpool3d_bwd(_p(x), _p(dy), _p(add), add_ld, add_off, _p(dx), N, D, H, W, Cc, pd, ph, pw, int(relu_mask), dt(x), _s()),
+          "fmri_maxpool3d_bwd")
     return dx
 
 
 def upsample_fwd(x, y, y_off=0, planar=False, pool=None):
     _need_cuda(x, y)
     N, D, H, W, Cc = x.shape
-    if pool is not None:
-        pd, ph, pw = _pool3(pool, planar)
-        assert tuple(y.shape[:-1]) == (N, D * pd, H * ph, W * pw), (tuple(x.shape), tuple(y.shape), pool)
-        check(lib().fmri_upsample_nearest_fwd(_p(x), _p(y), y.shape[-1], y_off, N, D, H, W, Cc, pd, ph, pw, dt(x), _s()),
-              "fmri_upsample_nearest_fwd")
-        return y
-    check(lib().fmri_upsample_nearest2x_fwd(_p(x), _p(y), y.shape[-1], y_off, N, D, H, W, Cc, dt(x), int(planar), _s()),
-          "fmri_upsample_nearest2x_fwd")
+    pd, ph, pw = _pool3(pool, planar)
+    assert tuple(y.shape[:-1]) == (N, D * pd, H * ph, W * pw), (tuple(x.shape), tuple(y.shape), pool)
+    check(lib().fmri_upsample_nearest_fwd(_p(x), _p(y), y.shape[-1], y_off, N, D, H, W, Cc, pd, ph, pw, dt(x), _s()),
+          "fmri_upsample_nearest_fwd")
     return y
 
 
 def upsample_bwd(dy, dx, dy_off=0, xmask=None, planar=False, pool=None):
     _need_cuda(dy, dx, xmask)
     N, D, H, W, Cc = dx.shape
-    if pool is not None:
-        pd, ph, pw = _pool3(pool, planar)
-        assert tuple(dy.shape[:-1]) == (N, D * pd, H * ph, W * pw), (tuple(dx.shape), tuple(dy.shape), pool)
-        check(lib().fmri_upsample_nearest_bwd(_p(dy), dy.shape[-1], dy_off, _p(xmask), _p(dx), N, D, H, W, Cc, pd, ph, pw, dt(dx), _s()),
-              "fmri_upsample_nearest_bwd")
-        return dx
-    check(lib().fmri_upsample_nearest2x_bwd(_p(dy), dy.shape[-1], dy_off, _p(xmask), _p(dx), N, D, H, W, Cc, dt(dx), int(planar), _s()),
-          "fmri_upsample_nearest2x_bwd")
+    pd, ph, pw = _pool3(pool, planar)
+    assert tuple(dy.shape[:-1]) == (N, D * pd, H * ph, W * pw), (tuple(dx.shape), tuple(dy.shape), pool)
+    check(lib().fmri_upsample_nearest_bwd(_p(dy), dy.shape[-1], dy_off, _p(xmask), _p(dx), N, D, H, W, Cc, pd, ph, pw, dt(dx), _s()),
+          "fmri_upsample_nearest_bwd")
     return dx
 
 

@@ -68,7 +68,7 @@ int fmri_conv3d_fwd(const void* src0, int C0, int up0, const void* src1, int C1,
  * The tile of y is still in LDS when it is stored; from those same stored values the kernel can also produce
  *   y_pool [N][D/2][H/2][W/2][Cout]  = MaxPooling3D(2) of y            (reference unet3d/unet.py:51 behind the encoder block :45-50)
  *   logits [N*D*H*W] fp32            = Conv3D(1, (1,1,1))(y) = sum_c w1[c]*y[v][c] + b1[0]   (reference unet.py:68, n_labels = 1)
- * so that neither fmri_maxpool3d_2x_fwd nor fmri_conv1x1_fwd has to read y back.  Either output may be NULL (not both).
+ * so that neither fmri_maxpool3d_fwd nor fmri_conv1x1_fwd has to read y back.  Either output may be NULL (not both).
  * fmri_conv3d_fwd_tail_ok: bit 0 = y_pool available, bit 1 = logits available for this shape (host-side query, no GPU needed). */
 int fmri_conv3d_fwd_tail_ok(int C0, int Cout, int N, int D, int H, int W, int dtype);
 int fmri_conv3d_fwd_tail(const void* src0, int C0, const void* w, const float* bias, void* y, void* y_pool, const float* w1,
@@ -246,26 +246,15 @@ int fmri_sigmoid_loss_bwd_weighted(const float* probs, const uint8_t* y_true, co
  * 2^-20 fixed-point integers (as the sums of fmri_sigmoid_dice_fwd): two calls agree bit for bit. */
 int fmri_label_sums(const float* probs, const uint8_t* y_true, int64_t nvox, int L, double* lsums, fmri_stream_t stream);
 
-/* ---- MaxPooling3D(2,2,2) — reference unet.py:51.  D,H,W are the INPUT dims (even). */
-int fmri_maxpool3d_2x_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int dtype, int planar,
-                          fmri_stream_t stream);
-/* MaxPool3DGrad fused with the skip-gradient add and the ReluGrad of the producer:
- *   dx[v][c] = ( (add ? add[v*add_ld + add_off + c] : 0) + (x[v][c] is the first max of its window ? dy[win][c] : 0) ) * (x>0 || !relu_mask) */
-int fmri_maxpool3d_2x_bwd(const void* x, const void* dy, const void* add, int add_ld, int add_off, void* dx, int N,
-                          int D, int H, int W, int C, int relu_mask, int dtype, int planar, fmri_stream_t stream);
-
-/* ---- UpSampling3D(2) — reference unet.py:138.  Materialising forward (writes channel slice [y_off, y_off+C) of a
- * tensor with y_ld channels); D,H,W are the LOW-resolution dims.  The conv kernels do not need it (fused). */
-int fmri_upsample_nearest2x_fwd(const void* x, void* y, int y_ld, int y_off, int N, int D, int H, int W, int C, int dtype,
-                                int planar, fmri_stream_t stream);
-/* backward: dx[v][c] = (sum over the 2x2x2 children of dy[child*dy_ld + dy_off + c]) * (xmask[v][c] > 0 || !xmask) */
-int fmri_upsample_nearest2x_bwd(const void* dy, int dy_ld, int dy_off, const void* xmask, void* dx, int N, int D, int H,
-                                int W, int C, int dtype, int planar, fmri_stream_t stream);
-
-/* ---- MaxPooling3D(pool_size) / UpSampling3D(size) with per-axis factors pd, ph, pw in 1..4 (not all 1), stride = window - the
- * anisotropic (2, 2, 1) of reference configs; a 2-D layer of a planar tensor is (1, ph, pw).  Same arithmetic, tie rule (first maximum
- * in (d, h, w) scan order), fused skip-gradient add / ReLU mask / xmask and fp32 child sum as the 2x entries above, which stay the path
- * of 2x2x2 windows.  FMRI_E_SHAPE: a factor outside 1..4, all factors 1, a pooled dimension that is no multiple of its factor, a
+/* ---- MaxPooling3D(pool_size) / UpSampling3D(size) — reference unet.py:51, :138 — with per-axis factors pd, ph, pw in 1..4 (not all 1),
+ * stride = window: 2x2x2, the anisotropic (2, 2, 1) of reference configs; a 2-D layer of a planar tensor is (1, ph, pw).  Windows 2x2x2
+ * and 1x2x2 run fully unrolled instantiations of the kernels, every other window the run-time one: the same arithmetic, in (d, h, w)
+ * scan order, in all of them.
+ *   maxpool_bwd: MaxPool3DGrad fused with the skip-gradient add and the ReluGrad of the producer:
+ *     dx[v][c] = ( (add ? add[v*add_ld + add_off + c] : 0) + (x[v][c] is the FIRST max of its window ? dy[win][c] : 0) ) * (x>0 || !relu_mask)
+ *   upsample_fwd: materialising (writes channel slice [y_off, y_off+C) of a tensor with y_ld channels); the conv kernels fuse it instead.
+ *   upsample_bwd: dx[v][c] = (fp32 sum over the children of dy[child*dy_ld + dy_off + c]) * (xmask[v][c] > 0 || !xmask)
+ * FMRI_E_SHAPE: a factor outside 1..4, all factors 1, a pooled dimension that is no multiple of its factor, a negative offset, a
  * channel slice [off, off + C) that does not fit in ld.
  * fmri_maxpool3d_*: D,H,W are the INPUT dims.  fmri_upsample_nearest_*: D,H,W are the LOW-resolution dims. */
 int fmri_maxpool3d_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int pd, int ph, int pw, int dtype,
@@ -400,7 +389,7 @@ int fmri_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
 
 /* ---- Keras 2.2.4 SGD / RMSprop / Adam with AMSGrad, and gradient clipping (keras/optimizers.py as published; restated without a Keras to
  * run against: parity-unpinned).  One launch over the flat buffers each; n <= 0: FMRI_E_SHAPE, a buffer that is not 16-byte aligned (gnorm:
- * 8-byte): FMRI_E_ALIGN - nothing is launched then.  Plain Adam stays on fmri_adam_step.
+ * 8-byte): FMRI_E_ALIGN - nothing is launched then.
  * The gradient every update sees (Optimizer.get_gradients, clip_norm), in fp32, left to right:
  *     g = grad_scale * G[i]
  *     gnorm != NULL and clipnorm > 0 and norm >= clipnorm:   g = g * clipnorm / norm       norm = (float)*gnorm, read on the device
@@ -409,7 +398,7 @@ int fmri_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
  * fmri_sgd_step      v = momentum * m - lr * g;  m <- v;  p <- p + v, or with nesterov != 0  p <- p + momentum * v - lr * g (that
  *                    increment is formed in float64 and rounded once: its two terms cancel where momentum and gradient oppose)
  * fmri_rmsprop_step  a <- rho * a + (1 - rho) * g^2;  p <- p - lr * g / (sqrt(a) + eps)
- * fmri_adam_step_ex  fmri_adam_step's update; vhat != NULL (AMSGrad): vhat <- max(vhat, v), p <- p - lr_t * m / (sqrt(vhat) + eps).
+ * fmri_adam_step_ex  fmri_adam_step's update, by the same kernel; vhat != NULL (AMSGrad): vhat <- max(vhat, v), p <- p - lr_t * m / (sqrt(vhat) + eps).
  *                    With vhat, gnorm NULL and clipvalue 0 it gives fmri_adam_step's bits.
  * lr (lr_t for Adam) carries Keras' `decay` and Adam's bias correction, both computed by the host.
  * fmri_grad_sumsq: out[0] (device, float64) = sum over i of (float(grad_scale * g[i]))^2, out[1] = sqrt(out[0]).  The squares are exact

@@ -98,7 +98,7 @@ def test_input_gradient_form_with_relu_mask(ops, case):
 @pytest.mark.parametrize("shape", [(1, 8, 16, 32, 16, 32), (2, 16, 32, 64, 32, 64)], ids=lambda c: "N%d_%dx%dx%d_%d_%d" % c)
 def test_pooled_copy_tail(ops, shape):
     """fmri_conv3d_fwd_tail in fp32: the drain also writes MaxPooling3D(2)(y) (reference unet3d/unet.py:45-51) - y bit-identical to the plain
-    launch, the pooled tensor bit-identical to fmri_maxpool3d_2x_fwd(y); no logits tail in fp32 (32-wide blocks)"""
+    launch, the pooled tensor bit-identical to fmri_maxpool3d_fwd(y, 2, 2, 2); no logits tail in fp32 (32-wide blocks)"""
     N, D, H, W, C0, Cout = shape
     assert ops.conv3d_fwd_tail_ok(C0, Cout, N, D, H, W, F32) == 1
     x = rnd((N, D, H, W, C0), 21, F32)

@@ -894,7 +894,7 @@ TAIL_CASES = [
 @pytest.mark.parametrize("case", TAIL_CASES, ids=[c[0] for c in TAIL_CASES])
 def test_conv3d_fwd_tail(ops, case):
     """fmri_conv3d_fwd_tail: the conv block's epilogue also writes MaxPooling3D(2)(y) and the final 1x1x1 conv's logits from the tile
-    in LDS.  y must be BIT-identical to fmri_conv3d_fwd, the pooled tensor to fmri_maxpool3d_2x_fwd(y) (same bf16 values, max is
+    in LDS.  y must be BIT-identical to fmri_conv3d_fwd, the pooled tensor to fmri_maxpool3d_fwd(y, 2, 2, 2) (same bf16 values, max is
     exact), the logits equal fmri_conv1x1_fwd(y) up to fp32 summation order; all three are checked against fp64 as well
     (reference unet3d/unet.py:45-51, :68)."""
     name, N, D, H, W, C0, Cout, bits = case
@@ -1014,7 +1014,7 @@ PLANAR_TAIL_CASES = [
 @pytest.mark.parametrize("case", PLANAR_TAIL_CASES, ids=[c[0] for c in PLANAR_TAIL_CASES])
 def test_conv3d_fwd_tail_planar(ops, case):
     """fmri_conv3d_fwd_tail_planar (2-D models): the planar conv block's epilogue also writes MaxPooling2D(2) of every slice and the final
-    1x1 conv's logits from the staged tile.  y BIT-identical to fmri_conv3d_fwd(planar), the pooled slices to fmri_maxpool3d_2x_fwd(planar),
+    1x1 conv's logits from the staged tile.  y BIT-identical to fmri_conv3d_fwd(planar), the pooled slices to fmri_maxpool3d_fwd(1, 2, 2),
     the logits equal to fmri_conv1x1_fwd up to fp32 summation order; y and logits against fp64 as well (reference unet/unet.py:57-67, :82)."""
     name, S, H, W, C0, Cout, act, bits = case
     bf = torch.bfloat16

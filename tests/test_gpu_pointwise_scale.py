@@ -215,15 +215,16 @@ def test_pool_and_upsample_refusals(ops):
     x = torch.zeros((1, 2, 4, 4, 8), device="cuda")
     y = torch.zeros((1, 2, 4, 4, 8), device="cuda")
     p = x.data_ptr()
-    assert L.fmri_maxpool3d_2x_fwd(p, y.data_ptr(), 1, 2, 3, 4, 8, 0, 0, s) == E_SHAPE          # odd H
-    assert L.fmri_maxpool3d_2x_fwd(p, y.data_ptr(), 1, 3, 4, 4, 8, 0, 0, s) == E_SHAPE          # odd D, 3-D
-    assert L.fmri_maxpool3d_2x_fwd(p, y.data_ptr(), 1, 2, 4, 4, 8, 7, 0, s) == E_DTYPE
-    assert L.fmri_maxpool3d_2x_bwd(p, p, 0, 0, 0, y.data_ptr(), 1, 2, 4, 5, 8, 1, 0, 0, s) == E_SHAPE
-    assert L.fmri_maxpool3d_2x_bwd(p, p, 0, 0, 0, y.data_ptr(), 1, 2, 4, 4, 8, 1, 7, 0, s) == E_DTYPE
-    assert L.fmri_upsample_nearest2x_fwd(p, y.data_ptr(), 8, 1, 1, 1, 2, 2, 8, 0, 0, s) == E_SHAPE  # ld < off + C
-    assert L.fmri_upsample_nearest2x_fwd(p, y.data_ptr(), 8, 0, 1, 1, 2, 2, 8, 7, 0, s) == E_DTYPE
-    assert L.fmri_upsample_nearest2x_bwd(p, 8, 1, 0, y.data_ptr(), 1, 1, 2, 2, 8, 0, 0, s) == E_SHAPE
-    assert L.fmri_upsample_nearest2x_bwd(p, 8, 0, 0, y.data_ptr(), 1, 1, 2, 2, 8, 7, 0, s) == E_DTYPE
+    w = (2, 2, 2)                                                                               # the fixed-window instantiations' entry
+    assert L.fmri_maxpool3d_fwd(p, y.data_ptr(), 1, 2, 3, 4, 8, *w, 0, s) == E_SHAPE            # odd H
+    assert L.fmri_maxpool3d_fwd(p, y.data_ptr(), 1, 3, 4, 4, 8, *w, 0, s) == E_SHAPE            # odd D, 3-D
+    assert L.fmri_maxpool3d_fwd(p, y.data_ptr(), 1, 2, 4, 4, 8, *w, 7, s) == E_DTYPE
+    assert L.fmri_maxpool3d_bwd(p, p, 0, 0, 0, y.data_ptr(), 1, 2, 4, 5, 8, *w, 1, 0, s) == E_SHAPE
+    assert L.fmri_maxpool3d_bwd(p, p, 0, 0, 0, y.data_ptr(), 1, 2, 4, 4, 8, *w, 1, 7, s) == E_DTYPE
+    assert L.fmri_upsample_nearest_fwd(p, y.data_ptr(), 8, 1, 1, 1, 2, 2, 8, *w, 0, s) == E_SHAPE  # ld < off + C
+    assert L.fmri_upsample_nearest_fwd(p, y.data_ptr(), 8, 0, 1, 1, 2, 2, 8, *w, 7, s) == E_DTYPE
+    assert L.fmri_upsample_nearest_bwd(p, 8, 1, 0, y.data_ptr(), 1, 1, 2, 2, 8, *w, 0, s) == E_SHAPE
+    assert L.fmri_upsample_nearest_bwd(p, 8, 0, 0, y.data_ptr(), 1, 1, 2, 2, 8, *w, 7, s) == E_DTYPE
     torch.cuda.synchronize()
     assert not bool(y.any())
 

@@ -2,11 +2,13 @@
 fmri_upsample_nearest_fwd / _bwd) and the models that use them - unet_model_3d / unet_model_2d with a pool size other than all 2s,
 unet_model_2d with SpatialDropout2D - on the layer-graph engine.
 
-Kernel level: exact against numpy restatements (windows flattened in (d, h, w) scan order; np.argmax returns the first maximum); pool
-(2, 2, 2) / planar (1, 2, 2) through the new entries is bit-identical to the 2x entries.
+Kernel level: exact against numpy restatements (windows flattened in (d, h, w) scan order; np.argmax returns the first maximum); the
+fixed-window instantiations, pool (2, 2, 2) / planar (1, 2, 2), reproduce the recorded bits of the 2x entries they replaced
+(tests/golden/pool_2x_digests.json), and (1, 2, 2) equals the run-time window (2, 2, 1) on rotated axes bit for bit.
 Model level: a torch-CPU float64 restatement written here (F.conv, F.max_pool(pool), F.interpolate(scale_factor=pool, 'nearest'), fixed
 dropout masks, autograd) with the bounds of test_gpu_engine.py::test_isensee_graph_engine_fp32_vs_oracle: logits 1e-3 relative, Dice 1e-4,
 gradients 5e-3 relative L2."""
+import json
 import os
 import sys
 
@@ -16,7 +18,9 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gpu_util import assert_same, rnd          # noqa: E402
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+from gpu_util import assert_same               # noqa: E402
+import make_pool_2x_fixture as FX              # noqa: E402  (the inputs of the recorded digests, and how a tensor is hashed)
 
 pytestmark = pytest.mark.gpu
 
@@ -150,36 +154,65 @@ def test_grid_stride_loop_wraps(C, dtype):
     _check_upsample((2, 16, 32, 64, C), (2, 2, 1), dtype, seed=14, slices=ADDS[1:2] if C == 32 else ADDS[2:])
 
 
+def _recorded():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pool_2x_digests.json")) as f:
+        return json.load(f)
+
+
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("C", CHANNELS)
 @pytest.mark.parametrize("planar", [False, True])
 def test_all_twos_equals_the_2x_kernels_bit_for_bit(planar, C, dtype):
-    """pool (2, 2, 2) - planar: (1, 2, 2) - through the new entries against the 2x entries on random, non-dyadic data: forward, backward
-    (skip gradient and ReLU mask on), both up-sampling directions"""
+    """pool=None and the explicit (2, 2, 2) - planar: (1, 2, 2) - give, output for output, the sha256 that the retired 2x entries gave on
+    the same non-dyadic inputs (tests/golden/pool_2x_digests.json, recorded by make_pool_2x_fixture.py on the last commit that had them):
+    forward, backward with skip gradient and ReLU mask and without both, both up-sampling directions through a channel slice"""
+    recorded, key = _recorded(), FX.case_key(planar, C, dtype)
+    for pool in (None, (1, 2, 2) if planar else (2, 2, 2)):
+        got = FX.pool_outputs(_ops(), planar, C, dtype, pool=pool)
+        assert len(got) == 6
+        for name, t in got.items():
+            assert FX.digest(t) == recorded["%s/%s" % (key, name)], (key, name, pool)
+
+
+def test_adam_step_equals_the_recorded_bits():
+    """three fmri_adam_step steps on 4,099 elements (quads and a 3-element tail), grad_scale 0.5: p, m and v hash to what the stand-alone
+    Adam kernel gave before it became an instantiation of the optimizer template (same fixture)"""
+    recorded = _recorded()
+    got = FX.adam_outputs(_ops().adam_step)
+    assert sorted(got) == ["m", "p", "v"]
+    for name, t in got.items():
+        assert FX.digest(t) == recorded["adam/%s" % name], name
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("C", CHANNELS)
+@pytest.mark.parametrize("vol", [(1, 5, 6, 4), (2, 4, 6, 4)])
+def test_fixed_122_equals_run_time_221_on_permuted_axes(vol, C, dtype):
+    """the one place where a fixed and the run-time instantiation meet: window (1, 2, 2) on x against window (2, 2, 1) on x with its axes
+    rotated (d, h, w) -> (h, w, d).  Both walk the same voxels in the same order, so every result agrees bit for bit after rotating back:
+    forward, backward with skip gradient and ReLU mask, both up-sampling directions through a channel slice, with xmask"""
     ops = _ops()
-    pool = (1, 2, 2) if planar else (2, 2, 2)
-    fine = (1, 5, 6, 4, C) if planar else (2, 4, 6, 4, C)
-    low = (fine[0], fine[1] // pool[0], fine[2] // 2, fine[3] // 2, C)
-    x = torch.relu(rnd(fine, 1, dtype))
-    dy, add = rnd(low, 2, dtype), rnd(fine[:-1] + (C + 16,), 3, dtype)
-    out = []
-    for p in (None, pool):
-        y = torch.empty(low, dtype=dtype, device="cuda")
-        ops.maxpool_fwd(x, y, planar=planar, pool=p)
-        dx = torch.empty(fine, dtype=dtype, device="cuda")
-        ops.maxpool_bwd(x, dy, dx, add=add, add_off=8, relu_mask=True, planar=planar, pool=p)
-        dx0 = torch.empty(fine, dtype=dtype, device="cuda")
-        ops.maxpool_bwd(x, dy, dx0, relu_mask=False, planar=planar, pool=p)
-        up = torch.zeros(fine[:-1] + (C + 16,), dtype=dtype, device="cuda")
-        ops.upsample_fwd(dy, up, y_off=8, planar=planar, pool=p)
-        dlow = torch.empty(low, dtype=dtype, device="cuda")
-        ops.upsample_bwd(add, dlow, dy_off=8, xmask=dy, planar=planar, pool=p)
-        dlow0 = torch.empty(low, dtype=dtype, device="cuda")
-        ops.upsample_bwd(add, dlow0, dy_off=0, planar=planar, pool=p)
-        out.append((y, dx, dx0, up, dlow, dlow0))
+    fine, low, wide = vol + (C,), (vol[0], vol[1], vol[2] // 2, vol[3] // 2, C), vol + (C + FX.WIDE,)
+    rot = lambda t: t.permute(0, 2, 3, 1, 4).contiguous()
+    back = lambda t: t.permute(0, 3, 1, 2, 4).contiguous()
+    new = lambda ref: torch.zeros_like(ref)
+    x = torch.relu(FX.formula(fine, 1, dtype))
+    dy, add = FX.formula(low, 2, dtype), FX.formula(wide, 3, dtype)
+    xr, dyr, addr = rot(x), rot(dy), rot(add)
+    a, b = dict(planar=True, pool=(1, 2, 2)), dict(pool=(2, 2, 1))
+    pairs = {
+        "maxpool fwd": (ops.maxpool_fwd(x, new(dy), **a), ops.maxpool_fwd(xr, new(dyr), **b)),
+        "maxpool bwd + add + mask": (ops.maxpool_bwd(x, dy, new(x), add=add, add_off=FX.OFF, relu_mask=True, **a),
+                                     ops.maxpool_bwd(xr, dyr, new(xr), add=addr, add_off=FX.OFF, relu_mask=True, **b)),
+        "upsample fwd": (ops.upsample_fwd(dy, new(add), y_off=FX.OFF, **a), ops.upsample_fwd(dyr, new(addr), y_off=FX.OFF, **b)),
+        "upsample bwd + xmask": (ops.upsample_bwd(add, new(dy), dy_off=FX.OFF, xmask=dy, **a),
+                                 ops.upsample_bwd(addr, new(dyr), dy_off=FX.OFF, xmask=dyr, **b)),
+        "upsample bwd": (ops.upsample_bwd(add, new(dy), dy_off=FX.OFF, **a), ops.upsample_bwd(addr, new(dyr), dy_off=FX.OFF, **b)),
+    }
     torch.cuda.synchronize()
-    for what, a, b in zip(("maxpool fwd", "maxpool bwd + add + mask", "maxpool bwd", "upsample fwd", "upsample bwd + xmask", "upsample bwd"), out[1], out[0]):
-        assert_same(a, b, what)
+    for what, (fixed, run_time) in pairs.items():
+        assert float(fixed.float().abs().max()) > 0, what
+        assert_same(back(run_time), fixed, what)
 
 
 def test_shape_errors_are_return_codes():
@@ -357,7 +390,7 @@ def test_unet2d_dropout_and_asymmetric_pool_fp32_vs_restatement(pool):
     assert eng.planar
     for o in eng.ops:
         if o["kind"] in ("maxpool", "upsample"):
-            assert o["pool"] == (None if pool == (2, 2) else pool)                 # all 2s stay on the 2x kernels
+            assert o["pool"] == (None if pool == (2, 2) else pool)                 # all 2s: None, the fixed-window kernels
     eng.load_keras_weights(W)
     eng.set_dropout_masks({k: torch.tensor(v, dtype=torch.float32).cuda() for k, v in masks.items()})
     xd = torch.from_numpy(x).cuda().unsqueeze(0).contiguous()

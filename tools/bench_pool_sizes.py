@@ -1,17 +1,18 @@
 #!/usr/bin/env python3
-"""Max-pooling / nearest up-sampling with per-axis factors (`fmri_maxpool3d_fwd / _bwd`, `fmri_upsample_nearest_fwd / _bwd`) next to the 2x
-kernels, and the models that use them.  Three sections (`--only kernels|model|bound`, default all):
+"""Max-pooling / nearest up-sampling with per-axis factors (`fmri_maxpool3d_fwd / _bwd`, `fmri_upsample_nearest_fwd / _bwd`), and the
+models that use them.  Three sections (`--only kernels|model|bound`, default all):
 
-kernels  bf16, the headline level-0 tensor 4 x 64 x 128 x 128 x 64 as the FINE side of every launch: the 2x kernels, the new kernels at
-         pool (2, 2, 2) on the same tensors, the new kernels at pool (2, 2, 1).  Device events around 20 back-to-back launches, 7 rounds with
-         the variants alternated inside a round, 2 warm-up rounds; median of the rounds, their min and max, and the bytes the launch has to
-         move (every tensor once) over the median.  Nothing in the product switches to the new kernels for (2, 2, 2): a report, not a gate.
+kernels  bf16, the headline level-0 tensor 4 x 64 x 128 x 128 x 64 as the FINE side of every launch: pool (2, 2, 2) and, planar, (1, 2, 2) -
+         the two fixed-window instantiations of the kernels - and (2, 2, 1), the run-time window.  Device events around 20 back-to-back
+         launches, 7 rounds, 2 warm-up rounds; median of the rounds, their min and max, and the bytes the launch has to move (every tensor
+         once) over the median.  A report, not a gate.
 model    ms per training step of unet_model_3d(pool_size=(2, 2, 1)) beside the (2, 2, 2) model, both bf16 at batch 4 x 128 x 128 x 16, depth 4,
          32 filters, both on the layer-graph engine; 5 alternated rounds of 20 steps after 10 warm-up steps each.
 bound    the bf16 (channel-padded) layer-graph engine against the fp32 one on unet_model_3d(input_shape=(1, 16, 16, 16), depth=3,
          n_base_filters=4), pool (2, 2, 2): max |logits_bf16 - logits_fp32| / max |logits_fp32| with the weights and the batch of
          tests/test_gpu_pool_sizes.py::test_unet3d_anisotropic_pool_bf16_padded_engine, whose bound is twice this figure.  This section uses
-         nothing this pool-size work added: `--root` points it at a checkout of the commit before it.
+         nothing the pool-size work added.
+`--root` imports the package (and `bench`) from another checkout: the same sections timed on that commit's kernels.
 """
 import argparse
 import os
@@ -64,21 +65,17 @@ def kernels():
     out_fine = torch.empty(fine, dtype=dt, device="cuda")
     nf = x.numel() * es
     print("# bf16, fine tensor %s = %.3f GB; bytes = every tensor of the launch once" % (fine, nf / 1e9))
-    for pool in ((2, 2, 2), (2, 2, 1)):
+    for pool in ((2, 2, 2), (2, 2, 1), (1, 2, 2)):
         low = (fine[0], fine[1] // pool[0], fine[2] // pool[1], fine[3] // pool[2], fine[4])
         nl = nf // (pool[0] * pool[1] * pool[2])
         y = torch.empty(low, dtype=dt, device="cuda")
         dy = torch.randn(low, generator=g, device="cuda").to(dt)
-        forms = [("new", pool)] + ([("2x", None)] if pool == (2, 2, 2) else [])
+        kw = dict(pool=pool, planar=pool[0] == 1)
         tag = "pool %s" % (pool,)
-        report(tag, rounds({"maxpool fwd, %s" % f: (lambda p=p: ops.maxpool_fwd(x, y, pool=p)) for f, p in forms}),
-               {"maxpool fwd, %s" % f: nf + nl for f, _ in forms})
-        report(tag, rounds({"maxpool bwd, %s" % f: (lambda p=p: ops.maxpool_bwd(x, dy, out_fine, relu_mask=False, pool=p)) for f, p in forms}),
-               {"maxpool bwd, %s" % f: nf + nl + nf for f, _ in forms})
-        report(tag, rounds({"upsample fwd, %s" % f: (lambda p=p: ops.upsample_fwd(dy, out_fine, pool=p)) for f, p in forms}),
-               {"upsample fwd, %s" % f: nl + nf for f, _ in forms})
-        report(tag, rounds({"upsample bwd, %s" % f: (lambda p=p: ops.upsample_bwd(dfine, y, pool=p)) for f, p in forms}),
-               {"upsample bwd, %s" % f: nf + nl for f, _ in forms})
+        report(tag, rounds({"maxpool fwd": lambda: ops.maxpool_fwd(x, y, **kw)}), {"maxpool fwd": nf + nl})
+        report(tag, rounds({"maxpool bwd": lambda: ops.maxpool_bwd(x, dy, out_fine, relu_mask=False, **kw)}), {"maxpool bwd": nf + nl + nf})
+        report(tag, rounds({"upsample fwd": lambda: ops.upsample_fwd(dy, out_fine, **kw)}), {"upsample fwd": nl + nf})
+        report(tag, rounds({"upsample bwd": lambda: ops.upsample_bwd(dfine, y, **kw)}), {"upsample bwd": nf + nl})
 
 
 def model():

@@ -38,7 +38,7 @@ def _stats(name):
         nm = re.sub(r"\(anonymous namespace\)::", "", r["Name"]).replace("void ", "").split("(")[0]
         c, t = out.get(nm, (0, 0.0))
         out[nm] = (c + int(r["Calls"]), t + float(r["TotalDurationNs"]) / 1e6)
-    steps = sum(c for n, (c, _) in out.items() if n == "k_adam")
+    steps = sum(c for n, (c, _) in out.items() if n.split("<")[0] == "k_adam")        # k_adam, later k_adam<CLIP, AMS>; not k_adam_ex
     return out, steps, stamp
 
 
