@@ -1284,6 +1284,152 @@ extern "C" int fmri_tile_finalize(const double* acc, const int32_t* cnt, double*
     return FMRI_OK;
 }
 
+// ---- the volume stays on the device around the tile loop: mirrored / padded / cropped copies in, mirrored / cropped means out
+// (reference prediction.py:65-85 predict_flips, :138-146 the two paddings, :204-208 the crop of pad_for_fit).
+// Both kernels walk their OUTPUT as the flat array it is, EPT consecutive elements per thread stored as one vector (the launch picks EPT
+// from the base address alone, so odd row pitches keep the wide store); the coordinates of the first element come from two divisions
+// (32-bit ones while every tensor stays below 2^31 elements) and are counted up from there.  The lanes of a wave cover one contiguous
+// span of the output and, mirrored or not, one contiguous span of every input row they touch.
+struct FlipGeo {
+    int n[3];        // extent of the un-mirrored side (pad_flip: src; finalize_flip: out)
+    int a[3];        // extent of the other side (pad_flip: dst; finalize_flip: acc)
+    int lo[3];
+    int mask;
+};
+template <typename V, int NB> __device__ __forceinline__ void store_bytes(void* dst, const V* v) {
+    if (NB == 16) { uint4 u; __builtin_memcpy(&u, v, 16); *reinterpret_cast<uint4*>(dst) = u; }
+    else if (NB == 8) { uint2 u; __builtin_memcpy(&u, v, 8); *reinterpret_cast<uint2*>(dst) = u; }
+    else { unsigned u; __builtin_memcpy(&u, v, 4); *reinterpret_cast<unsigned*>(dst) = u; }
+}
+// dst[o] = fill where u = o - lo leaves [0, n) on any axis, else src[m(u)], m mirroring the axes of `mask`: np.pad(np.flip(src, axes),
+// ..., constant_values=fill) followed by a crop (negative lo).  (TD)value is round-to-nearest, numpy's astype.
+template <typename TS, typename TD, int EPT, typename IT>
+__global__ void __launch_bounds__(256) k_volume_pad_flip(const TS* __restrict__ src, TD* __restrict__ dst, FlipGeo G, TD fill, int64_t total) {
+    const int64_t chunks = (total + EPT - 1) / EPT;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < chunks; t += (int64_t)gridDim.x * blockDim.x) {
+        const IT i0 = (IT)(t * EPT);
+        const IT r = i0 / (IT)G.a[2];
+        int oz = (int)(i0 - r * (IT)G.a[2]);
+        int ox = (int)(r / (IT)G.a[1]);
+        int oy = (int)(r - (IT)ox * (IT)G.a[1]);
+        const int left = total - t * EPT < EPT ? (int)(total - t * EPT) : EPT;
+        TD v[EPT];
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            TD e = fill;
+            if (j < left) {
+                int ux = ox - G.lo[0], uy = oy - G.lo[1], uz = oz - G.lo[2];
+                if (ux >= 0 && ux < G.n[0] && uy >= 0 && uy < G.n[1] && uz >= 0 && uz < G.n[2]) {
+                    if (G.mask & 1) ux = G.n[0] - 1 - ux;
+                    if (G.mask & 2) uy = G.n[1] - 1 - uy;
+                    if (G.mask & 4) uz = G.n[2] - 1 - uz;
+                    e = (TD)src[((IT)ux * (IT)G.n[1] + (IT)uy) * (IT)G.n[2] + (IT)uz];
+                }
+                if (++oz == G.a[2]) { oz = 0; if (++oy == G.a[1]) { oy = 0; ++ox; } }
+            }
+            v[j] = e;
+        }
+        TD* const d = dst + t * EPT;
+        if (left == EPT) store_bytes<TD, EPT * (int)sizeof(TD)>(d, v);
+        else {
+#pragma unroll
+            for (int j = 0; j < EPT; ++j)
+                if (j < left) d[j] = v[j];
+        }
+    }
+}
+template <typename TS, typename TD, typename IT>
+static void launch_volume_pad_flip(const void* src, void* dst, const FlipGeo& G, double fill, int64_t total, hipStream_t s) {
+    const uintptr_t a = (uintptr_t)dst;
+    const int ept = (a & 15) == 0 ? 16 / (int)sizeof(TD) : (a & 7) == 0 ? 8 / (int)sizeof(TD) : 1;
+#define L_(E_) k_volume_pad_flip<TS, TD, E_, IT><<<grid_for(ceil_div64(total, E_), 256, 4096), 256, 0, s>>>((const TS*)src, (TD*)dst, G, (TD)fill, total)
+    if constexpr (sizeof(TD) == 4) {
+        if (ept == 4) { L_(4); return; }
+    }
+    if (ept == 2) L_(2); else L_(1);
+#undef L_
+}
+extern "C" int fmri_volume_pad_flip(const void* src, int src_dtype, int X, int Y, int Z, void* dst, int dst_dtype, int OX, int OY, int OZ,
+                                    const int32_t* lo, int flip_mask, double fill, fmri_stream_t stream) {
+    if (!src || !dst || !lo || src == dst || X <= 0 || Y <= 0 || Z <= 0 || OX <= 0 || OY <= 0 || OZ <= 0 || (flip_mask & ~7)) return FMRI_E_SHAPE;
+    for (int k = 0; k < 3; ++k)
+        if (lo[k] < -(1 << 30) || lo[k] > (1 << 30)) return FMRI_E_SHAPE;
+    if ((src_dtype != FMRI_F32 && src_dtype != FMRI_F64) || (dst_dtype != FMRI_F32 && dst_dtype != FMRI_F64)) return FMRI_E_DTYPE;
+    if (((uintptr_t)src % (src_dtype == FMRI_F64 ? 8 : 4)) || ((uintptr_t)dst % (dst_dtype == FMRI_F64 ? 8 : 4))) return FMRI_E_ALIGN;
+    const FlipGeo G = {{X, Y, Z}, {OX, OY, OZ}, {lo[0], lo[1], lo[2]}, flip_mask};
+    const int64_t total = (int64_t)OX * OY * OZ, stotal = (int64_t)X * Y * Z;
+    const bool small = total + 4 < ((int64_t)1 << 31) && stotal < ((int64_t)1 << 31);
+    hipStream_t s = as_stream(stream);
+#define D_(TS_, TD_) do { if (small) launch_volume_pad_flip<TS_, TD_, unsigned>(src, dst, G, fill, total, s); \
+                          else launch_volume_pad_flip<TS_, TD_, int64_t>(src, dst, G, fill, total, s); } while (0)
+    if (src_dtype == FMRI_F64) { if (dst_dtype == FMRI_F32) D_(double, float); else D_(double, double); }
+    else { if (dst_dtype == FMRI_F32) D_(float, float); else D_(float, double); }
+#undef D_
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+// out[g][c] = acc[a][c] / (double)cnt[a], a = lo + m(g): k_tile_finalize's division read through the mirror and the crop, so a variant's
+// means land un-mirrored in the caller's slot.  A zero count divides by 1 and is counted once per voxel.
+template <int EPT, typename IT>
+__global__ void __launch_bounds__(256) k_tile_finalize_flip(const double* __restrict__ acc, const int32_t* __restrict__ cnt, double* __restrict__ out,
+                                                            int32_t* __restrict__ bad, FlipGeo G, int C, int64_t total) {
+    const int64_t chunks = (total + EPT - 1) / EPT;
+    int nbad = 0;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < chunks; t += (int64_t)gridDim.x * blockDim.x) {
+        const IT i0 = (IT)(t * EPT);
+        const IT vox = i0 / (IT)C;
+        int c = (int)(i0 - vox * (IT)C);
+        const IT r = vox / (IT)G.n[2];
+        int gz = (int)(vox - r * (IT)G.n[2]);
+        int gx = (int)(r / (IT)G.n[1]);
+        int gy = (int)(r - (IT)gx * (IT)G.n[1]);
+        const int left = total - t * EPT < EPT ? (int)(total - t * EPT) : EPT;
+        double v[EPT];
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            double e = 0.0;
+            if (j < left) {
+                const int ax = G.lo[0] + ((G.mask & 1) ? G.n[0] - 1 - gx : gx);
+                const int ay = G.lo[1] + ((G.mask & 2) ? G.n[1] - 1 - gy : gy);
+                const int az = G.lo[2] + ((G.mask & 4) ? G.n[2] - 1 - gz : gz);
+                const IT a = ((IT)ax * (IT)G.a[1] + (IT)ay) * (IT)G.a[2] + (IT)az;
+                int n = cnt[a];
+                if (n <= 0) { nbad += c == 0; n = 1; }
+                e = acc[a * (IT)C + (IT)c] / (double)n;
+                if (++c == C) { c = 0; if (++gz == G.n[2]) { gz = 0; if (++gy == G.n[1]) { gy = 0; ++gx; } } }
+            }
+            v[j] = e;
+        }
+        double* const d = out + t * EPT;
+        if (left == EPT) store_bytes<double, EPT * 8>(d, v);
+        else {
+#pragma unroll
+            for (int j = 0; j < EPT; ++j)
+                if (j < left) d[j] = v[j];
+        }
+    }
+    if (nbad) atomicAdd(bad, nbad);
+}
+extern "C" int fmri_tile_finalize_flip(const double* acc, const int32_t* cnt, int AX, int AY, int AZ, int C, double* out, int X, int Y, int Z,
+                                       const int32_t* lo, int flip_mask, int32_t* bad, fmri_stream_t stream) {
+    if (!acc || !cnt || !out || !bad || !lo || AX <= 0 || AY <= 0 || AZ <= 0 || C <= 0 || X <= 0 || Y <= 0 || Z <= 0 || (flip_mask & ~7)) return FMRI_E_SHAPE;
+    const int A[3] = {AX, AY, AZ}, N[3] = {X, Y, Z};
+    for (int k = 0; k < 3; ++k)
+        if (lo[k] < 0 || lo[k] > A[k] - N[k]) return FMRI_E_SHAPE;          // the window [lo, lo + n) lies inside acc
+    if (((((uintptr_t)acc) | ((uintptr_t)out)) & 7) || ((((uintptr_t)cnt) | ((uintptr_t)bad)) & 3)) return FMRI_E_ALIGN;
+    const FlipGeo G = {{X, Y, Z}, {AX, AY, AZ}, {lo[0], lo[1], lo[2]}, flip_mask};
+    const int64_t total = (int64_t)X * Y * Z * C, atotal = (int64_t)AX * AY * AZ * C;
+    const bool small = total + 2 < ((int64_t)1 << 31) && atotal < ((int64_t)1 << 31);
+    const bool wide = ((uintptr_t)out & 15) == 0;
+    hipStream_t s = as_stream(stream);
+#define L_(E_, IT_) k_tile_finalize_flip<E_, IT_><<<grid_for(ceil_div64(total, E_), 256, 4096), 256, 0, s>>>(acc, cnt, out, bad, G, C, total)
+    if (small) { if (wide) L_(2, unsigned); else L_(1, unsigned); }
+    else { if (wide) L_(2, int64_t); else L_(1, int64_t); }
+#undef L_
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
 // ---- several labels: a label map straight from the overlap-add, and training targets from a label map
 // out[v] per voxel from q_c = acc[v][c] / cnt[v] (float64, fmri_tile_finalize's division).  C == 1: values[0] where q_0 > threshold
 // (reference prediction.py:257); C > 1: values[k], k the FIRST index of the maximum (np.argmax), 0 where max q < threshold (:219-222).

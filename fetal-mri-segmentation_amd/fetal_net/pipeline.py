@@ -13,8 +13,12 @@ arithmetic around it: the spline zoom of `Zoom` in both directions, the median o
 `preproc` filter of `fetal_net.preprocess` and the z-scoring (`fmri_hip.ops.window_intensities_f64`, `laplace_f64`,
 `gaussian_gradient_magnitude_f64`, `norm_minmax_f64`, `normalize_f64`, tests/test_gpu_intensity.py): scipy's and numpy's own arithmetic
 in float64, so host and device give the same values.  `Stage.intensities` uploads the volume once, runs window -> scaling zoom ->
-filter -> z-score on the device tensor and downloads once; the other calls upload their input and download their result.  Border, crop
-and paste are once-per-volume host passes.  File I/O is the caller's (`fetal_net.utils.nifti`).  `predict_volume(...)` keeps the keyword
+filter -> z-score on the device tensor and downloads once.  With a model that has the device tile loop the first stage is ONE chain on
+one tensor - resolution zoom, intensities, border, the tile loop of every flip variant, their median, crop, zoom back
+(`VolumePipeline._run_first_resident`, `Stage._infer_resident`): one upload, one download each for what the model saw and for its
+prediction, and a float64 CUDA tensor stays one.  Elsewhere (a foreign model, a caller's own `preproc`, `augment='all'`, `device=False`)
+the calls upload their input and download their result, and border and crop are host passes; the second stage's crop and paste always
+are.  File I/O is the caller's (`fetal_net.utils.nifti`).  `predict_volume(...)` keeps the keyword
 surface of the reference's `main()` for callers that want the one-call form.
 """
 import numpy as np
@@ -22,6 +26,7 @@ from scipy import ndimage
 
 from . import preprocess
 from .postprocess import _device_ok, postprocess_prediction
+from . import prediction
 from .prediction import patch_wise_prediction, predict_augment, predict_flips
 from .utils.cut_relevant_areas import check_bounding_box, find_bounding_box
 
@@ -112,6 +117,9 @@ class Zoom(Resampling):
         self.device = device
 
     def forward(self, vol):
+        if preprocess._is_device_tensor(vol):
+            from fmri_hip import ops
+            return ops.zoom_f64(vol, self.factors, order=3)
         if np.ndim(vol) == 3 and _use_device(vol, self.device):
             from fmri_hip import ops
             return _on_device(lambda v: ops.zoom_f64(v, self.factors, order=3), vol)
@@ -120,6 +128,11 @@ class Zoom(Resampling):
     def backward(self, pred):
         # leading axes (a stack of TTA variants) are left alone
         back = [1.0 / f for f in self.factors]
+        if preprocess._is_device_tensor(pred):
+            import torch
+            from fmri_hip import ops
+            out = [ops.zoom_f64(one, back, order=self.order_back) for one in pred.reshape((-1,) + tuple(pred.shape[-3:]))]
+            return out[0] if pred.dim() == 3 else torch.stack(out).reshape(tuple(pred.shape[:-3]) + tuple(out[0].shape))
         if _use_device(pred, self.device):
             from fmri_hip import ops
             flat = pred.reshape((-1,) + pred.shape[-3:])
@@ -136,11 +149,27 @@ class Border(Resampling):
         self.width = int(width)
 
     def forward(self, vol):
+        if preprocess._is_device_tensor(vol):                 # a float64 CUDA volume stays one: fmri_minmax_f64, fmri_volume_pad_flip
+            return self._resized(vol, self.width, minimum_fill=True)
         return np.pad(vol, self.width, mode="constant", constant_values=vol.min())
 
     def backward(self, pred):
         w = self.width
+        if preprocess._is_device_tensor(pred):
+            return self._resized(pred, -w) if w else pred
         return pred[(Ellipsis,) + (slice(w, -w),) * 3] if w else pred
+
+    @staticmethod
+    def _resized(t, w, minimum_fill=False):
+        """the three trailing axes of a float64 CUDA tensor grown by w voxels of the volume's minimum on every side (w < 0: cropped)"""
+        import torch
+        from fmri_hip import ops
+        t = t.contiguous()
+        fill = ops.minmax_f64(t)[0] if minimum_fill else 0.0
+        out = torch.empty(tuple(t.shape[:-3]) + tuple(int(n) + 2 * w for n in t.shape[-3:]), dtype=t.dtype, device=t.device)
+        for src, dst in zip(t.reshape((-1,) + tuple(t.shape[-3:])), out.reshape((-1,) + tuple(out.shape[-3:]))):
+            ops.volume_pad_flip(src, dst, (w, w, w), 0, fill)
+        return out
 
 
 class Box(Resampling):
@@ -185,7 +214,14 @@ class Stage(object):
     def intensities(self, vol, resamplings=None):
         """windowing -> the model-specific scaling (recorded in `resamplings`) -> the config's own hook -> z-scoring, in the reference's
         order.  Under the device rule (a float64 volume [X,Y,Z]) the steps run on ONE device tensor: one upload, one download; a caller's
-        own callable is handed a numpy array in between, as on the host."""
+        own callable is handed a numpy array in between, as on the host.  A float64 CUDA tensor [X,Y,Z] stays one."""
+        if preprocess._is_device_tensor(vol):
+            scale = self.config.get("scale_data") if resamplings is not None else None
+            pre = self.preproc if resamplings is not None else None
+            if pre is not None and not self.preproc_named:
+                raise TypeError("a caller's own preproc callable takes host volumes (got a device tensor)")
+            norm = self.norm if self.norm is not None and any(self.norm.values()) else None
+            return self._intensities_on_device(vol, resamplings, scale, pre, norm)
         scale = self.config.get("scale_data") if resamplings is not None else None
         pre = self.preproc if resamplings is not None else None
         norm = self.norm if self.norm is not None and any(self.norm.values()) else None
@@ -210,7 +246,8 @@ class Stage(object):
     def _intensities_on_device(self, vol, resamplings, scale, pre, norm):
         import torch
         from fmri_hip import ops
-        t = torch.from_numpy(np.ascontiguousarray(vol)).cuda()
+        keep = preprocess._is_device_tensor(vol)               # the caller's tensor in, the tensor this chain ends with out
+        t = vol if keep else torch.from_numpy(np.ascontiguousarray(vol)).cuda()
         if self.intensity is not None:
             t = INTENSITY_METHODS[self.intensity](t)
         if scale is not None:
@@ -226,14 +263,57 @@ class Stage(object):
             t = torch.from_numpy(np.ascontiguousarray(back)).cuda()
         if norm is not None:
             t = ops.normalize_f64(t, norm["mean"], norm["std"])
-        return t.cpu().numpy()
+        return t if keep else t.cpu().numpy()
 
     def infer(self, vol, keep_variants=False):
-        """probabilities of `vol` [X,Y,Z]: tiled prediction, or the median over the stage's test-time augmentation variants"""
+        """probabilities of `vol` [X,Y,Z]: tiled prediction, or the median over the stage's test-time augmentation variants.  With a
+        model that has the device tile loop and `augment` None or 'flip' the volume goes up once, the variants are mirrored, tiled and
+        mirrored back on the device, their median is taken on the resident stack and the result comes down once (`_infer_resident`); a
+        float64 CUDA tensor stays one.  'all' and foreign models take `_infer_host`."""
+        why = self._resident_refusal(vol)
+        if why is None:
+            return self._infer_resident(vol, keep_variants)
+        if preprocess._is_device_tensor(vol):
+            raise TypeError("Stage.infer of a device tensor needs the resident tile loop: " + why)
+        return self._infer_host(vol, keep_variants)
+
+    def _resident_refusal(self, vol):
+        """None when `vol` takes the resident route, else the reason it does not"""
+        if self.augment == "all":
+            return "augment='all' rotates its variants on the host route"
+        why = prediction._device_tile_loop_refusal(self.model)
+        if why is not None:
+            return why
+        if preprocess._is_device_tensor(vol):
+            import torch
+            ok = vol.dtype == torch.float64 and vol.dim() == 3 and min(vol.shape) > 1
+        else:
+            ok = isinstance(vol, np.ndarray) and vol.dtype == np.float64 and vol.ndim == 3 and min(vol.shape) > 1
+            if ok and not (prediction.resident_tta_default() and _use_device(vol, self.device)):
+                return "the host route is asked for (device=False, FMRI_TTA_RESIDENT=0) or no GPU is there"
+        return None if ok else "a float64 volume [X,Y,Z] with every extent above 1 is needed"
+
+    def _infer_resident(self, vol, keep_variants):
+        from fmri_hip import ops
+        tensor = preprocess._is_device_tensor(vol)
+        t = vol.contiguous() if tensor else prediction._upload_f64(vol)
+        variants = prediction._flip_variants(tuple(t.shape)) if self.augment == "flip" else [(0, 0)]
+        stack = prediction._resident_flip_stack(t, self.model, self.overlap, self.patch, variants)
+        if stack.shape[-1] == 1:
+            stack = stack[..., 0]
+        if self.augment != "flip":
+            out = stack[0]
+        else:
+            out = stack if keep_variants else ops.median_stack_f64(stack)
+        return out if tensor else prediction._download(out)
+
+    def _infer_host(self, vol, keep_variants=False):
+        """the route of foreign models and of augment='all': every variant a patch_wise_prediction of a host volume, the stack of their
+        results reduced by `median_of_variants` (also the other arm of tools/bench_tta.py)"""
         if self.augment == "all":
             variants = predict_augment(vol, model=self.model, overlap_factor=self.overlap, num_augments=self.n_augment, patch_shape=self.patch)
         elif self.augment == "flip":
-            variants = np.stack(predict_flips(vol, model=self.model, overlap_factor=self.overlap, config=self.config))
+            variants = np.stack(prediction._predict_flips_host(vol, model=self.model, overlap_factor=self.overlap, config=self.config))
         else:
             return np.asarray(patch_wise_prediction(model=self.model, data=vol[np.newaxis], overlap_factor=self.overlap,
                                                     patch_shape=self.patch)).squeeze()
@@ -259,6 +339,8 @@ class VolumePipeline(object):
 
     def run_first(self, volume, keep_variants=False):
         """-> (what the first model saw before its border, its prediction on the input grid)"""
+        if self._chain_on_device(volume):
+            return self._run_first_resident(volume, keep_variants)
         steps = []
         vol = volume
         xy, z = self.resolution
@@ -270,6 +352,37 @@ class VolumePipeline(object):
         steps.append(Border(CONTEXT_MARGIN))
         pred = self.first.infer(steps[-1].forward(vol), keep_variants)
         return seen, _undo(pred, steps)
+
+    def _chain_on_device(self, volume):
+        """whether run_first's steps all have a device form for `volume`: then they run on ONE tensor"""
+        first = self.first
+        if preprocess._is_device_tensor(volume):
+            return True
+        if not (isinstance(volume, np.ndarray) and volume.ndim == 3 and volume.dtype == np.float64 and volume.size):
+            return False
+        if first.preproc is not None and not first.preproc_named:
+            return False                                      # a caller's own callable works on host arrays
+        if not (_use_device(volume, self.device) and _use_device(volume, first.device) and prediction.resident_tta_default()):
+            return False
+        if first.augment == "all" or prediction._device_tile_loop_refusal(first.model) is not None:
+            return False
+        out_shape = first.model.output_shape                  # (Border.backward crops the three LAST axes: one label, squeezed away)
+        return int(out_shape[1] if prediction._is3d(first.model) else out_shape[-1]) == 1
+
+    def _run_first_resident(self, volume, keep_variants):
+        """run_first on one device tensor: resolution zoom, intensities, border, tile loop and variants, crop, zoom back - one upload,
+        and one download each for what the model saw and for its prediction (a CUDA tensor in gives CUDA tensors out)"""
+        tensor = preprocess._is_device_tensor(volume)
+        t = volume if tensor else prediction._upload_f64(volume)
+        steps = []
+        xy, z = self.resolution
+        if (xy, z) != (1.0, 1.0):
+            steps.append(Zoom([xy, xy, z], order_back=1, device=self.device))
+            t = steps[-1].forward(t)
+        seen = self.first.intensities(t, steps)
+        steps.append(Border(CONTEXT_MARGIN))
+        pred = _undo(self.first.infer(steps[-1].forward(seen), keep_variants), steps)
+        return (seen, pred) if tensor else (prediction._download(seen), prediction._download(pred))
 
     def region_of_interest(self, mask):
         lo, hi = find_bounding_box(mask)

@@ -6,8 +6,10 @@ MI355X: the padded volume is uploaded once, tiles are gathered on the device (fm
 engine and overlap-added in float64 on the device (fmri_tile_scatter_accumulate / fmri_tile_finalize); one hipGraph per
 tile-batch size replays gather -> network -> scatter.  A 2-D model with previous-slice truth channels (`truth_data` with
 `prev_truth_index` / `prev_truth_size`) stays on the device as well: the padded truth volume goes up beside the data and the gather appends
-its slices to every tile (fmri_tile_gather_stack).  Any other object with `.output_shape` / `.predict(ndarray)` (the
-reference's duck-typing contract) is driven through the same geometry with host-side tiles.
+its slices to every tile (fmri_tile_gather_stack).  A volume that is already on the device - a float64 CUDA tensor, or the one upload
+of `predict_flips` / `fetal_net.pipeline` - runs the same captured loop without touching the host: fmri_volume_pad_flip writes the
+mirrored, padded volume, fmri_tile_finalize_flip the cropped, un-mirrored means (`_resident_overlap_add`).  Any other object with
+`.output_shape` / `.predict(ndarray)` (the reference's duck-typing contract) is driven through the same geometry with host-side tiles.
 """
 import gc
 import itertools
@@ -61,7 +63,9 @@ def _is3d(model):
     return int(np.sum(np.array(model.output_shape[1:]) > 1)) > 2
 
 
-def _geometry(model, data, patch_shape, overlap_factor):
+def _geometry_of_shape(model, shape, patch_shape, overlap_factor):
+    """the tiling of a volume of `shape` (X, Y, Z), values aside: is3d, the two paddings, the padded extent, the tile corners, the
+    accumulator's extent"""
     out_shape = model.output_shape
     is3d = _is3d(model)
     prediction_shape = tuple(out_shape[-3:]) if is3d else tuple(out_shape[-3:-1]) + (1,)
@@ -69,17 +73,25 @@ def _geometry(model, data, patch_shape, overlap_factor):
     max_overlap = np.subtract(patch_shape, (1, 1, 1))
     overlap = min_overlap + (overlap_factor * (max_overlap - min_overlap)).astype(int)
     pad0 = _half_pads(np.subtract(patch_shape, prediction_shape))
+    shape_0 = tuple(int(n) + p[0] + p[1] for n, p in zip(shape, pad0))
+    pad_for_fit = _half_pads(np.maximum(np.subtract(patch_shape, shape_0), 0))
+    vshape = tuple(n + p[0] + p[1] for n, p in zip(shape_0, pad_for_fit))
+    indices = get_set_of_patch_indices_full((0, 0, 0), np.subtract(vshape, patch_shape), np.subtract(patch_shape, overlap))
+    data_shape = list(np.asarray(shape) + np.sum(pad_for_fit, -1))
+    data_shape += [out_shape[1]] if is3d else [out_shape[-1]]
+    return is3d, pad0, pad_for_fit, vshape, indices, data_shape
+
+
+def _geometry(model, data, patch_shape, overlap_factor):
+    is3d, pad0, pad_for_fit, vshape, indices, data_shape = _geometry_of_shape(model, data.shape[-3:], patch_shape, overlap_factor)
     # the reference pads with the 1st percentile unconditionally (prediction.py:138-146); with zero pad widths np.pad returns the data
     # unchanged, so the percentile (a sort-sized pass over the whole volume, twice) is only computed when something is padded
     data_0 = data[0]
     if np.sum(pad0) > 0:
         data_0 = np.pad(data_0, pad0, mode='constant', constant_values=np.percentile(data_0, q=1))
-    pad_for_fit = _half_pads(np.maximum(np.subtract(patch_shape, data_0.shape), 0))
     if np.sum(pad_for_fit) > 0:
         data_0 = np.pad(data_0, pad_for_fit, 'constant', constant_values=np.percentile(data_0, q=1))
-    indices = get_set_of_patch_indices_full((0, 0, 0), np.subtract(data_0.shape, patch_shape), np.subtract(patch_shape, overlap))
-    data_shape = list(np.asarray(data.shape[-3:]) + np.sum(pad_for_fit, -1))
-    data_shape += [out_shape[1]] if is3d else [out_shape[-1]]
+    assert tuple(data_0.shape) == vshape
     return is3d, pad0, pad_for_fit, data_0, indices, data_shape
 
 
@@ -92,7 +104,9 @@ def _unpad(arr, pad_for_fit):
 
 def patch_wise_prediction(model, data, patch_shape, overlap_factor=0, batch_size=5, permute=False, truth_data=None,
                           prev_truth_index=None, prev_truth_size=None):
-    """data (1,X,Y,Z) -> (X,Y,Z,C) float64 mean of all tiles covering each voxel."""
+    """data (1,X,Y,Z) -> (X,Y,Z,C) float64 mean of all tiles covering each voxel.  A float64 CUDA tensor stays one: the tile loop then
+    runs on the resident volume (`_resident_overlap_add`) and the means come back as a CUDA tensor; that form needs the device tile loop
+    (an engine model, no permute, no truth_data) and raises TypeError where it does not apply."""
     return _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size, None)
 
 
@@ -121,6 +135,10 @@ def _label_values(n_labels, labels):
 
 def _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size, label_map):
     """patch_wise_prediction (label_map None) / patch_wise_label_map ((threshold, values): the device path then returns the uint8 map)"""
+    if _is_device_tensor(data):                              # a float64 CUDA tensor stays one (the convention of fetal_net.preprocess)
+        if label_map is not None:
+            raise TypeError("patch_wise_label_map takes host volumes (got a device tensor)")
+        return _patch_wise_resident(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data)
     is3d, pad0, pad_for_fit, data_0, indices, data_shape = _geometry(model, data, patch_shape, overlap_factor)
     layout2d = getattr(model, "_input_layout", "") == "channels_last_2d"
     # previous-slice truth on the device: 2-D models only (a 3-D model's truth channels are concatenated along z, reference prediction.py:100-110)
@@ -165,23 +183,19 @@ def _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, t
     return predicted_output / predicted_count
 
 
-def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d=True, truth_0=None, aux_dz=0, aux_nz=0,
-                        label_map=None):
-    """Upload once, then per tile batch: gather -> network -> float64 overlap-add, all on the device.  The static buffers
-    (volume, accumulators, tile batch, index list) and one captured hipGraph per distinct batch size are cached on the
-    model and re-used for every following volume of the same padded shape.  2-D models: a tile (px, py, slices) IS the
-    channels-last input of the network (the slice stack is the channel axis) and its output is one slice (px, py, 1).
-    truth_0 (2-D models): the padded truth volume (data_0's extent); every tile then carries aux_nz more channels, its truth slices from
-    aux_dz slices past the tile's corner (reference batch_iterator, prediction.py:98-114).
-    label_map (threshold, values): finished slabs become label bytes on the device (fmri_tile_finalize_labels) and the uint8 map
-    (X, Y, Z) is what comes down and is returned; None: the float64 means (X, Y, Z, C)."""
+def _tile_loop_state(model, vshape, n, patch_shape, batch_size, data_shape, is3d=True, aux_dz=0, aux_nz=0):
+    """-> (state, tile-group size).  The static buffers of the device tile loop (volume, accumulators, tile batch, index list) and one
+    captured hipGraph per distinct batch size - gather -> network -> float64 overlap-add - cached on the model and re-used for every
+    following volume of the same padded shape `vshape` tiled into `n` tiles, whichever loop drives them (`_device_overlap_add` from host
+    memory, `_resident_overlap_add` from a device tensor).  2-D models: a tile (px, py, slices) IS the channels-last input of the
+    network (the slice stack is the channel axis) and its output is one slice (px, py, 1); with aux_nz every tile carries aux_nz more
+    channels, its truth slices from aux_dz slices past the tile's corner (reference batch_iterator, prediction.py:98-114)."""
     import torch
     from fmri_hip import ops
     patch = tuple(int(p) for p in patch_shape)
-    vshape = tuple(int(s) for s in data_0.shape)
+    vshape = tuple(int(s) for s in vshape)
     ashape = tuple(int(s) for s in data_shape)
     use_graph = os.environ.get("FMRI_HIPGRAPH", "1") == "1"
-    n = len(indices)
     if not is3d:
         # 2-D: a tile is a 5-slice stack and the caller's batch (reference default 5) is far too small to fill the device - the MFMA
         # kernels also want the slice count in multiples of 4.  The overlap-add does not depend on how tiles are grouped (float64 sums)
@@ -193,9 +207,9 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
         groups = -(-n // max(batch_size, 12))
         batch_size = -(-n // groups)
     sizes = sorted({min(batch_size, n - i) for i in range(0, n, batch_size)}, reverse=True)
-    aux_nz = int(aux_nz) if truth_0 is not None else 0
+    aux_nz = int(aux_nz)
     aux_dz = int(aux_dz) if aux_nz else 0
-    assert aux_nz == 0 or (not is3d and tuple(truth_0.shape) == vshape)
+    assert aux_nz == 0 or not is3d
     key = (vshape, ashape, patch, tuple(sizes), use_graph, aux_dz, aux_nz)
     st = model.__dict__.get("_tile_state")
     if st is None or st["key"] != key:
@@ -245,6 +259,25 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
                 pb["graph"] = g
             st["per_b"][B] = pb
         model.__dict__["_tile_state"] = st
+    return st, batch_size
+
+
+def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d=True, truth_0=None, aux_dz=0, aux_nz=0,
+                        label_map=None):
+    """Upload once, then per tile batch the captured gather -> network -> float64 overlap-add of `_tile_loop_state`, all on the device.
+    truth_0 (2-D models): the padded truth volume (data_0's extent), see `_tile_loop_state`.
+    label_map (threshold, values): finished slabs become label bytes on the device (fmri_tile_finalize_labels) and the uint8 map
+    (X, Y, Z) is what comes down and is returned; None: the float64 means (X, Y, Z, C)."""
+    import torch
+    from fmri_hip import ops
+    patch = tuple(int(p) for p in patch_shape)
+    vshape = tuple(int(s) for s in data_0.shape)
+    ashape = tuple(int(s) for s in data_shape)
+    n = len(indices)
+    aux_nz = int(aux_nz) if truth_0 is not None else 0
+    aux_dz = int(aux_dz) if aux_nz else 0
+    assert aux_nz == 0 or tuple(truth_0.shape) == vshape
+    st, batch_size = _tile_loop_state(model, vshape, n, patch, batch_size, ashape, is3d, aux_dz, aux_nz)
     # ---- the volume goes up and the result comes down in x-slabs, pipelined with the tile groups (VERDICT r3 item 7: 23 % of a volume's
     # time was host work - a pageable 42 MB upload in front of the first tile and a pageable 84 MB float64 download behind the last).
     # Tiles are ordered x-major (itertools.product), so tile group g only needs the x-range up to its last tile's end, and every voxel
@@ -308,6 +341,92 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
     down.synchronize()
     main.synchronize()
     return out_host.numpy(), int(bad.item()) == 0
+
+
+def _is_device_tensor(data):
+    return type(data).__module__.startswith("torch") and hasattr(data, "is_cuda") and bool(data.is_cuda)
+
+
+def _device_tile_loop_refusal(model, permute=False, truth_data=None):
+    """None when the device tile loop applies to `model` without previous-slice truth, else the reason it does not"""
+    if not isinstance(model, Model):
+        return "the model is no engine Model of this package (%s)" % type(model).__name__
+    if model._unsupported is not None:
+        return "the engine does not run this model (%s)" % (model._unsupported,)
+    if getattr(model, "_input_layout", "") not in ("channels_first_3d", "channels_last_2d"):
+        return "the model's input layout %r has no device tile loop" % (getattr(model, "_input_layout", None),)
+    if permute:
+        return "permute=True runs on host tiles"
+    if truth_data is not None:
+        return "truth_data comes with host volumes only"
+    return None
+
+
+def _resident_overlap_add(model, vol, patch_shape, overlap_factor, batch_size, variants, stack):
+    """The device tile loop on a volume that is already there.  vol: float64 CUDA tensor (X, Y, Z), unpadded; variants: one
+    (forward flip mask, backward flip mask) pair per slot of stack, a float64 CUDA tensor (K, X, Y, Z, C).  Per variant: the mirrored,
+    padded fp32 volume of the tiler is written by fmri_volume_pad_flip (the 1st-percentile pad constants come from ops.percentile_f64,
+    once per call - mirroring does not change them - and only when something is padded), the captured graphs of `_tile_loop_state`
+    replay over the same index list as the host-fed loop, and fmri_tile_finalize_flip writes the means, cropped and mirrored back, into
+    the variant's slot.  Nothing is copied to the host but the count of uncovered voxels, once, at the end."""
+    import torch
+    from fmri_hip import ops
+    shape = tuple(int(s) for s in vol.shape)
+    is3d, pad0, pad_for_fit, vshape, indices, data_shape = _geometry_of_shape(model, shape, patch_shape, overlap_factor)
+    patch = tuple(int(p) for p in patch_shape)
+    n = len(indices)
+    with torch.cuda.device(vol.device):
+        st, batch_size = _tile_loop_state(model, vshape, n, patch, batch_size, data_shape, is3d)
+        assert tuple(stack.shape) == (len(variants),) + shape + (int(data_shape[3]),) and stack.dtype == torch.float64
+        lo0, lo1 = [p[0] for p in pad0], [p[0] for p in pad_for_fit]
+        padded0, padded1 = np.sum(pad0) > 0, np.sum(pad_for_fit) > 0
+        fill0 = fill1 = 0.0
+        mid = None                                   # the float64 volume between the two paddings, when both are there
+        if padded0 or padded1:
+            fill0 = fill1 = float(ops.percentile_f64(vol, 1))
+        if padded0 and padded1:
+            mid = torch.empty(tuple(s + p[0] + p[1] for s, p in zip(shape, pad0)), dtype=torch.float64, device=vol.device)
+            fill1 = float(ops.percentile_f64(ops.volume_pad_flip(vol, mid, lo0, 0, fill0), 1))
+        idx_all = torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).to(vol.device)
+        bad = torch.zeros(1, dtype=torch.int32, device=vol.device)
+        if st.get("up_stream") is not None:
+            torch.cuda.current_stream().wait_stream(st["up_stream"])
+        for k, (fwd, back) in enumerate(variants):
+            if mid is not None:
+                ops.volume_pad_flip(ops.volume_pad_flip(vol, mid, lo0, fwd, fill0), st["vol"], lo1, 0, fill1)
+            else:
+                ops.volume_pad_flip(vol, st["vol"], lo0 if padded0 else lo1, fwd, fill0)
+            st["acc"].zero_()
+            st["cnt"].zero_()
+            for i in range(0, n, batch_size):
+                bidx = idx_all[i:min(n, i + batch_size)]
+                pb = st["per_b"][int(bidx.shape[0])]
+                pb["idx"].copy_(bidx)
+                if pb["graph"] is not None:
+                    pb["graph"].replay()
+                else:
+                    pb["body"]()
+            ops.tile_finalize_flip(st["acc"], st["cnt"], stack[k], bad, lo1, back)
+        assert int(bad.item()) == 0, 'Found zeros in count'
+    return stack
+
+
+def _resident_stack(model, vol, n_variants):
+    import torch
+    n_out = int(model.output_shape[1] if _is3d(model) else model.output_shape[-1])
+    return torch.empty((n_variants,) + tuple(int(s) for s in vol.shape) + (n_out,), dtype=torch.float64, device=vol.device)
+
+
+def _patch_wise_resident(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data):
+    """patch_wise_prediction of a float64 CUDA tensor (1, X, Y, Z) -> float64 CUDA tensor (X, Y, Z, C)"""
+    import torch
+    why = _device_tile_loop_refusal(model, permute, truth_data)
+    if why is None and not (data.dtype == torch.float64 and data.dim() == 4 and data.shape[0] == 1 and data.numel() > 0):
+        why = "a float64 tensor (1, X, Y, Z) is needed (got %s %s)" % (data.dtype, tuple(data.shape))
+    if why is not None:
+        raise TypeError("patch_wise_prediction of a device tensor needs the device tile loop: " + why)
+    vol = data[0].contiguous()
+    return _resident_overlap_add(model, vol, patch_shape, overlap_factor, batch_size, [(0, 0)], _resident_stack(model, vol, 1))[0]
 
 
 def get_prediction_labels(prediction, threshold=0.5, labels=None):
@@ -377,17 +496,88 @@ def flip_it(data_, axes):
     return np.flip(data_, axis=axes) if axes else data_
 
 
-def predict_flips(data, model, overlap_factor, config):
-    """the 8 axis-flip variants, each predicted patch-wise and flipped back; returns the list (reference prediction.py:65-85)"""
+FLIP_AXES = [axes for r in range(4) for axes in itertools.combinations([0, 1, 2], r)]      # the reference's variant order
+
+
+def _predict_flips_host(data, model, overlap_factor, config):
+    """the 8 axis-flip variants, each mirrored with numpy, predicted patch-wise from host memory and flipped back (reference
+    prediction.py:65-85): the route of models without the device tile loop, and the other arm of tools/bench_tta.py"""
     patch_shape = list(config["patch_shape"]) + [config["patch_depth"]]
     predictions = []
-    for r in range(4):
-        for axes in itertools.combinations([0, 1, 2], r):
-            flipped = flip_it(data, axes)
-            pred = patch_wise_prediction(model=model, data=np.expand_dims(flipped.squeeze(), 0), overlap_factor=overlap_factor,
-                                         patch_shape=patch_shape).squeeze()
-            predictions.append(flip_it(pred, axes).squeeze())
+    for axes in FLIP_AXES:
+        flipped = flip_it(data, axes)
+        pred = patch_wise_prediction(model=model, data=np.expand_dims(flipped.squeeze(), 0), overlap_factor=overlap_factor,
+                                     patch_shape=patch_shape).squeeze()
+        predictions.append(flip_it(pred, axes).squeeze())
     return predictions
+
+
+def _flip_variants(shape):
+    """(forward mask, backward mask) of every variant for `data` of `shape`, or None where the masks cannot say what the host route
+    does.  The host route mirrors the axes of `data` as given and mirrors the squeezed prediction (X, Y, Z[, C]) back along the same axis
+    NUMBERS: for data (X, Y, Z) the two are one mask; for data (1, X, Y, Z) - the reference's call - axis 0 is the singleton, so the
+    forward flip of axis k mirrors spatial axis k - 1 and the backward flip mirrors spatial axis k."""
+    from fmri_hip.ops import flip_mask_of
+    if len(shape) == 4 and shape[0] == 1:
+        lead = 1
+    elif len(shape) == 3:
+        lead = 0
+    else:
+        return None
+    if min(shape[lead:]) < 2:                                 # squeeze() would drop a spatial axis
+        return None
+    return [(flip_mask_of(a - lead for a in axes if a >= lead), flip_mask_of(axes)) for axes in FLIP_AXES]
+
+
+def resident_tta_default():
+    """whether host volumes take the resident route by default (FMRI_TTA_RESIDENT=0 keeps them on the host-fed route: A/B runs)"""
+    return os.environ.get("FMRI_TTA_RESIDENT", "1") != "0"
+
+
+def _resident_flip_stack(vol, model, overlap_factor, patch_shape, variants):
+    """the variants' predictions of a float64 CUDA volume (X, Y, Z) as one resident stack (K, X, Y, Z, C)"""
+    return _resident_overlap_add(model, vol, patch_shape, overlap_factor, 5, variants, _resident_stack(model, vol, len(variants)))
+
+
+def _upload_f64(arr):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float64)).cuda()
+
+
+def _download(t):
+    """device tensor -> numpy array backed by pinned memory of its own (one asynchronous copy, then a wait)"""
+    import torch
+    host = torch.empty(tuple(t.shape), dtype=t.dtype, pin_memory=True)
+    host.copy_(t, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return host.numpy()
+
+
+def predict_flips(data, model, overlap_factor, config):
+    """the 8 axis-flip variants, each predicted patch-wise and flipped back; returns the list (reference prediction.py:65-85).  With a
+    model that has the device tile loop the volume goes up once, every variant is mirrored, tiled and mirrored back on the device
+    (`_resident_overlap_add`) and the stack of 8 comes down once; a float64 CUDA tensor stays one: the list then holds 8 views of one
+    resident stack (8, X, Y, Z[, C]).  Any other model takes `_predict_flips_host`."""
+    patch_shape = list(config["patch_shape"]) + [config["patch_depth"]]
+    tensor = _is_device_tensor(data)
+    why = _device_tile_loop_refusal(model)
+    variants = _flip_variants(tuple(data.shape)) if why is None else None
+    if tensor:
+        import torch
+        if why is None and (variants is None or data.dtype != torch.float64):
+            why = "a float64 tensor (X, Y, Z) or (1, X, Y, Z) is needed (got %s %s)" % (data.dtype, tuple(data.shape))
+        if why is not None:
+            raise TypeError("predict_flips of a device tensor needs the device tile loop: " + why)
+    elif variants is None or not (isinstance(data, np.ndarray) and data.dtype == np.float64 and resident_tta_default()
+                                  and _hip_rotate_ok()):
+        return _predict_flips_host(data, model, overlap_factor, config)
+    vol = data if tensor else _upload_f64(data)
+    stack = _resident_flip_stack(vol.reshape(vol.shape[-3:]).contiguous(), model, overlap_factor, patch_shape, variants)
+    if stack.shape[-1] == 1:
+        stack = stack[..., 0]
+    if not tensor:
+        stack = _download(stack)
+    return [stack[k] for k in range(len(variants))]
 
 
 def _hip_rotate_ok():

@@ -3,6 +3,7 @@ import ctypes as C
 import os
 
 F32, BF16 = 0, 1
+F64 = 3                 # fmri_volume_pad_flip only
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA = 0, 1, 2
 
@@ -116,6 +117,8 @@ SIGNATURES = {
     "fmri_tile_gather_stack": [p, p, i32, i32, i32, p, i32, i32, i32, i32, i32, i32, p, i32, p],
     "fmri_tile_scatter_accumulate": [p, p, i32, i32, i32, i32, i32, p, p, i32, i32, i32, p],
     "fmri_tile_finalize": [p, p, p, p, i64, i32, p],
+    "fmri_volume_pad_flip": [p, i32, i32, i32, i32, p, i32, i32, i32, i32, p, i32, C.c_double, p],
+    "fmri_tile_finalize_flip": [p, p, i32, i32, i32, i32, p, i32, i32, i32, p, i32, p, p],
     "fmri_labels_expand_u8": [p, i64, p, i32, p, p],
     "fmri_tile_finalize_labels": [p, p, p, p, i64, i32, C.c_double, p, p],
     "fmri_cast": [p, i32, p, i32, i64, p],

@@ -1,7 +1,7 @@
 """torch-tensor front-ends of the C ABI.  torch is plumbing only: device memory, the current HIP stream, dtypes."""
 import torch
 
-from ._lib import lib, check, F32, BF16, ACT_NONE, ACT_RELU, IMPL_AUTO
+from ._lib import lib, check, F32, BF16, F64, ACT_NONE, ACT_RELU, IMPL_AUTO
 
 
 def dt(t):
@@ -319,6 +319,61 @@ def tile_finalize(acc, cnt, out, bad):
     _need_cuda(acc, cnt, out, bad)
     Cc = acc.shape[-1]
     check(lib().fmri_tile_finalize(_p(acc), _p(cnt), _p(out), _p(bad), cnt.numel(), Cc, _s()), "fmri_tile_finalize")
+
+
+def _dt_vol(t):
+    if t.dtype == torch.float32:
+        return F32
+    if t.dtype == torch.float64:
+        return F64
+    raise TypeError("unsupported dtype %s (float32 or float64)" % t.dtype)
+
+
+def _lo3(lo):
+    import ctypes
+    vals = [int(v) for v in lo]
+    if len(vals) != 3:
+        raise ValueError("lo: one offset per axis (got %r)" % (lo,))
+    return (ctypes.c_int32 * 3)(*vals)
+
+
+def flip_mask_of(axes):
+    """the 3-bit mask of a tuple of mirrored axes (bit k = axis k)"""
+    mask = 0
+    for a in axes:
+        mask |= 1 << int(a)
+    return mask
+
+
+def volume_pad_flip(src, dst, lo=(0, 0, 0), flip_mask=0, fill=0.0):
+    """dst (OX, OY, OZ) = np.pad(np.flip(src, axes of flip_mask), ..., constant_values=fill) with lo voxels in front of every axis, cut to
+    dst's extent (a negative lo crops); src (X, Y, Z); each float32 or float64, converted as numpy's astype (fmri_volume_pad_flip)"""
+    _need_cuda(src, dst)
+    if src.dim() != 3 or dst.dim() != 3:
+        raise ValueError("volume_pad_flip: 3-D volumes (got %s -> %s)" % (tuple(src.shape), tuple(dst.shape)))
+    X, Y, Z = src.shape
+    OX, OY, OZ = dst.shape
+    with torch.cuda.device(dst.device):
+        check(lib().fmri_volume_pad_flip(_p(src), _dt_vol(src), X, Y, Z, _p(dst), _dt_vol(dst), OX, OY, OZ, _lo3(lo), int(flip_mask),
+                                         float(fill), _s()), "fmri_volume_pad_flip")
+    return dst
+
+
+def tile_finalize_flip(acc, cnt, out, bad, lo=(0, 0, 0), flip_mask=0):
+    """out (X, Y, Z, C) float64 = acc / cnt (tile_finalize's division) of the window [lo, lo + (X, Y, Z)) of acc (AX, AY, AZ, C), mirrored
+    along the axes of flip_mask; bad (int32, accumulated) counts the window's voxels with a zero count (fmri_tile_finalize_flip)"""
+    _need_cuda(acc, cnt, out, bad)
+    if acc.dim() != 4 or out.dim() != 4 or tuple(cnt.shape) != tuple(acc.shape[:3]) or out.shape[3] != acc.shape[3]:
+        raise ValueError("tile_finalize_flip: acc (AX, AY, AZ, C), cnt (AX, AY, AZ), out (X, Y, Z, C) (got %s, %s, %s)" % (
+            tuple(acc.shape), tuple(cnt.shape), tuple(out.shape)))
+    if acc.dtype != torch.float64 or out.dtype != torch.float64 or cnt.dtype != torch.int32 or bad.dtype != torch.int32:
+        raise TypeError("tile_finalize_flip: float64 acc and out, int32 cnt and bad")
+    AX, AY, AZ, Cc = acc.shape
+    X, Y, Z = out.shape[:3]
+    with torch.cuda.device(out.device):
+        check(lib().fmri_tile_finalize_flip(_p(acc), _p(cnt), AX, AY, AZ, Cc, _p(out), X, Y, Z, _lo3(lo), int(flip_mask), _p(bad), _s()),
+              "fmri_tile_finalize_flip")
+    return out
 
 
 MAX_LABELS = 32

@@ -30,7 +30,8 @@ extern "C" {
 typedef void* fmri_stream_t; /* hipStream_t */
 
 enum { FMRI_OK = 0, FMRI_E_SHAPE = -1, FMRI_E_ALIGN = -2, FMRI_E_ARCH = -3, FMRI_E_LAUNCH = -4, FMRI_E_DTYPE = -5 };
-enum { FMRI_F32 = 0, FMRI_BF16 = 1, FMRI_U8 = 2 /* label volumes of fmri_affine_sample only */ };
+enum { FMRI_F32 = 0, FMRI_BF16 = 1, FMRI_U8 = 2 /* label volumes of fmri_affine_sample only */,
+       FMRI_F64 = 3 /* the volumes of fmri_volume_pad_flip only */ };
 enum { FMRI_ACT_NONE = 0, FMRI_ACT_RELU = 1, FMRI_ACT_LEAKY = 2 };
 /* which implementation a conv call may use: AUTO picks MFMA when the shape allows it */
 enum { FMRI_IMPL_AUTO = 0, FMRI_IMPL_GENERIC = 1, FMRI_IMPL_MFMA = 2 };
@@ -432,6 +433,20 @@ int fmri_tile_scatter_accumulate(const float* pred, const int32_t* idx, int B, i
 /* out (double) [n][C] = acc / cnt ; *bad (int32, accumulated) counts voxels with cnt == 0 (reference asserts none) */
 int fmri_tile_finalize(const double* acc, const int32_t* cnt, double* out, int32_t* bad, int64_t nvox, int C,
                        fmri_stream_t stream);
+/* ---- the volume stays on the device around the tile loop (reference prediction.py:65-85 predict_flips, :138-146 the paddings, the crop
+ * of pad_for_fit).  `lo`: 3 int32 in HOST memory (read at enqueue); flip_mask: bit k mirrors axis k, m(u)_k = n_k - 1 - u_k.
+ * fmri_volume_pad_flip: src [X][Y][Z], dst [OX][OY][OZ], each FMRI_F32 or FMRI_F64 (else FMRI_E_DTYPE).  With u = o - lo: dst[o] = fill
+ *   where u leaves [0, X) x [0, Y) x [0, Z), else src[m(u)] - np.pad(np.flip(src, axes), ..., constant_values=fill) and, with negative lo,
+ *   a crop.  Values and `fill` are converted to dst's type round-to-nearest (numpy's astype).  src != dst.
+ * fmri_tile_finalize_flip: out (double) [X][Y][Z][C] = acc[a][c] / (double)cnt[a], a = lo + m(g) (m over out's extent); acc (double)
+ *   [AX][AY][AZ][C], cnt (int32) [AX][AY][AZ].  *bad (accumulated) counts the voxels of out whose count is 0; their divisor is 1.  lo = 0,
+ *   flip_mask = 0 and equal extents: fmri_tile_finalize's bytes.
+ * Both: a NULL pointer, a non-positive extent, a flip_mask outside 0..7, |lo| > 2^30 (pad_flip) or a window [lo, lo + n) that leaves acc
+ *   (finalize_flip) is FMRI_E_SHAPE; a pointer not aligned to its element FMRI_E_ALIGN; nothing is launched then. */
+int fmri_volume_pad_flip(const void* src, int src_dtype, int X, int Y, int Z, void* dst, int dst_dtype, int OX, int OY, int OZ,
+                         const int32_t* lo, int flip_mask, double fill, fmri_stream_t stream);
+int fmri_tile_finalize_flip(const double* acc, const int32_t* cnt, int AX, int AY, int AZ, int C, double* out, int X, int Y, int Z,
+                            const int32_t* lo, int flip_mask, int32_t* bad, fmri_stream_t stream);
 
 /* ---- several labels (reference generator.py:404-419 get_multi_class_labels, prediction.py:214-274).  `values`: L label values, uint8,
  * HOST memory (read at enqueue), 1 <= L <= 32, every value in 1..255 and no value twice - anything else is FMRI_E_SHAPE.
