@@ -995,9 +995,9 @@ __global__ void k_adam(float* __restrict__ p, const float* __restrict__ g, float
 }
 
 // n and alignment rules of the optimizer entries; the clipping instantiation only where something clips
-#define OPT_REFUSE(n, bits)                                  \
+#define OPT_REFUSE(n, bits, all_there)                       \
     do {                                                     \
-        if ((n) <= 0) return FMRI_E_SHAPE;                   \
+        if ((n) <= 0 || !(all_there)) return FMRI_E_SHAPE;   \
         if ((bits) & 15) return FMRI_E_ALIGN;                \
     } while (0)
 static inline bool opt_clips(const double*& gnorm, float clipnorm, float clipvalue) {
@@ -1007,7 +1007,7 @@ static inline bool opt_clips(const double*& gnorm, float clipnorm, float clipval
 
 extern "C" int fmri_sgd_step(float* p, const float* g, float* m, int64_t n, float lr, float momentum, int nesterov, float grad_scale,
                              const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream) {
-    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m));
+    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m), p && g && m);
     const bool clip = opt_clips(gnorm, clipnorm, clipvalue);
     if (((uintptr_t)gnorm) & 7) return FMRI_E_ALIGN;
     const int grid = grid_for(n / 4 + 1, 256, 2048);
@@ -1022,7 +1022,7 @@ extern "C" int fmri_sgd_step(float* p, const float* g, float* m, int64_t n, floa
 
 extern "C" int fmri_rmsprop_step(float* p, const float* g, float* a, int64_t n, float lr, float rho, float eps, float grad_scale,
                                  const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream) {
-    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)a));
+    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)a), p && g && a);
     const bool clip = opt_clips(gnorm, clipnorm, clipvalue);
     if (((uintptr_t)gnorm) & 7) return FMRI_E_ALIGN;
     const int grid = grid_for(n / 4 + 1, 256, 2048);
@@ -1035,7 +1035,7 @@ extern "C" int fmri_rmsprop_step(float* p, const float* g, float* a, int64_t n, 
 
 extern "C" int fmri_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
                               float eps, float grad_scale, fmri_stream_t stream) {
-    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v));
+    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v), p && g && m && v);
     k_adam<false, false><<<grid_for(n / 4 + 1, 256, 2048), 256, 0, as_stream(stream)>>>(p, g, m, v, nullptr, n, lr_t, beta1, beta2, eps,
                                                                                         grad_scale, nullptr, 0.f, 0.f);
     FMRI_LAUNCH_CHECK();
@@ -1044,7 +1044,7 @@ extern "C" int fmri_adam_step(float* p, const float* g, float* m, float* v, int6
 
 extern "C" int fmri_adam_step_ex(float* p, const float* g, float* m, float* v, float* vhat, int64_t n, float lr_t, float beta1, float beta2,
                                  float eps, float grad_scale, const double* gnorm, float clipnorm, float clipvalue, fmri_stream_t stream) {
-    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)vhat));
+    OPT_REFUSE(n, ((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)vhat), p && g && m && v);          // vhat may be NULL (no AMSGrad)
     const bool clip = opt_clips(gnorm, clipnorm, clipvalue);
     if (((uintptr_t)gnorm) & 7) return FMRI_E_ALIGN;
     const int grid = grid_for(n / 4 + 1, 256, 2048);

@@ -389,8 +389,9 @@ int fmri_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
                    float eps, float grad_scale, fmri_stream_t stream);
 
 /* ---- Keras 2.2.4 SGD / RMSprop / Adam with AMSGrad, and gradient clipping (keras/optimizers.py as published; restated without a Keras to
- * run against: parity-unpinned).  One launch over the flat buffers each; n <= 0: FMRI_E_SHAPE, a buffer that is not 16-byte aligned (gnorm:
- * 8-byte): FMRI_E_ALIGN - nothing is launched then.
+ * run against: parity-unpinned).  One launch over the flat buffers each; n <= 0 or a NULL p / g / moment buffer (SGD keeps m at momentum 0
+ * too; only AMSGrad's vhat may be NULL): FMRI_E_SHAPE, a buffer that is not 16-byte aligned (gnorm: 8-byte): FMRI_E_ALIGN - nothing is
+ * launched then.  fmri_adam_step refuses the same way.
  * The gradient every update sees (Optimizer.get_gradients, clip_norm), in fp32, left to right:
  *     g = grad_scale * G[i]
  *     gnorm != NULL and clipnorm > 0 and norm >= clipnorm:   g = g * clipnorm / norm       norm = (float)*gnorm, read on the device

@@ -269,6 +269,13 @@ def test_refusals_launch_nothing():
         if name != "sumsq":
             assert call(n, p + 4, g) == ALIGN, name
     assert L.fmri_sgd_step(p, g, m, n, 0.1, 0.9, 1, 1.0, out.data_ptr() + 4, 1.0, 0.0, s) == ALIGN      # the norm: 8-byte rule
+    # a missing buffer (a caller that drops SGD's moments at momentum 0, say) is refused, not launched on; only AMSGrad's vhat may be NULL
+    assert L.fmri_sgd_step(p, g, None, n, 0.1, 0.0, 0, 1.0, None, 0.0, 0.0, s) == SHAPE
+    assert L.fmri_sgd_step(None, g, m, n, 0.1, 0.9, 0, 1.0, None, 0.0, 0.0, s) == SHAPE
+    assert L.fmri_rmsprop_step(p, g, None, n, 0.1, 0.9, 1e-7, 1.0, None, 0.0, 0.0, s) == SHAPE
+    assert L.fmri_rmsprop_step(p, None, v, n, 0.1, 0.9, 1e-7, 1.0, None, 0.0, 0.0, s) == SHAPE
+    assert L.fmri_adam_step(p, g, None, v, n, 0.1, 0.9, 0.999, 1e-7, 1.0, s) == SHAPE
+    assert L.fmri_adam_step_ex(p, g, m, None, h, n, 0.1, 0.9, 0.999, 1e-7, 1.0, None, 0.0, 0.0, s) == SHAPE
     torch.cuda.synchronize()
     for t in bufs:
         assert np.array_equal(_host(t), keep)
