@@ -28,7 +28,7 @@ struct AffineB {                        // per patch of a launch: the volume, it
 };
 // (cx, cy, cz) = A . (pi, pj, pk, 1), the products fused in a WRITTEN-OUT order: left to the compiler's contraction, two kernels that share the
 // expression a0 pi + a1 pj + a2 pk + a3 can fuse different products and round the last bit of a coordinate differently.  The order is the
-// one k_affine_sample has always compiled to (its results do not move), and k_affine_sample_slices shares it bit for bit.
+// one k_affine_sample has always compiled to (its results do not move), with and without a slice table.
 __device__ __forceinline__ void affine_point(const Affine34& A, double pi, double pj, double pk, double& cx, double& cy, double& cz) {
     cx = fma(A.a[2], pk, fma(A.a[1], pj, A.a[0] * pi)) + A.a[3];
     cy = fma(A.a[6], pk, fma(A.a[4], pi, A.a[5] * pj)) + A.a[7];
@@ -56,54 +56,38 @@ __device__ __forceinline__ float sample_at(const TI* __restrict__ vol, int X, in
     }
     return v;
 }
-template <typename TI, typename TO>
-__global__ void k_affine_sample(AffineB P, int nx, int ny, int nz, int order, TO* __restrict__ out, int ld, int64_t out_stride) {
-    const int pb = blockIdx.y;
-    const TI* __restrict__ vol = static_cast<const TI*>(P.vol[pb]);
-    const int X = P.X[pb], Y = P.Y[pb], Z = P.Z[pb], x0 = P.x0[pb], y0 = P.y0[pb], z0 = P.z0[pb];
-    const float cval = P.cval[pb];
-    const Affine34& A = P.A[pb];
-    out += pb * out_stride;
-    const int64_t total = (int64_t)nx * ny * nz;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int k = (int)(t % nz);
-        const int64_t q = t / nz;
-        const int j = (int)(q % ny), i = (int)(q / ny);
-        const double pi = x0 + i, pj = y0 + j, pk = z0 + k;
-        double cx, cy, cz;
-        affine_point(A, pi, pj, pk, cx, cy, cz);
-        st_any<TO>(out, q * ld + k, sample_at<TI>(vol, X, Y, Z, cx, cy, cz, order, cval));
-    }
-}
-
-// Inter-slice motion of a fetal stack (not in the reference): k_affine_sample with one in-plane rigid map PER OUTPUT SLICE, folded into the
-// gather - the moved slices are read from the volume once, with one interpolation.  tab: device fp64 [patches][nzt][6]; output slice k of
-// patch pb takes row r = k + z_off as (i', j') = (m0 i + m1 j + m2, m3 i + m4 j + m5) in PATCH coordinates, and the source point is
+// SLICES - inter-slice motion of a fetal stack (not in the reference): one in-plane rigid map PER OUTPUT SLICE, folded into the gather - the
+// moved slices are read from the volume once, with one interpolation.  tab: device fp64 [patches][nzt][6]; output slice k of patch pb takes
+// row r = k + z_off as (i', j') = (m0 i + m1 j + m2, m3 i + m4 j + m5) in PATCH coordinates, and the source point is
 // A . (corner + (i', j', k), 1).  A row outside [0, nzt) is the identity: z_off places the label / previous-truth slices (a sub-range of the
-// image's slices) under the image slice they belong to.  An identity row gives k_affine_sample's coordinates bit for bit (1 * i + 0 * j + 0).
-template <typename TI, typename TO>
-__global__ void k_affine_sample_slices(AffineB P, const double* __restrict__ tab, int nzt, int z_off, int nx, int ny, int nz, int order,
-                                       TO* __restrict__ out, int ld, int64_t out_stride) {
+// image's slices) under the image slice they belong to.  An identity row gives the table-free coordinates bit for bit (1 * i + 0 * j + 0).
+template <typename TI, typename TO, bool SLICES>
+__global__ void k_affine_sample(AffineB P, const double* __restrict__ tab, int nzt, int z_off, int nx, int ny, int nz, int order,
+                                TO* __restrict__ out, int ld, int64_t out_stride) {
     const int pb = blockIdx.y;
     const TI* __restrict__ vol = static_cast<const TI*>(P.vol[pb]);
     const int X = P.X[pb], Y = P.Y[pb], Z = P.Z[pb], x0 = P.x0[pb], y0 = P.y0[pb], z0 = P.z0[pb];
     const float cval = P.cval[pb];
     const Affine34& A = P.A[pb];
     out += pb * out_stride;
-    tab += (int64_t)pb * nzt * 6;
+    if constexpr (SLICES) tab += (int64_t)pb * nzt * 6;
     const int64_t total = (int64_t)nx * ny * nz;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int k = (int)(t % nz);
         const int64_t q = t / nz;
         const int j = (int)(q % ny), i = (int)(q / ny);
-        const int r = k + z_off;
-        double ip = i, jp = j;
-        if (r >= 0 && r < nzt) {
-            const double* __restrict__ m = tab + 6 * r;
-            ip = m[0] * i + m[1] * j + m[2];
-            jp = m[3] * i + m[4] * j + m[5];
+        double pi = x0 + i, pj = y0 + j;
+        if constexpr (SLICES) {
+            const int r = k + z_off;
+            double ip = i, jp = j;
+            if (r >= 0 && r < nzt) {
+                const double* __restrict__ m = tab + 6 * r;
+                ip = m[0] * i + m[1] * j + m[2];
+                jp = m[3] * i + m[4] * j + m[5];
+            }
+            pi = x0 + ip, pj = y0 + jp;
         }
-        const double pi = x0 + ip, pj = y0 + jp, pk = z0 + k;
+        const double pk = z0 + k;
         double cx, cy, cz;
         affine_point(A, pi, pj, pk, cx, cy, cz);
         st_any<TO>(out, q * ld + k, sample_at<TI>(vol, X, Y, Z, cx, cy, cz, order, cval));
@@ -829,9 +813,13 @@ extern "C" int fmri_shot_noise_step(void* x, int64_t n, int dtype, const float* 
     return FMRI_OK;
 }
 
-static int elastic_warp_launch(const void* src, int dtype, int X, int Y, int C, int src_ld, const float* d0, const float* d1, int order, void* dst,
-                               int dst_ld, int64_t src_stride, int64_t dst_stride, int64_t d_stride, int B, hipStream_t st) {
+extern "C" int fmri_elastic_warp_batch(const void* src, int dtype, int X, int Y, int C, int src_ld, int64_t src_stride, const float* d, int order,
+                                      void* dst, int dst_ld, int64_t dst_stride, int B, fmri_stream_t stream) {
+    if (X < 1 || Y < 1 || C < 1 || src_ld < C || dst_ld < C || (order != 0 && order != 1) || !d || src == dst || B < 1 || B > 65535) return FMRI_E_SHAPE;
+    hipStream_t st = as_stream(stream);
     const dim3 grid(grid_for((int64_t)X * Y * C), B);
+    const float *d0 = d, *d1 = d + (int64_t)X * Y;
+    const int64_t d_stride = (int64_t)2 * X * Y;
     if (dtype == FMRI_F32)
         k_elastic_warp<float><<<grid, 256, 0, st>>>((const float*)src, X, Y, C, src_ld, d0, d1, order, (float*)dst, dst_ld, src_stride, dst_stride, d_stride);
     else if (dtype == FMRI_U8)
@@ -840,17 +828,6 @@ static int elastic_warp_launch(const void* src, int dtype, int X, int Y, int C, 
     else return FMRI_E_DTYPE;
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
-}
-extern "C" int fmri_elastic_warp(const void* src, int dtype, int X, int Y, int C, int src_ld, const float* d0, const float* d1, int order, void* dst,
-                                int dst_ld, fmri_stream_t stream) {
-    if (X < 1 || Y < 1 || C < 1 || src_ld < C || dst_ld < C || (order != 0 && order != 1) || !d0 || !d1 || src == dst) return FMRI_E_SHAPE;
-    return elastic_warp_launch(src, dtype, X, Y, C, src_ld, d0, d1, order, dst, dst_ld, 0, 0, 0, 1, as_stream(stream));
-}
-extern "C" int fmri_elastic_warp_batch(const void* src, int dtype, int X, int Y, int C, int src_ld, int64_t src_stride, const float* d, int order,
-                                      void* dst, int dst_ld, int64_t dst_stride, int B, fmri_stream_t stream) {
-    if (X < 1 || Y < 1 || C < 1 || src_ld < C || dst_ld < C || (order != 0 && order != 1) || !d || src == dst || B < 1 || B > 65535) return FMRI_E_SHAPE;
-    return elastic_warp_launch(src, dtype, X, Y, C, src_ld, d, d + (int64_t)X * Y, order, dst, dst_ld, src_stride, dst_stride, (int64_t)2 * X * Y, B,
-                               as_stream(stream));
 }
 
 extern "C" int fmri_piecewise_affine2(const void* src, int dtype, int X, int Y, int C, int src_ld, const double* tri, int order, void* dst, int dst_ld,
@@ -879,102 +856,50 @@ extern "C" int fmri_coarse_dropout(void* x, int dtype, int X, int Y, int C, int 
     return FMRI_OK;
 }
 
-static int affine_sample_launch(const AffineB& P, int B, int vol_dtype, int nx, int ny, int nz, int order, void* out, int out_dtype, int out_ld,
-                                int64_t out_stride, hipStream_t st) {
-    const dim3 grid(grid_for((int64_t)nx * ny * nz), B);
-#define FMRI_AS(TI, TO) k_affine_sample<TI, TO><<<grid, 256, 0, st>>>(P, nx, ny, nz, order, (TO*)out, out_ld, out_stride)
-    if (vol_dtype == FMRI_F32 && out_dtype == FMRI_F32) FMRI_AS(float, float);
-    else if (vol_dtype == FMRI_F32 && out_dtype == FMRI_BF16) FMRI_AS(float, bf16_t);
-    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_U8) FMRI_AS(uint8_t, uint8_t);
-    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_F32) FMRI_AS(uint8_t, float);
-    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_BF16) FMRI_AS(uint8_t, bf16_t);
-    else return FMRI_E_DTYPE;
-#undef FMRI_AS
-    FMRI_LAUNCH_CHECK();
-    return FMRI_OK;
-}
-extern "C" int fmri_affine_sample(const void* vol, int vol_dtype, int X, int Y, int Z, const double* affine, int x0, int y0, int z0, int nx,
-                                  int ny, int nz, int order, float cval, void* out, int out_dtype, int out_ld, fmri_stream_t stream) {
-    if (X < 1 || Y < 1 || Z < 1 || nx < 1 || ny < 1 || nz < 1 || out_ld < nz || (order != 0 && order != 1) || !affine) return FMRI_E_SHAPE;
-    AffineB P;
-    P.vol[0] = vol;
-    P.X[0] = X; P.Y[0] = Y; P.Z[0] = Z; P.x0[0] = x0; P.y0[0] = y0; P.z0[0] = z0;
-    P.cval[0] = cval;
-    for (int i = 0; i < 12; ++i) P.A[0].a[i] = affine[i];
-    return affine_sample_launch(P, 1, vol_dtype, nx, ny, nz, order, out, out_dtype, out_ld, 0, as_stream(stream));
-}
-extern "C" int fmri_affine_sample_batch(int B, const void* const* vols, const int* dims, const double* affines, const int* corners, const float* cvals,
-                                        int vol_dtype, int nx, int ny, int nz, int order, void* out, int out_dtype, int out_ld, int64_t out_stride,
-                                        fmri_stream_t stream) {
-    if (B < 1 || !vols || !dims || !affines || !corners || !cvals || nx < 1 || ny < 1 || nz < 1 || out_ld < nz || (order != 0 && order != 1))
-        return FMRI_E_SHAPE;
-    const int esz = out_dtype == FMRI_F32 ? 4 : (out_dtype == FMRI_BF16 ? 2 : 1);
-    for (int b0 = 0; b0 < B; b0 += AFF_MAXB) {
-        const int nb = B - b0 < AFF_MAXB ? B - b0 : AFF_MAXB;
-        AffineB P;
-        for (int b = 0; b < nb; ++b) {
-            const int g = b0 + b;
-            if (!vols[g] || dims[3 * g] < 1 || dims[3 * g + 1] < 1 || dims[3 * g + 2] < 1) return FMRI_E_SHAPE;
-            P.vol[b] = vols[g];
-            P.X[b] = dims[3 * g]; P.Y[b] = dims[3 * g + 1]; P.Z[b] = dims[3 * g + 2];
-            P.x0[b] = corners[3 * g]; P.y0[b] = corners[3 * g + 1]; P.z0[b] = corners[3 * g + 2];
-            P.cval[b] = cvals[g];
-            for (int i = 0; i < 12; ++i) P.A[b].a[i] = affines[12 * g + i];
-        }
-        const int rc = affine_sample_launch(P, nb, vol_dtype, nx, ny, nz, order, (char*)out + (int64_t)b0 * out_stride * esz, out_dtype, out_ld, out_stride,
-                                            as_stream(stream));
-        if (rc != FMRI_OK) return rc;
+// the parameters of patches b0 .. b0 + nb - 1 of a call, by value
+static bool affine_fill(AffineB& P, int b0, int nb, const void* const* vols, const int* dims, const double* affines, const int* corners,
+                        const float* cvals) {
+    for (int b = 0; b < nb; ++b) {
+        const int g = b0 + b;
+        if (!vols[g] || dims[3 * g] < 1 || dims[3 * g + 1] < 1 || dims[3 * g + 2] < 1) return false;
+        P.vol[b] = vols[g];
+        P.X[b] = dims[3 * g]; P.Y[b] = dims[3 * g + 1]; P.Z[b] = dims[3 * g + 2];
+        P.x0[b] = corners[3 * g]; P.y0[b] = corners[3 * g + 1]; P.z0[b] = corners[3 * g + 2];
+        P.cval[b] = cvals[g];
+        for (int i = 0; i < 12; ++i) P.A[b].a[i] = affines[12 * g + i];
     }
-    return FMRI_OK;
+    return true;
 }
-
-static int affine_sample_slices_launch(const AffineB& P, int B, const double* tab, int nzt, int z_off, int vol_dtype, int nx, int ny, int nz, int order,
-                                       void* out, int out_dtype, int out_ld, int64_t out_stride, hipStream_t st) {
+// tab == nullptr: the instantiation without the table lines (the table gather is 16-23 % slower)
+static int affine_sample_launch(const AffineB& P, int B, const double* tab, int nzt, int z_off, int vol_dtype, int nx, int ny, int nz, int order,
+                                void* out, int out_dtype, int out_ld, int64_t out_stride, hipStream_t st) {
     const dim3 grid(grid_for((int64_t)nx * ny * nz), B);
-#define FMRI_AS(TI, TO) k_affine_sample_slices<TI, TO><<<grid, 256, 0, st>>>(P, tab, nzt, z_off, nx, ny, nz, order, (TO*)out, out_ld, out_stride)
-    if (vol_dtype == FMRI_F32 && out_dtype == FMRI_F32) FMRI_AS(float, float);
-    else if (vol_dtype == FMRI_F32 && out_dtype == FMRI_BF16) FMRI_AS(float, bf16_t);
-    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_U8) FMRI_AS(uint8_t, uint8_t);
-    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_F32) FMRI_AS(uint8_t, float);
-    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_BF16) FMRI_AS(uint8_t, bf16_t);
+#define FMRI_AS(TI, TO)                                                                                                                   \
+    if (tab) k_affine_sample<TI, TO, true><<<grid, 256, 0, st>>>(P, tab, nzt, z_off, nx, ny, nz, order, (TO*)out, out_ld, out_stride); \
+    else k_affine_sample<TI, TO, false><<<grid, 256, 0, st>>>(P, nullptr, 0, 0, nx, ny, nz, order, (TO*)out, out_ld, out_stride)
+    if (vol_dtype == FMRI_F32 && out_dtype == FMRI_F32) { FMRI_AS(float, float); }
+    else if (vol_dtype == FMRI_F32 && out_dtype == FMRI_BF16) { FMRI_AS(float, bf16_t); }
+    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_U8) { FMRI_AS(uint8_t, uint8_t); }
+    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_F32) { FMRI_AS(uint8_t, float); }
+    else if (vol_dtype == FMRI_U8 && out_dtype == FMRI_BF16) { FMRI_AS(uint8_t, bf16_t); }
     else return FMRI_E_DTYPE;
 #undef FMRI_AS
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
-extern "C" int fmri_affine_sample_slices(const void* vol, int vol_dtype, int X, int Y, int Z, const double* affine, const double* table, int nz_table,
-                                         int z_off, int x0, int y0, int z0, int nx, int ny, int nz, int order, float cval, void* out, int out_dtype,
-                                         int out_ld, fmri_stream_t stream) {
-    if (X < 1 || Y < 1 || Z < 1 || nx < 1 || ny < 1 || nz < 1 || out_ld < nz || (order != 0 && order != 1) || !affine || !table || nz_table < 1)
-        return FMRI_E_SHAPE;
-    AffineB P;
-    P.vol[0] = vol;
-    P.X[0] = X; P.Y[0] = Y; P.Z[0] = Z; P.x0[0] = x0; P.y0[0] = y0; P.z0[0] = z0;
-    P.cval[0] = cval;
-    for (int i = 0; i < 12; ++i) P.A[0].a[i] = affine[i];
-    return affine_sample_slices_launch(P, 1, table, nz_table, z_off, vol_dtype, nx, ny, nz, order, out, out_dtype, out_ld, 0, as_stream(stream));
-}
-extern "C" int fmri_affine_sample_slices_batch(int B, const void* const* vols, const int* dims, const double* affines, const double* table, int nz_table,
-                                               int z_off, const int* corners, const float* cvals, int vol_dtype, int nx, int ny, int nz, int order,
-                                               void* out, int out_dtype, int out_ld, int64_t out_stride, fmri_stream_t stream) {
-    if (B < 1 || !vols || !dims || !affines || !table || nz_table < 1 || !corners || !cvals || nx < 1 || ny < 1 || nz < 1 || out_ld < nz ||
+extern "C" int fmri_affine_sample_batch(int B, const void* const* vols, const int* dims, const double* affines, const double* table, int nz_table,
+                                        int z_off, const int* corners, const float* cvals, int vol_dtype, int nx, int ny, int nz, int order, void* out,
+                                        int out_dtype, int out_ld, int64_t out_stride, fmri_stream_t stream) {
+    if (B < 1 || !vols || !dims || !affines || (table && nz_table < 1) || !corners || !cvals || nx < 1 || ny < 1 || nz < 1 || out_ld < nz ||
         (order != 0 && order != 1))
         return FMRI_E_SHAPE;
     const int esz = out_dtype == FMRI_F32 ? 4 : (out_dtype == FMRI_BF16 ? 2 : 1);
     for (int b0 = 0; b0 < B; b0 += AFF_MAXB) {
         const int nb = B - b0 < AFF_MAXB ? B - b0 : AFF_MAXB;
         AffineB P;
-        for (int b = 0; b < nb; ++b) {
-            const int g = b0 + b;
-            if (!vols[g] || dims[3 * g] < 1 || dims[3 * g + 1] < 1 || dims[3 * g + 2] < 1) return FMRI_E_SHAPE;
-            P.vol[b] = vols[g];
-            P.X[b] = dims[3 * g]; P.Y[b] = dims[3 * g + 1]; P.Z[b] = dims[3 * g + 2];
-            P.x0[b] = corners[3 * g]; P.y0[b] = corners[3 * g + 1]; P.z0[b] = corners[3 * g + 2];
-            P.cval[b] = cvals[g];
-            for (int i = 0; i < 12; ++i) P.A[b].a[i] = affines[12 * g + i];
-        }
-        const int rc = affine_sample_slices_launch(P, nb, table + (int64_t)b0 * nz_table * 6, nz_table, z_off, vol_dtype, nx, ny, nz, order,
-                                                   (char*)out + (int64_t)b0 * out_stride * esz, out_dtype, out_ld, out_stride, as_stream(stream));
+        if (!affine_fill(P, b0, nb, vols, dims, affines, corners, cvals)) return FMRI_E_SHAPE;
+        const int rc = affine_sample_launch(P, nb, table ? table + (int64_t)b0 * nz_table * 6 : nullptr, nz_table, z_off, vol_dtype, nx, ny, nz, order,
+                                            (char*)out + (int64_t)b0 * out_stride * esz, out_dtype, out_ld, out_stride, as_stream(stream));
         if (rc != FMRI_OK) return rc;
     }
     return FMRI_OK;

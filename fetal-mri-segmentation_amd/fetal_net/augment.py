@@ -157,7 +157,7 @@ def contrast_augment(data, min_per, max_per):
 # moves between them), whole slices lose signal (spin history) and the surface coil modulates the intensity smoothly.  Four optional keys of
 # the `augment` dict: slice_motion {prob, slice_prob, rotate (degrees, std), translate (voxels, std)}, gamma {prob, range (lo, hi)},
 # bias_field {prob, order 1..3, coefficient}, slice_intensity {prob, slice_prob, sigma}.  The draws below are the written semantics; the device
-# generator applies them with csrc/augment.hip (k_affine_sample_slices, k_mri_intensity_ws), the float64 forms here are their host twins.
+# generator applies them with csrc/augment.hip (k_affine_sample with a slice table, k_mri_intensity_ws), the float64 forms here are their host twins.
 MRI_KEYS = ("slice_motion", "gamma", "bias_field", "slice_intensity")
 GAMMA_RANGE, BIAS_ORDER, BIAS_COEFFICIENT = (0.7, 1.5), 3, 0.5
 

@@ -4,7 +4,7 @@ The reference builds each patch on one host thread (fetal_net/generator.py:222-3
 extract_patch -> convert_data) and Keras copies the batch to the device; with the convolutions at MFMA speed that thread is the
 bottleneck.  Here every (padded) volume of the split is uploaded once - 288 GB of HBM holds any dataset of this kind - and a patch
 is: the reference's random draws on the host (same order, same generators => same transformation for the same seed), then one
-fmri_affine_sample launch for the image (trilinear, cval = volume minimum) and one for the labels (nearest, cval = 0) straight
+fmri_affine_sample_batch launch for the image (trilinear, cval = volume minimum) and one for the labels (nearest, cval = 0) straight
 into the batch tensors, then the elementwise intensity passes.  The generator yields torch CUDA tensors in the reference's logical
 layouts ((N,1,X,Y,Z) / (N,X,Y,C) float32 images, uint8 labels); Model.train_on_batch / fit_generator take them as they are.
 A data file with a non-empty `mask` array (the distance masks of the mask-weighted loss, reference generator.py:18-21) makes the generator
@@ -28,9 +28,10 @@ imgaug's piecewise_affine (commented out in the reference's default config, conf
 between the affine sampling and the elastic transform (augment.py:344-347), on the reference's 2 x 2 grid.
 The noise fields (normal, uniform and Poisson draws) are made inside the kernels by a counter-based generator (Philox4x32-10 keyed by
 `noise_seed`; csrc/augment.hip), not by numpy: same distributions, other streams.  The patches of a batch are PLANNED one after the other
-on the host (every draw of the reference, in its order) and then LAUNCHED together, one launch per step of the chain (`_Sampler.plan` /
-`launch_batch`, previous-slice truth channels included); configurations the batch kernels do not cover (piecewise affine, the Gaussian
-filter, drop_easy_patches' interleaved draws) go patch by patch (`launch_one`) - same draws, same batches (tests/test_gpu_augment.py).
+on the host (every draw of the reference, in its order) and then LAUNCHED together, one launch per step of ONE chain (`_Sampler.plan` /
+`_chain`, previous-slice truth channels included).  The steps without a batch kernel (piecewise affine, the Gaussian filter, elastic fields
+wider than the in-kernel generator covers) run inside that chain for the patches that drew them; drop_easy_patches' interleaved draws and
+`batched=False` run the same chain on batches of one - same draws, same batches (tests/golden/generator_chain_digests.json).
 
 Departures from the reference: four optional `augment` keys it does not have, the acquisition effects of a fetal stack of 2-D slices -
 slice_motion, gamma, bias_field, slice_intensity (fetal_net/augment.py: draw_mri_parameters and the float64 host forms).  There is no
@@ -157,8 +158,7 @@ class _Sampler(object):
         self.truth_index, self.truth_size = truth_index, truth_size
         self.prev_truth_index, self.prev_truth_size = prev_truth_index, prev_truth_size
         self.n_chan = self.patch_shape[2] + (prev_truth_size if prev_truth_index is not None else 0)
-        self.stats, self.ws = ops.aug_workspace(ddf.device)
-        self.stats_b = self.ws_b = None                  # the batch path's [B] workspaces, made on first use
+        self.stats_b = self.ws_b = None                  # the chain's [B] workspaces, made on first use
         self.seed, self.seq = int(noise_seed), 0
         self.batched = True
         self.gen = torch.Generator(device=ddf.device)
@@ -184,8 +184,7 @@ class _Sampler(object):
 
     def plan(self, index):
         """every HOST draw of one patch, in the reference's order (numpy's global state, python's `random`, this sampler's private imgaug
-        state and the call numbers of its in-kernel draws), and the matrices they give - nothing is enqueued.  -> dict for launch_one /
-        launch_batch."""
+        state and the call numbers of its in-kernel draws), and the matrices they give - nothing is enqueued.  -> dict for launch / _chain."""
         ddf, ps = self.ddf, self.patch_shape
         data, truth = ddf.data[index], ddf.truth[index]
         corner = [np.random.randint(low=0, high=h) for h in np.array(truth.shape) - np.array(ps)]
@@ -272,27 +271,24 @@ class _Sampler(object):
     def sample_into(self, index, x_slot, y_slot, m_slot=None):
         """one patch: x_slot: float32 view (X, Y, n_chan) of the batch tensor; y_slot: uint8 view (X, Y, truth_size); m_slot: float32 view
         (X, Y, truth_size) for the distance mask, when the data file has masks"""
-        self.launch_one(self.plan(index), x_slot, y_slot, m_slot)
-
-    def batchable(self, plans):
-        """can launch_batch take these plans?  Not: piecewise affine, a Gaussian filter on some patch, an elastic kernel wider than the
-        one-launch field kernel - those go patch by patch (launch_one)"""
-        return all(q["corners"] is None and q["elastic_seq"] >= 0 and not (q["p"] is not None and q["p"]["apply_gaussian_filter"]) for q in plans)
+        self._chain([self.plan(index)], x_slot.unsqueeze(0), y_slot.unsqueeze(0), None if m_slot is None else m_slot.unsqueeze(0))
 
     def launch(self, plans, x, y, m=None):
-        """x (B, X, Y, n_chan) float32, y (B, X, Y, truth_size) uint8, m like y in float32 or None: the patches of `plans`, in order"""
-        if self.batched and self.batchable(plans):
-            self.launch_batch(plans, x, y, m)
+        """x (B, X, Y, n_chan) float32, y (B, X, Y, truth_size) uint8, m like y in float32 or None: the patches of `plans`, in order - launched
+        together, or (batched=False) each as a batch of one"""
+        if self.batched:
+            self._chain(plans, x, y, m)
         else:
             for b, q in enumerate(plans):
-                self.launch_one(q, x[b], y[b], None if m is None else m[b])
+                self._chain([q], x[b:b + 1], y[b:b + 1], None if m is None else m[b:b + 1])
 
-    def launch_batch(self, plans, x, y, m=None):
-        """the patches of a batch with ONE launch per step of the chain (fmri_*_batch): 2-3 gathers, the elastic fields and 2-3 warps, the
-        min / max, then only the intensity steps some patch of the batch drew.  Same arithmetic, same draws as launch_one patch by patch
-        (tests/test_gpu_augment.py).  With previous-slice truth channels the image slices are sampled, warped and augmented in a dense
-        (B, X, Y, slices) staging tensor - launch_one works on a contiguous copy as well, so the kernels see the same layout and draw the same
-        counters - and copied in front of the truth channels, which are sampled (nearest, outside = 0) and warped with the same fields."""
+    def _chain(self, plans, x, y, m):
+        """THE chain, in the reference's order, ONE launch per step for all of `plans` (fmri_*_batch): 2-4 gathers, the elastic fields and 2-4
+        warps, the min / max, then only the intensity steps some patch drew.  The steps without a batch kernel - piecewise affine, the Gaussian
+        filter, elastic fields wider than the one-launch field kernel - run inside it for the patches that drew them, in batch order.  A patch
+        without a warp in a warped batch goes through the batch warp with zero fields: the identity, bit for bit.  With previous-slice truth
+        channels the image slices are sampled, warped and augmented in a dense (B, X, Y, slices) staging tensor and copied in front of the
+        truth channels, which are sampled (nearest, outside = 0) and warped with the same fields."""
         ops, ddf, torch, ps = self.ops, self.ddf, self.torch, self.patch_shape
         B = len(plans)
         prev = self.prev_truth_index is not None
@@ -300,55 +296,51 @@ class _Sampler(object):
         idx = [q["index"] for q in plans]
         tshape = (ps[0], ps[1], self.truth_size)
         warped = any(q["elastic_seq"] for q in plans)
-
-        def target(dst, shape, dtype):
-            return dst if not warped else torch.empty((B,) + tuple(shape), device=dst.device, dtype=dtype)
-
         d = None
         if warped:
-            d = ops.elastic_fields_rng_batch((ps[0], ps[1]), [q["p"]["elastic_transform_scale"] if q["elastic_seq"] else 0.0 for q in plans],
-                                             self.augment["elastic_transform"]["sigma"], self.seed, [q["elastic_seq"] for q in plans], device=x.device)
+            alphas = [q["p"]["elastic_transform_scale"] if q["elastic_seq"] else 0.0 for q in plans]
+            sigma = self.augment["elastic_transform"]["sigma"]
+            if all(q["elastic_rng"] for q in plans):
+                d = ops.elastic_fields_rng_batch((ps[0], ps[1]), alphas, sigma, self.seed, [q["elastic_seq"] for q in plans], device=x.device)
+            else:                                            # a kernel wider than ELASTIC_RNG_KMAX: host fields from self.gen, patch after patch
+                d = torch.zeros((B, 2, ps[0], ps[1]), device=x.device, dtype=torch.float32)
+                for b, q in enumerate(plans):
+                    if q["elastic_seq"]:
+                        d[b, 0], d[b, 1] = ops.elastic_fields((ps[0], ps[1]), alphas[b], sigma, generator=self.gen)
         corners_t = [(q["corner"][0], q["corner"][1], q["corner"][2] + self.truth_index) for q in plans]
-        table = self._slice_tables(plans)
+        table = self._slice_tables(plans)                    # None unless some patch drew slice motion: the plain gather then
 
-        def gather(vols, affines, corners, size, out, order, cvals, z_off, out_ld=None):
-            # some patch drew slice motion: the gather that moves output slice k by table row k + z_off (z_off: where `out` sits among the
-            # image slices); else the plain gather, called as ever
-            if table is None:
-                return ops.affine_sample_batch(vols, affines, corners, size, out, order, cvals, out_ld=out_ld)
-            return ops.affine_sample_slices_batch(vols, affines, corners, size, out, order, cvals, table, z_off, out_ld=out_ld)
+        def sample(vols, affines, corners, size, dst, order, cvals, z_off, dst_ld=None):
+            """gather (output slice k moved by table row k + z_off), then imgaug's two resamplings: piecewise affine on the patches that drew
+            one (reference augment.py:344-347), the elastic warp on all (:349-353) -> dst"""
+            t = torch.empty((B,) + tuple(size), device=dst.device, dtype=dst.dtype) if warped else dst
+            ops.affine_sample_batch(vols, affines, corners, size, t, order, cvals, table=table, z_off=z_off, out_ld=None if warped else dst_ld)
+            for b, q in enumerate(plans):
+                if q["corners"] is not None:
+                    ops.piecewise_affine(t[b].clone(), q["corners"], order, t[b])
+            if warped:
+                ops.elastic_warp_batch(t, d, order, dst)
 
         # image: trilinear, outside = the volume's minimum; labels: nearest, outside = 0 (identity affine = the plain crop)
-        xt = target(xd, ps, torch.float32)
-        gather([ddf.data[i] for i in idx], [q["A"] for q in plans], [q["corner"] for q in plans], ps, xt, 1, [ddf.min[i] for i in idx], 0)
-        yt = target(y, tshape, torch.uint8)
-        gather([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_t, tshape, yt, 0, [0.0] * B, self.truth_index)
-        if warped:
-            ops.elastic_warp_batch(xt, d, 1, xd)
-            ops.elastic_warp_batch(yt, d, 0, y)
+        sample([ddf.data[i] for i in idx], [q["A"] for q in plans], [q["corner"] for q in plans], ps, xd, 1, [ddf.min[i] for i in idx], 0)
+        sample([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_t, tshape, y, 0, [0.0] * B, self.truth_index)
         if m is not None:
             # augmented: outside the mask = 0 (interpolate_affine_range, cval 0); plain crop: edge values
             src = [ddf.mask[q["index"]] if q["p"] is not None else ddf.mask_for_crops(q["index"]) for q in plans]
-            mt = target(m, tshape, torch.float32)
-            gather(src, [q["Am"] for q in plans], corners_t, tshape, mt, 0, [0.0] * B, self.truth_index)
-            if warped:
-                ops.elastic_warp_batch(mt, d, 0, m)
+            sample(src, [q["Am"] for q in plans], corners_t, tshape, m, 0, [0.0] * B, self.truth_index)
         if prev:
-            pshape = (ps[0], ps[1], self.prev_truth_size)
             corners_p = [(q["corner"][0], q["corner"][1], q["corner"][2] + self.prev_truth_index) for q in plans]
-            xp = x[..., ps[2]:]
-            pt = torch.empty((B,) + pshape, device=x.device, dtype=torch.float32) if warped else xp
-            gather([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_p, pshape, pt, 0, [0.0] * B, self.prev_truth_index,
-                   out_ld=None if warped else self.n_chan)
-            if warped:
-                ops.elastic_warp_batch(pt, d, 0, xp)
+            sample([ddf.truth[i] for i in idx], [q["At"] for q in plans], corners_p, (ps[0], ps[1], self.prev_truth_size), x[..., ps[2]:], 0,
+                   [0.0] * B, self.prev_truth_index, dst_ld=self.n_chan)
         if any(q["p"] is not None and q["need_intensity"] for q in plans):
-            self._intensity_batch(plans, xd)
+            self._intensity(plans, xd)
         if prev:
             x[..., :ps[2]] = xd
 
-    def _intensity_batch(self, plans, x):
-        """the intensity steps of launch_batch on the dense image slices x (B, X, Y, slices)"""
+    def _intensity(self, plans, x):
+        """the intensity steps of the chain on the dense image slices x (B, X, Y, slices).  Every step wants the image's range
+        (rescale_intensity's out_range, MinMaxScaler): taken ONCE, then each kernel that rewrites a patch leaves its new range in stats[b] for
+        the next one; the noise draws are made in the kernels (Philox keyed by noise_seed, one counter value per call) - fmri_hip.h"""
         ops = self.ops
         B = len(plans)
         stats, ws = self._workspace(B)
@@ -364,7 +356,14 @@ class _Sampler(object):
         if any(r[0] for r in params):
             ops.rescale_intensity_ws_batch(x, stats, ws, params)
         self._mri_intensity_launch(plans, x, stats, ws)                  # acquisition effects: behind the reference's contrast, before its noises
-        # order of reference augment.py:354-367: (gaussian filter,) shot (poisson) noise, speckle, gaussian noise; coarse dropout last
+        # order of reference augment.py:354-367: gaussian filter, shot (poisson) noise, speckle, gaussian noise; coarse dropout last
+        for b, q in enumerate(plans):
+            if q["p"] is not None and q["p"]["apply_gaussian_filter"]:
+                img = x[b]
+                smooth = ops.gaussian_filter_f32(img, q["p"]["gaussian_sigma"])
+                if smooth is not img:
+                    img.copy_(smooth)
+                ops.minmax_ws(img, stats[b], ws[b])
         if any(q["shot_seq"] for q in plans):
             ops.shot_noise_rng_batch(x, stats, ws, self.seed, [q["shot_seq"] for q in plans])
         for key, aug_key, kind in (("speckle_seq", "speckle_noise", 1), ("gaussian_seq", "gaussian_noise", 0)):
@@ -379,92 +378,6 @@ class _Sampler(object):
         if self.stats_b is None or self.stats_b.shape[0] < B:
             self.stats_b, self.ws_b = self.ops.aug_workspace(self.ddf.device, max(B, 2))
         return self.stats_b[:B], self.ws_b[:B]
-
-    def launch_one(self, q, x_slot, y_slot, m_slot=None):
-        """one planned patch, launch by launch (every configuration; the batch path's reference in the tests)"""
-        ops, ddf = self.ops, self.ddf
-        index, corner, p, A, At, Am = q["index"], q["corner"], q["p"], q["A"], q["At"], q["Am"]
-        data, truth = ddf.data[index], ddf.truth[index]
-        ps = self.patch_shape
-        zt = corner[2] + self.truth_index
-        elastic, corners = None, q["corners"]
-        if q["elastic_seq"]:
-            sigma = self.augment["elastic_transform"]["sigma"]
-            if q["elastic_rng"]:
-                elastic = ops.elastic_fields_rng((ps[0], ps[1]), p["elastic_transform_scale"], sigma, self.seed, q["elastic_seq"], device=ddf.device)
-            else:
-                elastic = ops.elastic_fields((ps[0], ps[1]), p["elastic_transform_scale"], sigma, generator=self.gen)
-        warped = elastic is not None or corners is not None
-
-        def target(slot, shape, dtype):
-            return slot if not warped else self.torch.empty(shape, device=slot.device, dtype=dtype)
-
-        def settle(tmp, slot, order):
-            if corners is not None:
-                tmp = ops.piecewise_affine(tmp, corners, order, slot if elastic is None else self.torch.empty_like(tmp))
-            if elastic is not None:
-                ops.elastic_warp(tmp, elastic[0], elastic[1], order, slot)
-
-        table = self._slice_tables([q])
-
-        def gather(vol, affine, start, size, out, order, cval, z_off, out_ld=None):
-            if table is None:
-                return ops.affine_sample(vol, affine, start, size, out, order=order, cval=cval, out_ld=out_ld)
-            return ops.affine_sample_slices(vol, affine, start, size, out, table[0], z_off, order=order, cval=cval, out_ld=out_ld)
-
-        tshape = (ps[0], ps[1], self.truth_size)
-        # image: trilinear, outside = the volume's minimum; labels: nearest, outside = 0 (identity affine = the plain crop)
-        xt = target(x_slot[..., :ps[2]], ps, self.torch.float32)
-        gather(data, A, corner, ps, xt, 1, ddf.min[index], 0, out_ld=self.n_chan if not warped else ps[2])
-        settle(xt, x_slot[..., :ps[2]], 1)
-        yt = target(y_slot, tshape, self.torch.uint8)
-        gather(truth, At, (corner[0], corner[1], zt), tshape, yt, 0, 0.0, self.truth_index, out_ld=self.truth_size)
-        settle(yt, y_slot, 0)
-        if m_slot is not None:
-            # augmented: outside the mask = 0 (interpolate_affine_range, cval 0); plain crop: edge values
-            src = ddf.mask[index] if p is not None else ddf.mask_for_crops(index)
-            mt = target(m_slot, tshape, self.torch.float32)
-            gather(src, Am, (corner[0], corner[1], zt), tshape, mt, 0, 0.0, self.truth_index, out_ld=self.truth_size)
-            settle(mt, m_slot, 0)
-        img = x_slot if self.n_chan == ps[2] else None
-        if p is not None:
-            if q["need_intensity"]:
-                if img is None:                            # image channels interleaved with the previous-slice truth: work on a copy
-                    img = x_slot[..., :ps[2]].contiguous()
-                # Every step below wants the image's range (rescale_intensity's out_range, MinMaxScaler): taken ONCE, then each kernel that
-                # rewrites the image leaves the new range in `stats` for the next one; the noise draws are made in the kernels (Philox keyed by
-                # noise_seed, one counter value per call) - fmri_hip.h "in-kernel draws"
-                stats, ws = self.stats, self.ws
-                ops.minmax_ws(img, stats, ws)
-                if p["contrast"] is not None or p["intensity_multiplication"] != 1:
-                    lo, hi = p["contrast"] if p["contrast"] is not None else (0.0, 0.0)
-                    ops.rescale_intensity_ws(img, stats, ws, p["contrast"] is not None, lo, hi, p["intensity_multiplication"])
-                self._mri_intensity_launch([q], img.unsqueeze(0), stats, ws)      # acquisition effects: behind contrast, before the filter and the noises
-                # order of reference augment.py:354-367: gaussian filter, shot (poisson) noise, speckle, gaussian noise
-                if p["apply_gaussian_filter"]:
-                    smooth = ops.gaussian_filter_f32(img, p["gaussian_sigma"])
-                    if smooth is not img:
-                        img.copy_(smooth)
-                    ops.minmax_ws(img, stats, ws)
-                if q["shot_seq"]:
-                    ops.shot_noise_rng(img, stats, ws, self.seed, q["shot_seq"])
-                for key, aug_key, kind in (("speckle_seq", "speckle_noise", 1), ("gaussian_seq", "gaussian_noise", 0)):
-                    if q[key]:
-                        ops.noise_rng(img, stats, ws, kind, self.augment[aug_key]["sigma"], self.seed, q[key])
-                if q["dropout_seq"]:
-                    cd = self.augment["coarse_dropout"]
-                    ops.coarse_dropout_rng(img, q["grid"], cd["rate"], stats, bool(cd.get("per_channel", True)), self.seed, q["dropout_seq"])
-                if img is not x_slot:
-                    x_slot[..., :ps[2]] = img
-        if self.prev_truth_index is not None:
-            zp = corner[2] + self.prev_truth_index
-            prev = self.torch.empty((ps[0], ps[1], self.prev_truth_size), device=x_slot.device, dtype=self.torch.float32)
-            gather(truth, At, (corner[0], corner[1], zp), (ps[0], ps[1], self.prev_truth_size), prev, 0, 0.0, self.prev_truth_index)
-            if corners is not None:
-                prev = ops.piecewise_affine(prev, corners, 0, self.torch.empty_like(prev))
-            if elastic is not None:
-                prev = ops.elastic_warp(prev, elastic[0], elastic[1], 0, self.torch.empty_like(prev))
-            x_slot[..., ps[2]:] = prev
 
 
 def device_data_generator(data_file, index_list, batch_size=1, n_labels=1, labels=None, augment=None, patch_shape=None,
@@ -484,8 +397,8 @@ def device_data_generator(data_file, index_list, batch_size=1, n_labels=1, label
     distance_masks (None | True | spacing per axis): for a data file without masks, make the distance masks of the mask-weighted loss on
     the device when the volumes are uploaded (DeviceDataFile) and yield ([x, masks], y); a DeviceDataFile handed in was built with its own.
 
-    batched: launch the patches of a batch together, one launch per step of the sampling / augmentation chain (the default; configurations
-    the batch kernels do not cover go patch by patch on their own); False: always patch by patch - same draws, same batches.
+    batched: launch the patches of a batch together, one launch per step of the sampling / augmentation chain (the default; a step without a
+    batch kernel runs for the patches that drew it); False: the same chain patch by patch, each a batch of one - same draws, same batches.
 
     prefetch (0 | n): n > 0 starts a producer thread with a HIP stream of its own that keeps up to n batches ready (the role of Keras'
     GeneratorEnqueuer behind the reference's fit_generator, training.py:110-124).  A batch is 11-13 short gather / element-wise launches

@@ -138,19 +138,15 @@ SIGNATURES = {
     "fmri_conv2d_upcat_wgrad": [p, i32, p, i32, p, p, p, p, i32, i32, i32, i32, i32, p, i64, p],
     "fmri_sigmoid_dice_fwd_weighted": [p, p, p, p, p, i64, p],
     "fmri_sigmoid_loss_bwd_weighted": [p, p, p, p, p, i64, i32, f32, f32, f32, p],
-    "fmri_affine_sample": [p, i32, i32, i32, i32, p, i32, i32, i32, i32, i32, i32, i32, f32, p, i32, i32, p],
     "fmri_minmax": [p, i64, i32, p, p],
     "fmri_rescale_intensity": [p, i64, i32, p, i32, f32, f32, f32, p],
     "fmri_noise_augment": [p, i64, i32, p, p, i32, f32, p],
     "fmri_shot_noise_step": [p, i64, i32, p, p, p, p, i32, p],
     "fmri_correlate1d_f32": [p, p, i32, i32, i32, i32, p, i32, i32, p],
-    "fmri_elastic_warp": [p, i32, i32, i32, i32, i32, p, p, i32, p, i32, p],
     "fmri_coarse_dropout": [p, i32, i32, i32, i32, i32, p, i32, i32, i32, p, p],
-    "fmri_affine_sample_batch": [i32, p, p, p, p, p, i32, i32, i32, i32, i32, p, i32, i32, i64, p],
     "fmri_minmax_ws_batch": [p, i64, i64, i32, i32, p, p, p],
     "fmri_rescale_intensity_ws_batch": [p, i64, i64, i32, i32, p, p, p, p],
-    "fmri_affine_sample_slices": [p, i32, i32, i32, i32, p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, p, i32, i32, p],
-    "fmri_affine_sample_slices_batch": [i32, p, p, p, p, i32, i32, p, p, i32, i32, i32, i32, i32, p, i32, i32, i64, p],
+    "fmri_affine_sample_batch": [i32, p, p, p, p, i32, i32, p, p, i32, i32, i32, i32, i32, p, i32, i32, i64, p],
     "fmri_mri_intensity_ws_batch": [p, i32, i32, i32, i64, i32, i32, p, p, p, p, p],
     "fmri_noise_rng_batch": [p, i64, i64, i32, i32, p, p, i32, f32, u64, p, p],
     "fmri_shot_noise_rng_batch": [p, i64, i64, i32, i32, p, p, u64, p, p],

@@ -727,23 +727,6 @@ def _dt_any(t):
     return U8 if t.dtype == torch.uint8 else dt(t)
 
 
-def affine_sample(vol, affine, start, size, out, order=1, cval=0.0, out_ld=None):
-    """out[(i*ny + j)*out_ld + k] = vol sampled at affine . (start + (i,j,k), 1); `affine` is a host 3x4 / 4x4 array-like.
-    `out` may be a view into a wider channels-last tensor (pass its row length as out_ld)."""
-    import ctypes
-    import numpy as np
-    if not vol.is_cuda or not out.is_cuda or not vol.is_contiguous():
-        raise RuntimeError("fmri_hip ops need device tensors (no CPU path)")
-    X, Y, Z = vol.shape
-    a = np.ascontiguousarray(np.asarray(affine, dtype=np.float64)[:3, :4]).reshape(12)
-    arr = (ctypes.c_double * 12)(*a.tolist())
-    nx, ny, nz = (int(v) for v in size)
-    check(lib().fmri_affine_sample(_p(vol), _dt_any(vol), X, Y, Z, ctypes.cast(arr, ctypes.c_void_p), int(start[0]), int(start[1]), int(start[2]),
-                                   nx, ny, nz, int(order), float(cval), _p(out), _dt_any(out), int(out_ld if out_ld is not None else nz), _s()),
-          "fmri_affine_sample")
-    return out
-
-
 def minmax(x, out2):
     _need_cuda(x, out2)
     check(lib().fmri_minmax(_p(x), x.numel(), dt(x), _p(out2), _s()), "fmri_minmax")
@@ -1666,22 +1649,6 @@ def elastic_fields(shape2d, alpha, sigma, generator=None, noise=None):
     return f[1].contiguous(), f[0].contiguous()
 
 
-def elastic_warp(src, d0, d1, order, out):
-    """out[i, j, c] = src[:, :, c] at (i - d0[i, j], j - d1[i, j]), order 0 / 1, mode 'nearest' (fmri_elastic_warp); src, out: (X, Y, C) float32 or
-    uint8 device tensors whose last axis may be a view into a wider row (stride(1) = row length)."""
-    _need_cuda(d0, d1)
-    if not src.is_cuda or not out.is_cuda:
-        raise RuntimeError("fmri_hip ops need device tensors (no CPU path)")
-    X, Y, C = src.shape
-    assert tuple(out.shape) == (X, Y, C) and out.dtype == src.dtype and tuple(d0.shape) == (X, Y) == tuple(d1.shape)
-    assert d0.dtype == torch.float32 and d1.dtype == torch.float32
-    for t in (src, out):
-        assert t.stride(2) == 1 and t.stride(0) == Y * t.stride(1), "rows of equal length, channels contiguous"
-    check(lib().fmri_elastic_warp(_p(src), _dt_any(src), X, Y, C, int(src.stride(1)), _p(d0), _p(d1), int(order), _p(out), int(out.stride(1)), _s()),
-          "fmri_elastic_warp")
-    return out
-
-
 def piecewise_affine_matrices(shape2d, dest_yx):
     """the two triangle maps of imgaug PiecewiseAffine(nb_rows=2, nb_cols=2): corners (0,0), (0,w), (h,0), (h,w) (y, x) moved to dest_yx (4, 2);
     triangle 0 = {p0, p2, p3}: in = d0 + (y/h)(d2 - d0) + (x/w)(d3 - d2); triangle 1 = {p0, p1, p3}: in = d0 + (x/w)(d1 - d0) + (y/h)(d3 - d1).
@@ -1803,9 +1770,13 @@ def coarse_dropout_rng_batch(xb, grids, rate, stats, per_channel, seed, seqs):
     return xb
 
 
-def affine_sample_batch(vols, affines, corners, size, out, order, cvals, out_ld=None):
-    """out[b] (dense (nx, ny, nz) patches, equally spaced) = vols[b] sampled at affines[b] . (corners[b] + (i, j, k), 1): fmri_affine_sample for the
-    patches of a batch in one launch.  vols: device tensors of one dtype (float32 or uint8), each (X, Y, Z) contiguous; affines (B, 4, 4) or (B, 3, 4).
+def affine_sample_batch(vols, affines, corners, size, out, order, cvals, table=None, z_off=0, out_ld=None):
+    """out[b] (dense (nx, ny, nz) patches, equally spaced) = vols[b] sampled at affines[b] . (corners[b] + (i, j, k), 1), order 0 (nearest) / 1
+    (trilinear), cvals[b] outside the volume: the patches of a batch in one launch (fmri_affine_sample_batch).  vols: device tensors of one dtype
+    (float32 or uint8), each (X, Y, Z) contiguous; affines (B, 4, 4) or (B, 3, 4), host.
+    table: inter-slice motion - output slice k of patch b is displaced in-plane by row k + z_off of table[b] (device float64 (B, nz_table, 6):
+    (i', j') = (m0 i + m1 j + m2, m3 i + m4 j + m5) in patch coordinates; a row outside the table is the identity) before the affine; z_off: where
+    the first output slice sits among the image slices the table was drawn for.  None: the plain gather.
     out_ld: row length of out when its last axis is a view into wider rows (the previous-slice truth channels behind the image slices)"""
     import ctypes
     import numpy as np
@@ -1821,71 +1792,18 @@ def affine_sample_batch(vols, affines, corners, size, out, order, cvals, out_ld=
     for v in vols:
         if not v.is_cuda or not v.is_contiguous() or v.dtype != vols[0].dtype or v.dim() != 3:
             raise RuntimeError("fmri_hip ops need contiguous device volumes of one dtype")
-    ptrs = (ctypes.c_void_p * B)(*[v.data_ptr() for v in vols])
-    dims = np.ascontiguousarray([v.shape for v in vols], dtype=np.int32)
-    A = np.ascontiguousarray(np.asarray(affines, dtype=np.float64)[:, :3, :4])
-    cr = np.ascontiguousarray(corners, dtype=np.int32)
-    cv = np.ascontiguousarray(cvals, dtype=np.float32)
-    assert A.shape == (B, 3, 4) and cr.shape == (B, 3) and cv.shape == (B,)
-    check(lib().fmri_affine_sample_batch(B, ctypes.cast(ptrs, ctypes.c_void_p), dims.ctypes.data, A.ctypes.data, cr.ctypes.data, cv.ctypes.data,
-                                         _dt_any(vols[0]), nx, ny, nz, int(order), _p(out), _dt_any(out), out_ld, int(out.stride(0)), _s()),
-          "fmri_affine_sample_batch")
-    return out
-
-
-def _slice_table(table, B):
-    """device fp64 (B, nz_table, 6) -> nz_table"""
-    if not (table.is_cuda and table.dtype == torch.float64 and table.is_contiguous() and table.dim() == 3 and table.shape[0] == B
-            and table.shape[1] >= 1 and table.shape[2] == 6):
+    if table is not None and not (table.is_cuda and table.dtype == torch.float64 and table.is_contiguous() and table.dim() == 3
+                                  and table.shape[0] == B and table.shape[1] >= 1 and table.shape[2] == 6):
         raise RuntimeError("slice table: a contiguous device float64 tensor (patches, rows, 6)")
-    return int(table.shape[1])
-
-
-def affine_sample_slices_batch(vols, affines, corners, size, out, order, cvals, table, z_off=0, out_ld=None):
-    """affine_sample_batch with inter-slice motion: output slice k of patch b is displaced in-plane by row k + z_off of table[b] (device float64
-    (B, nz_table, 6): (i', j') = (m0 i + m1 j + m2, m3 i + m4 j + m5) in patch coordinates; a row outside the table is the identity) before the
-    affine - fmri_affine_sample_slices_batch.  z_off: where the first output slice sits among the image slices the table was drawn for."""
-    import ctypes
-    import numpy as np
-    B = len(vols)
-    nx, ny, nz = (int(v) for v in size)
-    if out_ld is None:
-        assert out.is_cuda and tuple(out.shape) == (B, nx, ny, nz) and out[0].is_contiguous()
-        out_ld = nz
-    else:
-        out_ld = int(out_ld)
-        assert out.is_cuda and tuple(out.shape) == (B, nx, ny, nz) and out_ld >= nz
-        assert out.stride(3) == 1 and out.stride(2) == out_ld and out.stride(1) == ny * out_ld, "rows of out_ld elements, channels contiguous"
-    for v in vols:
-        if not v.is_cuda or not v.is_contiguous() or v.dtype != vols[0].dtype or v.dim() != 3:
-            raise RuntimeError("fmri_hip ops need contiguous device volumes of one dtype")
-    nzt = _slice_table(table, B)
     ptrs = (ctypes.c_void_p * B)(*[v.data_ptr() for v in vols])
     dims = np.ascontiguousarray([v.shape for v in vols], dtype=np.int32)
     A = np.ascontiguousarray(np.asarray(affines, dtype=np.float64)[:, :3, :4])
     cr = np.ascontiguousarray(corners, dtype=np.int32)
     cv = np.ascontiguousarray(cvals, dtype=np.float32)
     assert A.shape == (B, 3, 4) and cr.shape == (B, 3) and cv.shape == (B,)
-    check(lib().fmri_affine_sample_slices_batch(B, ctypes.cast(ptrs, ctypes.c_void_p), dims.ctypes.data, A.ctypes.data, _p(table), nzt, int(z_off),
-                                                cr.ctypes.data, cv.ctypes.data, _dt_any(vols[0]), nx, ny, nz, int(order), _p(out), _dt_any(out), out_ld,
-                                                int(out.stride(0)), _s()), "fmri_affine_sample_slices_batch")
-    return out
-
-
-def affine_sample_slices(vol, affine, start, size, out, table, z_off=0, order=1, cval=0.0, out_ld=None):
-    """affine_sample with inter-slice motion (affine_sample_slices_batch for one patch): table is a device float64 (nz_table, 6)"""
-    import ctypes
-    import numpy as np
-    if not vol.is_cuda or not out.is_cuda or not vol.is_contiguous():
-        raise RuntimeError("fmri_hip ops need device tensors (no CPU path)")
-    nzt = _slice_table(table.unsqueeze(0), 1)
-    X, Y, Z = vol.shape
-    a = np.ascontiguousarray(np.asarray(affine, dtype=np.float64)[:3, :4]).reshape(12)
-    arr = (ctypes.c_double * 12)(*a.tolist())
-    nx, ny, nz = (int(v) for v in size)
-    check(lib().fmri_affine_sample_slices(_p(vol), _dt_any(vol), X, Y, Z, ctypes.cast(arr, ctypes.c_void_p), _p(table), nzt, int(z_off), int(start[0]),
-                                          int(start[1]), int(start[2]), nx, ny, nz, int(order), float(cval), _p(out), _dt_any(out),
-                                          int(out_ld if out_ld is not None else nz), _s()), "fmri_affine_sample_slices")
+    check(lib().fmri_affine_sample_batch(B, ctypes.cast(ptrs, ctypes.c_void_p), dims.ctypes.data, A.ctypes.data, _p(table),
+                                         0 if table is None else int(table.shape[1]), int(z_off), cr.ctypes.data, cv.ctypes.data, _dt_any(vols[0]),
+                                         nx, ny, nz, int(order), _p(out), _dt_any(out), out_ld, int(out.stride(0)), _s()), "fmri_affine_sample_batch")
     return out
 
 
@@ -1942,7 +1860,9 @@ def elastic_fields_rng_batch(shape2d, alphas, sigma, seed, seqs, device="cuda"):
 
 
 def elastic_warp_batch(src, d, order, out):
-    """out[b] = src[b] warped by the fields d[b] (elastic_fields_rng_batch); src, out: (B, X, Y, C) float32 or uint8, patches dense / equally spaced"""
+    """out[b, i, j, c] = src[b, :, :, c] at (i - d[b, 0, i, j], j - d[b, 1, i, j]), order 0 / 1, mode 'nearest' (fmri_elastic_warp_batch); d: the
+    fields of elastic_fields_rng_batch (or elastic_fields' pairs, stacked); src, out: (B, X, Y, C) float32 or uint8, patches equally spaced, the
+    last axis may be a view into a wider row (stride(2) = row length)"""
     _need_cuda(d)
     B, X, Y, C = src.shape
     assert src.is_cuda and out.is_cuda and tuple(out.shape) == (B, X, Y, C) and out.dtype == src.dtype and tuple(d.shape) == (B, 2, X, Y)
@@ -1954,7 +1874,28 @@ def elastic_warp_batch(src, d, order, out):
     return out
 
 
-# one patch = a batch of one (tests; the generator's per-patch path)
+# one patch = a batch of one (tests, the footprint audit)
+def affine_sample(vol, affine, start, size, out, order=1, cval=0.0, out_ld=None):
+    """`out` (nx, ny, nz) may be a view into a wider channels-last tensor (pass its row length as out_ld)"""
+    return affine_sample_slices(vol, affine, start, size, out, None, 0, order, cval, out_ld)
+
+
+def affine_sample_slices(vol, affine, start, size, out, table, z_off=0, order=1, cval=0.0, out_ld=None):
+    """table: a device float64 (nz_table, 6), or None"""
+    ob = out.unsqueeze(0)
+    if out_ld is not None:                # rows of out_ld elements from out's first element on, whatever shape the caller's view has
+        nx, ny, nz = (int(v) for v in size)
+        ob = out.as_strided((1, nx, ny, nz), (nx * ny * out_ld, ny * out_ld, out_ld, 1))
+    affine_sample_batch([vol], [affine], [start], size, ob, order, [cval], None if table is None else table.unsqueeze(0), z_off, out_ld)
+    return out
+
+
+def elastic_warp(src, d0, d1, order, out):
+    """src, out: (X, Y, C) float32 or uint8, the last axis may be a view into a wider row; d0, d1 (X, Y): ops.elastic_fields' pair"""
+    elastic_warp_batch(src.unsqueeze(0), torch.stack([d0, d1]).unsqueeze(0), order, out.unsqueeze(0))
+    return out
+
+
 def minmax_ws(x, stats, ws):
     minmax_ws_batch(x.unsqueeze(0), stats, ws)
     return stats

@@ -30,7 +30,7 @@ extern "C" {
 typedef void* fmri_stream_t; /* hipStream_t */
 
 enum { FMRI_OK = 0, FMRI_E_SHAPE = -1, FMRI_E_ALIGN = -2, FMRI_E_ARCH = -3, FMRI_E_LAUNCH = -4, FMRI_E_DTYPE = -5 };
-enum { FMRI_F32 = 0, FMRI_BF16 = 1, FMRI_U8 = 2 /* label volumes of fmri_affine_sample only */,
+enum { FMRI_F32 = 0, FMRI_BF16 = 1, FMRI_U8 = 2 /* label volumes of fmri_affine_sample_batch only */,
        FMRI_F64 = 3 /* the volumes of fmri_volume_pad_flip only */ };
 enum { FMRI_ACT_NONE = 0, FMRI_ACT_RELU = 1, FMRI_ACT_LEAKY = 2 };
 /* which implementation a conv call may use: AUTO picks MFMA when the shape allows it */
@@ -462,12 +462,7 @@ int fmri_tile_finalize_labels(const double* acc, const int32_t* cnt, uint8_t* ou
 /* ---- device-side patch sampler + intensity augmentation.  Replaces, per training patch, the host chain
  * reference fetal_net/generator.py:246-328 (add_data / extract_patch) -> augment.py:222-377 (augment_data) ->
  * utils/utils.py:100-113 (interpolate_affine_range = scipy.ndimage.map_coordinates, mode='constant').
- * out[(i*ny + j)*out_ld + k] = sample of vol [X][Y][Z] at  affine . (x0+i, y0+j, z0+k, 1)   for i<nx, j<ny, k<nz.
- * affine: 12 doubles, row-major 3x4, HOST memory (read at enqueue).  order 0 = nearest (floor(c+0.5)), 1 = trilinear; a source
- * point outside [0, n-1] on any axis gives cval.  vol_dtype F32|U8, out_dtype F32|BF16 (U8 -> U8|F32|BF16).  out_ld >= nz lets a
- * patch land in a channel slice of a wider [..][C] tensor (2-D models: previous-slice truth appended to the slice stack). */
-int fmri_affine_sample(const void* vol, int vol_dtype, int X, int Y, int Z, const double* affine, int x0, int y0, int z0, int nx, int ny,
-                       int nz, int order, float cval, void* out, int out_dtype, int out_ld, fmri_stream_t stream);
+ * The gather is fmri_affine_sample_batch below; the fed-draw intensity steps follow. */
 /* out2 (device, 2 floats) = {min, max} of x[0..n) — the image range rescale_intensity(out_range='image') and MinMaxScaler need */
 int fmri_minmax(const void* x, int64_t n, int dtype, float* out2, fmri_stream_t stream);
 /* contrast != 0: x = clip(x, lo, hi) rescaled from [lo, hi] to [stats[0], stats[1]] (skimage rescale_intensity, reference
@@ -484,14 +479,6 @@ int fmri_noise_augment(void* x, int64_t n, int dtype, const float* stats, const 
  * draws[t] ~ Poisson(rates[t]) (fp32, device).  stats = fmri_minmax of x before phase 0. */
 int fmri_shot_noise_step(void* x, int64_t n, int dtype, const float* stats, int* present, float* rates, const float* draws, int phase,
                          fmri_stream_t stream);
-/* imgaug ElasticTransformation as the reference applies it (fetal_net/augment.py:149-170; in the DEFAULT config, fetal/config_utils.py:104-107):
- * dst[i][j][c] = src[:, :, c] sampled at (i - d0[i][j], j - d1[i][j]) - one in-plane displacement field for every slice c and for image, truth,
- * previous-slice truth and mask alike; order 1 (image: bilinear) or 0 (labels: nearest, floor(c + 0.5)), mode 'nearest' (coordinates clamped) -
- * the scipy branch of imgaug 0.4.0's `_map_coordinates` (its cv2.remap branch, taken for float images where cv2 is importable, quantises
- * coordinates to 1/32 pixel; parity unpinned, see oracle/augment_oracle.py).
- * src, dst: [X][Y] rows of src_ld / dst_ld elements (>= C), dtype FMRI_F32 or FMRI_U8; d0, d1 fp32 [X][Y].  src != dst. */
-int fmri_elastic_warp(const void* src, int dtype, int X, int Y, int C, int src_ld, const float* d0, const float* d1, int order, void* dst,
-                      int dst_ld, fmri_stream_t stream);
 /* imgaug PiecewiseAffine on the reference's 2 x 2 grid (fetal_net/augment.py:131-146; commented out in the default config): output pixel (i, j) of
  * every slice reads the source at tri_t . (i, j, 1), t = 0 where j * X <= i * Y (the triangle below the diagonal (0,0) - (X,Y) of skimage's Delaunay
  * triangulation of the four corners), else t = 1; tri: 2 x (2 x 3) fp64 on the HOST, rows = (source row, source column).  order 1 / 0, scipy
@@ -515,11 +502,21 @@ int fmri_coarse_dropout(void* x, int dtype, int X, int Y, int C, int ld, const u
  * instead of ~35 per patch with the draws taken from torch's generator (tools/r05/prof_generator.py).  The fed-draw forms above stay: the
  * parity tests hand them the oracle's own draws. */
 #define FMRI_AUG_WS_INTS 1568
-/* fmri_affine_sample for B patches: patch b reads vols[b] (extent dims[3b..], all of vol_dtype) at affines[12b..] . (corners[3b..] + (i, j, k), 1)
- * with outside value cvals[b] and lands at out + b * out_stride elements.  vols: HOST array of device pointers. */
-int fmri_affine_sample_batch(int B, const void* const* vols, const int* dims, const double* affines, const int* corners, const float* cvals,
-                             int vol_dtype, int nx, int ny, int nz, int order, void* out, int out_dtype, int out_ld, int64_t out_stride,
-                             fmri_stream_t stream);
+/* The gather, for the B patches of a batch in one launch (one patch: B = 1).  Patch b lands at out + b * out_stride elements:
+ *   out[(i*ny + j)*out_ld + k] = sample of vols[b] [X][Y][Z] (extent dims[3b..], all of vol_dtype) at affines[12b..] . (x0+i, y0+j, z0+k, 1)
+ * for i<nx, j<ny, k<nz, (x0, y0, z0) = corners[3b..].  affines: 12 doubles per patch, row-major 3x4.  order 0 = nearest (floor(c+0.5)),
+ * 1 = trilinear; a source point outside [0, n-1] on any axis gives cvals[b].  vol_dtype F32|U8, out_dtype F32|BF16 (U8 -> U8|F32|BF16).
+ * out_ld >= nz lets a patch land in a channel slice of a wider [..][C] tensor (2-D models: previous-slice truth appended to the slice
+ * stack).  vols: HOST array of device pointers; dims, affines, corners, cvals: HOST arrays, read at enqueue.
+ * table (DEVICE doubles [B][nz_table][6], or NULL) - inter-slice motion, an acquisition effect of a fetal stack of 2-D slices (not in the
+ * reference; fetal_net/augment.py holds the float64 host form): one in-plane rigid map per OUTPUT SLICE, folded into the gather.  Output
+ * slice k takes row r = k + z_off: (i', j') = (m0 i + m1 j + m2, m3 i + m4 j + m5) in patch coordinates, and the source point is
+ * affine . (corner + (i', j', k), 1); a row index outside [0, nz_table) is the identity.  z_off places a sub-range of slices (labels, mask,
+ * previous-slice truth) under the image slices they belong to.  A table of identity rows {1, 0, 0, 0, 1, 0} gives the table-free output bit
+ * for bit.  NULL: the plain gather (a kernel without the table lines); nz_table and z_off are ignored. */
+int fmri_affine_sample_batch(int B, const void* const* vols, const int* dims, const double* affines, const double* table, int nz_table, int z_off,
+                             const int* corners, const float* cvals, int vol_dtype, int nx, int ny, int nz, int order, void* out, int out_dtype,
+                             int out_ld, int64_t out_stride, fmri_stream_t stream);
 /* stats[b] = {min, max} of patch b: fmri_minmax in ONE launch for all patches (the last workgroup of a patch decodes and re-arms ws[b]) */
 int fmri_minmax_ws_batch(const void* x, int64_t n, int64_t stride, int B, int dtype, float* stats, int* ws, fmri_stream_t stream);
 /* fmri_rescale_intensity (reference augment.py:125-128, :351-352) per patch; params[b] = {mode, lo, hi, mult}: mode 0 skip, 1 multiply by
@@ -527,17 +524,7 @@ int fmri_minmax_ws_batch(const void* x, int64_t n, int64_t stride, int B, int dt
 int fmri_rescale_intensity_ws_batch(void* x, int64_t n, int64_t stride, int B, int dtype, float* stats, int* ws, const float* params,
                                     fmri_stream_t stream);
 /* ---- acquisition effects of a fetal stack of 2-D slices (not in the reference; fetal_net/augment.py holds the float64 host forms).
- * fmri_affine_sample with one in-plane rigid map per OUTPUT SLICE (inter-slice motion), folded into the gather.  table: DEVICE doubles
- * [nz_table][6] ([B][nz_table][6] for the batch).  Output slice k takes row r = k + z_off: (i', j') = (m0 i + m1 j + m2, m3 i + m4 j + m5)
- * in patch coordinates, and the source point is affine . (corner + (i', j', k), 1); a row index outside [0, nz_table) is the identity.
- * z_off places a sub-range of slices (labels, mask, previous-slice truth) under the image slices they belong to.  Everything else as
- * fmri_affine_sample / fmri_affine_sample_batch; a table of identity rows {1, 0, 0, 0, 1, 0} gives their output bit for bit. */
-int fmri_affine_sample_slices(const void* vol, int vol_dtype, int X, int Y, int Z, const double* affine, const double* table, int nz_table, int z_off,
-                              int x0, int y0, int z0, int nx, int ny, int nz, int order, float cval, void* out, int out_dtype, int out_ld,
-                              fmri_stream_t stream);
-int fmri_affine_sample_slices_batch(int B, const void* const* vols, const int* dims, const double* affines, const double* table, int nz_table, int z_off,
-                                    const int* corners, const float* cvals, int vol_dtype, int nx, int ny, int nz, int order, void* out, int out_dtype,
-                                    int out_ld, int64_t out_stride, fmri_stream_t stream);
+ * Inter-slice motion is the `table` of fmri_affine_sample_batch. */
 /* gamma, bias field and slice gain on the dense patches [X][Y][Z] of a batch, one launch.  params: HOST floats [B][FMRI_MRI_PARAMS] =
  * {gamma, vmin, terms, coef[20]}; gains: HOST array of B device pointers (Z floats each), or NULL.  Per voxel, in this order:
  *   gamma (0 = skip)        v = ((v - lo) / (hi - lo)) ^ gamma * (hi - lo) + lo, {lo, hi} = stats[b]; a constant patch is left alone
@@ -563,7 +550,13 @@ int fmri_shot_noise_rng_batch(void* x, int64_t n, int64_t stride, int B, int dty
  * = 2 u - 1 with u = (word (p & 3) of Philox(p >> 2, 0, seqs[b], 1) >> 8) / 2^24. */
 int fmri_elastic_fields_rng_batch(float* d, int X, int Y, int k, const double* weights, const float* alphas, uint64_t seed, const uint32_t* seqs,
                                   int B, fmri_stream_t stream);
-/* fmri_elastic_warp for B patches with the fields of fmri_elastic_fields_rng_batch: patch b = src + b * src_stride -> dst + b * dst_stride */
+/* imgaug ElasticTransformation as the reference applies it (fetal_net/augment.py:149-170; in the DEFAULT config, fetal/config_utils.py:104-107),
+ * for the B patches of a batch with the fields d of fmri_elastic_fields_rng_batch (d0 = d[b][0], d1 = d[b][1]); patch b = src + b * src_stride
+ * -> dst + b * dst_stride:  dst[i][j][c] = src[:, :, c] sampled at (i - d0[i][j], j - d1[i][j]) - one in-plane displacement field for every
+ * slice c and for image, truth, previous-slice truth and mask alike; order 1 (image: bilinear) or 0 (labels: nearest, floor(c + 0.5)), mode
+ * 'nearest' (coordinates clamped) - the scipy branch of imgaug 0.4.0's `_map_coordinates` (its cv2.remap branch, taken for float images where
+ * cv2 is importable, quantises coordinates to 1/32 pixel; parity unpinned, see oracle/augment_oracle.py).
+ * src, dst: [X][Y] rows of src_ld / dst_ld elements (>= C), dtype FMRI_F32 or FMRI_U8.  src != dst. */
 int fmri_elastic_warp_batch(const void* src, int dtype, int X, int Y, int C, int src_ld, int64_t src_stride, const float* d, int order, void* dst,
                             int dst_ld, int64_t dst_stride, int B, fmri_stream_t stream);
 /* fmri_coarse_dropout with the keep grid drawn in the kernel: cell (si, sj[, c]) of patch b's grids[2b] x grids[2b+1] (x kc) grid is dropped

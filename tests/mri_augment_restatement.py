@@ -9,7 +9,7 @@ import scipy.ndimage
 # included (profiles/r12_mri_augment.log: 3.8e-8 ... 8.32e-7, the largest on a generator patch under an order-3 field), and doubled - the
 # project's "2x measured" rule.
 MRI_INTENSITY_TOL = 2 * 8.32e-7
-GATHER_ATOL = 1e-5                      # the bound tests/test_gpu_augment.py holds fmri_affine_sample to
+GATHER_ATOL = 1e-5                      # the bound tests/test_gpu_augment.py holds fmri_affine_sample_batch to
 
 
 def slice_coordinates(affine, corner, size, table, z_off):
@@ -33,7 +33,7 @@ def inside(coords, shape):
 
 def gather_slices(vol, affine, corner, size, table, z_off, order, cval):
     """-> (patch float64, coords): map_coordinates(mode='constant') per output point inside the volume, cval outside (no interpolation beyond
-    the edges: the inside-test of fmri_affine_sample)"""
+    the edges: the inside-test of fmri_affine_sample_batch)"""
     c = slice_coordinates(affine, corner, size, table, z_off)
     ok = inside(c, vol.shape)
     out = np.full(tuple(size), float(cval))

@@ -8,6 +8,8 @@ elementwise intensity passes 1e-5 relative (fp32 arithmetic vs fp64 oracle)."""
 import json
 import os
 import random
+import sys
+import types
 
 import numpy as np
 import pytest
@@ -15,6 +17,9 @@ import scipy.ndimage
 import torch
 
 from oracle import augment_oracle as OA
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import make_generator_chain_fixture as FX      # noqa: E402  (the inputs of the recorded digests, and how a tensor is hashed)
 
 pytestmark = pytest.mark.gpu
 
@@ -728,3 +733,43 @@ def test_elastic_fields_rng_equals_the_host_restatement_of_its_draws(ops, X, Y, 
     assert np.abs(want).max() > 0.02 * alpha
     e0, _ = ops.elastic_fields_rng((X, Y), alpha, sigma, seed, seq + 1)
     assert not torch.equal(e0, d0)
+
+
+# ------------------------------------------------------------------------------------------------ one chain, one gather: the recorded bits
+@pytest.fixture(scope="module")
+def chain_digests(golden_dir):
+    with open(os.path.join(golden_dir, "generator_chain_digests.json")) as f:
+        recorded = json.load(f)
+    assert sorted(recorded) == FX.expected_keys()                      # every case is there; none is skipped below
+    return recorded
+
+
+@pytest.mark.parametrize("name", list(FX.GENERATOR_CASES))
+def test_generator_batches_are_those_of_the_two_chain_generator_bit_for_bit(chain_digests, name):
+    """x, y and mask of two batches per case, patch by patch and launched together, against the digests recorded on the last commit whose
+    generator had a patch-by-patch chain (launch_one) beside the batch chain (tests/golden/make_generator_chain_fixture.py lists what each
+    case reaches: plain crops, the reference's default augmentation, two 16-patch chunks, previous-slice truth, piecewise affine, a mixed
+    Gaussian-filter batch, host elastic fields in call order, the fetal keys, drop_easy_patches).  No tolerance: the same bytes."""
+    for batched in (False, True):
+        got = FX.generator_outputs(name, batched)
+        bad = [k for k, t in got.items() if FX.digest(t) != chain_digests["generator/%s/batched=%d/%s" % (name, batched, k)]]
+        assert not bad, (name, batched, bad)
+
+
+def test_gather_and_warp_front_ends_give_the_retired_entry_points_bits(ops, chain_digests):
+    """ops.affine_sample / affine_sample_slices (batches of one) and ops.affine_sample_batch with and without table= against the digests of
+    fmri_affine_sample, fmri_affine_sample_slices, fmri_affine_sample_batch and fmri_affine_sample_slices_batch; ops.elastic_warp (a batch of
+    one) against fmri_elastic_warp's - f32 -> f32 trilinear, u8 -> u8 and u8 -> f32 nearest, a channel slice of a wider row, B in {1, 3, 19},
+    identity and moving table rows, z_off 0 and 2"""
+    def single(vol, affine, start, size, out, order, cval, table, z_off, out_ld):
+        if table is None:
+            return ops.affine_sample(vol, affine, start, size, out, order=order, cval=cval, out_ld=out_ld)
+        return ops.affine_sample_slices(vol, affine, start, size, out, table, z_off, order=order, cval=cval, out_ld=out_ld)
+
+    def batch(vols, affines, corners, size, out, order, cvals, table, z_off, out_ld):
+        return ops.affine_sample_batch(vols, affines, corners, size, out, order, cvals, table=table, z_off=z_off, out_ld=out_ld)
+
+    got = dict(FX.gather_outputs(types.SimpleNamespace(single=single, batch=batch)), **FX.warp_outputs(ops.elastic_warp))
+    assert sorted(got) == [k for k in FX.expected_keys() if not k.startswith("generator/")]
+    bad = [k for k, t in got.items() if FX.digest(t) != chain_digests[k]]
+    assert not bad, bad

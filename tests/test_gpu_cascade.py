@@ -280,13 +280,21 @@ def test_prev_truth_generator_batched_equals_patch_by_patch(monkeypatch, prev):
     vols, truths = _synth(9, [(56, 60, 24), (50, 64, 30)])
     mk = [np.random.RandomState(5).rand(*t.shape).astype(np.float32) for t in truths]
     df = _DataFile(vols, truths, mk)
+    from fmri_hip import ops
     outs = []
     for batched in (False, True):
         with monkeypatch.context() as mp:
-            if batched:
-                def no_single(*a, **k):
-                    raise AssertionError("a prev-truth batch went patch by patch")
-                mp.setattr(DG._Sampler, "launch_one", no_single)
+            # a prev-truth batch is launched together: the gather is entered 4 times per launch() call - image, labels, mask, previous truth -
+            # whatever the number of plans
+            calls = {"launch": 0, "gather": 0}
+
+            def counted(name, inner):
+                def f(*a, **k):
+                    calls[name] += 1
+                    return inner(*a, **k)
+                return f
+            mp.setattr(DG._Sampler, "launch", counted("launch", DG._Sampler.launch))
+            mp.setattr(ops, "affine_sample_batch", counted("gather", ops.affine_sample_batch))
             np.random.seed(21)
             random.seed(21)
             gen = DG.device_data_generator(df, [0, 1], batch_size=7, augment=aug, patch_shape=(32, 32, 5), skip_blank=True, categorical=False,
@@ -297,6 +305,7 @@ def test_prev_truth_generator_batched_equals_patch_by_patch(monkeypatch, prev):
                 (x, m), y = next(gen)
                 b += [x.cpu().numpy(), m.cpu().numpy(), y.cpu().numpy()]
             gen.close()
+        assert calls["launch"] >= 3 and (not batched or calls["gather"] == 4 * calls["launch"]), calls
         outs.append(b)
     for a, b in zip(*outs):
         assert a.shape == b.shape and np.array_equal(a, b)

@@ -1,4 +1,4 @@
-"""The fetal acquisition augmenters on the device: the gather with a per-slice motion table (fmri_affine_sample_slices[_batch]) and the gamma / bias
+"""The fetal acquisition augmenters on the device: the gather with a per-slice motion table (fmri_affine_sample_batch, table=) and the gamma / bias
 field / slice gain launch (fmri_mri_intensity_ws_batch) against the float64 restatement of tests/mri_augment_restatement.py, and the device
 generator with the four new `augment` keys."""
 import random
@@ -93,7 +93,7 @@ def test_gather_batch_shapes(ops, volumes, B, size, nzt, z_off, wide):
     for src, host, order, dtype, cvals in ((dv, (vol, vol2), 1, torch.float32, cv), (dl, (lab, lab2), 0, torch.uint8, [0.0] * B)):
         buf = torch.full((B,) + size[:2] + (ld,), 77, device="cuda", dtype=dtype)
         out = buf[..., 2:2 + size[2]] if wide else buf
-        ops.affine_sample_slices_batch([src[p] for p in pick], affines, corners, size, out, order, cvals, dtab, z_off, out_ld=ld if wide else None)
+        ops.affine_sample_batch([src[p] for p in pick], affines, corners, size, out, order, cvals, table=dtab, z_off=z_off, out_ld=ld if wide else None)
         got = out.cpu().numpy()
         margin = np.inf
         for b in range(B):
@@ -124,7 +124,7 @@ def test_identity_table_is_the_plain_gather_bit_for_bit(ops, volumes, order, dty
     cv = [float(vol.min()) if order else 0.0] * B
     ident = torch.from_numpy(np.tile(np.array(IDENTITY), (B, 4, 1))).cuda()
     a = ops.affine_sample_batch(src, affines, corners, size, torch.empty((B,) + size, device="cuda", dtype=dtype), order, cv)
-    b = ops.affine_sample_slices_batch(src, affines, corners, size, torch.empty((B,) + size, device="cuda", dtype=dtype), order, cv, ident, 0)
+    b = ops.affine_sample_batch(src, affines, corners, size, torch.empty((B,) + size, device="cuda", dtype=dtype), order, cv, table=ident)
     assert torch.equal(a, b)
 
 
@@ -141,7 +141,7 @@ def test_identity_table_is_the_plain_gather_bit_for_bit_on_a_million_voxels(ops,
     ident = torch.from_numpy(np.tile(np.array(IDENTITY), (B, size[2], 1))).cuda()
     cv = [-4.0 if order else 0.0] * B
     a = ops.affine_sample_batch([vol] * B, affines, corners, size, torch.empty((B,) + size, device="cuda", dtype=dtype), order, cv)
-    b = ops.affine_sample_slices_batch([vol] * B, affines, corners, size, torch.empty((B,) + size, device="cuda", dtype=dtype), order, cv, ident, 0)
+    b = ops.affine_sample_batch([vol] * B, affines, corners, size, torch.empty((B,) + size, device="cuda", dtype=dtype), order, cv, table=ident)
     assert torch.equal(a, b) and float((a != cv[0]).float().mean()) > 0.5
 
 

@@ -4,7 +4,7 @@
 1. chain: device ms per batch of the device generator's sampling chain (HIP events around `--batches` batches enqueued behind a blocker) with the
    reference's default augmentation, without and with the four keys at prob 1 (and with slice_motion alone, gamma + bias_field alone); the arms alternate round by round in
    one process on the same global draws, medians with min - max; and the launches per batch of either arm, counted from the calls into the library.
-2. gather: fmri_affine_sample_slices_batch with an identity table against fmri_affine_sample_batch on the same patches, image (trilinear) and
+2. gather: fmri_affine_sample_batch with an identity table against the same call without a table on the same patches, image (trilinear) and
    labels (nearest), alternated, us per launch with the bytes the gather has to move; and fmri_mri_intensity_ws_batch beside
    fmri_rescale_intensity_ws_batch on the same batch.
 Prints one JSON line."""
@@ -120,9 +120,9 @@ def main():
     vox = B * patch[0] * patch[1] * patch[2]
     gather = {
         "image_plain": lambda: ops.affine_sample_batch([ddf.data[i] for i in idx], affines, corners, patch, xo, 1, [ddf.min[i] for i in idx]),
-        "image_identity_table": lambda: ops.affine_sample_slices_batch([ddf.data[i] for i in idx], affines, corners, patch, xo, 1, [ddf.min[i] for i in idx], ident),
+        "image_identity_table": lambda: ops.affine_sample_batch([ddf.data[i] for i in idx], affines, corners, patch, xo, 1, [ddf.min[i] for i in idx], table=ident),
         "labels_plain": lambda: ops.affine_sample_batch([ddf.truth[i] for i in idx], affines, corners, patch, yo, 0, [0.0] * B),
-        "labels_identity_table": lambda: ops.affine_sample_slices_batch([ddf.truth[i] for i in idx], affines, corners, patch, yo, 0, [0.0] * B, ident),
+        "labels_identity_table": lambda: ops.affine_sample_batch([ddf.truth[i] for i in idx], affines, corners, patch, yo, 0, [0.0] * B, table=ident),
     }
     ref = gather["image_plain"]().clone()
     out["identity_table_equal"] = bool(torch.equal(gather["image_identity_table"](), ref))
