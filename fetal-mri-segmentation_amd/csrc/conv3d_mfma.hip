@@ -79,7 +79,12 @@ k_conv_fwd_mfma(SrcB s, const bf16_t* __restrict__ wt, const float* __restrict__
     constexpr int NTHREADS = fw::NTHREADS;
     constexpr int TD = CUBE ? 8 : fw::TD, TH = CUBE ? 8 : fw::TH, TW = CUBE ? 8 : fw::TW;
     constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2, HVOX = HD * HH * HW;
-    constexpr int H_INSTR = (HVOX * 4 + 63) / 64, HALO_BYTES = H_INSTR * 1024;
+    // a halo slot also stages the finished tile (8 waves x 64 voxels x BN channels of bf16: 64 KiB at BN = 64).  The 10^3 box of the CUBE tiling
+    // is 63 KiB: with 64-wide blocks the last wave's stage ran 1 KiB past its slot, into the other halo slot or the filter ring - by then
+    // the next item's rows or its first filter slab (wrong results on every second item of a workgroup, i.e. with more pairs than CUs)
+    constexpr int H_INSTR = (HVOX * 4 + 63) / 64, STAGE_BYTES = 8 * 64 * 32 * NT * 2;
+    constexpr int HALO_BYTES = H_INSTR * 1024 > STAGE_BYTES ? H_INSTR * 1024 : STAGE_BYTES;
+    static_assert(STAGE_BYTES <= HALO_BYTES && 2 * HALO_BYTES + 2 * 3 * 32 * NT * 64 <= 160 * 1024, "epilogue staging must fit the consumed halo slot");
     static_assert(!(RES && MODE != 0) && !(CUBE && (PL || MODE != 0 || RES)), "unsupported combination");
     (void)NTHREADS;
     constexpr bool PAR = MODE != 0;
