@@ -868,6 +868,176 @@ extern "C" int fmri_label_sums(const float* probs, const uint8_t* y_true, int64_
     return FMRI_OK;
 }
 
+// ---- overlap losses from per-label sums: Tversky, focal Tversky, Generalised Dice, boundary term (not in the reference's loss table:
+// Salehi et al. 2017, Abraham & Khan 2019, Sudre et al. 2017, Kervadec et al. 2019; sign convention of the reference, loss = -coefficient).
+// With I_l = sum y p, Sy_l = sum y, Sp_l = sum p of label l (fmri_label_sums) and s = smooth:
+//   T(I, Sy, Sp) = (I + s) / (I + alpha (Sp - I) + beta (Sy - I) + s)          alpha weighs false positives, beta false negatives
+//   kind 0  Tversky              L = -T of the sums of all labels together (as dice_coefficient flattens); default s = 1
+//   kind 1  focal Tversky        L = (1 - T)^(1/gamma), the same T
+//   kind 2  label-mean Tversky   L = -(1/L) sum_l T_l, T_l of label l's own sums (alpha = beta = s = 1/2: label_wise_dice_coefficient)
+//   kind 3  label-mean focal     L = (1/L) sum_l (1 - T_l)^(1/gamma)
+//   kind 4  Generalised Dice     L = 1 - (2 sum_l w_l I_l + s) / (sum_l w_l (Sy_l + Sp_l) + s), w_l = 1 / Sy_l^2, s = 1e-5; a label absent
+//           from the batch (Sy_l = 0) takes the largest weight among the labels present, all weights are 1 when none is present; the
+//           weights are constants with respect to p
+//   boundary term (single label, any kind): + boundary_weight * Bd / n, Bd = sum_v phi_v p_v, phi = (1 - 2 y) * dist (the distance mask
+//           holds each voxel's distance to the nearest voxel of the other class: phi is negative inside, positive outside), n = sums[7]
+// The focal kinds have a pole of the gradient at T = 1 (gamma > 1): the derivative -(1/gamma) u^(1/gamma - 1) is taken at
+// u = max(1 - T, 1e-7); the value is max(1 - T, 0)^(1/gamma), unclamped.
+// Since dI_l/dp = y and dSp_l/dp = 1, every one of them has the gradient
+//   dL/dlogit[v][l] = grad_scale * (A_l y[v][l] + B_l + boundary_scale * phi_v) * p (1 - p),  A_l = dL/dI_l, B_l = dL/dSp_l.
+// k_overlap_coeffs (ONE wave, lane l = label l, wave sums in a fixed order, all float64) writes coef = {A_0, B_0, ... A_{L-1}, B_{L-1},
+// value, value without the boundary term}; k_overlap_loss_bwd is the streaming pass.
+__device__ __forceinline__ double wave_all_sum(double v) { return __shfl(wave_sum(v), 0); }
+__device__ __forceinline__ double wave_all_max(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o));
+    return __shfl(v, 0);
+}
+__global__ void __launch_bounds__(64) k_overlap_coeffs(const double* __restrict__ lsums, const double* __restrict__ sums,
+                                                       const double* __restrict__ bd, double* __restrict__ coef, int L, int kind, double alpha,
+                                                       double beta, double gamma, double s, double bweight) {
+    const int l = threadIdx.x;
+    const bool on = l < L;
+    double I = on ? lsums[3 * l] : 0.0, Sy = on ? lsums[3 * l + 1] : 0.0, Sp = on ? lsums[3 * l + 2] : 0.0;
+    double A = 0.0, B = 0.0, value = 0.0;
+    if (kind <= 3) {
+        const bool per_label = kind >= 2, focal = (kind & 1) != 0;
+        if (!per_label) { I = wave_all_sum(I); Sy = wave_all_sum(Sy); Sp = wave_all_sum(Sp); }
+        const double N = I + s, D = (1.0 - alpha - beta) * I + (beta * Sy + alpha * Sp) + s;       // = I + alpha (Sp - I) + beta (Sy - I) + s
+        const double T = N / D;
+        const double dT_dI = (D - N * (1.0 - alpha - beta)) / (D * D), dT_dSp = -alpha * N / (D * D);
+        double f = -T, df = -1.0;                                         // f(T) and f'(T)
+        if (focal) {
+            const double u = fmax(1.0 - T, 1e-7);
+            f = pow(fmax(1.0 - T, 0.0), 1.0 / gamma);
+            df = -pow(u, 1.0 / gamma - 1.0) / gamma;
+        }
+        const double share = per_label ? 1.0 / (double)L : 1.0;
+        A = share * df * dT_dI;
+        B = share * df * dT_dSp;
+        value = per_label ? wave_all_sum(on ? share * f : 0.0) : f;
+    } else {
+        const bool present = on && Sy > 0.0;
+        const double wmax = wave_all_max(present ? 1.0 / (Sy * Sy) : 0.0);        // 0: no label of the batch is present
+        const double w = !on ? 0.0 : wmax == 0.0 ? 1.0 : present ? 1.0 / (Sy * Sy) : wmax;
+        const double num = 2.0 * wave_all_sum(w * I) + s, den = wave_all_sum(w * (Sy + Sp)) + s;
+        A = -2.0 * w / den;
+        B = num * w / (den * den);
+        value = 1.0 - num / den;
+    }
+    if (on) {
+        coef[2 * l] = A;
+        coef[2 * l + 1] = B;
+    }
+    if (l == 0) {
+        coef[2 * L] = value + (bd ? bweight * bd[0] / sums[7] : 0.0);
+        coef[2 * L + 1] = value;
+    }
+}
+// Streaming pass: 4 B + 1 B in (+ 4 B of the distance mask), 4 B out per element.  The grid is a multiple of L workgroups, so the grid
+// stride (in elements, x VEC) is a multiple of L and a thread keeps the labels of its first trip: its VEC coefficient pairs are loaded once,
+// as floats, into named registers (k_label_sums' rule: no per-thread array, no dynamic register indexing).  VEC = 4: 16-byte loads and
+// stores of probs / dist / dlogits, 4-byte loads of y; the launcher checks alignment and n % 4.
+template <int VEC, bool DIST>
+__global__ void __launch_bounds__(256) k_overlap_loss_bwd(const float* __restrict__ probs, const uint8_t* __restrict__ y, const float* __restrict__ dist,
+                                                          const double* __restrict__ coef, float* __restrict__ dl, int64_t n, int L,
+                                                          float bscale, float gs) {
+    const int64_t tid = blockIdx.x * (int64_t)256 + threadIdx.x, step = (int64_t)gridDim.x * 256;          // step % L == 0
+    const int l0 = (int)((tid * VEC) % L);
+    auto one = [&](float p, float t, float d, float a, float b) {
+        float c = a * t + b;
+        if constexpr (DIST) c += bscale * (1.f - 2.f * t) * d;
+        return gs * c * (p * (1.f - p));
+    };
+    if constexpr (VEC == 4) {
+        const int l1 = l0 + 1 < L ? l0 + 1 : 0, l2 = l1 + 1 < L ? l1 + 1 : 0, l3 = l2 + 1 < L ? l2 + 1 : 0;
+        const float a0 = (float)coef[2 * l0], b0 = (float)coef[2 * l0 + 1], a1 = (float)coef[2 * l1], b1 = (float)coef[2 * l1 + 1];
+        const float a2 = (float)coef[2 * l2], b2 = (float)coef[2 * l2 + 1], a3 = (float)coef[2 * l3], b3 = (float)coef[2 * l3 + 1];
+        const int64_t nv = n / 4;
+        for (int64_t i = tid; i < nv; i += step) {
+            const float4 p = reinterpret_cast<const float4*>(probs)[i];
+            const uchar4 t = reinterpret_cast<const uchar4*>(y)[i];
+            float4 d = make_float4(0.f, 0.f, 0.f, 0.f), g;
+            if constexpr (DIST) d = reinterpret_cast<const float4*>(dist)[i];
+            g.x = one(p.x, (float)t.x, d.x, a0, b0);
+            g.y = one(p.y, (float)t.y, d.y, a1, b1);
+            g.z = one(p.z, (float)t.z, d.z, a2, b2);
+            g.w = one(p.w, (float)t.w, d.w, a3, b3);
+            reinterpret_cast<float4*>(dl)[i] = g;
+        }
+    } else {
+        const float a = (float)coef[2 * l0], b = (float)coef[2 * l0 + 1];
+        for (int64_t i = tid; i < n; i += step) dl[i] = one(probs[i], (float)y[i], DIST ? dist[i] : 0.f, a, b);
+    }
+}
+// Bd = sum_v (1 - 2 y_v) dist_v p_v (single label): wave sums, four partials per workgroup in LDS, one atomic per workgroup into bd[0] -
+// float64 by default, a 2^-20 fixed-point integer in the SAME 8-byte slot under a deterministic registration (k_label_sums_finish converts it)
+template <int VEC>
+__global__ void __launch_bounds__(256) k_boundary_sum(const float* __restrict__ probs, const uint8_t* __restrict__ y, const float* __restrict__ dist,
+                                                      int64_t n, double* __restrict__ bd) {
+    double acc = 0;
+    const int64_t tid = blockIdx.x * (int64_t)256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    if constexpr (VEC == 4) {
+        const int64_t nv = n / 4;
+        for (int64_t i = tid; i < nv; i += step) {
+            const float4 p = reinterpret_cast<const float4*>(probs)[i], d = reinterpret_cast<const float4*>(dist)[i];
+            const uchar4 t = reinterpret_cast<const uchar4*>(y)[i];
+            acc += (double)((1.f - 2.f * (float)t.x) * d.x * p.x);
+            acc += (double)((1.f - 2.f * (float)t.y) * d.y * p.y);
+            acc += (double)((1.f - 2.f * (float)t.z) * d.z * p.z);
+            acc += (double)((1.f - 2.f * (float)t.w) * d.w * p.w);
+        }
+    } else {
+        for (int64_t i = tid; i < n; i += step) acc += (double)((1.f - 2.f * (float)y[i]) * dist[i] * probs[i]);
+    }
+    __shared__ double red[4];
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double r = red[0] + red[1] + red[2] + red[3];
+        if (g_det_cfg.base != nullptr)
+            atomicAdd(reinterpret_cast<unsigned long long*>(bd), (unsigned long long)__double2ll_rn(r * 1048576.0));
+        else atomicAdd(bd, r);
+    }
+}
+static inline bool overlap_vec4(int64_t n, const void* a, const void* b, const void* c, const void* y) {
+    return n % 4 == 0 && !((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) && !(((uintptr_t)y) & 3);
+}
+extern "C" int fmri_boundary_sum(const float* probs, const uint8_t* y_true, const float* dist, int64_t nvox, double* bd, fmri_stream_t stream) {
+    if (!probs || !y_true || !dist || !bd || nvox <= 0) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    if (hipMemsetAsync(bd, 0, sizeof(double), s) != hipSuccess) return FMRI_E_LAUNCH;
+    if (overlap_vec4(nvox, probs, dist, nullptr, y_true)) k_boundary_sum<4><<<grid_for(nvox / 4, 256, 512), 256, 0, s>>>(probs, y_true, dist, nvox, bd);
+    else k_boundary_sum<1><<<grid_for(nvox, 256, 512), 256, 0, s>>>(probs, y_true, dist, nvox, bd);
+    if (h_det_on) k_label_sums_finish<<<1, 64, 0, s>>>(bd, 1);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+extern "C" int fmri_overlap_coeffs(const double* lsums, const double* sums, const double* bd, double* coef, int L, int kind, float alpha,
+                                   float beta, float gamma, float smooth, float boundary_weight, fmri_stream_t stream) {
+    if (!lsums || !sums || !coef || L < 1 || L > FMRI_MAX_LABELS || kind < 0 || kind > 4 || !(alpha >= 0.f) || !(beta >= 0.f) || !(gamma >= 1.f) ||
+        (bd && L != 1))
+        return FMRI_E_SHAPE;
+    k_overlap_coeffs<<<1, 64, 0, as_stream(stream)>>>(lsums, sums, bd, coef, L, kind, (double)alpha, (double)beta, (double)gamma, (double)smooth,
+                                                     (double)boundary_weight);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+extern "C" int fmri_overlap_loss_bwd(const float* probs, const uint8_t* y_true, const float* dist, const double* coef, float* dlogits,
+                                     int64_t nvox, int L, float boundary_scale, float grad_scale, fmri_stream_t stream) {
+    if (!probs || !y_true || !coef || !dlogits || nvox <= 0 || L < 1 || L > FMRI_MAX_LABELS || (dist && L != 1)) return FMRI_E_SHAPE;
+    hipStream_t s = as_stream(stream);
+    const int64_t n = nvox * L;
+    const bool v4 = overlap_vec4(n, probs, dlogits, dist, y_true);
+    const int grid = (grid_for(v4 ? n / 4 : n, 256, 2048) + L - 1) / L * L;
+#define OVL_(V_, D_) k_overlap_loss_bwd<V_, D_><<<grid, 256, 0, s>>>(probs, y_true, dist, coef, dlogits, n, L, boundary_scale, grad_scale)
+    if (v4) { if (dist) OVL_(4, true); else OVL_(4, false); }
+    else { if (dist) OVL_(1, true); else OVL_(1, false); }
+#undef OVL_
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ Keras Adam / SGD / RMSprop / AMSGrad, clipping
 // Reference: Adam(lr=initial_learning_rate) at unet3d/unet.py:85; Keras 2.2 update rule (epsilon outside the sqrt).  The other optimizers
 // and the clipping: Keras 2.2.4 keras/optimizers.py as published (restated from the published source: no Keras was at hand to run against, so these

@@ -396,11 +396,11 @@ class _Stager(object):
             xe = m._to_device_x(xd)
             ye = m._to_device_y(yd)
             w = None
-            if getattr(m.loss, "mask_weighted", False):
+            if _takes_mask(m.loss):
                 if masks is None:
                     raise ValueError("this model was built with mask_shape: feed [x, masks] (reference generator.py:397-401)")
                 md = masks if _is_device_tensor(masks) else self._upload(slot, "m", masks, np.float32, torch.float32)
-                w = torch.exp(-md.float() / m.loss.dist_sigma).reshape(-1).contiguous()
+                w = _mask_weight(m.loss, md)
             ready = torch.cuda.Event()
             ready.record(self.copy)
         for t in (xe, ye, w):
@@ -417,6 +417,24 @@ class _Stager(object):
             slot.done = self.torch.cuda.Event()
         slot.done.record(self.torch.cuda.current_stream())
         slot.free.set()
+
+
+def _ops():
+    from fmri_hip import ops
+    return ops
+
+
+def _takes_mask(loss):
+    """the loss consumes the model's second input: dice_and_xent_mask (as exp(-mask / sigma)) or dice_and_boundary (the distances themselves)"""
+    return bool(getattr(loss, "mask_weighted", False) or getattr(loss, "mask_input", False))
+
+
+def _mask_weight(loss, t):
+    """the per-voxel float the loss kernels take, from the device tensor of the distance mask"""
+    import torch
+    if getattr(loss, "mask_input", False):
+        return t.float().reshape(-1).contiguous()
+    return torch.exp(-t.float() / loss.dist_sigma).reshape(-1).contiguous()
 
 
 class _PendingLogs(object):
@@ -525,6 +543,8 @@ class Model(object):
     # -- Keras surface -----------------------------------------------------------------------------------------------
     def compile(self, optimizer=None, loss=None, metrics=None, **kw):
         self.optimizer = optimizer if optimizer is not None else Adam()
+        if loss is M.tversky_loss or loss is M.focal_tversky_loss:
+            loss = loss()                # the factory itself, as a config's `getattr(fetal_net.metrics, name)` gives it: its defaults
         self.loss = loss
         self.metrics = list(metrics or [])
 
@@ -608,6 +628,7 @@ class Model(object):
         if self.loss is not None:
             try:
                 self._engine.loss_kind, self._engine.loss_param = self._loss_kind()
+                self._engine.loss_overlap = self._loss_overlap()
             except NotImplementedError:
                 pass                    # predict-only use of a model compiled with an unsupported loss
         return self._engine
@@ -668,10 +689,19 @@ class Model(object):
                  M.vod_coefficient_loss: (4, 1.0), M.double_dice_loss: (5, 10.0), M.weighted_dice_coefficient_loss: (6, 1.0)}
         if getattr(self.loss, "mask_weighted", False):       # dice_and_xent_mask(mask_input): Dice + w * mean(exp(-mask/sigma) * xent)
             return (2, self.loss.xent_weight)
+        if getattr(self.loss, "overlap_kind", None) is not None:
+            # fmri_overlap_coeffs / fmri_overlap_loss_bwd: (ops.LOSS_OVERLAP + kind, smooth); alpha, beta, gamma, boundary_weight: _loss_overlap
+            return (_ops().LOSS_OVERLAP + int(self.loss.overlap_kind), float(self.loss.smooth))
         if self.loss not in table:
             raise NotImplementedError("loss %r is not differentiated on the device (available: %s)" % (
-                getattr(self.loss, "__name__", self.loss), ", ".join(sorted(f.__name__ for f in table))))
+                getattr(self.loss, "__name__", self.loss), ", ".join(sorted([f.__name__ for f in table] + [f.__name__ for f in M.OVERLAP_LOSSES]))))
         return table[self.loss]
+
+    def _loss_overlap(self):
+        """(alpha, beta, gamma, boundary_weight) of a compiled overlap loss (metrics.tversky_loss(...) and its kin; the engine's default else)"""
+        f = self.loss
+        return (float(getattr(f, "alpha", 0.5)), float(getattr(f, "beta", 0.5)), float(getattr(f, "gamma", 1.0)),
+                float(getattr(f, "boundary_weight", 0.0)))
 
     def _check_loss(self):
         self._loss_kind()
@@ -694,18 +724,19 @@ class Model(object):
         return out
 
     def _loss_weight(self, x):
-        """per-voxel cross-entropy weight exp(-mask / sigma) from the model's second input (reference metrics.py:89-95), or None"""
-        if not getattr(self.loss, "mask_weighted", False):
+        """per-voxel cross-entropy weight exp(-mask / sigma) from the model's second input (reference metrics.py:89-95), the distance
+        mask itself for dice_and_boundary, or None"""
+        if not _takes_mask(self.loss):
             return None
         import torch
         if not isinstance(x, (list, tuple)) or len(x) < 2:
             raise ValueError("this model was built with mask_shape: feed [x, masks] (reference generator.py:397-401)")
         m = x[1]
         t = m if _is_device_tensor(m) else torch.from_numpy(np.ascontiguousarray(np.asarray(m), dtype=np.float32)).cuda(non_blocking=True)
-        return torch.exp(-t.float() / self.loss.dist_sigma).reshape(-1).contiguous()
+        return _mask_weight(self.loss, t)
 
     # -- steps: enqueue now, read the metric sums later --------------------------------------------------------------------------
-    LOG_RING = 8          # pinned fp64 buffers (16 metric sums + room for 3 * 32 label-wise sums) for the metric sums in flight (the training thread runs at most this many steps ahead)
+    LOG_RING = 8          # pinned fp64 buffers (16 metric sums + room for 3 * 32 label-wise sums and the overlap losses' slots: ops.SUMS_TOTAL) for the metric sums in flight (the training thread runs at most this many steps ahead)
 
     def _stage_inline(self, x, y):
         """(x, y) of a direct train_on_batch / test_on_batch call -> _Staged on the calling thread's stream"""
@@ -728,14 +759,14 @@ class Model(object):
             sums = eng.loss_forward(staged.y, staged.weight)
         ring = self.__dict__.get("_log_ring")
         if ring is None:
-            ring = self.__dict__["_log_ring"] = dict(k=0, slots=[[torch.empty(16 + 96, dtype=torch.float64).pin_memory(), torch.cuda.Event(), None]
+            ring = self.__dict__["_log_ring"] = dict(k=0, slots=[[torch.empty(_ops().SUMS_TOTAL, dtype=torch.float64).pin_memory(), torch.cuda.Event(), None]
                                                                  for _ in range(self.LOG_RING)])
         slot = ring["slots"][ring["k"] % self.LOG_RING]
         ring["k"] += 1
         if slot[2] is not None:
             slot[2].values()                                         # the buffer's previous owner reads it before it is overwritten
-        if getattr(eng, "label_metrics", 0):
-            sums = eng.log_sums()                                    # the label-wise sums ride behind the 16, in the same copy
+        if getattr(eng, "label_metrics", 0) or _ops().is_overlap_loss(eng.loss_kind):
+            sums = eng.log_sums()                                    # the label-wise sums (and an overlap loss's value) ride behind the 16, in the same copy
         buf = slot[0][:sums.numel()]
         buf.copy_(sums, non_blocking=True)
         slot[1].record(torch.cuda.current_stream())
@@ -967,7 +998,10 @@ class Model(object):
         self.save(path, include_optimizer=False, weights_only=True)
 
     def _checkpoint_meta(self):
-        meta = dict(format="fmri-npz-1", builder=self._builder, builder_kwargs=_jsonable(self._builder_kwargs),
+        kwargs = dict(self._builder_kwargs or {})
+        if getattr(self.loss, "loss_params", None) and "loss_function" in kwargs and not _takes_mask(self.loss):
+            kwargs["loss_function"] = self.loss                       # a factory's loss compiled after the build: recorded with its arguments
+        meta = dict(format="fmri-npz-1", builder=self._builder, builder_kwargs=_jsonable(kwargs),
                     optimizer=self.optimizer.get_config() if self.optimizer else None,
                     loss=getattr(self.loss, "__name__", None),
                     metrics=[m if isinstance(m, str) else getattr(m, "__name__", str(m)) for m in self.metrics])
@@ -1072,6 +1106,8 @@ def _jsonable(d):
     for k, v in (d or {}).items():
         if callable(v):
             out[k] = {"__callable__": getattr(v, "__name__", str(v))}
+            if getattr(v, "loss_params", None):
+                out[k]["params"] = dict(v.loss_params)         # a loss made by a factory (metrics.tversky_loss(...)): the factory's arguments
         elif isinstance(v, (np.integer,)):
             out[k] = int(v)
         elif isinstance(v, (np.floating,)):

@@ -70,7 +70,7 @@ def isensee2017_model_3d(input_shape=(1, 128, 128, 128), n_base_filters=16, dept
         from ...metrics import MaskInput
         loss_function = loss_function(MaskInput())
         model._mask_shape = tuple(int(v) for v in mask_shape)
-        if not getattr(loss_function, "mask_weighted", False):
+        if not (getattr(loss_function, "mask_weighted", False) or getattr(loss_function, "mask_input", False)):
             unsupported.append("mask_shape with a loss factory other than dice_and_xent_mask")
     if activation_name not in ("sigmoid", None, "linear"):
         unsupported.append("activation_name %r (only 'sigmoid', or None / 'linear': the output is then the logits)" % (activation_name,))

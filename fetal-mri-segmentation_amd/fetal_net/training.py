@@ -42,6 +42,8 @@ def _builder_call(name, kwargs):
     resolved = {}
     for k, v in kwargs.items():
         resolved[k] = getattr(fetal_net.metrics, v["__callable__"]) if (isinstance(v, dict) and "__callable__" in v) else v
+        if isinstance(v, dict) and v.get("params"):
+            resolved[k] = resolved[k](**v["params"])          # a factory's loss (tversky_loss, focal_tversky_loss) with its recorded arguments
     return getattr(fetal_net.model, name)(**resolved)
 
 

@@ -49,6 +49,9 @@ SIGNATURES = {
     "fmri_weighted_dice_fwd": [p, p, p, p, i32, i64, i32, f32, p],
     "fmri_weighted_dice_bwd": [p, p, p, p, p, i32, i64, i32, f32, f32, p],
     "fmri_label_sums": [p, p, i64, i32, p, p],
+    "fmri_boundary_sum": [p, p, p, i64, p, p],
+    "fmri_overlap_coeffs": [p, p, p, p, i32, i32, f32, f32, f32, f32, f32, p],
+    "fmri_overlap_loss_bwd": [p, p, p, p, p, i64, i32, f32, f32, p],
     "fmri_maxpool3d_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_maxpool3d_bwd": [p, p, p, i32, i32, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],
     "fmri_upsample_nearest_fwd": [p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, p],

@@ -44,6 +44,7 @@ class ChainEngine(object):
     # ---- what Model reads and sets on its engine: the loss is the segmenter's, parameters and optimizer state are the norm net's
     loss_kind = property(lambda self: self.seg.loss_kind, lambda self, v: setattr(self.seg, "loss_kind", v))
     loss_param = property(lambda self: self.seg.loss_param, lambda self, v: setattr(self.seg, "loss_param", v))
+    loss_overlap = property(lambda self: self.seg.loss_overlap, lambda self, v: setattr(self.seg, "loss_overlap", v))
     beta1 = property(lambda self: self.norm.beta1, lambda self, v: setattr(self.norm, "beta1", v))
     t = property(lambda self: self.norm.t, lambda self, v: setattr(self.norm, "t", v))
     P = property(lambda self: self.norm.P)

@@ -71,6 +71,15 @@ def reserve_deterministic_scratch(nbytes, dev):
     ops.set_deterministic_scratch(_DET_SCRATCH[0])
 
 
+def refuse_overlap_data_parallel(loss_kind, dist_ctx):
+    """the overlap losses are differentiated from per-label sums, which no data-parallel context all-reduces: refused by name there"""
+    if ops.is_overlap_loss(loss_kind) and dist_ctx is not None and dist_ctx.world > 1:
+        name = [k for k, v in ops.LOSS_KINDS.items() if v == loss_kind][0]
+        raise NotImplementedError("%s (with dice_and_boundary, one of the overlap losses: %s) is differentiated from per-label sums, which "
+                                  "are not all-reduced: data-parallel training takes one of the other losses"
+                                  % (name, ", ".join(sorted(k for k, v in ops.LOSS_KINDS.items() if ops.is_overlap_loss(v)))))
+
+
 # The optimizer of EngineBase.optimizer_step: Keras 2.2.4's Adam / SGD / RMSprop with their argument names (keras/optimizers.py as
 # published; parity-unpinned, see include/fmri_hip.h).  The default is the plain Adam every builder compiles with.
 DEFAULT_OPTIMIZER = dict(kind="adam", beta_1=0.9, beta_2=0.999, epsilon=1e-7, decay=0.0, amsgrad=False,      # adam
@@ -100,13 +109,15 @@ class EngineBase(object):
         self.Vhat = None                              # AMSGrad's running maximum of V: allocated by set_optimizer when asked for
         self._gnorm_work = self._gnorm = None         # clipnorm: workspace and {sum of squares, norm} of ops.grad_sumsq
         self.loss_kind, self.loss_param = 0, 1.0      # ops.LOSS_KINDS: 0 = dice_coefficient_loss
+        self.loss_overlap = (0.5, 0.5, 1.0, 0.0)      # (alpha, beta, gamma, boundary_weight) of an overlap loss; loss_param is its smooth
         # the weight gradients run on their own stream (FMRI_WGRAD_STREAM=0: on the main stream)
         self._wg_stream = torch.cuda.Stream(device=self.dev) if (training and self.dev.type == "cuda" and self.sw["WGRAD_STREAM"]) else None
         # ONE tensor for the engine's lifetime: captured hipGraphs of other batch sizes keep its address (re-creating it per buffer
         # set left them writing into freed memory, which the allocator then handed to the tile index list of the next volume)
         # Behind the 16 metric sums, in the same tensor: the 3 * L label-wise sums (ops.label_sums) of a model that carries label-wise Dice
-        # metrics (label_metrics = L, set by the model; 0: no launch, nothing read back) - one pinned read-back takes both (log_sums)
-        self._sums_all = torch.zeros(16 + 3 * ops.MAX_LABELS, dtype=torch.float64, device=self.dev)
+        # metrics (label_metrics = L, set by the model; 0: no launch, nothing read back) - one pinned read-back takes both (log_sums).
+        # Behind those, for the overlap losses only (ops.SUMS_BD ...): the boundary sum, the coefficient pairs and the loss value
+        self._sums_all = torch.zeros(ops.SUMS_TOTAL, dtype=torch.float64, device=self.dev)
         self.sums = self._sums_all[:16]
         self.label_metrics = 0
 
@@ -159,9 +170,23 @@ class EngineBase(object):
     def loss_forward(self, y_true, weight=None):
         """y_true uint8 [nvox*L] device.  probs + the 8 metric sums (accumulated into zeroed self.sums)."""
         self.sums.zero_()
+        overlap = ops.is_overlap_loss(self.loss_kind)
+        if overlap:
+            weight, dist = None, weight              # the model's second input is the distance mask itself (dice_and_boundary)
+            refuse_overlap_data_parallel(self.loss_kind, self.dist)
         ops.sigmoid_dice_fwd(self.logits, y_true, self.probs, self.sums, weight=weight)
-        if self.label_metrics:
-            ops.label_sums(self.probs.reshape(-1), y_true, self.label_metrics, self._sums_all[16:])
+        if self.label_metrics or overlap:
+            # (one launch for both: the label-wise metrics read the sums the loss is differentiated from)
+            ops.label_sums(self.probs.reshape(-1), y_true, self.plan.n_labels, self._sums_all[16:])
+        if overlap:
+            L = self.plan.n_labels
+            alpha, beta, gamma, bweight = self.loss_overlap
+            bd = None
+            if dist is not None:
+                bd = self._sums_all[ops.SUMS_BD:ops.SUMS_BD + 1]
+                ops.boundary_sum(self.probs.reshape(-1), y_true, dist, bd)
+            ops.overlap_coeffs(self._sums_all[16:], self.sums, self._overlap_coef(), L, self.loss_kind - ops.LOSS_OVERLAP, alpha, beta, gamma,
+                               self.loss_param, bd=bd, boundary_weight=bweight)
         if self.loss_kind == ops.LOSS_WEIGHTED_DICE:
             ns, nl = self._wdice_groups()
             if getattr(self, "_gsums", None) is None or self._gsums.numel() < 3 * ns * nl:
@@ -171,8 +196,15 @@ class EngineBase(object):
             self.dist.all_reduce_sums(self.sums)
         return self.sums
 
+    def _overlap_coef(self):
+        """the [L][2] coefficient pairs + two value slots of the overlap losses, ending at the fixed value slots of _sums_all"""
+        return self._sums_all[ops.SUMS_OVERLAP_VALUE - 2 * self.plan.n_labels:]
+
     def log_sums(self):
-        """what a step's read-back copies: the 16 metric sums, with the [L][3] label-wise sums behind them when label_metrics is set"""
+        """what a step's read-back copies: the 16 metric sums, with the [L][3] label-wise sums behind them when label_metrics is set; an
+        overlap loss: the whole tensor, the loss value of fmri_overlap_coeffs included"""
+        if ops.is_overlap_loss(self.loss_kind):
+            return self._sums_all
         return self._sums_all[:16 + 3 * self.label_metrics] if self.label_metrics else self.sums
 
     def set_label_metrics(self, n):
@@ -204,6 +236,11 @@ class EngineBase(object):
         if seg_loss and self.loss_kind == ops.LOSS_WEIGHTED_DICE:
             ns, nl = self._wdice_groups()
             ops.weighted_dice_bwd(self.probs, y_true, self._gsums, self.sums, self.dlogits, ns, nl, grad_scale=grad_scale)
+        elif seg_loss and ops.is_overlap_loss(self.loss_kind):
+            L = self.plan.n_labels
+            bscale = self.loss_overlap[3] / float(self.probs.numel() // L) if weight is not None else 0.0
+            ops.overlap_loss_bwd(self.probs.reshape(-1), y_true, self._overlap_coef(), self.dlogits.reshape(-1), L, dist=weight,
+                                 boundary_scale=bscale, grad_scale=grad_scale)
         elif seg_loss:
             ops.sigmoid_loss_bwd(self.probs, y_true, self.sums, self.dlogits, self.loss_kind, self.loss_param, smooth=1.0, grad_scale=grad_scale,
                                  weight=weight)

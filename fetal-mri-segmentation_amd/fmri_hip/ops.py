@@ -607,6 +607,54 @@ LOSS_KINDS = {"dice_coefficient_loss": 0, "binary_crossentropy_loss": 1, "dice_a
               "double_dice_loss": 5, "weighted_dice_coefficient_loss": 6}
 LOSS_WEIGHTED_DICE = 6          # not a kind of fmri_sigmoid_loss_bwd: per-(sample, label) sums, fmri_weighted_dice_fwd / _bwd
 WEIGHTED_DICE_SMOOTH = 1e-5     # reference metrics.py:39
+# The overlap losses of fmri_overlap_coeffs / fmri_overlap_loss_bwd (per-label sums): loss_kind = LOSS_OVERLAP + the kernels' kind 0..4
+LOSS_OVERLAP = 7
+LOSS_KINDS.update({"tversky_loss": 7, "focal_tversky_loss": 8, "label_tversky_loss": 9, "label_focal_tversky_loss": 10,
+                   "generalised_dice_loss": 11})
+GDL_SMOOTH = 1e-5
+# An engine's sums tensor: the 16 metric sums, the [L][3] label sums, then (overlap losses only) the boundary sum Bd, the [L][2] coefficient
+# pairs right-aligned in front of the two value slots, so that the loss value sits at ONE index whatever L is
+SUMS_BD = 16 + 3 * MAX_LABELS                       # 112
+SUMS_OVERLAP_VALUE = SUMS_BD + 2 + 2 * MAX_LABELS   # 178: the loss value, 179: the value without the boundary term
+SUMS_TOTAL = SUMS_OVERLAP_VALUE + 2
+
+
+def is_overlap_loss(kind):
+    return LOSS_OVERLAP <= int(kind) < LOSS_OVERLAP + 5
+
+
+def boundary_sum(probs, y_true, dist, bd):
+    """bd float64 [1] (overwritten) = sum (1 - 2 y) * dist * p over the voxels of a single-label batch; dist: the fp32 distance mask"""
+    _need_cuda(probs, y_true, dist, bd)
+    n = probs.numel()
+    if probs.dtype != torch.float32 or dist.dtype != torch.float32 or y_true.dtype != torch.uint8 or y_true.numel() != n or dist.numel() != n \
+            or bd.dtype != torch.float64 or bd.numel() < 1:
+        raise ValueError("boundary_sum: fp32 probs and distances, uint8 targets of one size (single label), one float64 sum")
+    check(lib().fmri_boundary_sum(_p(probs), _p(y_true), _p(dist), n, _p(bd), _s()), "fmri_boundary_sum")
+
+
+def overlap_coeffs(lsums, sums, coef, n_labels, kind, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, bd=None, boundary_weight=0.0):
+    """coef float64 [2 * L + 2] = the (A_l, B_l) pairs, the loss value and the value without the boundary term, from lsums [3 * L]
+    (label_sums), the 16 metric sums and, for the boundary term, bd (boundary_sum): one single-wave launch (include/fmri_hip.h)"""
+    _need_cuda(lsums, sums, coef, bd)
+    L = int(n_labels)
+    if any(t.dtype != torch.float64 for t in (lsums, sums, coef) + ((bd,) if bd is not None else ())) or lsums.numel() < 3 * L \
+            or sums.numel() < 16 or coef.numel() < 2 * L + 2:
+        raise ValueError("overlap_coeffs: float64 lsums [3 L], sums [16], coef [2 L + 2]")
+    check(lib().fmri_overlap_coeffs(_p(lsums), _p(sums), _p(bd), _p(coef), L, int(kind), float(alpha), float(beta), float(gamma),
+                                    float(smooth), float(boundary_weight), _s()), "fmri_overlap_coeffs")
+
+
+def overlap_loss_bwd(probs, y_true, coef, dlogits, n_labels, dist=None, boundary_scale=0.0, grad_scale=1.0):
+    """dlogits = grad_scale * (A_l y + B_l + boundary_scale * (1 - 2 y) dist) * p (1 - p), element [v * L + l]"""
+    _need_cuda(probs, y_true, coef, dlogits, dist)
+    L, n = int(n_labels), probs.numel()
+    if probs.dtype != torch.float32 or dlogits.dtype != torch.float32 or y_true.dtype != torch.uint8 or coef.dtype != torch.float64 \
+            or L < 1 or n % L or y_true.numel() != n or dlogits.numel() != n or coef.numel() < 2 * L \
+            or (dist is not None and (dist.dtype != torch.float32 or dist.numel() * L != n)):
+        raise ValueError("overlap_loss_bwd: fp32 probs / dlogits and uint8 targets of nvox * L elements, float64 coef [2 L], fp32 dist [nvox]")
+    check(lib().fmri_overlap_loss_bwd(_p(probs), _p(y_true), _p(dist), _p(coef), _p(dlogits), n // L, L, float(boundary_scale),
+                                      float(grad_scale), _s()), "fmri_overlap_loss_bwd")
 
 
 def weighted_dice_fwd(probs, y_true, gsums, sums, nsamples, n_labels, smooth=WEIGHTED_DICE_SMOOTH):
@@ -637,7 +685,12 @@ def sigmoid_loss_bwd(probs, y_true, sums, dlogits, kind, param=1.0, smooth=1.0, 
 
 
 def loss_value_from_sums(s, kind, param=1.0, smooth=1.0):
-    """host-side value of the loss `kind` from the 16 metric sums (float64)"""
+    """host-side value of the loss `kind` from the 16 metric sums (float64); an overlap loss: the value fmri_overlap_coeffs wrote, which
+    rides behind the sums (s = the engine's log_sums)"""
+    if is_overlap_loss(kind):
+        if len(s) <= SUMS_OVERLAP_VALUE:
+            raise ValueError("an overlap loss takes its value from slot %d of the engine's log_sums(), got %d sums" % (SUMS_OVERLAP_VALUE, len(s)))
+        return float(s[SUMS_OVERLAP_VALUE])
     I, Sy, Sp, n = float(s[0]), float(s[1]), float(s[2]), float(s[7])
     dice = (2 * I + smooth) / (Sy + Sp + smooth)
     if kind == 0:

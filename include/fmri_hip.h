@@ -247,6 +247,29 @@ int fmri_sigmoid_loss_bwd_weighted(const float* probs, const uint8_t* y_true, co
  * 2^-20 fixed-point integers (as the sums of fmri_sigmoid_dice_fwd): two calls agree bit for bit. */
 int fmri_label_sums(const float* probs, const uint8_t* y_true, int64_t nvox, int L, double* lsums, fmri_stream_t stream);
 
+/* ---- overlap losses differentiated from the per-label sums (not in the reference's loss table; loss = -coefficient as there).
+ * With I, Sy, Sp = lsums[l][0..2], s = smooth and T(I, Sy, Sp) = (I + s) / (I + alpha (Sp - I) + beta (Sy - I) + s):
+ *   kind 0 Tversky: -T of the sums over all labels      kind 1 focal Tversky: (1 - T)^(1/gamma), the same T
+ *   kind 2 label-mean Tversky: -(1/L) sum_l T_l          kind 3 label-mean focal Tversky: (1/L) sum_l (1 - T_l)^(1/gamma)
+ *   kind 4 Generalised Dice: 1 - (2 sum_l w_l I_l + s) / (sum_l w_l (Sy_l + Sp_l) + s), w_l = 1 / Sy_l^2 (a label with Sy_l = 0 takes the
+ *          largest weight among the labels present; all weights 1 when none is present); alpha, beta, gamma unused
+ *   the focal derivative is taken at max(1 - T, 1e-7) (it has a pole at T = 1 for gamma > 1); the value is max(1 - T, 0)^(1/gamma)
+ *   boundary term (bd / dist given, L = 1 only): + boundary_weight * Bd / n, Bd = sum_v (1 - 2 y_v) dist_v p_v, n = sums[7]
+ * fmri_boundary_sum: bd[0] (OVERWRITTEN) = Bd; dist = the distance mask, nvox floats.
+ * fmri_overlap_coeffs: ONE wave, float64: coef[2 l] = A_l = dL/dI_l, coef[2 l + 1] = B_l = dL/dSp_l, coef[2 L] = the loss value (with the
+ *   boundary term when bd is given), coef[2 L + 1] = the value without it.  bd: NULL or the sum of fmri_boundary_sum; sums: the 16 of
+ *   fmri_sigmoid_dice_fwd.
+ * fmri_overlap_loss_bwd: dlogits[v * L + l] = grad_scale * (A_l y + B_l + boundary_scale * (1 - 2 y) dist[v]) * p (1 - p); dist NULL or
+ *   nvox floats (L = 1), boundary_scale = boundary_weight / n.  16-byte loads and stores when nvox * L % 4 == 0 and the pointers allow.
+ * Under fmri_set_deterministic the boundary sum meets as 2^-20 fixed-point integers, as the label sums do: two calls agree bit for bit.
+ * FMRI_E_SHAPE: L outside 1..32, nvox <= 0, a NULL required pointer, kind outside 0..4, alpha or beta negative, gamma < 1, bd or dist
+ * with L != 1. */
+int fmri_boundary_sum(const float* probs, const uint8_t* y_true, const float* dist, int64_t nvox, double* bd, fmri_stream_t stream);
+int fmri_overlap_coeffs(const double* lsums, const double* sums, const double* bd, double* coef, int L, int kind, float alpha, float beta,
+                        float gamma, float smooth, float boundary_weight, fmri_stream_t stream);
+int fmri_overlap_loss_bwd(const float* probs, const uint8_t* y_true, const float* dist, const double* coef, float* dlogits, int64_t nvox,
+                          int L, float boundary_scale, float grad_scale, fmri_stream_t stream);
+
 /* ---- MaxPooling3D(pool_size) / UpSampling3D(size) — reference unet.py:51, :138 — with per-axis factors pd, ph, pw in 1..4 (not all 1),
  * stride = window: 2x2x2, the anisotropic (2, 2, 1) of reference configs; a 2-D layer of a planar tensor is (1, ph, pw).  Windows 2x2x2
  * and 1x2x2 run fully unrolled instantiations of the kernels, every other window the run-time one: the same arithmetic, in (d, h, w)
