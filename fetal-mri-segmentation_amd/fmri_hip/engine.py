@@ -19,8 +19,9 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import lib, ACT_NONE, ACT_RELU, IMPL_AUTO
+from ._lib import ACT_NONE, ACT_RELU, IMPL_AUTO
 from .engine_base import EngineBase, flat_to_kernel, glorot_uniform, kernel_to_flat
+from .up_routes import D2s, Fold, Onetap, Upcat, candidates
 
 
 class UNetPlan:
@@ -99,14 +100,11 @@ class UNetEngine(EngineBase):
         self.input_grad = bool(input_grad and training)
         self.planar = plan.ndim == 2      # 2-D: tensors are [1][slices][H][W][C], every op is planar (no coupling along D)
         if self.deterministic:
-            # FMRI_DETERMINISTIC=1 (EngineBase) keeps to routes whose sums are ordered, and gives these up:
-            #   * the parity-form weight gradient, whose scratch is filled by fp32 atomics (_upcat_layers): the fused-upsample 27-tap one;
-            #   * the statistics a conv launch forms in its epilogue (the four producer waves of a workgroup meet in its slot with fp64
-            #     atomics): the separate reductions, which add their workgroups' partials in block order - the FMRI_NORM_FUSE=0 path;
-            #   * every route of the transposed conv but the direct k2s2 kernels (the folded one sums border classes with fp32 atomics,
-            #     the one-tap parity form uses the parity-form weight gradient, the 2-D depth-to-space one accumulates outside G) - the
-            #     FMRI_DECONV_FOLD=0 path without the one-tap form.
-            self.sw["NORM_FUSE"], self.sw["DECONV_FOLD"] = 0, False
+            # FMRI_DETERMINISTIC=1 (EngineBase) keeps to routes whose sums are ordered: the decoder routes that say so of themselves
+            # (up_routes: `ordered`), and not the statistics a conv launch forms in its epilogue (the four producer waves of a workgroup
+            # meet in its slot with fp64 atomics) but the separate reductions, which add their workgroups' partials in block order - the
+            # FMRI_NORM_FUSE=0 path
+            self.sw["NORM_FUSE"] = 0
         self._bufsets = {}
         self._build_params(seed)
         self.set_batch(batch)
@@ -147,106 +145,27 @@ class UNetEngine(EngineBase):
                                           "8 x 2^k <= 512 channels, at most 4 labels)" % (cf, p.n_labels))
         if self.training:
             self._det_register(self.G)
+        # the candidate routes of every decoder level (up_routes.candidates), keyed by block a's name, deepest level first
+        self.fold = None                  # the index tables of deconv_fold, shared by the folded levels
+        self.up_routes = OrderedDict((lv[0]["name"], candidates(self, lv[0], p.up.get(lv[0]["level"]))) for lv in p.dec)
         # compute-dtype copies of the 3x3x3 filters (and no pack table yet: it holds their addresses)
-        self.Wf, self.Wd, self.Wup, self._ptab = {}, {}, {}, None
-        self.upcat = self._upcat_layers()
-        self.Wt = {}                      # compute-dtype copies of the transposed-conv filters [8][Cout][Cin]
+        self.Wf, self.Wd, self._ptab = {}, {}, None
         self.moving = {}                  # batch-norm moving mean / variance (inference statistics), fp32 [2][C]
         first = p.enc[0][0]["name"]
         for name, L in self.layout.items():
-            if L["kind"] == "deconv":
-                self.Wt[name] = torch.empty((8, L["cout"], L["cin"]), dtype=self.dtype, device=dev)
             if L.get("norm") and p.norm == "batch":
                 mv = torch.zeros((2, L["cout"]), dtype=torch.float32, device=dev)
                 mv[1].fill_(1.0)
                 self.moving[name] = mv
-            if L["kind"] != "conv":
+            if L["kind"] != "conv" or (name in self.up_routes and not self.up_routes[name][0].plain_a):
                 continue
-            if name in self.upcat:
-                # up-sample + concat + conv in parity form (fmri_conv3d_upcat_*): pre-summed 2x2x2 filters per output parity for the
-                # up-sampled channels, plain 27-tap filters for the skip channels
-                c0, c1 = self.upcat[name]
-                npar = 4 if self.planar else 8           # parity classes = pre-summed taps per class (2-D: (ph,pw) x 2x2 taps)
-                W = dict(up_f=torch.empty((npar, npar, L["cout"], c0), dtype=self.dtype, device=dev),
-                         sk_f=torch.empty((27, L["cout"], c1), dtype=self.dtype, device=dev), up_d=None, sk_d=None)
-                if self.training:
-                    W["up_d"] = torch.empty((npar, npar, c0, L["cout"]), dtype=self.dtype, device=dev)
-                    W["sk_d"] = torch.empty((27, c1, L["cout"]), dtype=self.dtype, device=dev)
-                self.Wup[name] = W
-                if not self.planar:
-                    continue                             # 2-D keeps the 9-tap images too: batches whose slice count does not tile fall back
             self.Wf[name] = torch.empty((27, L["cout"], L["cin"]), dtype=self.dtype, device=dev)
             # (the first conv's input-gradient image: only with input_grad, and only where fmri_conv3d_first_dgrad - which reads the forward
             # image - does not take the shape)
             if self.training and (name != first or (self.input_grad and not self._first_dgrad_ok())):
                 self.Wd[name] = torch.empty((27, L["cin"], L["cout"]), dtype=self.dtype, device=dev)
-        # Deconvolution3D(k = 2, s = 2) (reference unet.py:135): output voxel 2g+p = W[p] . x[g] + b, i.e. the parity form with ONE
-        # non-zero tap per parity class (low-res offset 0) - it rides the same MFMA kernels (fmri_conv3d_upcat_* with C1 = 0)
-        self.Wdc = {}
-        if not self.planar and self.dtype == torch.bfloat16 and not self.deterministic:
-            for lvl, u in p.up.items():
-                L = self.layout[u["name"]]
-                D, H, W = p.level_dims(lvl)
-                if ops.conv3d_upcat_ok(L["cin"], 0, L["cout"], D, H, W, self.dtype) == 3:
-                    Wd_ = dict(up_f=torch.zeros((8, 8, L["cout"], L["cin"]), dtype=self.dtype, device=dev), up_d=None, dw27=None)
-                    if self.training:
-                        Wd_["up_d"] = torch.zeros((8, 8, L["cin"], L["cout"]), dtype=self.dtype, device=dev)
-                        Wd_["dw27"] = torch.zeros((27, L["cout"], L["cin"]), dtype=torch.float32, device=dev)   # never read
-                    self.Wdc[u["name"]] = Wd_
-        # 2-D twin (Deconvolution2D, reference unet/unet.py get_up_convolution): the 4 taps are 4 independent 1x1 convs, run as ONE planar
-        # 3x3 MFMA conv to 4*Cout channels whose only non-zero tap is the centre one, followed by a depth-to-space copy
-        self.Wd2 = {}
-        if self.planar and self.dtype == torch.bfloat16 and not self.deterministic:
-            for lvl, u in p.up.items():
-                L = self.layout[u["name"]]
-                _, S, H, W = (1,) + p.level_dims(lvl + 1, 4)                  # low-res dims (the slice count does not matter here)
-                if lib().fmri_conv3d_uses_mfma(L["cin"], 0, 4 * L["cout"], 4, H, W, 1) & 1:
-                    Wd_ = dict(w32=torch.zeros((27, 4 * L["cout"], L["cin"]), dtype=torch.float32, device=dev),
-                               wf=torch.empty((27, 4 * L["cout"], L["cin"]), dtype=self.dtype, device=dev), wd=None,
-                               b4=torch.zeros(4 * L["cout"], dtype=torch.float32, device=dev))
-                    if self.training:
-                        Wd_["wd"] = torch.empty((27, L["cin"], 4 * L["cout"]), dtype=self.dtype, device=dev)
-                        Wd_["dw"] = torch.zeros((27, 4 * L["cout"], L["cin"]), dtype=torch.float32, device=dev)
-                        Wd_["db"] = torch.zeros(4 * L["cout"], dtype=torch.float32, device=dev)
-                    self.Wd2[u["name"]] = Wd_
-        # Deconvolution3D -> concatenate -> Conv3D FOLDED into one parity-form convolution of the low-res tensor (round 3; fmri_hip/deconv_fold.py,
-        # fmri_conv3d_upcat_fwd_bias27): the transposed conv's output is never materialised and the decoder 'a' conv does 8 instead of 27 taps
-        # on its up-sampled channels, exactly as in the UpSampling3D variant - with pre-MULTIPLIED instead of pre-summed filters.  Keyed by the
-        # 'a' conv's name.  FMRI_DECONV_FOLD=0 keeps the two-step form (transposed conv as one-tap parity form, then the plain 27-tap conv).
-        self.Wfd, self.fold = {}, None
-        if (not self.planar and self.dtype == torch.bfloat16 and p.norm is None and self.sw["DECONV_FOLD"] and self.sw["FWD_WS"]):
-            from .deconv_fold import DeconvFold
-            for lv in p.dec:
-                a = lv[0]
-                if a["level"] not in p.up:
-                    continue
-                u = p.up[a["level"]]
-                Lu = self.layout[u["name"]]
-                D, H, W = p.level_dims(a["level"])
-                if Lu["cout"] == a["c_up"] and ops.conv3d_upcat_ok(Lu["cin"], a["c_skip"], a["cout"], D, H, W, self.dtype) == 3:
-                    if self.fold is None:
-                        self.fold = DeconvFold(dev)
-                    # weight GEMMs of the largest levels with bf16 operands (fp32 accumulation): 0.3 % relative error on filters that
-                    # are rounded to bf16 for the MFMA kernels anyway, 2.3x faster at 256 x 512 x 512 (tools/bench_fold.py); below
-                    # 2^25 multiply-adds per block fp32 is as fast
-                    F = dict(u=u["name"], cmid=Lu["cout"], cin=Lu["cin"], cs=a["c_skip"],
-                             gd=torch.bfloat16 if a["cout"] * Lu["cout"] * Lu["cin"] >= (1 << 25) else None,
-                             up_f=torch.empty((8, 8, a["cout"], Lu["cin"]), dtype=self.dtype, device=dev),
-                             sk_f=torch.empty((27, a["cout"], a["c_skip"]), dtype=self.dtype, device=dev), up_d=None, sk_d=None,
-                             bias27=torch.zeros((27, a["cout"]), dtype=torch.float32, device=dev))
-                    if self.training:
-                        F["up_d"] = torch.empty((8, 8, Lu["cin"], a["cout"]), dtype=self.dtype, device=dev)
-                        F["sk_d"] = torch.empty((27, a["c_skip"], a["cout"]), dtype=self.dtype, device=dev)
-                        F["s27"] = torch.zeros((27, a["cout"]), dtype=torch.float32, device=dev)
-                    self.Wfd[a["name"]] = F
-        self._folded_up = set(F["u"] for F in self.Wfd.values())          # transposed convs that no longer run on their own
-        self.dwc_scratch = None
-        need = [64 * self.layout[n]["cout"] * self.upcat[n][0] for n in self.upcat_wgrad] + \
-               [64 * self.layout[n]["cout"] * self.layout[n]["cin"] for n in self.Wdc] + \
-               [64 * self.layout[n]["cout"] * F["cin"] for n, F in self.Wfd.items()]
-        if self.training and need:
-            self.dwc_scratch = torch.empty(max(need), dtype=torch.float32, device=dev)
-        self._par8 = torch.arange(8, device=dev)
+        need = [r.scratch() for cands in self.up_routes.values() for r in cands]
+        self.dwc_scratch = torch.empty(max(need), dtype=torch.float32, device=dev) if self.training and any(need) else None
         self.init_glorot(seed)
 
     def w_view(self, name, buf=None):
@@ -351,30 +270,26 @@ class UNetEngine(EngineBase):
                     W[L["norm"] + "/moving_mean"], W[L["norm"] + "/moving_variance"] = mv[0].copy(), mv[1].copy()
         return W
 
-    def _upcat_layers(self):
-        """decoder 'a' convs (UpSampling3D -> concatenate -> Conv3D, reference unet.py:132-138,61,102) that take the parity form:
-        name -> (up-sampled channels, skip channels).  FMRI_UPCAT=0 keeps the 27-tap fused-upsample kernel (A/B switch)."""
-        p = self.plan
-        out = {}
-        self.upcat_wgrad = set()                           # ... of which the weight gradient takes the parity form too (never in deterministic mode)
-        # (fp32, round 6: the parity form runs on the fp32 instantiation of the same MFMA kernels where fmri_conv3d_upcat_ok says so - 3-D,
-        # channels in multiples of 16; FMRI_F32_MFMA=0 keeps fp32 on the VALU kernels and with them on the 27-tap fused-upsample form)
-        if (self.dtype != torch.bfloat16 and self.planar) or not self.sw["UPCAT"]:
-            return out
-        for lv in p.dec:
-            a = lv[0]
-            if a["level"] in p.up:
-                continue                                   # Deconvolution3D variant: the up-sampled tensor is materialised
-            c1 = p.enc[a["level"]][1]["cout"]
-            c0 = a["cin"] - c1
-            # 2-D: the slices ride the kernels' D axis; 4 of them (one tile) stand in for "a batch that tiles" (see _use_upcat)
-            D, H, W = p.level_dims(a["level"], 4) if self.planar else p.level_dims(a["level"])
-            ok = ops.conv3d_upcat_ok(c0, c1, a["cout"], D, H, W, self.dtype, planar=self.planar)
-            if ok & 1:
-                out[a["name"]] = (c0, c1)
-                if ok & 2 and not self.deterministic:
-                    self.upcat_wgrad.add(a["name"])
-        return out
+    # What the decoder levels were built with, whichever batch size is current - read by the tests and by the benchmark's FLOP count.
+    def _built(self, cls):
+        """the candidate routes of class cls, shallowest level first"""
+        return [r for cands in reversed(self.up_routes.values()) for r in cands if type(r) is cls]
+
+    @property
+    def upcat(self):
+        """decoder 'a' convs that can take the parity form: name -> (up-sampled channels, skip channels)"""
+        return OrderedDict((r.a["name"], (r.a["c_up"], r.a["c_skip"])) for r in self._built(Upcat))
+
+    @property
+    def upcat_wgrad(self):
+        """... of which the weight gradient takes the parity form too (never in deterministic mode)"""
+        return set(r.a["name"] for r in self._built(Upcat) if r.wgrad)
+
+    # the weight images of the parity-form and folded levels by block a's name, of the one-tap and 2-D transposed convs by their own
+    Wup = property(lambda self: OrderedDict((r.a["name"], r.W) for r in self._built(Upcat)))
+    Wfd = property(lambda self: OrderedDict((r.a["name"], r.W) for r in self._built(Fold)))
+    Wdc = property(lambda self: OrderedDict((r.u["name"], r.W) for r in self._built(Onetap)))
+    Wd2 = property(lambda self: OrderedDict((r.u["name"], r.W) for r in self._built(D2s)))
 
     def _first_dgrad_ok(self):
         """does fmri_conv3d_first_dgrad take the first convolution's input gradient? (3-D bf16 shapes of ops.conv3d_first_dgrad_ok; it does
@@ -385,16 +300,15 @@ class UNetEngine(EngineBase):
 
     def _use_upcat(self, name):
         """parity form for this layer at the CURRENT batch size (2-D: the slice count must be a multiple of the 4-slice tile)"""
-        return self.route["up"].get(name) == "upcat"
+        return type(self.up.get(name)) is Upcat
 
     def _pack_table(self):
         """the plain and the parity-form images as one table for ops.pack_weights_batched: (table, blocks, the tensors whose raw addresses the
-        table holds, P's address when it was built) - rebuilt when P has moved since, dropped wherever Wf / Wd / Wup are allocated"""
+        table holds, P's address when it was built) - rebuilt when P has moved since, dropped wherever the images are allocated"""
         if self._ptab is None or self._ptab[3] != self.P.data_ptr():
-            ent = [("plain", self.w_view(n), self.Wf[n], self.Wd.get(n)) for n in self.Wf if n not in self.Wfd]
-            for n, W in self.Wup.items():
-                c0, c1 = self.upcat[n]
-                ent.append(("up", self.w_view(n), c0, c1, W["up_f"], W["up_d"], W["sk_f"], W["sk_d"], self.planar))
+            ent = [("plain", self.w_view(n), self.Wf[n], self.Wd.get(n)) for n in self.Wf]
+            for cands in reversed(self.up_routes.values()):
+                ent += [e for r in cands for e in r.pack_entries()]
             self._ptab = (ops.pack_table(ent, self.dev) if ent else (None, 0)) + (ent, self.P.data_ptr())
         return self._ptab
 
@@ -402,35 +316,13 @@ class UNetEngine(EngineBase):
         """compute-dtype images of the fp32 parameters (forward filters, tap-flipped transposed filters for the input gradients, parity
         filters), on the current stream.  Every plain / parity-form image in ONE launch: per-layer launches are launch-bound - 14 of them
         cost the configs[1] step 0.12 ms wherever they run, also on a side stream under the next step's first convolutions (rounds 2-5,
-        retired: profiles/r06_pack_batched_ab.log, tools/r06/pack_cost.py).  Folded layers and transposed-conv images: per layer."""
+        retired: profiles/r06_pack_batched_ab.log, tools/r06/pack_cost.py).  The images of a level's preferred route that are not in the
+        table (folded layers, transposed convs): per layer, shallowest level first."""
         tab, nb = self._pack_table()[:2]
         if tab is not None:
             ops.pack_weights_batched(tab, nb, self.dtype)
-        for name, F in self.Wfd.items():
-            w3 = self.w_view(name)
-            weff, b27 = self.fold.effective(w3, self.w_view(F["u"]), self.b_view(name), self.b_view(F["u"]), F["cmid"], gemm_dtype=F["gd"])
-            F["up_f"].copy_(weff)
-            F["bias27"].copy_(b27)
-            F["sk_f"].copy_(w3[:, :, F["cmid"]:])
-            if F["up_d"] is not None:
-                F["up_d"].copy_(weff[:, self.fold.mirror].transpose(-1, -2))            # Wc[p][1 - t']^T (fmri_conv3d_pack_up_weights' w_up_dgrad)
-                F["sk_d"].copy_(w3[:, :, F["cmid"]:].flip(0).transpose(1, 2))           # tap-flipped transposed skip filters
-        for name, wt in self.Wt.items():
-            if name in self._folded_up:
-                continue
-            if name in self.Wd2:
-                Wd_, L = self.Wd2[name], self.layout[name]
-                Wd_["w32"][13] = self.w_view(name)[:4].reshape(4 * L["cout"], L["cin"])
-                Wd_["b4"].copy_(self.b_view(name).repeat(4))
-                ops.pack_weights(Wd_["w32"], Wd_["wf"], Wd_["wd"])
-                continue
-            if name in self.Wdc:                          # parity p reads low-res offset 0 = combined tap 7 - p (mirrored: tap p)
-                Wd_, w8 = self.Wdc[name], self.w_view(name)
-                Wd_["up_f"][self._par8, 7 - self._par8] = w8.to(self.dtype)
-                if Wd_["up_d"] is not None:
-                    Wd_["up_d"][self._par8, self._par8] = w8.transpose(1, 2).to(self.dtype)
-                continue
-            ops.cast(self.w_view(name), wt)
+        for cands in reversed(self.up_routes.values()):
+            cands[0].refresh()
 
     # ------------------------------------------------------------------------------------------------ buffers
     def set_batch(self, N):
@@ -441,12 +333,12 @@ class UNetEngine(EngineBase):
             self._build_buffers()
             self._bufsets[key] = dict(act=self.act, grad=getattr(self, "grad", None), logits=self.logits, probs=self.probs,
                                       dlogits=getattr(self, "dlogits", None), pre=self.pre, nstats=self.nstats, nss=self.nss, norm_ws=self.norm_ws,
-                                      wgrad_ws=getattr(self, "wgrad_ws", None), route=self.route, dx_in=self.dx_in, dx_tmp=self.dx_tmp,
+                                      wgrad_ws=getattr(self, "wgrad_ws", None), route=self.route, up=self.up, dx_in=self.dx_in, dx_tmp=self.dx_tmp,
                                       dummy_y=torch.zeros(self.logits.numel(), dtype=torch.uint8, device=self.dev))
         b = self._bufsets[key]
         self.N, self.act, self.grad, self.logits, self.probs, self.dlogits = N, b["act"], b["grad"], b["logits"], b["probs"], b["dlogits"]
         self.pre, self.nstats, self.nss, self.norm_ws, self.wgrad_ws = b["pre"], b["nstats"], b["nss"], b["norm_ws"], b["wgrad_ws"]
-        self.route, self.dx_in, self.dx_tmp = b["route"], b["dx_in"], b["dx_tmp"]
+        self.route, self.up, self.dx_in, self.dx_tmp = b["route"], b["up"], b["dx_in"], b["dx_tmp"]
         self._dummy_y = b["dummy_y"]       # per buffer set and never freed: captured hipGraphs keep raw pointers to it
 
     def _dims(self, level):
@@ -488,24 +380,18 @@ class UNetEngine(EngineBase):
                 return False
             return ops.conv3d_fwd_ntail_ok(c0, c1, cout, *self._dims(level), self.dtype)
 
-        for lv in p.dec:
-            a, u = lv[0], p.up.get(lv[0]["level"])
-            if a["name"] in self.Wfd:
-                r["up"][a["name"]] = "fold"
-            elif u is not None:
-                r["up"][a["name"]] = ("d2s" if u["name"] in self.Wd2 and self.N % 4 == 0 else "onetap" if u["name"] in self.Wdc else "deconv")
-            else:
-                r["up"][a["name"]] = "upcat" if a["name"] in self.Wup and (not self.planar or self.N % 4 == 0) else "upsample"
-            r["upcat_wgrad"][a["name"]] = r["up"][a["name"]] == "upcat" and a["name"] in self.upcat_wgrad
+        self.up = OrderedDict()                             # block a -> the route object behind route["up"][a]
+        for name, cands in self.up_routes.items():
+            self.up[name] = next(c for c in cands if c.takes(self.N))
+            r["up"][name] = self.up[name].name
+            r["upcat_wgrad"][name] = self.up[name].wgrad
         tails = self.dtype == torch.bfloat16 and sw["TAIL_FUSE"] and (sw["TAIL_FUSE_2D"] or not self.planar)
         for lv in p.enc + p.dec:
             a, b = lv
             for c in lv:
                 r["tail"][c["name"]] = (ops.conv3d_fwd_tail_ok(c["cin"], c["cout"], *self._dims(c["level"]), self.dtype, planar=self.planar)
                                         if tails and not c.get("norm") else 0)
-                c0, c1 = (c["c_up"], c["c_skip"]) if "c_up" in c else (c["cin"], 0)
-                if r["up"].get(c["name"]) == "upcat":       # the parity form's skip launch writes the output
-                    c0, c1 = c1, 0
+                c0, c1 = self.up[c["name"]].writer() if c["name"] in self.up else (c["cin"], 0)
                 r["stats"][c["name"]] = ntail(c0, c1, c["cout"], c["level"], 1)
             r["dz"][a["name"]] = ntail(b["cout"], 0, a["cout"], a["level"], 2)
             r["dz"][b["name"]] = False                      # its gradient comes from a pooling / up-sampling / 1x1x1 backward, not from a conv launch
@@ -534,7 +420,7 @@ class UNetEngine(EngineBase):
         for ld in range(p.depth - 1):
             A["pool_%d" % ld] = torch.empty(self._dims(ld + 1) + (p.enc[ld][1]["cout"],), dtype=dt, device=dev)
         for lv in p.dec:
-            if lv[0]["level"] in p.up and lv[0]["name"] not in self.Wfd:      # (a folded transposed conv's output never exists)
+            if self.up[lv[0]["name"]].up_output:
                 u = p.up[lv[0]["level"]]
                 A[u["name"]] = torch.empty(self._dims(u["level"]) + (u["cout"],), dtype=dt, device=dev)
             for c in lv:
@@ -561,9 +447,9 @@ class UNetEngine(EngineBase):
             Gd[name] = torch.empty_like(t)            # gradient w.r.t. the tensor (conv blocks: w.r.t. the pre-activation)
         for lv in p.dec:
             a = lv[0]
-            # gradient of the concatenated conv input; the parity form writes the up-sampled part straight at low resolution,
+            # gradient of the concatenated conv input; the parity forms write the up-sampled part straight at low resolution,
             # so only the skip channels remain
-            ccat = a["c_skip"] if self.route["up"][a["name"]] in ("upcat", "fold") else a["cin"]
+            ccat = a["c_skip"] if self.up[a["name"]].cat_skip_only else a["cin"]
             Gd["cat_%d" % a["level"]] = torch.empty(self._dims(a["level"]) + (ccat,), dtype=dt, device=dev)
         self.dlogits = torch.empty_like(self.logits)
         # scratch for the slab flush of the MFMA weight-gradient kernel (max over the layers of this plan)
@@ -589,10 +475,11 @@ class UNetEngine(EngineBase):
         """what the epilogue of conv block `c` produces besides its output (_plan_routes)"""
         return self.route["tail"][c["name"]]
 
-    def _block_fwd(self, c, src0, src1, up0, bn_training, pool=None, final=None):
+    def _block_fwd(self, c, src0, src1, up0, bn_training, pool=None, final=None, conv=None):
         """one [conv -> (norm) -> ReLU] block (reference create_convolution_block, unet.py:89-115).  pool: tensor that receives
         MaxPooling3D(2) of the block's output; final: the final 1x1x1 conv descriptor whose logits the epilogue computes - both only
-        when the route plan's tail bits say so (the caller checks)."""
+        when the route plan's tail bits say so (the caller checks); conv(src0, src1, out, act, summed, per_instance): the launch of a
+        decoder route that runs the block's convolution in a form of its own."""
         name = c["name"]
         out, act = (self.pre[name], ACT_NONE) if c.get("norm") else (self.act[name], ACT_RELU)
         if pool is not None or final is not None:
@@ -605,12 +492,8 @@ class UNetEngine(EngineBase):
         per, eos = self._norm_mode()
         want_sums = bool(c.get("norm")) and not (self.plan.norm == "batch" and not bn_training)
         summed = want_sums and self.route["stats"][name]
-        if self.route["up"].get(name) == "upcat":
-            W = self.Wup[name]
-            if summed:
-                ops.conv3d_upcat_fwd_stats(src0, src1, W["up_f"], W["sk_f"], self.b_view(name), out, self.norm_ws, per, act=act)
-            else:
-                ops.conv3d_upcat_fwd(src0, src1, W["up_f"], W["sk_f"], self.b_view(name), out, act=act, planar=self.planar)
+        if conv is not None:
+            conv(src0, src1, out, act, summed, per)
         elif summed:
             ops.conv3d_fwd_stats(src0, src1, self.Wf[name], self.b_view(name), out, self.norm_ws, per, up0=up0, act=act)
         else:
@@ -658,24 +541,7 @@ class UNetEngine(EngineBase):
         for lv in p.dec:
             a, b = lv
             skip = A[p.enc[a["level"]][1]["name"]]
-            up = self.route["up"][a["name"]]
-            if up == "fold":
-                F = self.Wfd[a["name"]]
-                ops.conv3d_upcat_fwd_bias27(h, skip, F["up_f"], F["sk_f"], F["bias27"], A[a["name"]], act=ACT_RELU)
-            elif up in ("d2s", "onetap", "deconv"):
-                u = p.up[a["level"]]
-                if up == "d2s":
-                    Wd_ = self.Wd2[u["name"]]
-                    t4 = self._d2s_tmp(u["name"], h, Wd_)
-                    ops.conv3d_fwd(h, None, Wd_["wf"], Wd_["b4"], t4, act=ACT_NONE, planar=True)
-                    self._d2s_views(A[u["name"]], t4)[0].copy_(self._d2s_views(A[u["name"]], t4)[1])
-                elif up == "onetap":
-                    ops.conv3d_upcat_fwd(h, None, self.Wdc[u["name"]]["up_f"], None, self.b_view(u["name"]), A[u["name"]], act=ACT_NONE)
-                else:
-                    ops.deconv_fwd(h, self.Wt[u["name"]], self.b_view(u["name"]), A[u["name"]], planar=self.planar)
-                self._block_fwd(a, A[u["name"]], skip, False, bn_training)
-            else:
-                self._block_fwd(a, h, skip, True, bn_training)
+            self.up[a["name"]].forward(h, skip, bn_training)
             # the last block also produces the logits of the final 1x1x1 conv (one label) in its epilogue when the kernel can do it
             fuse_final = lv is p.dec[-1] and p.n_labels == 1 and (self.route["tail"][b["name"]] & 2)
             h = self._block_fwd(b, A[a["name"]], None, False, bn_training, final=p.final if fuse_final else None)
@@ -685,9 +551,10 @@ class UNetEngine(EngineBase):
         return self.logits
 
     # ------------------------------------------------------------------------------------------------ backward
-    def _block_bwd(self, c, src0, src1, up0):
+    def _block_bwd(self, c, src0, src1, up0, wgrad=None):
         """G[c] holds dL/d(output of the block) (already ReLU-masked when the block has no norm).  Leaves dL/d(conv output) in
-        G[c] and accumulates the block's parameter gradients."""
+        G[c] and accumulates the block's parameter gradients - with wgrad(src0, src1, dy) where a decoder route brings a weight-gradient
+        launch of its own."""
         name = c["name"]
         g = self.grad[name]
         if c.get("norm") and name in self._dz_ready:
@@ -701,44 +568,16 @@ class UNetEngine(EngineBase):
             ops.norm_act_bwd(self._as_samples(self.pre[name]), None, self._as_samples(g),
                              self.gb_view(name, "gamma"), self.nstats[name], self._as_samples(g), self.gb_view(name, "gamma", self.G),
                              self.gb_view(name, "beta", self.G), self.norm_ws, per, act=ACT_RELU, beta=self.gb_view(name, "beta"))
-        def wgrad():
-            if self.route["upcat_wgrad"].get(name):
-                ops.conv3d_upcat_wgrad(src0, src1, g, self.w_view(name, self.G), self.b_view(name, self.G), self.dwc_scratch,
-                                       workspace=self.wgrad_ws, planar=self.planar)
+        def launch():
+            if wgrad is not None:
+                wgrad(src0, src1, g)
             else:
                 ops.conv3d_wgrad(src0, src1, g, self.w_view(name, self.G), self.b_view(name, self.G), up0=up0, planar=self.planar,
                                  workspace=self.wgrad_ws)
             self._grad_ready(name)
 
         if self._params:
-            self._wgrad(wgrad)              # behind the event "dL/d(conv output) is final"
-
-    def _folded_bwd(self, a, x_low, skip, cat, low):
-        """backward of the folded transposed conv + conv of decoder block `a`: G[a] holds dL/d(conv output).  Weight gradients (side
-        stream): parity-filter gradients from the MFMA kernel, chained through the transposed conv's weights by fmri_hip.deconv_fold;
-        input gradients: w.r.t. the low-res tensor (parity-form launch over the space-to-depth view of dy) and the skip tensor."""
-        name, F = a["name"], self.Wfd[a["name"]]
-        g = self.grad[name]
-
-        def wgrad():
-            Cout = a["cout"]
-            dwc = self.dwc_scratch[:64 * Cout * F["cin"]]
-            ops.conv3d_upcat_wgrad_parts(x_low, skip, g, self.w_view(name, self.G), self.b_view(name, self.G), dwc, workspace=self.wgrad_ws)
-            s27 = F["s27"]
-            s27.zero_()
-            ops.border_class_sums(g, s27)
-            s27[13] = self.b_view(name, self.G) - s27.sum(0)        # interior class = all voxels (the conv's bias gradient) - the 26 border classes
-            dw3u, dwt, dbt = self.fold.chain(dwc.view(8, 8, Cout, F["cin"]), self.w_view(name), self.w_view(F["u"]), self.b_view(F["u"]), F["cmid"], s27,
-                                             gemm_dtype=F["gd"])
-            self.w_view(name, self.G)[:, :, :F["cmid"]].add_(dw3u)
-            self.w_view(F["u"], self.G).add_(dwt)
-            self.b_view(F["u"], self.G).add_(dbt)
-            self._grad_ready(name)
-            self._grad_ready(F["u"])
-
-        if self._params:
-            self._wgrad(wgrad)
-        ops.conv3d_upcat_dgrad(g, F["up_d"], F["sk_d"], self._mask_of(low), None, self.grad[low], cat)
+            self._wgrad(launch)             # behind the event "dL/d(conv output) is final"
 
     def _dgrad_into(self, b, a):
         """dL/d(output of block a) from block b's conv (whose only input is a's output) -> grad[a].  a normalised: the launch's epilogue
@@ -789,48 +628,7 @@ class UNetEngine(EngineBase):
             skip = A[p.enc[ld][1]["name"]]
             self._block_bwd(b, A[a["name"]], None, False)
             self._dgrad_into(b, a)
-            cat = Gd["cat_%d" % ld]
-            up = self.route["up"][a["name"]]
-            if up == "fold":
-                self._folded_bwd(a, A[low], skip, cat, low)
-            elif up in ("d2s", "onetap", "deconv"):
-                u = p.up[ld]
-                self._block_bwd(a, A[u["name"]], skip, False)
-                ops.conv3d_dgrad(Gd[a["name"]], self.Wd[a["name"]], cat, planar=self.planar)
-                if up == "d2s":
-                    Wd_, L = self.Wd2[u["name"]], self.layout[u["name"]]
-                    dyc = ops.slice_channels(cat, 0, Gd[u["name"]])
-                    t4 = self._d2s_tmp(u["name"], A[low], Wd_)
-                    yv, tv = self._d2s_views(dyc, t4)
-                    tv.copy_(yv)                                               # space-to-depth of the gradient
-                    ops.conv3d_dgrad(t4, Wd_["wd"], Gd[low], mask=self._mask_of(low), planar=True)
-                    if params:
-                        Wd_["dw"].zero_()
-                        Wd_["db"].zero_()
-                        ops.conv3d_wgrad(A[low], None, t4, Wd_["dw"], Wd_["db"], planar=True)
-                        self.w_view(u["name"], self.G)[:4].add_(Wd_["dw"][13].view(4, L["cout"], L["cin"]))
-                        self.b_view(u["name"], self.G).add_(Wd_["db"].view(4, L["cout"]).sum(0))
-                elif up == "onetap":
-                    Wd_ = self.Wdc[u["name"]]
-                    dyc = ops.slice_channels(cat, 0, Gd[u["name"]])          # the transposed conv's own slice of the concat gradient
-                    ops.conv3d_upcat_dgrad(dyc, Wd_["up_d"], None, self._mask_of(low), None, Gd[low], None)
-                    if params:
-                        ops.conv3d_upcat_wgrad(A[low], None, dyc, Wd_["dw27"], self.b_view(u["name"], self.G), self.dwc_scratch)
-                        L = self.layout[u["name"]]
-                        dwc = self.dwc_scratch[:64 * L["cout"] * L["cin"]].view(8, 8, L["cout"], L["cin"])
-                        self.w_view(u["name"], self.G).add_(dwc[self._par8, 7 - self._par8])
-                else:
-                    ops.deconv_bwd(A[low], self.Wt[u["name"]], cat, Gd[low], self.w_view(u["name"], self.G), self.b_view(u["name"], self.G),
-                                   dy_off=0, xmask=self._mask_of(low), planar=self.planar)
-                self._grad_ready(u["name"])
-            elif up == "upcat":
-                self._block_bwd(a, A[low], skip, True)
-                W = self.Wup[a["name"]]
-                ops.conv3d_upcat_dgrad(Gd[a["name"]], W["up_d"], W["sk_d"], self._mask_of(low), None, Gd[low], cat, planar=self.planar)
-            else:
-                self._block_bwd(a, A[low], skip, True)
-                ops.conv3d_dgrad(Gd[a["name"]], self.Wd[a["name"]], cat, planar=self.planar)
-                ops.upsample_bwd(cat, Gd[low], dy_off=0, xmask=self._mask_of(low), planar=self.planar)
+            self.up[a["name"]].backward(low, skip, Gd["cat_%d" % ld])
         # encoder, deepest level first
         for ld in range(p.depth - 1, -1, -1):
             ca, cb = p.enc[ld]
@@ -867,20 +665,6 @@ class UNetEngine(EngineBase):
         if not self.input_grad:
             raise RuntimeError("this engine was built without input_grad=True")
         return self.dx_in
-
-    def _d2s_tmp(self, name, x_low, Wd_):
-        """(1, S, H, W, 4*Cout) scratch of the 2-D transposed conv for the current slice count"""
-        key = "t4_%d" % x_low.shape[1]
-        if key not in Wd_:
-            Wd_[key] = torch.empty(tuple(x_low.shape[:-1]) + (Wd_["b4"].numel(),), dtype=self.dtype, device=self.dev)
-        return Wd_[key]
-
-    @staticmethod
-    def _d2s_views(y, t4):
-        """matching 6-D views (S, H, ah, W, aw, Cout) of the full-resolution tensor y (1,S,2H,2W,Cout) and of t4 (1,S,H,W,4*Cout)"""
-        _, S, H, W, C4 = t4.shape
-        C = C4 // 4
-        return y.view(S, H, 2, W, 2, C), t4.view(S, H, W, 2, 2, C).permute(0, 1, 3, 2, 4, 5)
 
     def _dec_input_name(self, ld):
         """name of the activation that is up-sampled into decoder level ld"""
