@@ -1358,12 +1358,41 @@ __global__ void k_tile_scatter(const float* __restrict__ pred, const int32_t* __
         atomicAdd(&cnt[o], 1);
     }
 }
-__global__ void k_tile_finalize(const double* __restrict__ acc, const int32_t* __restrict__ cnt, double* __restrict__ out,
+// Gaussian-importance blending (nnU-Net / MONAI mode="gaussian"): the tile voxel (x, y, z) counts with w = ((double)gx[x] * (double)gy[y]) *
+// (double)gz[z] - the first product is exact (two 24-bit significands), the second rounds once - acc += w * pred, wsum += w.  One thread per
+// tile voxel covers its C channels; tiles of one launch overlap, so every add is a float64 atomic; 64-bit index arithmetic throughout.
+__global__ void __launch_bounds__(256) k_tile_scatter_weighted(const float* __restrict__ pred, const int32_t* __restrict__ idx, int B, int px, int py,
+                                                               int pz, int C, const float* __restrict__ gx, const float* __restrict__ gy,
+                                                               const float* __restrict__ gz, double* __restrict__ acc,
+                                                               double* __restrict__ wsum, int X, int Y, int Z) {
+    const int64_t per = (int64_t)px * py * pz, total = per * B;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = i / per;
+        int64_t r = i - b * per;
+        const int64_t z = r % pz; r /= pz;
+        const int64_t y = r % py;
+        const int64_t x = r / py;
+        const int64_t ox = (int64_t)idx[3 * b] + x, oy = (int64_t)idx[3 * b + 1] + y, oz = (int64_t)idx[3 * b + 2] + z;
+        if (ox < 0 || oy < 0 || oz < 0 || ox >= X || oy >= Y || oz >= Z) continue;
+        const double w = ((double)gx[x] * (double)gy[y]) * (double)gz[z];
+        const int64_t o = (ox * Y + oy) * Z + oz;
+        for (int64_t c = 0; c < C; ++c) atomicAdd(&acc[o * C + c], w * (double)pred[i * C + c]);
+        atomicAdd(&wsum[o], w);
+    }
+}
+// The divisor of a voxel, D = int32_t (the tile count) or double (the weight sum): not positive -> the voxel is uncovered, divide by 1.
+template <typename D> __device__ __forceinline__ bool tile_divisor(D d, double* q) {
+    const bool covered = d > (D)0;
+    *q = covered ? (double)d : 1.0;
+    return covered;
+}
+template <typename D>
+__global__ void k_tile_finalize(const double* __restrict__ acc, const D* __restrict__ cnt, double* __restrict__ out,
                                 int32_t* __restrict__ bad, int64_t nvox, int C) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) {
-        int c = cnt[i];
-        if (c <= 0) { atomicAdd(bad, 1); c = 1; }
-        for (int k = 0; k < C; ++k) out[i * C + k] = acc[i * C + k] / (double)c;
+        double c;
+        if (!tile_divisor<D>(cnt[i], &c)) atomicAdd(bad, 1);
+        for (int k = 0; k < C; ++k) out[i * C + k] = acc[i * C + k] / c;
     }
 }
 extern "C" int fmri_tile_gather(const float* vol, int X, int Y, int Z, const int32_t* idx, int B, int px, int py, int pz,
@@ -1449,7 +1478,27 @@ extern "C" int fmri_tile_scatter_accumulate(const float* pred, const int32_t* id
 extern "C" int fmri_tile_finalize(const double* acc, const int32_t* cnt, double* out, int32_t* bad, int64_t nvox, int C,
                                   fmri_stream_t stream) {
     if (nvox <= 0 || C <= 0) return FMRI_E_SHAPE;
-    k_tile_finalize<<<grid_for(nvox, 256, 4096), 256, 0, as_stream(stream)>>>(acc, cnt, out, bad, nvox, C);
+    k_tile_finalize<int32_t><<<grid_for(nvox, 256, 4096), 256, 0, as_stream(stream)>>>(acc, cnt, out, bad, nvox, C);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+extern "C" int fmri_tile_scatter_weighted(const float* pred, const int32_t* idx, int B, int px, int py, int pz, int C, const float* gx,
+                                          const float* gy, const float* gz, double* acc, double* wsum, int X, int Y, int Z,
+                                          fmri_stream_t stream) {
+    if (!pred || !idx || !gx || !gy || !gz || !acc || !wsum) return FMRI_E_SHAPE;
+    if (B <= 0 || px <= 0 || py <= 0 || pz <= 0 || C <= 0 || X <= 0 || Y <= 0 || Z <= 0) return FMRI_E_SHAPE;
+    if (((((uintptr_t)pred) | ((uintptr_t)idx) | ((uintptr_t)gx) | ((uintptr_t)gy) | ((uintptr_t)gz)) & 3) ||
+        ((((uintptr_t)acc) | ((uintptr_t)wsum)) & 7)) return FMRI_E_ALIGN;
+    k_tile_scatter_weighted<<<grid_for((int64_t)B * px * py * pz, 256, 4096), 256, 0, as_stream(stream)>>>(pred, idx, B, px, py, pz, C, gx, gy, gz,
+                                                                                                        acc, wsum, X, Y, Z);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+extern "C" int fmri_tile_finalize_weighted(const double* acc, const double* wsum, double* out, int32_t* bad, int64_t nvox, int C,
+                                           fmri_stream_t stream) {
+    if (!acc || !wsum || !out || !bad || nvox <= 0 || C <= 0) return FMRI_E_SHAPE;
+    if (((((uintptr_t)acc) | ((uintptr_t)wsum) | ((uintptr_t)out)) & 7) || (((uintptr_t)bad) & 3)) return FMRI_E_ALIGN;
+    k_tile_finalize<double><<<grid_for(nvox, 256, 4096), 256, 0, as_stream(stream)>>>(acc, wsum, out, bad, nvox, C);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
@@ -1540,8 +1589,8 @@ extern "C" int fmri_volume_pad_flip(const void* src, int src_dtype, int X, int Y
 }
 // out[g][c] = acc[a][c] / (double)cnt[a], a = lo + m(g): k_tile_finalize's division read through the mirror and the crop, so a variant's
 // means land un-mirrored in the caller's slot.  A zero count divides by 1 and is counted once per voxel.
-template <int EPT, typename IT>
-__global__ void __launch_bounds__(256) k_tile_finalize_flip(const double* __restrict__ acc, const int32_t* __restrict__ cnt, double* __restrict__ out,
+template <int EPT, typename IT, typename D>
+__global__ void __launch_bounds__(256) k_tile_finalize_flip(const double* __restrict__ acc, const D* __restrict__ cnt, double* __restrict__ out,
                                                             int32_t* __restrict__ bad, FlipGeo G, int C, int64_t total) {
     const int64_t chunks = (total + EPT - 1) / EPT;
     int nbad = 0;
@@ -1563,9 +1612,9 @@ __global__ void __launch_bounds__(256) k_tile_finalize_flip(const double* __rest
                 const int ay = G.lo[1] + ((G.mask & 2) ? G.n[1] - 1 - gy : gy);
                 const int az = G.lo[2] + ((G.mask & 4) ? G.n[2] - 1 - gz : gz);
                 const IT a = ((IT)ax * (IT)G.a[1] + (IT)ay) * (IT)G.a[2] + (IT)az;
-                int n = cnt[a];
-                if (n <= 0) { nbad += c == 0; n = 1; }
-                e = acc[a * (IT)C + (IT)c] / (double)n;
+                double n;
+                if (!tile_divisor<D>(cnt[a], &n)) nbad += c == 0;
+                e = acc[a * (IT)C + (IT)c] / n;
                 if (++c == C) { c = 0; if (++gz == G.n[2]) { gz = 0; if (++gy == G.n[1]) { gy = 0; ++gx; } } }
             }
             v[j] = e;
@@ -1580,46 +1629,56 @@ __global__ void __launch_bounds__(256) k_tile_finalize_flip(const double* __rest
     }
     if (nbad) atomicAdd(bad, nbad);
 }
-extern "C" int fmri_tile_finalize_flip(const double* acc, const int32_t* cnt, int AX, int AY, int AZ, int C, double* out, int X, int Y, int Z,
-                                       const int32_t* lo, int flip_mask, int32_t* bad, fmri_stream_t stream) {
+template <typename D>
+static int tile_finalize_flip(const double* acc, const D* cnt, int AX, int AY, int AZ, int C, double* out, int X, int Y, int Z, const int32_t* lo,
+                              int flip_mask, int32_t* bad, fmri_stream_t stream) {
     if (!acc || !cnt || !out || !bad || !lo || AX <= 0 || AY <= 0 || AZ <= 0 || C <= 0 || X <= 0 || Y <= 0 || Z <= 0 || (flip_mask & ~7)) return FMRI_E_SHAPE;
     const int A[3] = {AX, AY, AZ}, N[3] = {X, Y, Z};
     for (int k = 0; k < 3; ++k)
         if (lo[k] < 0 || lo[k] > A[k] - N[k]) return FMRI_E_SHAPE;          // the window [lo, lo + n) lies inside acc
-    if (((((uintptr_t)acc) | ((uintptr_t)out)) & 7) || ((((uintptr_t)cnt) | ((uintptr_t)bad)) & 3)) return FMRI_E_ALIGN;
+    if (((((uintptr_t)acc) | ((uintptr_t)out)) & 7) || (((uintptr_t)cnt) & (sizeof(D) - 1)) || (((uintptr_t)bad) & 3)) return FMRI_E_ALIGN;
     const FlipGeo G = {{X, Y, Z}, {AX, AY, AZ}, {lo[0], lo[1], lo[2]}, flip_mask};
     const int64_t total = (int64_t)X * Y * Z * C, atotal = (int64_t)AX * AY * AZ * C;
     const bool small = total + 2 < ((int64_t)1 << 31) && atotal < ((int64_t)1 << 31);
     const bool wide = ((uintptr_t)out & 15) == 0;
     hipStream_t s = as_stream(stream);
-#define L_(E_, IT_) k_tile_finalize_flip<E_, IT_><<<grid_for(ceil_div64(total, E_), 256, 4096), 256, 0, s>>>(acc, cnt, out, bad, G, C, total)
+#define L_(E_, IT_) k_tile_finalize_flip<E_, IT_, D><<<grid_for(ceil_div64(total, E_), 256, 4096), 256, 0, s>>>(acc, cnt, out, bad, G, C, total)
     if (small) { if (wide) L_(2, unsigned); else L_(1, unsigned); }
     else { if (wide) L_(2, int64_t); else L_(1, int64_t); }
 #undef L_
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }
+extern "C" int fmri_tile_finalize_flip(const double* acc, const int32_t* cnt, int AX, int AY, int AZ, int C, double* out, int X, int Y, int Z,
+                                       const int32_t* lo, int flip_mask, int32_t* bad, fmri_stream_t stream) {
+    return tile_finalize_flip<int32_t>(acc, cnt, AX, AY, AZ, C, out, X, Y, Z, lo, flip_mask, bad, stream);
+}
+extern "C" int fmri_tile_finalize_flip_weighted(const double* acc, const double* wsum, int AX, int AY, int AZ, int C, double* out, int X, int Y,
+                                                int Z, const int32_t* lo, int flip_mask, int32_t* bad, fmri_stream_t stream) {
+    return tile_finalize_flip<double>(acc, wsum, AX, AY, AZ, C, out, X, Y, Z, lo, flip_mask, bad, stream);
+}
 
 // ---- several labels: a label map straight from the overlap-add, and training targets from a label map
 // out[v] per voxel from q_c = acc[v][c] / cnt[v] (float64, fmri_tile_finalize's division).  C == 1: values[0] where q_0 > threshold
 // (reference prediction.py:257); C > 1: values[k], k the FIRST index of the maximum (np.argmax), 0 where max q < threshold (:219-222).
-__global__ void __launch_bounds__(256) k_tile_finalize_labels(const double* __restrict__ acc, const int32_t* __restrict__ cnt,
+template <typename D>
+__global__ void __launch_bounds__(256) k_tile_finalize_labels(const double* __restrict__ acc, const D* __restrict__ cnt,
                                                               uint8_t* __restrict__ out, int32_t* __restrict__ bad, int64_t nvox, int C,
                                                               double threshold, FmriLabelValues V) {
     __shared__ __attribute__((aligned(4))) uint8_t vals[FMRI_MAX_LABELS];
     fmri_label_tables(V, C, vals, nullptr);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = cnt[i];
-        if (c <= 0) {
+        double c;
+        if (!tile_divisor<D>(cnt[i], &c)) {
             atomicAdd(bad, 1);
             out[i] = 0;
             continue;
         }
         const double* const row = acc + i * C;
-        double best = row[0] / (double)c;
+        double best = row[0] / c;
         int k = 0;
         for (int j = 1; j < C; ++j) {
-            const double q = row[j] / (double)c;
+            const double q = row[j] / c;
             if (q > best) { best = q; k = j; }
         }
         const bool keep = C == 1 ? best > threshold : !(best < threshold);
@@ -1630,7 +1689,16 @@ extern "C" int fmri_tile_finalize_labels(const double* acc, const int32_t* cnt, 
                                          double threshold, const uint8_t* values, fmri_stream_t stream) {
     FmriLabelValues V;
     if (!acc || !cnt || !out || !bad || nvox <= 0 || fmri_label_values(values, C, &V) != FMRI_OK) return FMRI_E_SHAPE;
-    k_tile_finalize_labels<<<grid_for(nvox, 256, 4096), 256, 0, as_stream(stream)>>>(acc, cnt, out, bad, nvox, C, threshold, V);
+    k_tile_finalize_labels<int32_t><<<grid_for(nvox, 256, 4096), 256, 0, as_stream(stream)>>>(acc, cnt, out, bad, nvox, C, threshold, V);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+extern "C" int fmri_tile_finalize_labels_weighted(const double* acc, const double* wsum, uint8_t* out, int32_t* bad, int64_t nvox, int C,
+                                                  double threshold, const uint8_t* values, fmri_stream_t stream) {
+    FmriLabelValues V;
+    if (!acc || !wsum || !out || !bad || nvox <= 0 || fmri_label_values(values, C, &V) != FMRI_OK) return FMRI_E_SHAPE;
+    if (((((uintptr_t)acc) | ((uintptr_t)wsum)) & 7) || (((uintptr_t)bad) & 3)) return FMRI_E_ALIGN;
+    k_tile_finalize_labels<double><<<grid_for(nvox, 256, 4096), 256, 0, as_stream(stream)>>>(acc, wsum, out, bad, nvox, C, threshold, V);
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }

@@ -191,9 +191,11 @@ class Stage(object):
     `patch_depth`, optional `scale_data`, optional `preproc`: a callable, or the name of a filter in `fetal_net.preprocess` as in the
     reference's configs); `intensity`: None or a key of INTENSITY_METHODS; `norm`: None or {'mean', 'std'}; `augment`: None | 'flip' (the
     8 flips) | 'all' (`n_augment` random variants); `device`: where the stage's intensity preparation, its zoom and the median over its
-    variants run (None / True / False as for `Zoom`)."""
+    variants run (None / True / False as for `Zoom`); `blend` / `blend_sigma_scale` (keyword-only): how overlapping tiles are combined, None
+    (every tile counts the same) or 'gaussian', as for `prediction.patch_wise_prediction`."""
 
-    def __init__(self, model, config, intensity=None, norm=None, augment=None, n_augment=0, overlap=0.9, device=None):
+    def __init__(self, model, config, intensity=None, norm=None, augment=None, n_augment=0, overlap=0.9, device=None, *, blend=None,
+                 blend_sigma_scale=prediction.DEFAULT_SIGMA_SCALE):
         if intensity is not None and intensity not in INTENSITY_METHODS:
             raise Exception("Unknown preprocess: {}".format(intensity))
         if augment not in (None, "flip", "all"):
@@ -206,6 +208,8 @@ class Stage(object):
             raise TypeError("config['preproc'] must be a callable or one of %s of fetal_net.preprocess (got %r)" % (preprocess.__all__, pre))
         self.model, self.config, self.intensity, self.norm = model, config, intensity, norm
         self.augment, self.n_augment, self.overlap, self.device = augment, n_augment, overlap, device
+        prediction._blend_key(blend, blend_sigma_scale)
+        self.blend = dict(blend=blend, blend_sigma_scale=blend_sigma_scale)
 
     @property
     def patch(self):
@@ -298,7 +302,7 @@ class Stage(object):
         tensor = preprocess._is_device_tensor(vol)
         t = vol.contiguous() if tensor else prediction._upload_f64(vol)
         variants = prediction._flip_variants(tuple(t.shape)) if self.augment == "flip" else [(0, 0)]
-        stack = prediction._resident_flip_stack(t, self.model, self.overlap, self.patch, variants)
+        stack = prediction._resident_flip_stack(t, self.model, self.overlap, self.patch, variants, **self.blend)
         if stack.shape[-1] == 1:
             stack = stack[..., 0]
         if self.augment != "flip":
@@ -311,12 +315,14 @@ class Stage(object):
         """the route of foreign models and of augment='all': every variant a patch_wise_prediction of a host volume, the stack of their
         results reduced by `median_of_variants` (also the other arm of tools/bench_tta.py)"""
         if self.augment == "all":
-            variants = predict_augment(vol, model=self.model, overlap_factor=self.overlap, num_augments=self.n_augment, patch_shape=self.patch)
+            variants = predict_augment(vol, model=self.model, overlap_factor=self.overlap, num_augments=self.n_augment, patch_shape=self.patch,
+                                       **self.blend)
         elif self.augment == "flip":
-            variants = np.stack(prediction._predict_flips_host(vol, model=self.model, overlap_factor=self.overlap, config=self.config))
+            variants = np.stack(prediction._predict_flips_host(vol, model=self.model, overlap_factor=self.overlap, config=self.config,
+                                                               **self.blend))
         else:
             return np.asarray(patch_wise_prediction(model=self.model, data=vol[np.newaxis], overlap_factor=self.overlap,
-                                                    patch_shape=self.patch)).squeeze()
+                                                    patch_shape=self.patch, **self.blend)).squeeze()
         return np.asarray(variants if keep_variants else median_of_variants(variants, self.device)).squeeze()
 
 
@@ -411,22 +417,28 @@ class VolumePipeline(object):
 
 def predict_volume(data, model, config, overlap_factor=0.9, preprocess_method=None, norm_params=None, augment=None, num_augment=0,
                    model2=None, config2=None, preprocess_method2=None, norm_params2=None, augment2=None, num_augment2=0,
-                   z_scale=None, xy_scale=None, return_all_preds=False, device=None):
+                   z_scale=None, xy_scale=None, return_all_preds=False, device=None, *, blend=None,
+                   blend_sigma_scale=prediction.DEFAULT_SIGMA_SCALE):
     """One-call form with the argument names of the reference's `main()` (predict_nifti2.py:98-160), on arrays: `data` = the volume as read
     from the NIfTI file.  Returns a dict: 'data' (the prepared volume the first model saw, before its border), 'prediction' (first stage, on
     the input grid) and, with model2 / config2, 'mask' and 'prediction_roi' (second stage on the padded bounding box, volume-sized).
     `device` (not in the reference): where the intensity preparation, the zooms and the variant medians run - None / True / False as for
-    `Zoom`.  config['preproc'] may name a filter of `fetal_net.preprocess`, as the reference's configs do."""
+    `Zoom`.  config['preproc'] may name a filter of `fetal_net.preprocess`, as the reference's configs do.
+    `blend` / `blend_sigma_scale` (not in the reference): how both stages combine overlapping tiles, as for `Stage`."""
     if config2 is not None and model2 is None:
         raise ValueError("config2 given without model2")
-    first = Stage(model, config, preprocess_method, norm_params, augment, num_augment, overlap_factor, device)
+    blending = dict(blend=blend, blend_sigma_scale=blend_sigma_scale)
+    first = Stage(model, config, preprocess_method, norm_params, augment, num_augment, overlap_factor, device, **blending)
     second = None if config2 is None else Stage(model2, config2, preprocess_method2, norm_params2, augment2, num_augment2, overlap_factor,
-                                                device)
+                                                device, **blending)
     return VolumePipeline(first, second, resolution=(xy_scale, z_scale), device=device)(data, keep_variants=return_all_preds)
 
 
 def secondary_prediction(mask, vol, config2, model2, preprocess_method2=None, norm_params2=None, overlap_factor=0.9, augment2=None,
-                         num_augment=32, return_all_preds=False, padding=ROI_PADDING):
-    """the second stage alone (reference predict_nifti2.py:25-53), for callers that already hold a first-stage mask"""
-    stage = Stage(model2, config2, preprocess_method2, norm_params2, augment2, num_augment, overlap_factor)
+                         num_augment=32, return_all_preds=False, padding=ROI_PADDING, *, blend=None,
+                         blend_sigma_scale=prediction.DEFAULT_SIGMA_SCALE):
+    """the second stage alone (reference predict_nifti2.py:25-53), for callers that already hold a first-stage mask; `blend` /
+    `blend_sigma_scale` as for `Stage`"""
+    stage = Stage(model2, config2, preprocess_method2, norm_params2, augment2, num_augment, overlap_factor, blend=blend,
+                  blend_sigma_scale=blend_sigma_scale)
     return VolumePipeline(None, stage, roi_padding=padding).run_second(np.asarray(vol), mask, keep_variants=return_all_preds)

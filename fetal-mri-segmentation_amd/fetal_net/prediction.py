@@ -10,6 +10,8 @@ its slices to every tile (fmri_tile_gather_stack).  A volume that is already on 
 of `predict_flips` / `fetal_net.pipeline` - runs the same captured loop without touching the host: fmri_volume_pad_flip writes the
 mirrored, padded volume, fmri_tile_finalize_flip the cropped, un-mirrored means (`_resident_overlap_add`).  Any other object with
 `.output_shape` / `.predict(ndarray)` (the reference's duck-typing contract) is driven through the same geometry with host-side tiles.
+Beyond the reference, `blend="gaussian"` (keyword-only, default None = the reference's uniform mean) weights every tile voxel by a Gaussian
+of its distance to the tile centre on all of these routes (`gaussian_tile_tables`; fmri_tile_scatter_weighted / fmri_tile_finalize*_weighted).
 """
 import gc
 import itertools
@@ -102,24 +104,72 @@ def _unpad(arr, pad_for_fit):
     return arr
 
 
+BLEND_MODES = (None, "gaussian")
+DEFAULT_SIGMA_SCALE = 0.125                  # nnU-Net's and MONAI's value
+
+
+def gaussian_tile_tables(tile, sigma_scale=DEFAULT_SIGMA_SCALE):
+    """The importance weights of a Gaussian-blended output tile (px, py, pz), one float32 table per axis:
+        g_a[i] = float32(exp(-0.5 * ((i - (p_a - 1) / 2) / (sigma_scale * p_a))**2)),  i = 0 .. p_a - 1,
+    computed in float64 and rounded once; an axis of extent 1 gives [1.0].  This is the only place that computes them: the host loop,
+    the kernels (fmri_tile_scatter_weighted reads these tables) and the tests all take the weight of a tile voxel as
+    w = (float64(gx[x]) * float64(gy[y])) * float64(gz[z]).  At the default sigma_scale the smallest entry lies above exp(-8), so w
+    cannot underflow."""
+    s = _sigma_scale(sigma_scale)
+    tables = []
+    for p in tile:
+        p = int(p)
+        if p <= 0:
+            raise ValueError("gaussian_tile_tables: tile extents must be positive (got %r)" % (tuple(tile),))
+        i = np.arange(p, dtype=np.float64)
+        tables.append(np.exp(-0.5 * ((i - (p - 1) / 2.0) / (s * p)) ** 2).astype(np.float32))
+    return tables
+
+
+def _sigma_scale(sigma_scale):
+    s = float(sigma_scale)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError("blend_sigma_scale must be a positive finite number (got %r)" % (sigma_scale,))
+    return s
+
+
+def _blend_key(blend, sigma_scale):
+    """the checked (blend, sigma_scale) pair the tile loops are keyed by: (None, None) for the unweighted mean"""
+    if blend not in BLEND_MODES:
+        raise ValueError("blend must be None or 'gaussian' (got %r)" % (blend,))
+    s = _sigma_scale(sigma_scale)
+    return (blend, s) if blend is not None else (None, None)
+
+
+def _tile_weights(tile, sigma_scale):
+    """float64 (px, py, pz): w = (gx[x] * gy[y]) * gz[z] of `gaussian_tile_tables`, in the order every route multiplies in"""
+    gx, gy, gz = (g.astype(np.float64) for g in gaussian_tile_tables(tile, sigma_scale))
+    return (gx[:, None, None] * gy[None, :, None]) * gz[None, None, :]
+
+
 def patch_wise_prediction(model, data, patch_shape, overlap_factor=0, batch_size=5, permute=False, truth_data=None,
-                          prev_truth_index=None, prev_truth_size=None):
+                          prev_truth_index=None, prev_truth_size=None, *, blend=None, blend_sigma_scale=DEFAULT_SIGMA_SCALE):
     """data (1,X,Y,Z) -> (X,Y,Z,C) float64 mean of all tiles covering each voxel.  A float64 CUDA tensor stays one: the tile loop then
     runs on the resident volume (`_resident_overlap_add`) and the means come back as a CUDA tensor; that form needs the device tile loop
-    (an engine model, no permute, no truth_data) and raises TypeError where it does not apply."""
-    return _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size, None)
+    (an engine model, no permute, no truth_data) and raises TypeError where it does not apply.
+    blend: None - the reference's rule, every tile counts the same - or 'gaussian': every tile voxel counts with the Gaussian importance
+    weight of `gaussian_tile_tables` (sigma = blend_sigma_scale * tile extent per axis), sum(w * p) / sum(w), on every route."""
+    return _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size, None,
+                       _blend_key(blend, blend_sigma_scale))
 
 
 def patch_wise_label_map(model, data, patch_shape, overlap_factor=0, batch_size=5, threshold=0.5, labels=None, permute=False,
-                         truth_data=None, prev_truth_index=None, prev_truth_size=None):
+                         truth_data=None, prev_truth_index=None, prev_truth_size=None, *, blend=None,
+                         blend_sigma_scale=DEFAULT_SIGMA_SCALE):
     """data (1,X,Y,Z) -> (X,Y,Z) uint8 label map: get_prediction_labels of patch_wise_prediction's mean, taken on the device.  The tile
     loop is patch_wise_prediction's - same captured graphs, same slab pipeline - with fmri_tile_finalize_labels in place of
     fmri_tile_finalize, so one byte per voxel comes down instead of 8 * C.  Wherever patch_wise_prediction leaves the device path
-    (permute, a foreign model object) the label map is get_prediction_labels of its result."""
+    (permute, a foreign model object) the label map is get_prediction_labels of its result.  blend / blend_sigma_scale: as for
+    patch_wise_prediction (the label rule is then applied to the blended means, fmri_tile_finalize_labels_weighted)."""
     n_labels = int(model.output_shape[1] if _is3d(model) else model.output_shape[-1])
     values = _label_values(n_labels, labels)
     out = _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size,
-                      (float(threshold), values))
+                      (float(threshold), values), _blend_key(blend, blend_sigma_scale))
     if out.dtype != np.uint8:                                # the host path's float64 means (X, Y, Z, C)
         out = np.asarray(prediction_to_image(np.moveaxis(out, -1, 0)[np.newaxis], label_map=True, threshold=threshold,
                                              labels=values)).astype(np.uint8)
@@ -133,12 +183,14 @@ def _label_values(n_labels, labels):
     return values
 
 
-def _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size, label_map):
-    """patch_wise_prediction (label_map None) / patch_wise_label_map ((threshold, values): the device path then returns the uint8 map)"""
+def _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, prev_truth_index, prev_truth_size, label_map,
+                blend=(None, None)):
+    """patch_wise_prediction (label_map None) / patch_wise_label_map ((threshold, values): the device path then returns the uint8 map);
+    blend: the pair of `_blend_key`"""
     if _is_device_tensor(data):                              # a float64 CUDA tensor stays one (the convention of fetal_net.preprocess)
         if label_map is not None:
             raise TypeError("patch_wise_label_map takes host volumes (got a device tensor)")
-        return _patch_wise_resident(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data)
+        return _patch_wise_resident(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, blend)
     is3d, pad0, pad_for_fit, data_0, indices, data_shape = _geometry(model, data, patch_shape, overlap_factor)
     layout2d = getattr(model, "_input_layout", "") == "channels_last_2d"
     # previous-slice truth on the device: 2-D models only (a 3-D model's truth channels are concatenated along z, reference prediction.py:100-110)
@@ -151,7 +203,7 @@ def _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, t
             truth_0 = np.pad(truth_0, pad_for_fit, 'constant', constant_values=0)
         out, count_ok = _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d, truth_0=truth_0,
                                             aux_dz=int(prev_truth_index) if truth_0 is not None else 0,
-                                            aux_nz=int(prev_truth_size) if truth_0 is not None else 0, label_map=label_map)
+                                            aux_nz=int(prev_truth_size) if truth_0 is not None else 0, label_map=label_map, blend=blend)
         assert count_ok, 'Found zeros in count'
         out = _unpad(out, pad_for_fit)
         assert np.array_equal(out.shape[:3], data[0].shape), 'prediction shape wrong'
@@ -166,7 +218,10 @@ def _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, t
     tb_iter = iter(ThreadedGenerator(batch_iterator(indices, batch_size, data_0, patch_shape, truth_0, prev_truth_index,
                                                     truth_patch_shape), queue_maxsize=50))
     predicted_output = np.zeros(data_shape)
-    predicted_count = np.zeros(data_shape, dtype=np.int16)
+    blended = blend[0] is not None
+    # blended: the float64 weight sums (X, Y, Z) take the place of the counts (the device rule, fmri_tile_scatter_weighted)
+    predicted_count = np.zeros(data_shape[:3]) if blended else np.zeros(data_shape, dtype=np.int16)
+    weights = {}                                             # output-tile extent -> float64 weights
     for curr_batch, batch_indices in tb_iter:
         curr_batch = np.asarray(curr_batch)
         if is3d:
@@ -175,21 +230,32 @@ def _patch_wise(model, data, patch_shape, overlap_factor, batch_size, permute, t
         prediction = prediction.transpose([0, 2, 3, 4, 1]) if is3d else np.expand_dims(prediction, -2)
         for patch, (x, y, z) in zip(prediction, batch_indices):
             xl, yl, zl = patch.shape[:-1]
+            if blended:
+                w = weights.get((xl, yl, zl))
+                if w is None:
+                    w = weights[(xl, yl, zl)] = _tile_weights((xl, yl, zl), blend[1])
+                predicted_output[x:x + xl, y:y + yl, z:z + zl, :] += w[..., None] * patch
+                predicted_count[x:x + xl, y:y + yl, z:z + zl] += w
+                continue
             predicted_output[x:x + xl, y:y + yl, z:z + zl, :] += patch
             predicted_count[x:x + xl, y:y + yl, z:z + zl] += 1
     assert np.all(predicted_count > 0), 'Found zeros in count'
+    if blended:
+        predicted_count = predicted_count[..., None]
     predicted_output, predicted_count = _unpad(predicted_output, pad_for_fit), _unpad(predicted_count, pad_for_fit)
     assert np.array_equal(predicted_count.shape[:-1], data[0].shape), 'prediction shape wrong'
     return predicted_output / predicted_count
 
 
-def _tile_loop_state(model, vshape, n, patch_shape, batch_size, data_shape, is3d=True, aux_dz=0, aux_nz=0):
+def _tile_loop_state(model, vshape, n, patch_shape, batch_size, data_shape, is3d=True, aux_dz=0, aux_nz=0, blend=(None, None)):
     """-> (state, tile-group size).  The static buffers of the device tile loop (volume, accumulators, tile batch, index list) and one
     captured hipGraph per distinct batch size - gather -> network -> float64 overlap-add - cached on the model and re-used for every
     following volume of the same padded shape `vshape` tiled into `n` tiles, whichever loop drives them (`_device_overlap_add` from host
     memory, `_resident_overlap_add` from a device tensor).  2-D models: a tile (px, py, slices) IS the channels-last input of the
     network (the slice stack is the channel axis) and its output is one slice (px, py, 1); with aux_nz every tile carries aux_nz more
-    channels, its truth slices from aux_dz slices past the tile's corner (reference batch_iterator, prediction.py:98-114)."""
+    channels, its truth slices from aux_dz slices past the tile's corner (reference batch_iterator, prediction.py:98-114).
+    blend (the pair of `_blend_key`): 'gaussian' appends the pair to the key; the state then holds the three device tables of the output
+    tile and the float64 weight sums `wsum` instead of the counts `cnt`, and the captured body ends in fmri_tile_scatter_weighted."""
     import torch
     from fmri_hip import ops
     patch = tuple(int(p) for p in patch_shape)
@@ -210,13 +276,20 @@ def _tile_loop_state(model, vshape, n, patch_shape, batch_size, data_shape, is3d
     aux_nz = int(aux_nz)
     aux_dz = int(aux_dz) if aux_nz else 0
     assert aux_nz == 0 or not is3d
+    blended = blend[0] is not None
     key = (vshape, ashape, patch, tuple(sizes), use_graph, aux_dz, aux_nz)
+    if blended:
+        key += (tuple(blend),)                               # (the unweighted key ends in aux_dz, aux_nz)
     st = model.__dict__.get("_tile_state")
     if st is None or st["key"] != key:
         st = dict(key=key, vol=torch.empty(vshape, dtype=torch.float32, device="cuda"),
                   aux=torch.empty(vshape, dtype=torch.float32, device="cuda") if aux_nz else None,
-                  acc=torch.zeros(ashape, dtype=torch.float64, device="cuda"),
-                  cnt=torch.zeros(ashape[:3], dtype=torch.int32, device="cuda"), per_b={})
+                  acc=torch.zeros(ashape, dtype=torch.float64, device="cuda"), per_b={})
+        if blended:
+            st["wsum"] = torch.zeros(ashape[:3], dtype=torch.float64, device="cuda")
+            st["tables"] = tuple(torch.from_numpy(g).cuda() for g in gaussian_tile_tables(patch if is3d else (patch[0], patch[1], 1), blend[1]))
+        else:
+            st["cnt"] = torch.zeros(ashape[:3], dtype=torch.int32, device="cuda")
         for B in sizes:
             eng = model.engine(B)
             # 3-D: (B, px, py, pz, 1) = NDHWC with one channel; 2-D: (1, B, px, py, slices [+ truth slices]) = the planar layout, slices as channels
@@ -232,7 +305,10 @@ def _tile_loop_state(model, vshape, n, patch_shape, batch_size, data_shape, is3d
                 else:
                     ops.tile_gather(st["vol"], pb["idx"], patch, pb["tiles"])
                 e.predict(pb["tiles"])
-                ops.tile_scatter_accumulate(e.probs, pb["idx"], opatch, st["acc"], st["cnt"])
+                if blended:
+                    ops.tile_scatter_weighted(e.probs, pb["idx"], opatch, st["tables"], st["acc"], st["wsum"])
+                else:
+                    ops.tile_scatter_accumulate(e.probs, pb["idx"], opatch, st["acc"], st["cnt"])
 
             pb["body"] = body
             if use_graph:
@@ -263,11 +339,13 @@ def _tile_loop_state(model, vshape, n, patch_shape, batch_size, data_shape, is3d
 
 
 def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_shape, is3d=True, truth_0=None, aux_dz=0, aux_nz=0,
-                        label_map=None):
+                        label_map=None, blend=(None, None)):
     """Upload once, then per tile batch the captured gather -> network -> float64 overlap-add of `_tile_loop_state`, all on the device.
     truth_0 (2-D models): the padded truth volume (data_0's extent), see `_tile_loop_state`.
     label_map (threshold, values): finished slabs become label bytes on the device (fmri_tile_finalize_labels) and the uint8 map
-    (X, Y, Z) is what comes down and is returned; None: the float64 means (X, Y, Z, C)."""
+    (X, Y, Z) is what comes down and is returned; None: the float64 means (X, Y, Z, C).
+    blend (the pair of `_blend_key`): with 'gaussian' the slabs are divided by their weight sums (fmri_tile_finalize_weighted /
+    fmri_tile_finalize_labels_weighted)."""
     import torch
     from fmri_hip import ops
     patch = tuple(int(p) for p in patch_shape)
@@ -277,7 +355,9 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
     aux_nz = int(aux_nz) if truth_0 is not None else 0
     aux_dz = int(aux_dz) if aux_nz else 0
     assert aux_nz == 0 or tuple(truth_0.shape) == vshape
-    st, batch_size = _tile_loop_state(model, vshape, n, patch, batch_size, ashape, is3d, aux_dz, aux_nz)
+    st, batch_size = _tile_loop_state(model, vshape, n, patch, batch_size, ashape, is3d, aux_dz, aux_nz, blend)
+    blended = blend[0] is not None
+    div = st["wsum"] if blended else st["cnt"]
     # ---- the volume goes up and the result comes down in x-slabs, pipelined with the tile groups (23 % of a volume's
     # time was host work - a pageable 42 MB upload in front of the first tile and a pageable 84 MB float64 download behind the last).
     # Tiles are ordered x-major (itertools.product), so tile group g only needs the x-range up to its last tile's end, and every voxel
@@ -293,7 +373,7 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
     up, down = st["up_stream"], st["down_stream"]
     main = torch.cuda.current_stream()
     st["acc"].zero_()
-    st["cnt"].zero_()
+    div.zero_()
     idx_all = torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).cuda()
     if label_map is None:
         out_dev = torch.empty_like(st["acc"])
@@ -331,9 +411,11 @@ def _device_overlap_add(model, data_0, indices, patch_shape, batch_size, data_sh
         final = ashape[0] if hi >= n else min(ashape[0], min(starts_x[hi:]))
         if final > done_to:
             if label_map is None:
-                ops.tile_finalize(st["acc"][done_to:final], st["cnt"][done_to:final], out_dev[done_to:final], bad)
+                (ops.tile_finalize_weighted if blended else ops.tile_finalize)(st["acc"][done_to:final], div[done_to:final],
+                                                                               out_dev[done_to:final], bad)
             else:
-                ops.tile_finalize_labels(st["acc"][done_to:final], st["cnt"][done_to:final], out_dev[done_to:final], bad, *label_map)
+                (ops.tile_finalize_labels_weighted if blended else ops.tile_finalize_labels)(
+                    st["acc"][done_to:final], div[done_to:final], out_dev[done_to:final], bad, *label_map)
             down.wait_stream(main)
             with torch.cuda.stream(down):
                 out_host[done_to:final].copy_(out_dev[done_to:final], non_blocking=True)
@@ -362,13 +444,14 @@ def _device_tile_loop_refusal(model, permute=False, truth_data=None):
     return None
 
 
-def _resident_overlap_add(model, vol, patch_shape, overlap_factor, batch_size, variants, stack):
+def _resident_overlap_add(model, vol, patch_shape, overlap_factor, batch_size, variants, stack, blend=(None, None)):
     """The device tile loop on a volume that is already there.  vol: float64 CUDA tensor (X, Y, Z), unpadded; variants: one
     (forward flip mask, backward flip mask) pair per slot of stack, a float64 CUDA tensor (K, X, Y, Z, C).  Per variant: the mirrored,
     padded fp32 volume of the tiler is written by fmri_volume_pad_flip (the 1st-percentile pad constants come from ops.percentile_f64,
     once per call - mirroring does not change them - and only when something is padded), the captured graphs of `_tile_loop_state`
     replay over the same index list as the host-fed loop, and fmri_tile_finalize_flip writes the means, cropped and mirrored back, into
-    the variant's slot.  Nothing is copied to the host but the count of uncovered voxels, once, at the end."""
+    the variant's slot (blend 'gaussian', the pair of `_blend_key`: fmri_tile_finalize_flip_weighted divides by the weight sums).  Nothing
+    is copied to the host but the count of uncovered voxels, once, at the end."""
     import torch
     from fmri_hip import ops
     shape = tuple(int(s) for s in vol.shape)
@@ -376,7 +459,9 @@ def _resident_overlap_add(model, vol, patch_shape, overlap_factor, batch_size, v
     patch = tuple(int(p) for p in patch_shape)
     n = len(indices)
     with torch.cuda.device(vol.device):
-        st, batch_size = _tile_loop_state(model, vshape, n, patch, batch_size, data_shape, is3d)
+        st, batch_size = _tile_loop_state(model, vshape, n, patch, batch_size, data_shape, is3d, blend=blend)
+        blended = blend[0] is not None
+        div = st["wsum"] if blended else st["cnt"]
         assert tuple(stack.shape) == (len(variants),) + shape + (int(data_shape[3]),) and stack.dtype == torch.float64
         lo0, lo1 = [p[0] for p in pad0], [p[0] for p in pad_for_fit]
         padded0, padded1 = np.sum(pad0) > 0, np.sum(pad_for_fit) > 0
@@ -397,7 +482,7 @@ def _resident_overlap_add(model, vol, patch_shape, overlap_factor, batch_size, v
             else:
                 ops.volume_pad_flip(vol, st["vol"], lo0 if padded0 else lo1, fwd, fill0)
             st["acc"].zero_()
-            st["cnt"].zero_()
+            div.zero_()
             for i in range(0, n, batch_size):
                 bidx = idx_all[i:min(n, i + batch_size)]
                 pb = st["per_b"][int(bidx.shape[0])]
@@ -406,7 +491,7 @@ def _resident_overlap_add(model, vol, patch_shape, overlap_factor, batch_size, v
                     pb["graph"].replay()
                 else:
                     pb["body"]()
-            ops.tile_finalize_flip(st["acc"], st["cnt"], stack[k], bad, lo1, back)
+            (ops.tile_finalize_flip_weighted if blended else ops.tile_finalize_flip)(st["acc"], div, stack[k], bad, lo1, back)
         assert int(bad.item()) == 0, 'Found zeros in count'
     return stack
 
@@ -417,7 +502,7 @@ def _resident_stack(model, vol, n_variants):
     return torch.empty((n_variants,) + tuple(int(s) for s in vol.shape) + (n_out,), dtype=torch.float64, device=vol.device)
 
 
-def _patch_wise_resident(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data):
+def _patch_wise_resident(model, data, patch_shape, overlap_factor, batch_size, permute, truth_data, blend=(None, None)):
     """patch_wise_prediction of a float64 CUDA tensor (1, X, Y, Z) -> float64 CUDA tensor (X, Y, Z, C)"""
     import torch
     why = _device_tile_loop_refusal(model, permute, truth_data)
@@ -426,7 +511,7 @@ def _patch_wise_resident(model, data, patch_shape, overlap_factor, batch_size, p
     if why is not None:
         raise TypeError("patch_wise_prediction of a device tensor needs the device tile loop: " + why)
     vol = data[0].contiguous()
-    return _resident_overlap_add(model, vol, patch_shape, overlap_factor, batch_size, [(0, 0)], _resident_stack(model, vol, 1))[0]
+    return _resident_overlap_add(model, vol, patch_shape, overlap_factor, batch_size, [(0, 0)], _resident_stack(model, vol, 1), blend)[0]
 
 
 def get_prediction_labels(prediction, threshold=0.5, labels=None):
@@ -499,7 +584,7 @@ def flip_it(data_, axes):
 FLIP_AXES = [axes for r in range(4) for axes in itertools.combinations([0, 1, 2], r)]      # the reference's variant order
 
 
-def _predict_flips_host(data, model, overlap_factor, config):
+def _predict_flips_host(data, model, overlap_factor, config, blend=None, blend_sigma_scale=DEFAULT_SIGMA_SCALE):
     """the 8 axis-flip variants, each mirrored with numpy, predicted patch-wise from host memory and flipped back (reference
     prediction.py:65-85): the route of models without the device tile loop, and the other arm of tools/bench_tta.py"""
     patch_shape = list(config["patch_shape"]) + [config["patch_depth"]]
@@ -507,7 +592,7 @@ def _predict_flips_host(data, model, overlap_factor, config):
     for axes in FLIP_AXES:
         flipped = flip_it(data, axes)
         pred = patch_wise_prediction(model=model, data=np.expand_dims(flipped.squeeze(), 0), overlap_factor=overlap_factor,
-                                     patch_shape=patch_shape).squeeze()
+                                     patch_shape=patch_shape, blend=blend, blend_sigma_scale=blend_sigma_scale).squeeze()
         predictions.append(flip_it(pred, axes).squeeze())
     return predictions
 
@@ -534,9 +619,10 @@ def resident_tta_default():
     return os.environ.get("FMRI_TTA_RESIDENT", "1") != "0"
 
 
-def _resident_flip_stack(vol, model, overlap_factor, patch_shape, variants):
+def _resident_flip_stack(vol, model, overlap_factor, patch_shape, variants, blend=None, blend_sigma_scale=DEFAULT_SIGMA_SCALE):
     """the variants' predictions of a float64 CUDA volume (X, Y, Z) as one resident stack (K, X, Y, Z, C)"""
-    return _resident_overlap_add(model, vol, patch_shape, overlap_factor, 5, variants, _resident_stack(model, vol, len(variants)))
+    return _resident_overlap_add(model, vol, patch_shape, overlap_factor, 5, variants, _resident_stack(model, vol, len(variants)),
+                                 _blend_key(blend, blend_sigma_scale))
 
 
 def _upload_f64(arr):
@@ -553,11 +639,13 @@ def _download(t):
     return host.numpy()
 
 
-def predict_flips(data, model, overlap_factor, config):
+def predict_flips(data, model, overlap_factor, config, *, blend=None, blend_sigma_scale=DEFAULT_SIGMA_SCALE):
     """the 8 axis-flip variants, each predicted patch-wise and flipped back; returns the list (reference prediction.py:65-85).  With a
     model that has the device tile loop the volume goes up once, every variant is mirrored, tiled and mirrored back on the device
     (`_resident_overlap_add`) and the stack of 8 comes down once; a float64 CUDA tensor stays one: the list then holds 8 views of one
-    resident stack (8, X, Y, Z[, C]).  Any other model takes `_predict_flips_host`."""
+    resident stack (8, X, Y, Z[, C]).  Any other model takes `_predict_flips_host`.  blend / blend_sigma_scale: as for
+    patch_wise_prediction, for every variant."""
+    _blend_key(blend, blend_sigma_scale)
     patch_shape = list(config["patch_shape"]) + [config["patch_depth"]]
     tensor = _is_device_tensor(data)
     why = _device_tile_loop_refusal(model)
@@ -570,9 +658,10 @@ def predict_flips(data, model, overlap_factor, config):
             raise TypeError("predict_flips of a device tensor needs the device tile loop: " + why)
     elif variants is None or not (isinstance(data, np.ndarray) and data.dtype == np.float64 and resident_tta_default()
                                   and _hip_rotate_ok()):
-        return _predict_flips_host(data, model, overlap_factor, config)
+        return _predict_flips_host(data, model, overlap_factor, config, blend, blend_sigma_scale)
     vol = data if tensor else _upload_f64(data)
-    stack = _resident_flip_stack(vol.reshape(vol.shape[-3:]).contiguous(), model, overlap_factor, patch_shape, variants)
+    stack = _resident_flip_stack(vol.reshape(vol.shape[-3:]).contiguous(), model, overlap_factor, patch_shape, variants, blend,
+                                 blend_sigma_scale)
     if stack.shape[-1] == 1:
         stack = stack[..., 0]
     if not tensor:
@@ -644,31 +733,35 @@ class _TTAVariant:
         return flip_it(out, self.mirror)
 
 
-def predict_augment(data, model, overlap_factor, patch_shape, num_augments=32):
+def predict_augment(data, model, overlap_factor, patch_shape, num_augments=32, *, blend=None, blend_sigma_scale=DEFAULT_SIGMA_SCALE):
     """Random intensity / mirror / swap / rotation variants of the volume (reference prediction.py:25-62), each predicted patch-wise on
     the device tile loop and mapped back; the volume-sized spline rotations run on the device too (fetal_net.spline_rotate).  Like the
-    reference, stacking succeeds only when all back-rotated predictions end up with one shape (num_augments = 1, or equal angles)."""
+    reference, stacking succeeds only when all back-rotated predictions end up with one shape (num_augments = 1, or equal angles).
+    blend / blend_sigma_scale: as for patch_wise_prediction, for every variant."""
+    _blend_key(blend, blend_sigma_scale)
     vmin, vmax = data.min(), data.max()
     vol = data.squeeze()
     out = []
     for _ in range(num_augments):
         variant = _TTAVariant.draw(vmin, vmax)
         pred = patch_wise_prediction(model=model, data=variant.forward(vol)[np.newaxis], overlap_factor=overlap_factor,
-                                     patch_shape=patch_shape).squeeze()
+                                     patch_shape=patch_shape, blend=blend, blend_sigma_scale=blend_sigma_scale).squeeze()
         out.append(variant.inverse(pred).squeeze())
     return np.stack(out, axis=0)
 
 
 def run_validation_case(data_index, output_dir, model, data_file, training_modalities, patch_shape, overlap_factor=0,
                         permute=False, prev_truth_index=None, prev_truth_size=None, use_augmentations=False, *, output_label_map=False,
-                        threshold=0.5, labels=None, postprocess_labels=None):
+                        threshold=0.5, labels=None, postprocess_labels=None, blend=None, blend_sigma_scale=DEFAULT_SIGMA_SCALE):
     """Predict one case of an opened data file (any object with `.root.data[i]` / `.root.truth[i]`) and write
     data_<modality>.nii.gz, truth.nii.gz, prediction.nii.gz under output_dir (reference prediction.py:277-330).
     output_label_map (reference docstring :284-288): also write prediction_labels.nii.gz, the uint8 label map of the prediction
     (prediction_to_image's rules with `threshold` and `labels`).
     postprocess_labels: None, or a dict of `fetal_net.postprocess.postprocess_label_map` options (may be empty; `threshold` and `labels`
-    above are its defaults): together with output_label_map, prediction_labels.nii.gz is then the cleaned label map of the prediction."""
+    above are its defaults): together with output_label_map, prediction_labels.nii.gz is then the cleaned label map of the prediction.
+    blend / blend_sigma_scale: how overlapping tiles are combined, as for patch_wise_prediction (a case predicted whole has no tiles)."""
     from .utils.nifti import save_nifti
+    _blend_key(blend, blend_sigma_scale)
     if not os.path.exists(output_dir):
         os.makedirs(output_dir)
     test_data = np.asarray([data_file.root.data[data_index]])
@@ -681,11 +774,12 @@ def run_validation_case(data_index, output_dir, model, data_file, training_modal
         mode = "whole"
     elif use_augmentations:
         mode = "augment"
-        prediction = predict_augment(data=test_data, model=model, overlap_factor=overlap_factor, patch_shape=patch_shape)
+        prediction = predict_augment(data=test_data, model=model, overlap_factor=overlap_factor, patch_shape=patch_shape, blend=blend,
+                                     blend_sigma_scale=blend_sigma_scale)
     else:
         prediction = patch_wise_prediction(model=model, data=test_data, overlap_factor=overlap_factor, patch_shape=patch_shape,
                                            truth_data=test_truth_data, prev_truth_index=prev_truth_index,
-                                           prev_truth_size=prev_truth_size)[np.newaxis]
+                                           prev_truth_size=prev_truth_size, blend=blend, blend_sigma_scale=blend_sigma_scale)[np.newaxis]
         mode = "patches"
     if output_label_map:
         if mode == "whole":                                   # (1, L, X, Y, Z) as the model gives it
@@ -711,7 +805,8 @@ def run_validation_case(data_index, output_dir, model, data_file, training_modal
 
 def run_validation_cases(validation_keys_file, model_file, training_modalities, hdf5_file, patch_shape, output_dir=".",
                          overlap_factor=0, permute=False, prev_truth_index=None, prev_truth_size=None, use_augmentations=False,
-                         data_file=None, model=None, *, output_label_map=False, threshold=0.5, labels=None, postprocess_labels=None):
+                         data_file=None, model=None, *, output_label_map=False, threshold=0.5, labels=None, postprocess_labels=None,
+                         blend=None, blend_sigma_scale=DEFAULT_SIGMA_SCALE):
     """reference prediction.py:333-351.  `hdf5_file` is opened with `fetal_net.data.open_data_file` (plain-layout files through libhdf5,
     PyTables files through PyTables when installed); callers may instead pass an already opened duck-typed `data_file` (and a `model`).
     The keyword-only arguments are run_validation_case's and go to every case."""
@@ -738,7 +833,8 @@ def run_validation_cases(validation_keys_file, model_file, training_modalities, 
                                     training_modalities=training_modalities, overlap_factor=overlap_factor, permute=permute,
                                     patch_shape=patch_shape, prev_truth_index=prev_truth_index, prev_truth_size=prev_truth_size,
                                     use_augmentations=use_augmentations, output_label_map=output_label_map, threshold=threshold,
-                                    labels=labels, postprocess_labels=postprocess_labels) for i in validation_indices]
+                                    labels=labels, postprocess_labels=postprocess_labels, blend=blend,
+                                    blend_sigma_scale=blend_sigma_scale) for i in validation_indices]
     finally:
         if own:
             data_file.close()

@@ -120,10 +120,14 @@ SIGNATURES = {
     "fmri_tile_gather_stack": [p, p, i32, i32, i32, p, i32, i32, i32, i32, i32, i32, p, i32, p],
     "fmri_tile_scatter_accumulate": [p, p, i32, i32, i32, i32, i32, p, p, i32, i32, i32, p],
     "fmri_tile_finalize": [p, p, p, p, i64, i32, p],
+    "fmri_tile_scatter_weighted": [p, p, i32, i32, i32, i32, i32, p, p, p, p, p, i32, i32, i32, p],
+    "fmri_tile_finalize_weighted": [p, p, p, p, i64, i32, p],
     "fmri_volume_pad_flip": [p, i32, i32, i32, i32, p, i32, i32, i32, i32, p, i32, C.c_double, p],
     "fmri_tile_finalize_flip": [p, p, i32, i32, i32, i32, p, i32, i32, i32, p, i32, p, p],
+    "fmri_tile_finalize_flip_weighted": [p, p, i32, i32, i32, i32, p, i32, i32, i32, p, i32, p, p],
     "fmri_labels_expand_u8": [p, i64, p, i32, p, p],
     "fmri_tile_finalize_labels": [p, p, p, p, i64, i32, C.c_double, p, p],
+    "fmri_tile_finalize_labels_weighted": [p, p, p, p, i64, i32, C.c_double, p, p],
     "fmri_cast": [p, i32, p, i32, i64, p],
     "fmri_conv3d_upcat_ok": [i32, i32, i32, i32, i32, i32, i32],
     "fmri_conv3d_upcat_fwd_bias27": [p, i32, p, i32, p, p, p, p, i32, i32, i32, i32, i32, i32, f32, i32, p],

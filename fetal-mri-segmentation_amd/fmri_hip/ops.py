@@ -321,6 +321,35 @@ def tile_finalize(acc, cnt, out, bad):
     check(lib().fmri_tile_finalize(_p(acc), _p(cnt), _p(out), _p(bad), cnt.numel(), Cc, _s()), "fmri_tile_finalize")
 
 
+def tile_scatter_weighted(pred, idx, patch, tables, acc, wsum):
+    """acc (X, Y, Z, C) float64 += w * pred and wsum (X, Y, Z) float64 += w for every tile voxel inside the volume, w = (gx[x] * gy[y]) * gz[z]
+    in float64 from the three float32 device tables `tables` of patch[0], patch[1], patch[2] entries (fmri_tile_scatter_weighted)"""
+    gx, gy, gz = tables
+    _need_cuda(pred, idx, gx, gy, gz, acc, wsum)
+    X, Y, Z, Cc = acc.shape
+    B = idx.shape[0]
+    if tuple(wsum.shape) != (X, Y, Z) or [g.numel() for g in tables] != [int(v) for v in patch] or pred.numel() != B * patch[0] * patch[1] * patch[2] * Cc:
+        raise ValueError("tile_scatter_weighted: pred (B, px, py, pz, C), one table entry per tile voxel and axis, wsum of acc's extent "
+                         "(got pred %s, tables %s, patch %s, acc %s, wsum %s)" % (tuple(pred.shape), [g.numel() for g in tables], tuple(patch),
+                                                                                  tuple(acc.shape), tuple(wsum.shape)))
+    if pred.dtype != torch.float32 or idx.dtype != torch.int32 or any(g.dtype != torch.float32 for g in tables) or \
+            acc.dtype != torch.float64 or wsum.dtype != torch.float64:
+        raise TypeError("tile_scatter_weighted: float32 pred and tables, int32 idx, float64 acc and wsum")
+    check(lib().fmri_tile_scatter_weighted(_p(pred), _p(idx), B, patch[0], patch[1], patch[2], Cc, _p(gx), _p(gy), _p(gz), _p(acc), _p(wsum),
+                                           X, Y, Z, _s()), "fmri_tile_scatter_weighted")
+
+
+def tile_finalize_weighted(acc, wsum, out, bad):
+    """out float64 like acc = acc / wsum; bad (int32, accumulated) counts the voxels with wsum <= 0, which divide by 1 (fmri_tile_finalize_weighted)"""
+    _need_cuda(acc, wsum, out, bad)
+    Cc = acc.shape[-1]
+    if acc.dtype != torch.float64 or wsum.dtype != torch.float64 or out.dtype != torch.float64 or bad.dtype != torch.int32:
+        raise TypeError("tile_finalize_weighted: float64 acc, wsum and out, int32 bad")
+    if acc.numel() != wsum.numel() * Cc or out.numel() != acc.numel():
+        raise ValueError("tile_finalize_weighted: acc and out (..., C), wsum (...) (got %s, %s, %s)" % (tuple(acc.shape), tuple(out.shape), tuple(wsum.shape)))
+    check(lib().fmri_tile_finalize_weighted(_p(acc), _p(wsum), _p(out), _p(bad), wsum.numel(), Cc, _s()), "fmri_tile_finalize_weighted")
+
+
 def _dt_vol(t):
     if t.dtype == torch.float32:
         return F32
@@ -376,6 +405,23 @@ def tile_finalize_flip(acc, cnt, out, bad, lo=(0, 0, 0), flip_mask=0):
     return out
 
 
+def tile_finalize_flip_weighted(acc, wsum, out, bad, lo=(0, 0, 0), flip_mask=0):
+    """tile_finalize_flip with the float64 weight sums wsum (AX, AY, AZ) in place of the counts: out = acc / wsum of the window, mirrored; bad
+    counts the window's voxels with wsum <= 0 (fmri_tile_finalize_flip_weighted)"""
+    _need_cuda(acc, wsum, out, bad)
+    if acc.dim() != 4 or out.dim() != 4 or tuple(wsum.shape) != tuple(acc.shape[:3]) or out.shape[3] != acc.shape[3]:
+        raise ValueError("tile_finalize_flip_weighted: acc (AX, AY, AZ, C), wsum (AX, AY, AZ), out (X, Y, Z, C) (got %s, %s, %s)" % (
+            tuple(acc.shape), tuple(wsum.shape), tuple(out.shape)))
+    if acc.dtype != torch.float64 or out.dtype != torch.float64 or wsum.dtype != torch.float64 or bad.dtype != torch.int32:
+        raise TypeError("tile_finalize_flip_weighted: float64 acc, wsum and out, int32 bad")
+    AX, AY, AZ, Cc = acc.shape
+    X, Y, Z = out.shape[:3]
+    with torch.cuda.device(out.device):
+        check(lib().fmri_tile_finalize_flip_weighted(_p(acc), _p(wsum), AX, AY, AZ, Cc, _p(out), X, Y, Z, _lo3(lo), int(flip_mask), _p(bad),
+                                                     _s()), "fmri_tile_finalize_flip_weighted")
+    return out
+
+
 MAX_LABELS = 32
 
 
@@ -411,6 +457,20 @@ def tile_finalize_labels(acc, cnt, out, bad, threshold, values):
         raise ValueError("tile_finalize_labels: %d label values for %d channels, uint8 output of cnt's size" % (len(vals), Cc))
     check(lib().fmri_tile_finalize_labels(_p(acc), _p(cnt), _p(out), _p(bad), cnt.numel(), Cc, float(threshold), vals, _s()),
           "fmri_tile_finalize_labels")
+
+
+def tile_finalize_labels_weighted(acc, wsum, out, bad, threshold, values):
+    """tile_finalize_labels with the float64 weight sums wsum in place of the counts: the label map of acc / wsum; wsum <= 0 gives 0 and counts
+    in bad (fmri_tile_finalize_labels_weighted)"""
+    _need_cuda(acc, wsum, out, bad)
+    vals = label_values(values)
+    Cc = acc.shape[-1]
+    if len(vals) != Cc or out.dtype != torch.uint8 or out.numel() != wsum.numel() or acc.numel() != wsum.numel() * Cc:
+        raise ValueError("tile_finalize_labels_weighted: %d label values for %d channels, uint8 output of wsum's size" % (len(vals), Cc))
+    if acc.dtype != torch.float64 or wsum.dtype != torch.float64 or bad.dtype != torch.int32:
+        raise TypeError("tile_finalize_labels_weighted: float64 acc and wsum, int32 bad")
+    check(lib().fmri_tile_finalize_labels_weighted(_p(acc), _p(wsum), _p(out), _p(bad), wsum.numel(), Cc, float(threshold), vals, _s()),
+          "fmri_tile_finalize_labels_weighted")
 
 
 def label_sums(probs, y_true, n_labels, lsums):

@@ -457,6 +457,22 @@ int fmri_tile_scatter_accumulate(const float* pred, const int32_t* idx, int B, i
 /* out (double) [n][C] = acc / cnt ; *bad (int32, accumulated) counts voxels with cnt == 0 (reference asserts none) */
 int fmri_tile_finalize(const double* acc, const int32_t* cnt, double* out, int32_t* bad, int64_t nvox, int C,
                        fmri_stream_t stream);
+/* ---- Gaussian-importance blending of the tiles (nnU-Net, MONAI sliding_window_inference(mode="gaussian"); not in the reference, whose
+ * rule is the unweighted pair above).  gx, gy, gz: fp32 device tables of px, py, pz entries, g_a[i] = float32(exp(-0.5 * ((i - (p_a - 1) / 2)
+ * / (sigma_scale * p_a))^2)) (fetal_net.prediction.gaussian_tile_tables).  The weight of the tile voxel (x, y, z) is
+ *   w = ((double)gx[x] * (double)gy[y]) * (double)gz[z]      (in this order: the first product is exact, the second rounds once).
+ * fmri_tile_scatter_weighted: acc (double) [X][Y][Z][C] += w * (double)pred[b][x][y][z][c] (pred fp32 [B][px][py][pz][C]) and wsum (double)
+ *   [X][Y][Z] += w at o = idx[b] + (x, y, z) (idx int32 [B][3], device); tile voxels whose o lies outside the volume are skipped.  The adds
+ *   are float64 atomics: where tiles overlap, the sums depend on the order of arrival in their last bits.
+ * fmri_tile_finalize_weighted: out (double) [n][C] = acc / wsum; a voxel with wsum <= 0 divides by 1 and *bad (int32, accumulated) counts it.
+ * fmri_tile_finalize_flip_weighted / fmri_tile_finalize_labels_weighted (declared next to their unweighted forms below): the same crop and
+ *   mirror / the same label rule, with q_c = acc / wsum and wsum <= 0 in place of cnt == 0.
+ * All four: a NULL pointer or a non-positive extent is FMRI_E_SHAPE, a pointer not aligned to its element FMRI_E_ALIGN; nothing is launched
+ *   then. */
+int fmri_tile_scatter_weighted(const float* pred, const int32_t* idx, int B, int px, int py, int pz, int C, const float* gx, const float* gy,
+                               const float* gz, double* acc, double* wsum, int X, int Y, int Z, fmri_stream_t stream);
+int fmri_tile_finalize_weighted(const double* acc, const double* wsum, double* out, int32_t* bad, int64_t nvox, int C,
+                                fmri_stream_t stream);
 /* ---- the volume stays on the device around the tile loop (reference prediction.py:65-85 predict_flips, :138-146 the paddings, the crop
  * of pad_for_fit).  `lo`: 3 int32 in HOST memory (read at enqueue); flip_mask: bit k mirrors axis k, m(u)_k = n_k - 1 - u_k.
  * fmri_volume_pad_flip: src [X][Y][Z], dst [OX][OY][OZ], each FMRI_F32 or FMRI_F64 (else FMRI_E_DTYPE).  With u = o - lo: dst[o] = fill
@@ -465,22 +481,31 @@ int fmri_tile_finalize(const double* acc, const int32_t* cnt, double* out, int32
  * fmri_tile_finalize_flip: out (double) [X][Y][Z][C] = acc[a][c] / (double)cnt[a], a = lo + m(g) (m over out's extent); acc (double)
  *   [AX][AY][AZ][C], cnt (int32) [AX][AY][AZ].  *bad (accumulated) counts the voxels of out whose count is 0; their divisor is 1.  lo = 0,
  *   flip_mask = 0 and equal extents: fmri_tile_finalize's bytes.
- * Both: a NULL pointer, a non-positive extent, a flip_mask outside 0..7, |lo| > 2^30 (pad_flip) or a window [lo, lo + n) that leaves acc
+ * fmri_tile_finalize_flip_weighted: the same with wsum (double) [AX][AY][AZ] in place of cnt: out[g][c] = acc[a][c] / wsum[a]; *bad counts
+ *   the voxels of out with wsum <= 0, their divisor is 1.  lo = 0, flip_mask = 0 and equal extents: fmri_tile_finalize_weighted's bytes.
+ * All three: a NULL pointer, a non-positive extent, a flip_mask outside 0..7, |lo| > 2^30 (pad_flip) or a window [lo, lo + n) that leaves acc
  *   (finalize_flip) is FMRI_E_SHAPE; a pointer not aligned to its element FMRI_E_ALIGN; nothing is launched then. */
 int fmri_volume_pad_flip(const void* src, int src_dtype, int X, int Y, int Z, void* dst, int dst_dtype, int OX, int OY, int OZ,
                          const int32_t* lo, int flip_mask, double fill, fmri_stream_t stream);
 int fmri_tile_finalize_flip(const double* acc, const int32_t* cnt, int AX, int AY, int AZ, int C, double* out, int X, int Y, int Z,
                             const int32_t* lo, int flip_mask, int32_t* bad, fmri_stream_t stream);
+int fmri_tile_finalize_flip_weighted(const double* acc, const double* wsum, int AX, int AY, int AZ, int C, double* out, int X, int Y, int Z,
+                                     const int32_t* lo, int flip_mask, int32_t* bad, fmri_stream_t stream);
 
 /* ---- several labels (reference generator.py:404-419 get_multi_class_labels, prediction.py:214-274).  `values`: L label values, uint8,
  * HOST memory (read at enqueue), 1 <= L <= 32, every value in 1..255 and no value twice - anything else is FMRI_E_SHAPE.
  * fmri_labels_expand_u8: out [n][L] (channels last) = (lab[v] == values[l]); a byte that is no label - background included - gives a zero row.
  * fmri_tile_finalize_labels: out[v] (uint8) from q_c = acc[v][c] / cnt[v] in float64 (fmri_tile_finalize's division).  C == 1: values[0]
  *   where q_0 > threshold, else 0; C > 1: values[k] with k the first index of the maximum q_c (np.argmax), 0 where max q < threshold.
- *   cnt[v] == 0: out[v] = 0 and *bad (accumulated) counts it. */
+ *   cnt[v] == 0: out[v] = 0 and *bad (accumulated) counts it.
+ * fmri_tile_finalize_labels_weighted: the same rule on q_c = acc[v][c] / wsum[v] (wsum double, fmri_tile_finalize_weighted's division);
+ *   wsum[v] <= 0: out[v] = 0 and *bad counts it.  NULL pointer or nvox <= 0: FMRI_E_SHAPE; acc / wsum not 8-byte or bad not 4-byte aligned:
+ *   FMRI_E_ALIGN. */
 int fmri_labels_expand_u8(const uint8_t* lab, int64_t n, const uint8_t* values, int L, uint8_t* out, fmri_stream_t stream);
 int fmri_tile_finalize_labels(const double* acc, const int32_t* cnt, uint8_t* out, int32_t* bad, int64_t nvox, int C, double threshold,
                               const uint8_t* values, fmri_stream_t stream);
+int fmri_tile_finalize_labels_weighted(const double* acc, const double* wsum, uint8_t* out, int32_t* bad, int64_t nvox, int C,
+                                       double threshold, const uint8_t* values, fmri_stream_t stream);
 
 /* ---- device-side patch sampler + intensity augmentation.  Replaces, per training patch, the host chain
  * reference fetal_net/generator.py:246-328 (add_data / extract_patch) -> augment.py:222-377 (augment_data) ->
