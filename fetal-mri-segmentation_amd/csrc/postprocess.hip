@@ -848,6 +848,189 @@ __global__ __launch_bounds__(256) void k_median_stack(const double* __restrict__
     }
 }
 
+// ---- agreement of the K test-time variants: ONE pass over the stack [K][nvox][C] that writes the median of k_median_stack (same network,
+// same bits) and, from the same registers, the variants' mean, population variance, the binary entropy of the mean, the share of variants
+// on the other side of the threshold than the median, and the set sizes |M|, |V_k|, |V_k & M| per channel (M = median > thr, V_k = v_k >
+// thr).  Mean, variance terms and the K-bit mask of v_k > thr are taken BEFORE the network reorders the registers.  fp64, contraction off,
+// one rounding per written operation: numpy in the same order gives the same bits (the entropy up to the two log2).
+//   C == 1: a thread takes VEC consecutive voxels; VEC = 2 (16-byte loads and stores) where every pointer and the row pitch allow it and
+//           2 * KB values fit the registers (KB <= 16), else 1.
+//   C  > 1: a thread takes ONE voxel and walks its C channels, so at every step all 64 lanes of a wave hold the same channel and one
+//           ballot per counter serves it exactly as for C == 1 (a thread per element would mix channels inside a wave and need a
+//           per-lane scatter into the counters); a wave's 8-byte loads of one step are C * 8 bytes apart and the C steps together use
+//           every byte of the lines they touch.
+// Counts: per counter one __ballot + popcount per wave (a 64-bit mask), lane s of the wave keeps counter s of the element in a register,
+// one LDS atomic per lane adds them to the workgroup's table, and the workgroup leaves with one 64-bit atomicAdd per non-zero counter.
+// The loop bounds are the same for every lane of a wave (lanes past the end are switched off by `live`), so every ballot is taken by the
+// full wave.  A workgroup counts fewer than 2^32 elements: the grid-stride loop gives it at most n / gridDim of them.
+// FULL = (K == KB): the instantiation of the full network (the eight flips), in which no `k < K` is left to evaluate.
+constexpr int TTA_CUS = 256;
+// workgroups per CU the grid is capped at, by KB: all of them resident at once (tools/kernel_resources.py: 76-122 registers at KB 8 and
+// 16, 146 at 32, 243-250 at 64), so the grid-stride loop has no second, thinner round of workgroups; 6 or 8 per CU measured no faster
+constexpr int tta_blocks_per_cu(int KB) { return KB <= 16 ? 4 : (KB == 32 ? 2 : 1); }
+constexpr int TTA_MAX_C = 16;
+
+template <int KB>
+__device__ __forceinline__ void tta_sort(double (&v)[KB]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int size = 2; size <= KB; size <<= 1)
+#pragma unroll
+        for (int d = size >> 1; d > 0; d >>= 1)
+#pragma unroll
+            for (int a = 0; a < KB; ++a) {
+                const int b = a ^ d;
+                if (b > a) {
+                    const double lo = fmin(v[a], v[b]), hi = fmax(v[a], v[b]);
+                    const bool up = (a & size) == 0;
+                    v[a] = up ? lo : hi;
+                    v[b] = up ? hi : lo;
+                }
+            }
+}
+
+struct TtaOut {
+    double *median, *mean, *variance, *entropy, *disagreement;
+};
+
+template <int KB, int VEC, bool FULL>
+__global__ __launch_bounds__(256) void k_tta_agreement(const double* __restrict__ stack, int K_, int64_t nvox, int C, double thr, TtaOut o,
+                                                       unsigned long long* __restrict__ counts) {
+#pragma clang fp contract(off)
+    const int K = FULL ? KB : K_;                             // FULL: K == KB, every `k < K` below folds away
+    constexpr int SLOTS = 2 * KB + 1;                         // register slots of a wave: 0 = |M|, 1 + k = |V_k|, 1 + KB + k = |V_k & M|
+    constexpr int NACC = (SLOTS + 63) / 64;
+    __shared__ unsigned int s_cnt[TTA_MAX_C * 129];
+    const int NC = 2 * K + 1;
+    const int lane = threadIdx.x & 63;
+    if (counts) {
+        for (int i = threadIdx.x; i < C * NC; i += 256) s_cnt[i] = 0u;
+        __syncthreads();
+    }
+    const int64_t n = nvox * C;                               // pitch of one variant
+    const int64_t units = C == 1 ? nvox / VEC : nvox;
+    const bool need_mu = o.mean || o.variance || o.entropy;
+    const unsigned long long valid = K == 64 ? ~0ull : (1ull << K) - 1ull;
+    const double dK = (double)K;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < units; base += (int64_t)gridDim.x * 256) {
+        const int64_t u = base + threadIdx.x;
+        const bool live = u < units;
+        for (int c = 0; c < C; ++c) {
+            const int64_t e = C == 1 ? u * VEC : u * C + c;   // first element of this thread's step
+            double v[VEC][KB];
+#pragma unroll
+            for (int k = 0; k < KB; ++k) {
+                if constexpr (VEC == 2) {
+                    double2 two = make_double2(0.0, 0.0);
+                    if (k < K && live) two = *reinterpret_cast<const double2*>(stack + (int64_t)k * n + e);
+                    v[0][k] = k < K ? two.x : (double)INFINITY;
+                    v[VEC - 1][k] = k < K ? two.y : (double)INFINITY;
+                } else {
+                    v[0][k] = k < K ? (live ? stack[(int64_t)k * n + e] : 0.0) : (double)INFINITY;
+                }
+            }
+            unsigned int acc[NACC];
+#pragma unroll
+            for (int i = 0; i < NACC; ++i) acc[i] = 0u;
+            double r_med[VEC], r_mu[VEC], r_var[VEC], r_ent[VEC], r_dis[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                double mu = 0.0, var = 0.0;
+                if (need_mu) {
+                    double s = v[j][0];
+#pragma unroll
+                    for (int k = 1; k < KB; ++k) s = k < K ? s + v[j][k] : s;
+                    mu = s / dK;
+                }
+                if (o.variance) {
+                    double q = 0.0;
+#pragma unroll
+                    for (int k = 0; k < KB; ++k) {
+                        const double dv = v[j][k] - mu;
+                        q = k < K ? q + dv * dv : q;
+                    }
+                    var = q / dK;
+                }
+                unsigned long long bits = 0ull;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) bits |= v[j][k] > thr ? 1ull << k : 0ull;
+                bits &= valid;                                // the +inf padding is no variant
+                tta_sort<KB>(v[j]);
+                double m0 = 0.0, m1 = 0.0;
+                const int k0 = (K - 1) / 2, k1 = K / 2;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    m0 = k == k0 ? v[j][k] : m0;
+                    m1 = k == k1 ? v[j][k] : m1;
+                }
+                const double med = (m0 + m1) / 2.0;
+                const bool m = med > thr;
+                r_med[j] = med;
+                r_mu[j] = mu;
+                r_var[j] = var;
+                r_ent[j] = 0.0;
+                if (o.entropy) {
+                    const double p = fmin(fmax(mu, 0.0), 1.0);
+                    if (p > 0.0 && p < 1.0) {
+                        const double q = 1.0 - p;
+                        r_ent[j] = -(p * log2(p) + q * log2(q));
+                    }
+                }
+                r_dis[j] = (double)__popcll(m ? ~bits & valid : bits) / dK;
+                if (counts) {
+                    const unsigned long long M = __ballot(live && m);
+                    acc[0] += lane == 0 ? (unsigned int)__popcll(M) : 0u;
+#pragma unroll
+                    for (int k = 0; k < KB; ++k)
+                        if (k < K) {
+                            const unsigned long long Vk = __ballot(live && ((bits >> k) & 1ull) != 0ull);
+                            const int sv = 1 + k, si = 1 + KB + k;
+                            acc[sv >> 6] += lane == (sv & 63) ? (unsigned int)__popcll(Vk) : 0u;
+                            acc[si >> 6] += lane == (si & 63) ? (unsigned int)__popcll(Vk & M) : 0u;
+                        }
+                }
+            }
+            if (live) {
+                if constexpr (VEC == 2) {
+                    *reinterpret_cast<double2*>(o.median + e) = make_double2(r_med[0], r_med[VEC - 1]);
+                    if (o.mean) *reinterpret_cast<double2*>(o.mean + e) = make_double2(r_mu[0], r_mu[VEC - 1]);
+                    if (o.variance) *reinterpret_cast<double2*>(o.variance + e) = make_double2(r_var[0], r_var[VEC - 1]);
+                    if (o.entropy) *reinterpret_cast<double2*>(o.entropy + e) = make_double2(r_ent[0], r_ent[VEC - 1]);
+                    if (o.disagreement) *reinterpret_cast<double2*>(o.disagreement + e) = make_double2(r_dis[0], r_dis[VEC - 1]);
+                } else {
+                    o.median[e] = r_med[0];
+                    if (o.mean) o.mean[e] = r_mu[0];
+                    if (o.variance) o.variance[e] = r_var[0];
+                    if (o.entropy) o.entropy[e] = r_ent[0];
+                    if (o.disagreement) o.disagreement[e] = r_dis[0];
+                }
+            }
+            if (counts) {
+#pragma unroll
+                for (int i = 0; i < NACC; ++i) {
+                    const int s = lane + 64 * i;              // register slot -> counter: the slots are laid out for KB, the table for K
+                    const int k = s == 0 ? 0 : (s <= KB ? s - 1 : s - 1 - KB);
+                    const int idx = s == 0 ? 0 : (s <= KB ? s : s - KB + K);
+                    if (s < SLOTS && k < K && acc[i] != 0u) atomicAdd(&s_cnt[c * NC + idx], acc[i]);
+                }
+            }
+        }
+    }
+    if (counts) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < C * NC; i += 256)
+            if (s_cnt[i] != 0u) atomicAdd(&counts[i], (unsigned long long)s_cnt[i]);
+    }
+}
+
+template <int KB, int VEC>
+void tta_go(const double* stack, int K, int64_t nvox, int C, double thr, const TtaOut& o, unsigned long long* counts, hipStream_t st) {
+    const int64_t units = C == 1 ? nvox / VEC : nvox;
+    const int grid = grid_for(units, 256, TTA_CUS * tta_blocks_per_cu(KB));
+    if (K == KB) k_tta_agreement<KB, VEC, true><<<grid, 256, 0, st>>>(stack, K, nvox, C, thr, o, counts);
+    else k_tta_agreement<KB, VEC, false><<<grid, 256, 0, st>>>(stack, K, nvox, C, thr, o, counts);
+}
+
 }  // namespace
 
 extern "C" int fmri_spline_lds_max_line(void) { return SPL_LDS_MAX; }
@@ -901,6 +1084,40 @@ extern "C" int fmri_median_stack_f64(const double* stack, int K, int64_t n, doub
     else if (K <= 16) k_median_stack<16><<<grid, 256, 0, st>>>(stack, K, n, out);
     else if (K <= 32) k_median_stack<32><<<grid, 256, 0, st>>>(stack, K, n, out);
     else k_median_stack<64><<<grid, 256, 0, st>>>(stack, K, n, out);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
+
+extern "C" int fmri_tta_agreement_f64(const double* stack, int K, int64_t nvox, int C, double threshold, double* median, double* mean,
+                                      double* variance, double* entropy, double* disagreement, uint64_t* counts, fmri_stream_t stream) {
+    if (!stack || !median || K < 1 || K > 64 || C < 1 || C > TTA_MAX_C || nvox <= 0) return FMRI_E_SHAPE;
+    const int64_t n = nvox * C;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(stack), s1 = s0 + (uintptr_t)K * (uintptr_t)n * sizeof(double);
+    double* const maps[5] = {median, mean, variance, entropy, disagreement};
+    bool wide = C == 1 && nvox % 2 == 0 && K <= 16 && s0 % 16 == 0;
+    for (double* m : maps) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(m);
+        if (m && a < s1 && a + (uintptr_t)n * sizeof(double) > s0) return FMRI_E_SHAPE;       // an output inside the stack
+        wide = wide && a % 16 == 0;
+    }
+    const size_t count_bytes = (size_t)C * (2 * K + 1) * sizeof(uint64_t);
+    const uintptr_t c0 = reinterpret_cast<uintptr_t>(counts);
+    if (counts && c0 < s1 && c0 + count_bytes > s0) return FMRI_E_SHAPE;
+    hipStream_t st = as_stream(stream);
+    if (counts && hipMemsetAsync(counts, 0, count_bytes, st) != hipSuccess) return FMRI_E_LAUNCH;
+    const TtaOut o{median, mean, variance, entropy, disagreement};
+    unsigned long long* const cnt = reinterpret_cast<unsigned long long*>(counts);
+    if (K <= 8) {
+        if (wide) tta_go<8, 2>(stack, K, nvox, C, threshold, o, cnt, st);
+        else tta_go<8, 1>(stack, K, nvox, C, threshold, o, cnt, st);
+    } else if (K <= 16) {
+        if (wide) tta_go<16, 2>(stack, K, nvox, C, threshold, o, cnt, st);
+        else tta_go<16, 1>(stack, K, nvox, C, threshold, o, cnt, st);
+    } else if (K <= 32) {
+        tta_go<32, 1>(stack, K, nvox, C, threshold, o, cnt, st);
+    } else {
+        tta_go<64, 1>(stack, K, nvox, C, threshold, o, cnt, st);
+    }
     FMRI_LAUNCH_CHECK();
     return FMRI_OK;
 }

@@ -192,10 +192,11 @@ class Stage(object):
     reference's configs); `intensity`: None or a key of INTENSITY_METHODS; `norm`: None or {'mean', 'std'}; `augment`: None | 'flip' (the
     8 flips) | 'all' (`n_augment` random variants); `device`: where the stage's intensity preparation, its zoom and the median over its
     variants run (None / True / False as for `Zoom`); `blend` / `blend_sigma_scale` (keyword-only): how overlapping tiles are combined, None
-    (every tile counts the same) or 'gaussian', as for `prediction.patch_wise_prediction`."""
+    (every tile counts the same) or 'gaussian', as for `prediction.patch_wise_prediction`; `threshold` (keyword-only): the label rule
+    `> threshold` that `infer(..., agreement=True)` counts the variants' masks by."""
 
     def __init__(self, model, config, intensity=None, norm=None, augment=None, n_augment=0, overlap=0.9, device=None, *, blend=None,
-                 blend_sigma_scale=prediction.DEFAULT_SIGMA_SCALE):
+                 blend_sigma_scale=prediction.DEFAULT_SIGMA_SCALE, threshold=0.5):
         if intensity is not None and intensity not in INTENSITY_METHODS:
             raise Exception("Unknown preprocess: {}".format(intensity))
         if augment not in (None, "flip", "all"):
@@ -210,6 +211,7 @@ class Stage(object):
         self.augment, self.n_augment, self.overlap, self.device = augment, n_augment, overlap, device
         prediction._blend_key(blend, blend_sigma_scale)
         self.blend = dict(blend=blend, blend_sigma_scale=blend_sigma_scale)
+        self.threshold = float(threshold)
 
     @property
     def patch(self):
@@ -269,17 +271,23 @@ class Stage(object):
             t = ops.normalize_f64(t, norm["mean"], norm["std"])
         return t if keep else t.cpu().numpy()
 
-    def infer(self, vol, keep_variants=False):
+    def infer(self, vol, keep_variants=False, agreement=False):
         """probabilities of `vol` [X,Y,Z]: tiled prediction, or the median over the stage's test-time augmentation variants.  With a
         model that has the device tile loop and `augment` None or 'flip' the volume goes up once, the variants are mirrored, tiled and
         mirrored back on the device, their median is taken on the resident stack and the result comes down once (`_infer_resident`); a
-        float64 CUDA tensor stays one.  'all' and foreign models take `_infer_host`."""
+        float64 CUDA tensor stays one.  'all' and foreign models take `_infer_host`.
+        agreement=True -> (that result, the `prediction.TTAAgreement` of the variants: uncertainty maps, set sizes, estimated Dice).  On
+        the resident route ONE kernel (`ops.tta_agreement_f64`) then reads the stack in place of the median kernel and writes the median
+        with the maps; with keep_variants=True it is taken from the very stack that is returned.  One variant has nothing to agree
+        with: augment=None raises ValueError."""
+        if agreement and self.augment is None:
+            raise ValueError("agreement=True needs test-time variants: augment='flip' or 'all' (got None)")
         why = self._resident_refusal(vol)
         if why is None:
-            return self._infer_resident(vol, keep_variants)
+            return self._infer_resident(vol, keep_variants, agreement)
         if preprocess._is_device_tensor(vol):
             raise TypeError("Stage.infer of a device tensor needs the resident tile loop: " + why)
-        return self._infer_host(vol, keep_variants)
+        return self._infer_host(vol, keep_variants, agreement)
 
     def _resident_refusal(self, vol):
         """None when `vol` takes the resident route, else the reason it does not"""
@@ -297,7 +305,7 @@ class Stage(object):
                 return "the host route is asked for (device=False, FMRI_TTA_RESIDENT=0) or no GPU is there"
         return None if ok else "a float64 volume [X,Y,Z] with every extent above 1 is needed"
 
-    def _infer_resident(self, vol, keep_variants):
+    def _infer_resident(self, vol, keep_variants, agreement=False):
         from fmri_hip import ops
         tensor = preprocess._is_device_tensor(vol)
         t = vol.contiguous() if tensor else prediction._upload_f64(vol)
@@ -307,13 +315,22 @@ class Stage(object):
             stack = stack[..., 0]
         if self.augment != "flip":
             out = stack[0]
+        elif agreement:
+            maps, counts = prediction._tta_agreement_device(stack, self.threshold, prediction.TTA_MAPS)
+            if not tensor:
+                maps = {name: prediction._download(m) for name, m in maps.items()}
+            agreed = prediction.TTAAgreement(maps.pop("median"), maps, counts, self.threshold)
+            if not keep_variants:
+                return agreed.median, agreed
+            return (stack if tensor else prediction._download(stack)), agreed
         else:
             out = stack if keep_variants else ops.median_stack_f64(stack)
         return out if tensor else prediction._download(out)
 
-    def _infer_host(self, vol, keep_variants=False):
+    def _infer_host(self, vol, keep_variants=False, agreement=False):
         """the route of foreign models and of augment='all': every variant a patch_wise_prediction of a host volume, the stack of their
-        results reduced by `median_of_variants` (also the other arm of tools/bench_tta.py)"""
+        results reduced by `median_of_variants` (also the other arm of tools/bench_tta.py); agreement=True: `prediction.tta_agreement`
+        of that stack under the stage's `device=` rule, its median the result"""
         if self.augment == "all":
             variants = predict_augment(vol, model=self.model, overlap_factor=self.overlap, num_augments=self.n_augment, patch_shape=self.patch,
                                        **self.blend)
@@ -323,6 +340,10 @@ class Stage(object):
         else:
             return np.asarray(patch_wise_prediction(model=self.model, data=vol[np.newaxis], overlap_factor=self.overlap,
                                                     patch_shape=self.patch, **self.blend)).squeeze()
+        if agreement:
+            variants = np.asarray(variants)
+            agreed = prediction.tta_agreement(variants, self.threshold, device=self.device)
+            return np.asarray(variants if keep_variants else agreed.median).squeeze(), agreed
         return np.asarray(variants if keep_variants else median_of_variants(variants, self.device)).squeeze()
 
 
@@ -343,10 +364,12 @@ class VolumePipeline(object):
         self.roi_padding = roi_padding
         self.mask_options = dict(gaussian_std=0.5, threshold=0.5) if mask_options is None else dict(mask_options)
 
-    def run_first(self, volume, keep_variants=False):
-        """-> (what the first model saw before its border, its prediction on the input grid)"""
+    def run_first(self, volume, keep_variants=False, agreement=False):
+        """-> (what the first model saw before its border, its prediction on the input grid); agreement=True adds a third element, the
+        `prediction.TTAAgreement` of the first stage's variants: its maps brought back to the input grid by the steps that bring the
+        prediction back (crop, zoom back), its counts and scores as taken on the grid the model saw"""
         if self._chain_on_device(volume):
-            return self._run_first_resident(volume, keep_variants)
+            return self._run_first_resident(volume, keep_variants, agreement)
         steps = []
         vol = volume
         xy, z = self.resolution
@@ -356,6 +379,9 @@ class VolumePipeline(object):
         vol = self.first.intensities(vol, steps)
         seen = vol
         steps.append(Border(CONTEXT_MARGIN))
+        if agreement:
+            pred, agreed = self.first.infer(steps[-1].forward(vol), keep_variants, True)
+            return seen, _undo(pred, steps), agreed.with_maps(lambda m: _undo(m, steps))
         pred = self.first.infer(steps[-1].forward(vol), keep_variants)
         return seen, _undo(pred, steps)
 
@@ -375,7 +401,7 @@ class VolumePipeline(object):
         out_shape = first.model.output_shape                  # (Border.backward crops the three LAST axes: one label, squeezed away)
         return int(out_shape[1] if prediction._is3d(first.model) else out_shape[-1]) == 1
 
-    def _run_first_resident(self, volume, keep_variants):
+    def _run_first_resident(self, volume, keep_variants, agreement=False):
         """run_first on one device tensor: resolution zoom, intensities, border, tile loop and variants, crop, zoom back - one upload,
         and one download each for what the model saw and for its prediction (a CUDA tensor in gives CUDA tensors out)"""
         tensor = preprocess._is_device_tensor(volume)
@@ -387,6 +413,10 @@ class VolumePipeline(object):
             t = steps[-1].forward(t)
         seen = self.first.intensities(t, steps)
         steps.append(Border(CONTEXT_MARGIN))
+        down = (lambda m: m) if tensor else prediction._download
+        if agreement:
+            pred, agreed = self.first.infer(steps[-1].forward(seen), keep_variants, True)
+            return down(seen), down(_undo(pred, steps)), agreed.with_maps(lambda m: down(_undo(m, steps)))
         pred = _undo(self.first.infer(steps[-1].forward(seen), keep_variants), steps)
         return (seen, pred) if tensor else (prediction._download(seen), prediction._download(pred))
 
@@ -398,47 +428,75 @@ class VolumePipeline(object):
             hi = np.minimum(hi + np.asarray(self.roi_padding), np.asarray(mask).shape)
         return Box(lo, hi, np.asarray(mask).shape)
 
-    def run_second(self, volume, mask, keep_variants=False):
+    def run_second(self, volume, mask, keep_variants=False, agreement=False):
         """the second model on the box around `mask`, cut from the ORIGINAL volume and prepared with the second stage's own parameters
-        (no scaling hook at this stage, as in the reference); zero outside the box"""
+        (no scaling hook at this stage, as in the reference); zero outside the box.  agreement=True -> (that, the second stage's
+        `prediction.TTAAgreement`): its maps pasted into zeros like the prediction, its counts and scores those of the box"""
         box = self.region_of_interest(mask)
         roi = self.second.intensities(box.forward(np.asarray(volume, dtype=np.float64)))
+        if agreement:
+            pred, agreed = self.second.infer(roi, keep_variants, True)
+            return box.backward(pred), agreed.with_maps(box.backward)
         return box.backward(self.second.infer(roi, keep_variants))
 
-    def __call__(self, volume, keep_variants=False):
-        volume = np.asarray(volume, dtype=np.float64).squeeze()
-        seen, pred = self.run_first(volume, keep_variants)
-        out = {"data": seen, "prediction": pred}
+    def __call__(self, volume, keep_variants=False, agreement=False):
+        """-> {'data', 'prediction'[, 'mask', 'prediction_roi']}; agreement=True adds 'agreement' (and 'agreement_roi' with a second
+        stage): the `prediction.TTAAgreement` of each stage's variants, see `run_first` / `run_second`.  A float64 CUDA volume takes the
+        one-stage pipeline (tensors in, tensors out); the second stage's crop and paste are host passes"""
+        if preprocess._is_device_tensor(volume):
+            if self.second is not None:
+                raise TypeError("a device tensor takes a one-stage pipeline: the second stage crops and pastes on the host")
+            volume = volume.squeeze()
+        else:
+            volume = np.asarray(volume, dtype=np.float64).squeeze()
+        if agreement:
+            seen, pred, agreed = self.run_first(volume, keep_variants, True)
+            out = {"data": seen, "prediction": pred, "agreement": agreed}
+        else:
+            seen, pred = self.run_first(volume, keep_variants)
+            out = {"data": seen, "prediction": pred}
         if self.second is not None:
             out["mask"] = postprocess_prediction(pred.squeeze(), **self.mask_options)
-            out["prediction_roi"] = self.run_second(volume, out["mask"], keep_variants)
+            if agreement:
+                out["prediction_roi"], out["agreement_roi"] = self.run_second(volume, out["mask"], keep_variants, True)
+            else:
+                out["prediction_roi"] = self.run_second(volume, out["mask"], keep_variants)
         return out
 
 
 def predict_volume(data, model, config, overlap_factor=0.9, preprocess_method=None, norm_params=None, augment=None, num_augment=0,
                    model2=None, config2=None, preprocess_method2=None, norm_params2=None, augment2=None, num_augment2=0,
                    z_scale=None, xy_scale=None, return_all_preds=False, device=None, *, blend=None,
-                   blend_sigma_scale=prediction.DEFAULT_SIGMA_SCALE):
+                   blend_sigma_scale=prediction.DEFAULT_SIGMA_SCALE, return_agreement=False):
     """One-call form with the argument names of the reference's `main()` (predict_nifti2.py:98-160), on arrays: `data` = the volume as read
     from the NIfTI file.  Returns a dict: 'data' (the prepared volume the first model saw, before its border), 'prediction' (first stage, on
     the input grid) and, with model2 / config2, 'mask' and 'prediction_roi' (second stage on the padded bounding box, volume-sized).
     `device` (not in the reference): where the intensity preparation, the zooms and the variant medians run - None / True / False as for
     `Zoom`.  config['preproc'] may name a filter of `fetal_net.preprocess`, as the reference's configs do.
-    `blend` / `blend_sigma_scale` (not in the reference): how both stages combine overlapping tiles, as for `Stage`."""
+    `blend` / `blend_sigma_scale` (not in the reference): how both stages combine overlapping tiles, as for `Stage`.
+    `return_agreement` (not in the reference): adds 'agreement' and, with a second stage, 'agreement_roi': the `prediction.TTAAgreement`
+    of each stage's test-time variants (every stage then needs an `augment`).  Their maps (median, mean, variance, entropy,
+    disagreement) come back on the input grid through the steps the prediction takes back (crop, zoom back, box); their counts,
+    variant Dice, estimated Dice and volume spread are passed through as taken on the grid the model saw.  Without the flag the
+    returned dict is what it was.  `data` may be a float64 CUDA tensor where the first stage takes the resident route and there is no
+    second stage: tensors in, tensors out (the agreement's counts and scores stay numpy)."""
     if config2 is not None and model2 is None:
         raise ValueError("config2 given without model2")
     blending = dict(blend=blend, blend_sigma_scale=blend_sigma_scale)
     first = Stage(model, config, preprocess_method, norm_params, augment, num_augment, overlap_factor, device, **blending)
     second = None if config2 is None else Stage(model2, config2, preprocess_method2, norm_params2, augment2, num_augment2, overlap_factor,
                                                 device, **blending)
-    return VolumePipeline(first, second, resolution=(xy_scale, z_scale), device=device)(data, keep_variants=return_all_preds)
+    return VolumePipeline(first, second, resolution=(xy_scale, z_scale), device=device)(data, keep_variants=return_all_preds,
+                                                                                        agreement=return_agreement)
 
 
 def secondary_prediction(mask, vol, config2, model2, preprocess_method2=None, norm_params2=None, overlap_factor=0.9, augment2=None,
                          num_augment=32, return_all_preds=False, padding=ROI_PADDING, *, blend=None,
-                         blend_sigma_scale=prediction.DEFAULT_SIGMA_SCALE):
+                         blend_sigma_scale=prediction.DEFAULT_SIGMA_SCALE, return_agreement=False):
     """the second stage alone (reference predict_nifti2.py:25-53), for callers that already hold a first-stage mask; `blend` /
-    `blend_sigma_scale` as for `Stage`"""
+    `blend_sigma_scale` as for `Stage`.  return_agreement=True -> (the prediction, the stage's `prediction.TTAAgreement`): maps pasted
+    back like the prediction, counts and scores as taken on the box the model saw"""
     stage = Stage(model2, config2, preprocess_method2, norm_params2, augment2, num_augment, overlap_factor, blend=blend,
                   blend_sigma_scale=blend_sigma_scale)
-    return VolumePipeline(None, stage, roi_padding=padding).run_second(np.asarray(vol), mask, keep_variants=return_all_preds)
+    return VolumePipeline(None, stage, roi_padding=padding).run_second(np.asarray(vol), mask, keep_variants=return_all_preds,
+                                                                       agreement=return_agreement)

@@ -669,6 +669,174 @@ def predict_flips(data, model, overlap_factor, config, *, blend=None, blend_sigm
     return [stack[k] for k in range(len(variants))]
 
 
+# --------------------------------------------------------------------------------------------------- agreement of the TTA variants
+TTA_MAPS = ("mean", "variance", "entropy", "disagreement")
+TTA_MAX_VARIANTS, TTA_MAX_CHANNELS = 64, 16
+
+
+def agreement_scores(counts):
+    """(variant_dice (K, C), estimated_dice (C,), volume_cv (C,)) from the set sizes counts (C, 2K + 1) = [|M|, |V_0| .. |V_K-1|,
+    |V_0 & M| .. |V_K-1 & M|] per channel: the Dice of every variant's mask with the consensus mask, 2 i / (a + b), 1.0 where both are
+    empty; its mean over the variants (the "estimated Dice" of TTA self-training); and the population standard deviation of the variants'
+    volumes |V_k| over their mean, 0.0 where the mean is 0."""
+    counts = np.asarray(counts, dtype=np.int64)
+    if counts.ndim != 2 or counts.shape[1] < 3 or counts.shape[1] % 2 == 0:
+        raise ValueError("counts (C, 2K + 1) are needed (got %s)" % (counts.shape,))
+    K = (counts.shape[1] - 1) // 2
+    a, b, i = counts[:, :1], counts[:, 1:1 + K], counts[:, 1 + K:]
+    both = (a + b).astype(np.float64)
+    dice = np.where(both == 0, 1.0, 2.0 * i / np.where(both == 0, 1.0, both))
+    vol = b.astype(np.float64)
+    mean = vol.mean(axis=1)
+    cv = np.where(mean == 0, 0.0, vol.std(axis=1) / np.where(mean == 0, 1.0, mean))
+    return np.ascontiguousarray(dice.T), dice.mean(axis=1), cv
+
+
+class TTAAgreement(object):
+    """What K test-time variants of one prediction agree on (`tta_agreement`).  `median` and the requested maps of TTA_MAPS (`mean`,
+    `variance`: the population variance, `entropy`: the binary entropy of the mean in bits, `disagreement`: the share of variants on the
+    other side of the threshold than the median) are shaped like one variant, arrays or device tensors as the input was; a map that was
+    not asked for is None.  `counts` (C, 2K + 1) int64, `variant_dice` (K, C), `estimated_dice` (C,), `volume_cv` (C,): numpy, see
+    `agreement_scores`.  They describe the grid the variants are on."""
+
+    def __init__(self, median, maps, counts, threshold):
+        self.median = median
+        for name in TTA_MAPS:
+            setattr(self, name, maps.get(name))
+        self.threshold = float(threshold)
+        self.counts = np.asarray(counts, dtype=np.int64)
+        self.variant_dice, self.estimated_dice, self.volume_cv = agreement_scores(self.counts)
+
+    def map_names(self):
+        return ("median",) + tuple(name for name in TTA_MAPS if getattr(self, name) is not None)
+
+    def with_maps(self, fn):
+        """the same counts and scores with every map replaced by fn(map): how the pipeline takes the maps back to the input grid"""
+        maps = {name: fn(getattr(self, name)) for name in self.map_names()}
+        return TTAAgreement(maps.pop("median"), maps, self.counts, self.threshold)
+
+    def as_dict(self):
+        out = {name: getattr(self, name) for name in self.map_names()}
+        out.update(threshold=self.threshold, counts=self.counts, variant_dice=self.variant_dice, estimated_dice=self.estimated_dice,
+                   volume_cv=self.volume_cv)
+        return out
+
+
+def _checked_maps(maps):
+    maps = tuple(maps)
+    if any(m not in TTA_MAPS for m in maps) or len(set(maps)) != len(maps):
+        raise ValueError("maps must be distinct names of %s (got %r)" % (TTA_MAPS, maps))
+    return maps
+
+
+def _variants_stack(variants):
+    """a list of K variants or a stack of them -> (one float64 stack (K, X, Y, Z[, C]), whether it is a device tensor).  A list of views
+    that lie one behind the other in one device buffer - what `predict_flips` returns for a tensor - is taken as that buffer, not copied."""
+    if isinstance(variants, (list, tuple)):
+        if len(variants) == 0:
+            raise ValueError("1 to %d variants are needed (got 0)" % TTA_MAX_VARIANTS)
+        if all(_is_device_tensor(v) for v in variants):
+            import torch
+            first = variants[0]
+            step = first.numel() * first.element_size()
+            if first.is_contiguous() and all(v.is_contiguous() and v.shape == first.shape and v.dtype == first.dtype
+                                             and v.untyped_storage().data_ptr() == first.untyped_storage().data_ptr()
+                                             and v.data_ptr() == first.data_ptr() + k * step for k, v in enumerate(variants)):
+                variants = torch.as_strided(first, (len(variants),) + tuple(first.shape), (first.numel(),) + tuple(first.stride()))
+            else:
+                variants = torch.stack(list(variants))
+        else:
+            variants = np.stack([np.asarray(v) for v in variants])
+    tensor = _is_device_tensor(variants)
+    if not tensor:
+        variants = np.asarray(variants)
+    import torch
+    if variants.dtype != (torch.float64 if tensor else np.float64):
+        raise ValueError("float64 variants are needed (got %s)" % (variants.dtype,))
+    shape = tuple(variants.shape)
+    if len(shape) not in (4, 5) or min(shape[1:], default=0) < 1:
+        raise ValueError("variants (K, X, Y, Z) or (K, X, Y, Z, C) are needed (got %s)" % (shape,))
+    if not 1 <= shape[0] <= TTA_MAX_VARIANTS:
+        raise ValueError("1 to %d variants are needed (got %d)" % (TTA_MAX_VARIANTS, shape[0]))
+    if len(shape) == 5 and shape[4] > TTA_MAX_CHANNELS:
+        raise ValueError("at most %d channels are supported (got %d)" % (TTA_MAX_CHANNELS, shape[4]))
+    return variants, tensor
+
+
+def _tta_agreement_host(stack, threshold, maps):
+    """numpy in the operation order of fmri_tta_agreement_f64 (include/fmri_hip.h): the same bits, the entropy up to the two log2"""
+    K = stack.shape[0]
+    C = stack.shape[4] if stack.ndim == 5 else 1
+    srt = np.sort(stack, axis=0)
+    out = {"median": (srt[(K - 1) // 2] + srt[K // 2]) / 2.0}
+    del srt
+    if set(maps) & {"mean", "variance", "entropy"}:
+        total = stack[0].copy()
+        for k in range(1, K):
+            total = total + stack[k]
+        mu = total / float(K)
+        if "mean" in maps:
+            out["mean"] = mu
+        if "variance" in maps:
+            q = np.zeros_like(mu)
+            for k in range(K):
+                d = stack[k] - mu
+                q = q + d * d
+            out["variance"] = q / float(K)
+        if "entropy" in maps:
+            p = np.minimum(np.maximum(mu, 0.0), 1.0)
+            inside = (p > 0.0) & (p < 1.0)
+            pi = p[inside]
+            qi = 1.0 - pi
+            ent = np.zeros_like(mu)
+            ent[inside] = -(pi * np.log2(pi) + qi * np.log2(qi))
+            out["entropy"] = ent
+    V = stack > threshold
+    M = out["median"] > threshold
+    if "disagreement" in maps:
+        out["disagreement"] = (V != M[np.newaxis]).sum(axis=0).astype(np.float64) / float(K)
+    Vc, Mc = V.reshape(K, -1, C), M.reshape(-1, C)
+    counts = np.empty((C, 2 * K + 1), dtype=np.int64)
+    counts[:, 0] = Mc.sum(axis=0)
+    counts[:, 1:1 + K] = Vc.sum(axis=1).T
+    counts[:, 1 + K:] = (Vc & Mc[np.newaxis]).sum(axis=1).T
+    return out, counts
+
+
+def _tta_agreement_device(stack, threshold, maps):
+    """the device form on a float64 CUDA stack (K, X, Y, Z[, C]); one read-back: the counts"""
+    from fmri_hip import ops
+    C = int(stack.shape[4]) if stack.dim() == 5 else 1
+    out = ops.tta_agreement_f64(stack.contiguous(), threshold, channels=C, maps=maps, counts=True)
+    return out, out.pop("counts").cpu().numpy()
+
+
+def tta_agreement(variants, threshold=0.5, *, maps=TTA_MAPS, device=None):
+    """How far K test-time variants of one prediction agree, without a truth -> TTAAgreement.  `variants`: a list of K predictions or
+    their stack, (K, X, Y, Z) or (K, X, Y, Z, C) with C independent sigmoid channels, float64: what `predict_flips` returns and what
+    `predict_augment` stacks, numpy or CUDA tensors (tensors in, tensor maps out).  Voxel-wise: the median, and of `maps` the mean, the
+    population variance, the binary entropy of the mean (bits) and the share of variants that disagree with the median's label
+    (`> threshold`, the rule of `prediction_to_image`).  Per case and channel: the sizes of the consensus mask, of every variant's mask and
+    of their intersections, and from them every variant's Dice with the consensus, their mean (the estimated Dice) and the coefficient
+    of variation of the variants' volumes.  device: None / True / False as for `pipeline.Zoom`; on the device one kernel reads the stack
+    once (`fmri_hip.ops.tta_agreement_f64`), on the host numpy does the same operations in the same order: the same bits, but for the
+    entropy's log2."""
+    maps = _checked_maps(maps)
+    stack, tensor = _variants_stack(variants)
+    if tensor:
+        if device is not None and not device:
+            raise ValueError("a device tensor cannot take the host form")
+        out, counts = _tta_agreement_device(stack, threshold, maps)
+        return TTAAgreement(out.pop("median"), out, counts, threshold)
+    from .pipeline import _use_device
+    if _use_device(stack[..., 0] if stack.ndim == 5 else stack, device):
+        out, counts = _tta_agreement_device(_upload_f64(stack), threshold, maps)
+        out = {name: _download(t) for name, t in out.items()}
+    else:
+        out, counts = _tta_agreement_host(stack, threshold, maps)
+    return TTAAgreement(out.pop("median"), out, counts, threshold)
+
+
 def _hip_rotate_ok():
     try:
         import torch

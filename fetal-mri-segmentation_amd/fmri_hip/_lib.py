@@ -87,6 +87,7 @@ SIGNATURES = {
     "fmri_spline_filter1d_f64": [p, i32, i32, i32, i32, i32, p],
     "fmri_spline_affine_f64": [p, i32, i32, i32, p, p, p, i32, i32, i32, C.c_double, p],
     "fmri_median_stack_f64": [p, i32, i64, p, p],
+    "fmri_tta_agreement_f64": [p, i32, i64, i32, C.c_double, p, p, p, p, p, p, p],
     "fmri_order_stats_workspace_bytes": [],
     "fmri_order_stats_f64": [p, i64, p, i32, p, p, p, p],
     "fmri_minmax_f64": [p, i64, p, p, p],

@@ -1256,6 +1256,36 @@ def median_stack_f64(stack):
     return out
 
 
+TTA_MAPS = ("mean", "variance", "entropy", "disagreement")
+
+
+def tta_agreement_f64(stack, threshold=0.5, channels=1, maps=TTA_MAPS, counts=True):
+    """What the K variants of a float64 device stack [K, ...] (channels > 1: [K, ..., channels], channels last) agree on, in one pass
+    (fmri_tta_agreement_f64, include/fmri_hip.h): a dict of float64 device tensors shaped like stack[0] - 'median' (the bits of
+    median_stack_f64) and every map named in `maps` - plus, with counts=True, 'counts': an int64 device tensor (channels, 2K + 1) of
+    |median > t|, |v_k > t| and |v_k > t and median > t| per channel.  1 <= K <= 64, 1 <= channels <= 16, finite values."""
+    _need_cuda(stack)
+    if stack.dtype != torch.float64 or stack.dim() < 2 or stack.numel() == 0:
+        raise ValueError("a non-empty float64 stack [K, ...] is needed (got %s %s)" % (stack.dtype, tuple(stack.shape)))
+    K, C = int(stack.shape[0]), int(channels)
+    if not 1 <= K <= 64:
+        raise ValueError("1 to 64 variants are needed (got %d)" % K)
+    if not 1 <= C <= 16 or (C > 1 and int(stack.shape[-1]) != C):
+        raise ValueError("channels must be 1, or the stack's last extent and at most 16 (got %d for %s)" % (C, tuple(stack.shape)))
+    maps = tuple(maps)
+    unknown = [m for m in maps if m not in TTA_MAPS]
+    if unknown or len(set(maps)) != len(maps):
+        raise ValueError("maps must be distinct names of %s (got %r)" % (TTA_MAPS, maps))
+    out = {name: torch.empty(stack.shape[1:], dtype=torch.float64, device=stack.device) for name in ("median",) + maps}
+    if counts:
+        out["counts"] = torch.empty((C, 2 * K + 1), dtype=torch.int64, device=stack.device)
+    with torch.cuda.device(stack.device):
+        check(lib().fmri_tta_agreement_f64(_p(stack), K, out["median"].numel() // C, C, float(threshold), _p(out["median"]),
+                                           _p(out.get("mean")), _p(out.get("variance")), _p(out.get("entropy")),
+                                           _p(out.get("disagreement")), _p(out.get("counts")), _s()), "fmri_tta_agreement_f64")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- discriminator head (discriminator.hip)
 # ---------------------------------------------------------------------------------------------------- intensity preparation (postprocess.hip)
 MAP_WINDOW, MAP_MINMAX, MAP_ZSCORE = 0, 1, 2

@@ -684,12 +684,26 @@ int fmri_edt_two_class_u8(const uint8_t* mask, double* out, double* scratch, int
  *   axis with an identity row is scipy's plane-by-plane form of rotate): order + 1 taps from floor(c) - order/2 (odd) or
  *   floor(c + 0.5) - order/2 (even), indices beyond the edge mirrored about the end samples.  coef != out.
  * fmri_median_stack_f64: out[v] = median of stack[k * n + v], k < K, 1 <= K <= 64 (else FMRI_E_SHAPE); even K: the two middle values
- *   added, then halved (np.median).  The values must not be NaN: the result is unspecified if one is. */
+ *   added, then halved (np.median).  The values must not be NaN: the result is unspecified if one is.
+ * fmri_tta_agreement_f64: what K test-time variants of one prediction agree on, in ONE pass over stack [K][nvox][C] (channels last).
+ *   Per element t = (voxel, c) with v_k = stack[k][t], every operation rounded on its own, in the order written:
+ *     median[t]        what fmri_median_stack_f64 writes (the same bits)
+ *     mean[t]          mu = (((v_0 + v_1) + v_2) + ...) / K
+ *     variance[t]      (sum over k, in k order, of (v_k - mu) * (v_k - mu)) / K              (population variance)
+ *     entropy[t]       p = min(max(mu, 0), 1):  -(p * log2 p + (1 - p) * log2(1 - p)) in bits, exactly 0 at p = 0 and p = 1
+ *     disagreement[t]  #{k : (v_k > threshold) != (median[t] > threshold)} / K
+ *     counts[c][0] = |M_c|, counts[c][1 + k] = |V_kc|, counts[c][1 + K + k] = |V_kc and M_c|, M = median > threshold, V_k = v_k >
+ *                      threshold: [C][2K + 1] exact 64-bit sums, set to zero by the call on `stream` before they are taken
+ *   mean, variance, entropy, disagreement and counts may each be NULL: nothing is computed or stored for a NULL output.  1 <= K <= 64,
+ *   1 <= C <= 16, nvox > 0, stack and median not NULL and no output inside the stack, else FMRI_E_SHAPE: nothing is launched, the outputs
+ *   are untouched.  The values must be finite. */
 int fmri_spline_lds_max_line(void);
 int fmri_spline_filter1d_f64(double* vol, int X, int Y, int Z, int axis, int order, fmri_stream_t stream);
 int fmri_spline_affine_f64(const double* coef, int X, int Y, int Z, const double* affine12_host, const int* orders3, double* out, int NX,
                            int NY, int NZ, double cval, fmri_stream_t stream);
 int fmri_median_stack_f64(const double* stack, int K, int64_t n, double* out, fmri_stream_t stream);
+int fmri_tta_agreement_f64(const double* stack, int K, int64_t nvox, int C, double threshold, double* median, double* mean,
+                           double* variance, double* entropy, double* disagreement, uint64_t* counts, fmri_stream_t stream);
 
 /* ---- intensity preparation of a contiguous fp64 volume in front of the model (reference prod/predict_nifti2.py:57-74 and
  * fetal_net/preprocess.py: the percentile window, laplace, gaussian_gradient_magnitude, min-max and z-score maps).  numpy's / scipy's own
