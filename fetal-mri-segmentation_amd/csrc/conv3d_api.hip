@@ -14,6 +14,8 @@ int conv3d_fwd_mfma(const void*, int, int, int, const void*, int, const void*, c
 int conv3d_wgrad_mfma_f32(const void*, int, int, const void*, int, const void*, float*, float*, int, int, int, int, int, hipStream_t);
 int conv3d_wgrad_mfma(const void*, int, int, int, const void*, int, const void*, float*, float*, int, int, int, int, int, void*, int64_t,
                       hipStream_t);
+int conv3d_wgrad_mfma_kd_slab(const void*, int, int, int, const void*, int, const void*, float*, int, float*, int, int, int, int, int, void*,
+                              int64_t, hipStream_t);
 int64_t conv3d_wgrad_mfma_ws_bytes(int C0, int C1, int Cout, int N, int D, int H, int W, int planar);
 int conv3d_upcat_wgrad_mfma(const void*, int, const void*, int, const void*, float*, float*, float*, int, int, int, int, int, int, void*, int64_t,
                             hipStream_t);
@@ -136,6 +138,12 @@ extern "C" int fmri_conv3d_wgrad(const void* src0, int C0, int up0, const void* 
         workspace_bytes = 0;
     }
     if (impl == FMRI_IMPL_MFMA && !can) return FMRI_E_SHAPE;
+    if (impl == FMRI_IMPL_MFMA_KD_SLAB) {                 // the kd-sharing kernel with the slab flush, whatever the size (tests)
+        if (!can || dtype != FMRI_BF16 || planar || up0 || !workspace) return FMRI_E_SHAPE;
+        if ((((uintptr_t)src0) | ((uintptr_t)src1) | ((uintptr_t)dy) | ((uintptr_t)workspace) | ((uintptr_t)dw)) & 15) return FMRI_E_ALIGN;
+        return conv3d_wgrad_mfma_kd_slab(src0, C0, up0, planar, src1, C1, dy, dw, C0 + C1, db, N, D, H, W, Cout, workspace, workspace_bytes,
+                                         as_stream(stream));
+    }
     if (can && impl != FMRI_IMPL_GENERIC) {
         if ((((uintptr_t)src0) | ((uintptr_t)src1) | ((uintptr_t)dy)) & 15) return FMRI_E_ALIGN;
         if (dtype == FMRI_F32) return conv3d_wgrad_mfma_f32(src0, C0, up0, src1, C1, dy, dw, db, N, D, H, W, Cout, as_stream(stream));

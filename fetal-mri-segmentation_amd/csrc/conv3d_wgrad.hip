@@ -4,6 +4,7 @@
 // Reference ops replaced: Conv3DBackpropFilterV2 / BiasAddGrad emitted by Keras for fetal_net/model/unet3d/unet.py:45-66,89-115,132-138.
 #define FMRI_MFMA_TU_WGRAD
 #include "mfma_common.h"
+#include "wgrad_slab_index.h"
 
 FMRI_DET_TU(mfma)
 
@@ -349,6 +350,8 @@ k_conv_wgrad_mfma(SrcB s, const bf16_t* __restrict__ dy, float* __restrict__ dw,
 // barrier domain for eight waves, 8-25 % slower.  Round 6 measured a (64 Cout, 32 Cin) block with one wave per SIMD level with this form:
 // DESIGN.md 3.4.)
 // Flush: fp32 atomics (128 contiguous bytes per half-wave).  Bit-identical sums on exactly representable data (tests).
+// SLAB (bf16 only): plain stores of the 27 x 32 x 32 partial sums into a workspace instead, reduced by k_wgrad_reduce_kd - the launches
+// below 0.3 TFLOP that come with a workspace (wgrad_kd_slab_launch).  Matrix loop, plane ring, cursor and DMA are the same code.
 // F32 (round 6, the fp32 parity mode on this kernel's structure): fp32 planes, a (32 Cout, 32 Cin) block on v_mfma_f32_32x32x2_f32 - rows of
 // 128 bytes for both operands, the plane ring / DMA pieces / cursor / flush of the bf16 kernel; a fragment is ONE voxel per half-wave
 // (lane = channel), so it is a plain ds_read_b32 per operand and MFMA, no transposing read.  One workgroup per CU (124 KiB of LDS).
@@ -456,10 +459,11 @@ struct WkArgs {
     float* dw;
     float* db;
     int N, D, H, W, Cout, nslab, dw_ld;
+    float* ws;                                           // slab flush (SLAB): the partial sums' workspace, see wgrad_slab_index.h
 };
 
 // everything a wave does, instantiated per tap group so that the accumulators are one fixed register set for the kernel's lifetime
-template <int G, bool F32 = false>
+template <int G, bool F32 = false, bool SLAB = false>
 __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int wv, int lane) {
     typedef WkCfg<F32> K;
     constexpr int EU = F32 ? 2 : 1;                      // 2-byte units per element: channel counts that are memory strides come in these (s.C0, s.C1)
@@ -654,18 +658,32 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
 #endif
     }
     // ---- flush: D rows = co, cols = ci; fp32 atomics, 128 contiguous bytes per half-wave (deterministic mode: fixed-point shadow)
+    // SLAB: plain stores of the workgroup's 27 x 32 x 32 partial sums into ws[slab][block] instead (same 128 contiguous bytes per half-wave;
+    // a workgroup without units stores its zeros), summed in a fixed slab order by k_wgrad_reduce_kd: no atomics on dw, no shadow needed.
+    // The bias sums STAY atomic (32 floats per workgroup of Cin block 0, through fmri_grad_add like the per-kd slab route: exact in the
+    // deterministic mode's fixed point, and in fp32 wherever the sums are exactly representable).
     const FmriDetCfg dc = g_det_cfg;
+    if constexpr (SLAB) {
+        static_assert(NH == 1 && !F32, "slab flush: the bf16 (32, 32) block");
+        float* const my = a.ws + wks::flush_index(slab, ncombo, combo, 0, 0, 0);
 #pragma unroll
-    for (int j = 0; j < NTAP; ++j) {
-        const int tap = 7 * G + j;
+        for (int j = 0; j < NTAP; ++j)
 #pragma unroll
-        for (int h = 0; h < NH; ++h)
+            for (int reg = 0; reg < 16; ++reg)
+                my[wks::flush_index(0, ncombo, 0, 7 * G + j, (reg & 3) + 8 * (reg >> 2) + 4 * hk, r)] = acc[j][0][reg];
+    } else {
 #pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int co = co0 + h * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hk;
-                const int ci = ccr + r;
-                fmri_grad_add(dc, &a.dw[((int64_t)tap * Cout + co) * a.dw_ld + ci], acc[j][h][reg]);
-            }
+        for (int j = 0; j < NTAP; ++j) {
+            const int tap = 7 * G + j;
+#pragma unroll
+            for (int h = 0; h < NH; ++h)
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int co = co0 + h * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hk;
+                    const int ci = ccr + r;
+                    fmri_grad_add(dc, &a.dw[((int64_t)tap * Cout + co) * a.dw_ld + ci], acc[j][h][reg]);
+                }
+        }
     }
     if (do_bias) {
 #pragma unroll
@@ -677,16 +695,16 @@ __device__ __forceinline__ void wk_run(const WkArgs& a, unsigned char* lds, int 
     }
 }
 
-template <bool F32 = false>
+template <bool F32 = false, bool SLAB = false>
 __global__ void __launch_bounds__(256, F32 ? 1 : 2) k_conv_wgrad_kd(WkArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[WkCfg<F32>::LDS_BYTES];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     switch (wv & 3) {                                     // tap group
-        case 0: wk_run<0, F32>(a, lds, wv, lane); break;
-        case 1: wk_run<1, F32>(a, lds, wv, lane); break;
-        case 2: wk_run<2, F32>(a, lds, wv, lane); break;
-        default: wk_run<3, F32>(a, lds, wv, lane); break;
+        case 0: wk_run<0, F32, SLAB>(a, lds, wv, lane); break;
+        case 1: wk_run<1, F32, SLAB>(a, lds, wv, lane); break;
+        case 2: wk_run<2, F32, SLAB>(a, lds, wv, lane); break;
+        default: wk_run<3, F32, SLAB>(a, lds, wv, lane); break;
     }
 }
 
@@ -1023,9 +1041,55 @@ k_wgrad_reduce(const float* __restrict__ ws, float* __restrict__ dw, int Cout, i
     }
 }
 
+// The same for the slab flush of k_conv_wgrad_kd (workspace image and indices: wgrad_slab_index.h): dw[tap][cob*32 + row][cib*32 + col] +=
+// sum over the slabs of block (cob, cib), row length dw_ld.  Block = 32 float4 columns x 8 slab groups; slab group g sums the slabs g, g + 8,
+// g + 16, ... in ascending order (four independent 16-byte loads in flight), the 8 group sums meet in LDS in group order: one fixed
+// summation order per element whatever the workgroups' arrival order was (bit-reproducible).  Grid = every column of the gradient: 27 x Cout x
+// Cin / 128 workgroups, the whole chip from 64 x 64 channels on.
+// (In the two-stream step this kernel takes ~57 us per launch, three times its exclusive time.  A form without LDS - a wave = 8 columns x 8
+// slab groups, the group sums combined by lane shuffles, so that its workgroups fit beside the other stream's LDS-filling convolution
+// workgroups - was SLOWER, alone (the seven small layers 0.787 -> 0.813 ms) and in the step (five of five pairs, -0.1 ... -0.5 %): 128
+// contiguous bytes per slab and wave instead of 512.  profiles/kd_slab3_ab.log; not kept.)
+__global__ void __launch_bounds__(256)
+k_wgrad_reduce_kd(const float* __restrict__ ws, float* __restrict__ dw, int Cout, int dw_ld, int nslab, int nblocks, int ncib) {
+    __shared__ float4 red[8][32];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int64_t q = (int64_t)blockIdx.x * 32 + tx;          // float4 column of the [block][tap][row][col] image
+    const bool ok = q < (int64_t)nblocks * wks::BLOCK_F4;
+    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
+    if (ok) {
+        const float4* const src = reinterpret_cast<const float4*>(ws);
+        int j = ty;
+        for (; j + 24 < nslab; j += 32) {
+            const float4 v0 = src[wks::reduce_src4(j, nblocks, q)], v1 = src[wks::reduce_src4(j + 8, nblocks, q)];
+            const float4 v2 = src[wks::reduce_src4(j + 16, nblocks, q)], v3 = src[wks::reduce_src4(j + 24, nblocks, q)];
+            a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
+            a1.x += v1.x; a1.y += v1.y; a1.z += v1.z; a1.w += v1.w;
+            a2.x += v2.x; a2.y += v2.y; a2.z += v2.z; a2.w += v2.w;
+            a3.x += v3.x; a3.y += v3.y; a3.z += v3.z; a3.w += v3.w;
+        }
+        for (; j < nslab; j += 8) {
+            const float4 v0 = src[wks::reduce_src4(j, nblocks, q)];
+            a0.x += v0.x; a0.y += v0.y; a0.z += v0.z; a0.w += v0.w;
+        }
+    }
+    red[ty][tx] = make_float4((a0.x + a1.x) + (a2.x + a3.x), (a0.y + a1.y) + (a2.y + a3.y), (a0.z + a1.z) + (a2.z + a3.z),
+                              (a0.w + a1.w) + (a2.w + a3.w));
+    __syncthreads();
+    if (ty == 0 && ok) {
+        float4 t = red[0][tx];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) { t.x += red[k][tx].x; t.y += red[k][tx].y; t.z += red[k][tx].z; t.w += red[k][tx].w; }
+        float4* dst = reinterpret_cast<float4*>(dw + wks::reduce_dst(q, ncib, Cout, dw_ld));
+        float4 d = *dst;
+        d.x += t.x; d.y += t.y; d.z += t.z; d.w += t.w;
+        *dst = d;
+    }
+}
+
 }  // namespace
 
-int fmri_f32_mfma();                    // FMRI_F32_MFMA (conv3d_mfma.hip)
+int fmri_f32_mfma();                 // FMRI_F32_MFMA (conv3d_mfma.hip)
 bool conv3d_wgrad_mfma_ok(int C0, int C1, int Cout, int D, int H, int W, int dtype) {
     if (dtype == FMRI_F32)                // k_conv_wgrad_kd<F32>: (32 Cout, 32 Cin) blocks of fp32 planes
         return fmri_f32_mfma() && !(C0 % 32) && !(C1 % 32) && C0 + C1 >= 32 && !(Cout % 32) && !(H % wg::TH) && !(W % wg::TW) &&
@@ -1048,6 +1112,10 @@ static void wgrad_plan(int C0, int C1, int Cout, int N, int D, int H, int W, int
     // want few workgroups and large ones many (load balance / tail): measured per layer at BASELINE config 2 (tools/bench_conv.py, sweep of
     // the workgroup count) >= 0.9 TFLOP layers are fastest at ~2048, the rest at ~768, the smallest at ~512.  The launches with a slab
     // workspace (plain store + one reduction pass instead of the atomic flush) use the same counts.
+    // (These counts also fix fmri_conv3d_wgrad_workspace_bytes, which is part of the engines' recorded launch schedule: they stay.  Since the
+    // kd-sharing slab route - wgrad_kd_slab_launch below - no 3-D launch of the benchmarked U-Net with a workspace runs this plan any more:
+    // what remains on it are 2-D slices, launches below 20 GFLOP and callers without a workspace, for which 512 against 768 was NOT
+    // re-measured inside a step - there is no such launch in the step to measure it on.)
     const double flops = 2.0 * (planar ? 9 : 27) * (double)Cin * Cout * (double)N * D * H * W;
     int target_wgs = flops >= 0.9e12 ? 2048 : (flops >= 0.06e12 ? 768 : 512);
     if (planar) target_wgs = 512;       // 2-D slices (one kd plane per combo): two workgroups per CU throughout (configs[3] step: 13.7 -> 13.5 ms)
@@ -1062,9 +1130,11 @@ int64_t conv3d_wgrad_mfma_ws_bytes(int C0, int C1, int Cout, int N, int D, int H
     return (int64_t)combos * nslab * (CIB == 32 ? 2 : 1) * 9 * 64 * CIB * (int64_t)sizeof(float);
 }
 
-// launches of at least this many FLOPs take the kd-sharing kernel with its atomic flush, smaller ones the per-kd kernel with the slab flush
-// (round 2, per layer and inside the step; see conv3d_wgrad_mfma_ld.  Round 6 tried 20 GFLOP: per launch -5 ... -13 % on four small layers,
-// but the step 0.7 % slower - their atomic flushes land on the input-gradient stream's kernels)
+// launches of at least this many FLOPs take the kd-sharing kernel with its ATOMIC flush (the slab flush measured ~4 % slower there: the
+// atomic flush overlaps other workgroups' MFMA work, the reduction is a serial tail).  Below it: with a workspace and from
+// WGRAD_KD_SLAB_MIN_GFLOP on, the kd-sharing kernel with the SLAB flush (wgrad_kd_slab_launch); else the per-kd kernel, with its slab flush
+// or - no workspace - atomics.  (Round 6 tried the atomic form from 20 GFLOP: per launch -5 ... -13 % on four small layers, but the step
+// 0.7 % slower - their atomic flushes land on the input-gradient stream's kernels.  The slab form has no such flush)
 constexpr double WGRAD_KD_MIN_FLOPS = 0.3e12;
 // FMRI_WGRAD_KD: 0 = the per-kd kernel everywhere, 2 (default) = the kd-sharing kernel on the launches below, 3 = the same plus the
 // fused-upsample launches
@@ -1087,6 +1157,62 @@ bool conv3d_wgrad_cout32_ok(int C0, int C1, int Cout, int N, int D, int H, int W
     if (dtype != FMRI_BF16 || (C0 % 32) || (C1 % 32) || C0 + C1 < 32 || (Cout % 32) || (H % wg::TH) || (W % wg::TW)) return false;
     return wgrad_takes_kd(C0, C1, Cout, N, D, H, W, planar, up0, false);
 }
+// ---- the kd-sharing kernel with the slab flush (k_conv_wgrad_kd<false, true> + k_wgrad_reduce_kd): launches with a workspace of at least
+// wgrad_kd_slab_min_gflop() GFLOP and below WGRAD_KD_MIN_FLOPS.  Against the per-kd kernel with its slab flush it stages every plane once
+// instead of three times (90 instead of 135 B of LDS-DMA per MFMA) and runs ONE resident round of workgroups whose partial sums are half the
+// bytes (2 per CU x 27 x 32 x 32 fp32 = 56 MB against 768 x 9 x 64 x 64 = 113 MB per launch); against its own atomic form (round 6, 20 GFLOP
+// threshold: per launch faster, the step 0.7 % slower) no atomic flush lands on the other stream's kernels.
+// Shapes the route accepts, established by reading wk_run before anything ran: 3-D, bf16, C0 / C1 / Cout multiples of 32, no fused
+// up-sampling, H % 8 == 0 and W % 16 == 0 (conv3d_wgrad_mfma_ok), ANY N and D >= 1.  The cases small layers produce:
+//   fewer units than slabs   the slab count is capped at the unit count (per = 1: no unit ever has a successor, nothing is issued ahead);
+//                            were it not, a workgroup with u >= u_end skips the loop and flushes zeros - stores, not "nothing"
+//   a slab starts mid-column the prologue issues planes d - 1, d, d + 1 of ITS unit; x_rsrc turns a plane outside [0, D) into a descriptor
+//                            of zero records, so d = 0 and d = D - 1 need nothing special
+//   last unit = top of a column   `more` is false: nothing issued, no cursor advance, no second barrier
+//   D = 8, two columns per sample (level 3)   every 8th unit takes the fresh-column path, whose plane -1 / 0 / 1 issues use the NEW column's
+//                            lane constants (col_setup runs before them) and whose ring slots are the three the old column no longer reads
+//   per not dividing the unit count   u_end = min(nunits, u + per): the last slab is short, slabs past the end are empty (zeros, as above)
+// No defect found; tests/test_gpu_wgrad_kd_slab.py runs each of these cases against fp64 bit for bit.
+//
+// Threshold 20 GFLOP (round 6's), i.e. all eight launches of the headline step below 0.3 TFLOP.  Measured on one MI355X, parent library
+// against this one, alternating (profiles/kd_slab_explore_ab.log; the final run of the tree is profiles/kd_slab_ab.log):
+//   exclusive ms per launch, per-kd slab -> kd-sharing slab          GFLOP   workgroups   partial sums
+//     conv3d_3  64 -> 64   64^2 x 32   0.1273 -> 0.1068               116    768 -> 512   113 -> 57 MB
+//     conv3d_4  64 -> 128              0.2152 -> 0.1931               232    768 -> 512   113 -> 57 MB
+//     conv3d_5  128 -> 128 32^2 x 16   0.0778 -> 0.0631                58    516 -> 512    76 -> 57 MB
+//     conv3d_6  128 -> 256             0.1186 -> 0.1016               116    768 -> 512   113 -> 57 MB
+//     conv3d_7  256 -> 256 16^2 x 8    0.0623 -> 0.0453                29    528 -> 512    78 -> 57 MB
+//     conv3d_8  256 -> 512             0.0932 -> 0.0727                58    576 -> 512    85 -> 57 MB
+//     conv3d_10 256 -> 256 32^2 x 16   0.2075 -> 0.1904               232    768 -> 512   113 -> 57 MB
+//     conv3d_9  both halves (its skip half is conv3d_10's launch into a 768-wide dw)   0.3675 -> 0.3499
+//   sum of the seven 0.902 -> 0.773 ms; partial sums written and read back per step 1.61 -> 0.91 GB
+//   inside the two-stream step, patches/s (two runs each): parent 307.26 307.27 | threshold 20: 310.94 312.85 | 40 (without conv3d_7):
+//   310.80 311.33 | 80 (without _5, _7, _8): 311.60 311.16 | 150 (only _4, _10 and the skip half of _9): 310.56 310.00.
+// No layer is slower on the route, alone or in the step, so none stays behind; below 20 GFLOP nothing was measured and nothing changes.
+constexpr int WGRAD_NOT_TAKEN = -1000;
+// FMRI_WGRAD_KD_SLAB_MIN_GFLOP: the lower threshold in GFLOP (0 = every launch below WGRAD_KD_MIN_FLOPS, 300 = none: the per-kd route)
+constexpr int WGRAD_KD_SLAB_MIN_GFLOP = 20;
+static int wgrad_kd_slab_min_gflop() {
+    static const int v = env_int("FMRI_WGRAD_KD_SLAB_MIN_GFLOP", WGRAD_KD_SLAB_MIN_GFLOP, {0, 20, 40, 80, 150, 300});
+    return v;
+}
+static bool wgrad_kd_slab_ok(int C0, int C1, int Cout, int planar, int up0) {
+    return !planar && !up0 && (C0 % 32 == 0) && (C1 % 32 == 0) && C0 + C1 >= 32 && (Cout % 32 == 0);
+}
+// WGRAD_NOT_TAKEN where the workspace does not hold one slab (the caller goes on to the per-kd route)
+static int wgrad_kd_slab_launch(const SrcB& s, const void* dy, float* dw, int dw_ld, float* db, int N, int D, int H, int W, int Cout,
+                                void* workspace, int64_t workspace_bytes, hipStream_t st) {
+    const int ncib = (s.C0 + s.C1) / 32, nblocks = (Cout / 32) * ncib;
+    const int nunits = N * D * (H / wg::TH) * (W / wg::TW);
+    const int nsl = wks::slab_count(2 * fwd_cu_count(), nblocks, workspace_bytes, nunits);
+    if (nsl < 1) return WGRAD_NOT_TAKEN;
+    if (((((uintptr_t)workspace) | ((uintptr_t)dw)) & 15) || (dw_ld & 3)) return WGRAD_NOT_TAKEN;      // the reduction's 16-byte accesses
+    const WkArgs wa{s, (const bf16_t*)dy, dw, db, N, D, H, W, Cout, nsl, dw_ld, (float*)workspace};
+    k_conv_wgrad_kd<false, true><<<nblocks * nsl, 256, 0, st>>>(wa);
+    k_wgrad_reduce_kd<<<nblocks * (wks::BLOCK_F4 / 32), 256, 0, st>>>((const float*)workspace, dw, Cout, dw_ld, nsl, nblocks, ncib);
+    FMRI_LAUNCH_CHECK();
+    return FMRI_OK;
+}
 // dw_ld: row length of the dw image the gradient is added into (>= C0 + C1; lets a launch over a subset of the input channels write
 // its columns of the full [27][Cout][Cin] gradient: pass dw already offset to the first column)
 int conv3d_wgrad_mfma_ld(const void* src0, int C0, int up0, int planar, const void* src1, int C1, const void* dy, float* dw, int dw_ld,
@@ -1095,6 +1221,7 @@ int conv3d_wgrad_mfma_ld(const void* src0, int C0, int up0, int planar, const vo
     const int Cin = C0 + C1;
     // The slab flush wins where the flush dominates (small layers: -25..35 %) and loses ~4 % on the >= 0.3 TFLOP layers, whose atomic
     // flush overlaps other workgroups' MFMA work while the reduction pass is a serial tail (tools/bench_conv.py, BENCH_WGRAD_WS=0|1).
+    // use_ws: the PER-KD kernel's slab flush (needs the queried bytes); the kd-sharing slab route below sizes itself to the bytes it is given.
     static const int force_slab = env_int("FMRI_WGRAD_SLAB", 0, {0, 1});      // 1: always use the workspace when given (bit-reproducible), 0: heuristic
     const double flops_ = 2.0 * (planar ? 9 : 27) * (double)(C0 + C1) * Cout * (double)N * D * H * W;
     const bool use_ws = workspace != nullptr && workspace_bytes >= conv3d_wgrad_mfma_ws_bytes(C0, C1, Cout, N, D, H, W, planar) &&
@@ -1106,9 +1233,16 @@ int conv3d_wgrad_mfma_ld(const void* src0, int C0, int up0, int planar, const vo
     // exclusive times, late round 2) the 4-wave form is level or ahead on EVERY launch that does not take the slab flush: dec0b 0.735 ->
     // 0.667 ms, the skip halves of dec0a / dec1a 1.33 -> 1.19 / 0.695 -> 0.657, dec1b 0.39 -> 0.367, nothing slower; weight-gradient
     // family 4.64 -> 4.34 ms per step, step 13.96 -> 13.73 ms.  FMRI_WGRAD_KD: 0 = off, 1 = only the layers with a 32-wide Cin block and
-    // >= 0.1 TFLOP (the default until then), 2 (default) = also every launch of >= 0.3 TFLOP without fused up-sampling (below that the
-    // per-kd kernel is ahead, with the slab flush or - callers without a workspace, e.g. the layer-graph engine - with the atomic one:
-    // Isensee defaults 11.3 vs 11.65 ms per step), 3 = the fused-upsample launches too.
+    // >= 0.1 TFLOP (the default until then), 2 (default) = also every launch of >= 0.3 TFLOP without fused up-sampling (below that,
+    // callers without a workspace - e.g. the layer-graph engine - stay on the per-kd kernel with its atomic flush: Isensee defaults 11.3 vs
+    // 11.65 ms per step), 3 = the fused-upsample launches too.
+    // Below 0.3 TFLOP WITH a workspace: the kd-sharing kernel with the slab flush (wgrad_kd_slab_launch above: shapes, threshold, figures);
+    // where it does not take the launch (2-D, fused up-sampling, below its threshold, no room for one slab) the per-kd kernel as before.
+    if (workspace != nullptr && wgrad_kd_mode() != 0 && flops_ < WGRAD_KD_MIN_FLOPS && flops_ >= 1e9 * wgrad_kd_slab_min_gflop() &&
+        wgrad_kd_slab_ok(C0, C1, Cout, planar, up0)) {
+        const int rc = wgrad_kd_slab_launch(s, dy, dw, dw_ld, db, N, D, H, W, Cout, workspace, workspace_bytes, st);
+        if (rc != WGRAD_NOT_TAKEN) return rc;
+    }
     if (wgrad_takes_kd(C0, C1, Cout, N, D, H, W, planar, up0, use_ws)) {
         const int combos_kd = (Cout / 32) * (Cin / 32);
         const int nunits = N * D * (H / wg::TH) * (W / wg::TW);
@@ -1161,6 +1295,16 @@ int conv3d_wgrad_mfma_f32(const void* src0, int C0, int up0, const void* src1, i
 int conv3d_wgrad_mfma(const void* src0, int C0, int up0, int planar, const void* src1, int C1, const void* dy, float* dw, float* db, int N,
                       int D, int H, int W, int Cout, void* workspace, int64_t workspace_bytes, hipStream_t st) {
     return conv3d_wgrad_mfma_ld(src0, C0, up0, planar, src1, C1, dy, dw, C0 + C1, db, N, D, H, W, Cout, workspace, workspace_bytes, st);
+}
+// FMRI_IMPL_MFMA_KD_SLAB: the kd-sharing kernel with the slab flush at ANY size it accepts (wgrad_kd_slab_ok), for the tests of the route at
+// small shapes.  dw_ld >= C0 + C1 as in conv3d_wgrad_mfma_ld.  A workspace that does not hold one slab: the per-kd route, as in the dispatch.
+int conv3d_wgrad_mfma_kd_slab(const void* src0, int C0, int up0, int planar, const void* src1, int C1, const void* dy, float* dw, int dw_ld,
+                              float* db, int N, int D, int H, int W, int Cout, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+    if (workspace == nullptr || dw_ld < C0 + C1 || !wgrad_kd_slab_ok(C0, C1, Cout, planar, up0)) return FMRI_E_SHAPE;
+    SrcB s{(const bf16_t*)src0, (const bf16_t*)src1, C0, C1, 0, 1, 0};
+    const int rc = wgrad_kd_slab_launch(s, dy, dw, dw_ld, db, N, D, H, W, Cout, workspace, workspace_bytes, st);
+    if (rc != WGRAD_NOT_TAKEN) return rc;
+    return conv3d_wgrad_mfma_ld(src0, C0, up0, planar, src1, C1, dy, dw, dw_ld, db, N, D, H, W, Cout, workspace, workspace_bytes, st);
 }
 
 // ---- weight gradient of up-sample + concat + conv in parity form.  dwc: fp32 scratch [8][8][Cout][C0] (zeroed here).

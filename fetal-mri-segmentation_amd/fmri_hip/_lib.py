@@ -6,6 +6,7 @@ F32, BF16 = 0, 1
 F64 = 3                 # fmri_volume_pad_flip only
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA = 0, 1, 2
+IMPL_MFMA_KD_SLAB = 3     # fmri_conv3d_wgrad only: the kd-sharing kernel with the slab flush at any size (needs a workspace)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FMRI_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libfmri_hip.so")   # FMRI_LIB: A/B builds

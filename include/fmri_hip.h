@@ -34,7 +34,11 @@ enum { FMRI_F32 = 0, FMRI_BF16 = 1, FMRI_U8 = 2 /* label volumes of fmri_affine_
        FMRI_F64 = 3 /* the volumes of fmri_volume_pad_flip only */ };
 enum { FMRI_ACT_NONE = 0, FMRI_ACT_RELU = 1, FMRI_ACT_LEAKY = 2 };
 /* which implementation a conv call may use: AUTO picks MFMA when the shape allows it */
-enum { FMRI_IMPL_AUTO = 0, FMRI_IMPL_GENERIC = 1, FMRI_IMPL_MFMA = 2 };
+enum { FMRI_IMPL_AUTO = 0, FMRI_IMPL_GENERIC = 1, FMRI_IMPL_MFMA = 2,
+       /* fmri_conv3d_wgrad only (a test hook: AUTO takes the same route by size): the kd-sharing MFMA kernel with the slab flush at any size.
+        * Needs bf16, 3-D, no fused up-sampling, a shape of the MFMA path and a workspace, else FMRI_E_SHAPE; a workspace too small for
+        * one slab of partial sums falls back to what FMRI_IMPL_MFMA runs.  Every other conv call treats it as AUTO. */
+       FMRI_IMPL_MFMA_KD_SLAB = 3 };
 
 int fmri_version(void);
 const char* fmri_error_string(int code);
@@ -104,7 +108,8 @@ int fmri_conv3d_first_dgrad(const void* dy, int Cout, const void* w, float* dx, 
  * Same dual-source / fused-upsample input description as fmri_conv3d_fwd.
  * workspace (optional, device, fp32 scratch of at least fmri_conv3d_wgrad_workspace_bytes(...) bytes): the MFMA path then flushes its
  * per-workgroup partial sums with plain stores and reduces them in a second launch (bit-reproducible, faster than the fp32-atomic
- * flush used when workspace == NULL).  fp32 planes on the MFMA path (channel counts in multiples of 32, 3-D) always use the atomic flush. */
+ * flush used when workspace == NULL).  3-D launches below 0.3 TFLOP run the kd-sharing kernel on it, in as many slabs of partial sums as
+ * the bytes handed over hold (at most one resident round of workgroups); with fewer bytes than one slab they run as without a workspace.  fp32 planes on the MFMA path (channel counts in multiples of 32, 3-D) always use the atomic flush. */
 int fmri_conv3d_wgrad(const void* src0, int C0, int up0, const void* src1, int C1, const void* dy, float* dw, float* db,
                       int N, int D, int H, int W, int Cout, int dtype, int impl, int planar, void* workspace,
                       int64_t workspace_bytes, fmri_stream_t stream);
